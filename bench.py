@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark: U-Net denoise steps/sec of DRMNet's reverse process on synthetic 3x128x256 refmaps.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, dtype, ...); --dump-outputs DIR
+    then also writes what the timed path computed in its last step as DIR/<name>.npy.  Everything else the line can carry (roofline and
+    kernel breakdown, PMC traffic, parity checks, the exact-fp32 / f16x3 passes, secondary workloads, CPU baseline) is --full's.
     N > 1 works both ways: launched by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or as the plain command above, in
     which case this process spawns the N ranks itself as fresh child processes BEFORE it touches the GPU and relays rank 0's line.
@@ -11,7 +14,7 @@ One "step" = one pass of the hot path over one batch: a full DRMNet reverse step
 the reference), all rows active, fp32, inputs resident in HBM.  value = sample-steps/s summed over all GPUs (weak scaling:
 every rank owns its own `--batch` refmaps; the path has no collective -- samples are independent).
 
-The JSON line carries
+With --full the JSON line also carries
   roofline     : dominant kernel = fused GroupNorm+SiLU+conv3x3 implicit GEMM (conv.hip); achieved = algorithmic conv3x3
                  FLOPs of its launches / their summed duration, both measured with HIP events on the launch stream inside the
                  timed region (library profiler, include/drmnet_hip.h drm_profile_*); peak = the dense MFMA peak of the mode;
@@ -42,7 +45,7 @@ GFLOP = {"illnet": {(128, 128): 202.66, (128, 256): 406.76}, "refnet": {(128, 12
          "obsnet": {(128, 128): 215.34, (128, 256): 448.24}}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -58,13 +61,22 @@ def parse():
                          "GroupNorm-fed 3x3 convs in one block-scaled fp8 MFMA (2.4e-5 .. 4e-5 rel-L2 per network against the reference, 1e-4 contract: "
                          "tests/test_gpu_f16mx.py); f16x3 = all three products on the f16 MFMA (~2e-6: passes the SAME tolerances as fp32, "
                          "tests/test_gpu_split.py); fp32 = v_mfma_f32_32x32x2_f32; f16 = reduced precision (~1e-3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure roofline.traffic in this run (the committed profile is imported instead, hash-gated)")
-    ap.add_argument("--no-strict-fp32", action="store_true", help="skip the short exact-fp32 pass that follows the headline measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (B = 128 / B = 1 steps, ObsNet DDIM chain at B = 256, full chain) that follow it")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the batch-1 parity forward passes (keeps a rocprofv3 trace of this command to the timed workload's launches)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                                                           "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of a larger output)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure (off by default; the --no-* options below "
+                                                        "switch parts of it off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) skip the library profiler (roofline, kernel breakdown)")
+    ap.add_argument("--no-live-traffic", action="store_true", help="(--full) skip the two rocprofv3 --pmc child runs that measure roofline.traffic in this run (the committed profile is imported instead, hash-gated)")
+    ap.add_argument("--no-strict-fp32", action="store_true", help="(--full) skip the short exact-fp32 pass that follows the headline measurement")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the secondary workloads (B = 128 / B = 1 steps, ObsNet DDIM chain at B = 256, full chain) that follow it")
+    ap.add_argument("--no-parity-check", action="store_true", help="(--full) skip the batch-1 parity forward passes (keeps a rocprofv3 trace of this command to the timed workload's launches)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run does only what the headline figure needs
+        args.no_cpu_baseline = args.no_profile = args.no_live_traffic = args.no_strict_fp32 = args.no_secondary = args.no_parity_check = True
+    return args
 
 
 def build_models(workload, dev, precision="fp32"):
@@ -118,10 +130,12 @@ def chain_inputs(B, dev, radius=128):
 
 
 def make_step(args, model, dev):
-    """Returns (callable running ONE step on the current stream, algorithmic GFLOP per sample-step, description)."""
+    """Returns (callable running ONE step on the current stream, algorithmic GFLOP per sample-step, description).  The callable's `outputs`
+    dict holds, by name, the tensors its last call handed back (--dump-outputs)."""
     from drmnet_amd import _lib, synth
 
     B, H, W = args.batch, args.height, args.width
+    last = {}
     if args.workload == "estimate_chain":
         # BASELINE configs[4] / SURVEY 8d config 5: object image + normals + mask -> refmap -> ObsNet DDIM-50 -> DRMNet loop
         # (150 steps, early exit off so the work is countable) -> Lr0, at the config shape (128x128 refmaps from 256x256 images)
@@ -133,9 +147,10 @@ def make_step(args, model, dev):
         state = {"n": 0}
 
         def step():
-            estimate_batch(drm, obs, imgs, normals, masks, early_exit=False, seed=100 + state["n"])
+            last["Lr0"], last["zK"], last["K"] = estimate_batch(drm, obs, imgs, normals, masks, early_exit=False, seed=100 + state["n"])
             state["n"] += 1
 
+        step.outputs = last
         gf = obs.ddim_steps * GFLOP["obsnet"].get((res, res), 0) + drm.max_timesteps * (GFLOP["illnet"].get((res, res), 0) + GFLOP["refnet"].get((res, res), 0))
         return step, gf, (f"full chain per object image: erosion + refmap_mask_make + ObsNet DDIM-{obs.ddim_steps} + DRMNet loop "
                           f"({drm.max_timesteps} steps, early exit off) at {res}x{res}; value counts object images")
@@ -157,6 +172,7 @@ def make_step(args, model, dev):
         gf = GFLOP["illnet"].get(key, 0) + GFLOP["refnet"].get(key, 0)
         step.state = Lr_k  # the tensor every step updates in place: main() checks it stays finite
         step.counter = state  # {"i": steps done}: the reverse-step index and the Philox key of the next step
+        step.outputs = {"Lr_k": Lr_k}
         return step, gf, "DRMNet reverse step = RefNet + z-MLP + IllNet + update (all rows active)"
     if args.workload in ("illnet", "refnet", "obsnet"):
         unet = {"illnet": lambda: model.illnet_model.diffusion_model, "refnet": lambda: model.refnet_model.diffusion_model,
@@ -168,12 +184,13 @@ def make_step(args, model, dev):
 
         def step():
             if args.workload == "illnet":
-                unet.forward_parts(xk, x, t_emb=t_emb)
+                last["out"] = unet.forward_parts(xk, x, t_emb=t_emb)
             elif args.workload == "refnet":
-                unet.forward_parts(xk, x, t)
+                last["out"] = unet.forward_parts(xk, x, t)
             else:
-                unet.forward_parts(xk, x, timesteps=t)
+                last["out"] = unet.forward_parts(xk, x, timesteps=t)
 
+        step.outputs = last
         return step, GFLOP[args.workload].get(key, 0), f"{args.workload} U-Net forward"
     # obsnet_ddim: one DDIM step (U-Net + fused update, Philox noise); obsnet_ddim_chain: the whole 50-step chain with the
     # captured-step hipGraph replay (BASELINE configs[2]: DDIM 50-step, batch 256, reduced precision, graph) -- one bench step = one chain
@@ -189,14 +206,43 @@ def make_step(args, model, dev):
         def chain():
             out, _ = s.ddim_sampling(x, tuple(x.shape), x_T=xT, seed=1)
             chain.state = out
+            last["x"] = out
 
         chain.units = 50  # denoise steps per bench step and sample
+        chain.outputs = last
         return chain, GFLOP["obsnet"].get(key, 0), "ObsNet DDIM chain, 50 steps (eta = 1, Philox noise), step 2 captured as a hipGraph and replayed"
 
     def step():
-        s.ddim_sampling(x, tuple(x.shape), x_T=xT, num_steps=1, seed=1)
+        last["x"], _ = s.ddim_sampling(x, tuple(x.shape), x_T=xT, num_steps=1, seed=1)
 
+    step.outputs = last
     return step, GFLOP["obsnet"].get(key, 0), "ObsNet DDIM step (eta=1)"
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outputs: dict, out_dir: str, budget: int = DUMP_BYTES) -> dict:
+    """Writes every tensor of `outputs` as out_dir/<name>.npy: float64 for float64 and integer tensors, float32 otherwise.  Each output gets an
+    equal share of `budget`; one larger than its share is written as a sample of its flattened values at sorted indices drawn from a generator
+    seeded by 0, so the same shape always gives the same sample.  Returns {name: {"shape", "dtype", "written"}} for the result line."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(outputs))
+    info = {}
+    for name, t in outputs.items():
+        t = torch.as_tensor(t).detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        dt, item = (torch.float64, 8) if wide else (torch.float32, 4)
+        flat = t.reshape(-1)
+        if flat.numel() * item > share:
+            idx = torch.randint(flat.numel(), (share // item,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        arr = (t if flat.numel() == t.numel() else flat).to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+        info[name] = {"shape": list(t.shape), "dtype": str(arr.dtype), "written": "all" if arr.size == t.numel() else f"seeded sample of {arr.size}"}
+    return info
 
 
 def parity_check(model, dev, precision):
@@ -858,7 +904,7 @@ def main():
     barrier()
     # the state the timed loop starts from (re-run in f16x3 afterwards: timed_state_check)
     state0 = getattr(step, "state", None)
-    state0 = None if state0 is None or not hasattr(step, "counter") else (state0.clone(), int(step.counter["i"]))
+    state0 = None if state0 is None or not hasattr(step, "counter") or args.no_parity_check else (state0.clone(), int(step.counter["i"]))
     profile = not args.no_profile
     if profile:  # the timed region instruments the dominant kernel family only (HIP events around the fused 3x3 convs)
         L.drm_profile_reset()
@@ -875,6 +921,8 @@ def main():
         print("bench.py: the sampler state went non-finite inside the timed region; the measurement is invalid", file=sys.stderr)
         sys.exit(3)
     state_final = None if state0 is None else state.clone()
+    # what the last timed step computed, before anything else runs a step (every rank runs the same seeded inputs: rank 0 writes)
+    dumped = dump_outputs(step.outputs, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     timed = None
     timed_variants = {}
     if profile:
@@ -1029,9 +1077,13 @@ def main():
             "roofline": roofline,
             **extra,
             "kernel_breakdown": breakdown,
-            "kernel_breakdown_note": "conv3x3 row and the roofline object: HIP events inside the timed region; other rows: a second, untimed pass of the same steps with every kernel family instrumented",
+            "kernel_breakdown_note": "conv3x3 row and the roofline object: HIP events inside the timed region; other rows: a second, untimed pass of the same steps with every kernel family instrumented"
+                                     if breakdown is not None else None,
         }
         out["state_finite"] = state_finite
+        out["full"] = args.full
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if state0 is not None and world == 1 and args.workload == "drmnet_step" and args.precision == "f16mx" and not args.no_parity_check:
             try:
                 out["timed_state_check"] = timed_state_check(args, model, dev, state0[0], state0[1], state_final)

@@ -16,6 +16,12 @@ import torch
 from . import _lib
 
 
+def ieee_sqrt(t: torch.Tensor) -> torch.Tensor:
+    """Square root rounded as IEEE 754 prescribes (numpy's), in t's dtype.  torch's CPU sqrt goes through the host's vector math library, whose
+    rounding depends on the code path it picks for the CPU: the schedule tables must not."""
+    return torch.from_numpy(np.sqrt(t.detach().cpu().numpy()))
+
+
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
     if ddim_discr_method == "uniform":
         c = num_ddpm_timesteps // num_ddim_timesteps
@@ -36,7 +42,7 @@ def make_ddim_sampling_parameters(alphacums: torch.Tensor, ddim_timesteps, eta, 
     alphas = ac[idx]  # fp32
     alphas_prev = torch.tensor([float(ac[0])] + [float(v) for v in ac[idx[:-1]]], dtype=torch.float64)
     recip = (1 - alphas).reciprocal().double()  # the one fp32-rounded factor of util.py:69
-    sigmas = eta * torch.sqrt(recip * (1 - alphas_prev) * (1 - alphas.double() / alphas_prev))
+    sigmas = eta * ieee_sqrt(recip * (1 - alphas_prev) * (1 - alphas.double() / alphas_prev))
     return sigmas, alphas, alphas_prev
 
 
@@ -59,7 +65,7 @@ class DDIMSampler(object):
         assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
         sig, a, a_prev = make_ddim_sampling_parameters(alphas_cumprod, self.ddim_timesteps, ddim_eta, verbose=verbose)
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sig, a, a_prev
-        self.ddim_sqrt_one_minus_alphas = torch.sqrt(1.0 - a)
+        self.ddim_sqrt_one_minus_alphas = ieee_sqrt(1.0 - a)
         # the five fp32 scalars p_sample_ddim derives per index through torch.full + fp32 tensor ops (ddim.py:243-258)
         S = len(self.ddim_timesteps)
         coef = np.zeros((S, 5), dtype=np.float32)
@@ -68,7 +74,7 @@ class DDIMSampler(object):
             ap = torch.full((1,), float(a_prev[i]))
             sg = torch.full((1,), float(sig[i]))
             s1m = torch.full((1,), float(self.ddim_sqrt_one_minus_alphas[i]))
-            coef[i] = [a_t.sqrt().item(), s1m.item(), ap.sqrt().item(), (1.0 - ap - sg**2).sqrt().item(), sg.item()]
+            coef[i] = [ieee_sqrt(a_t).item(), s1m.item(), ieee_sqrt(ap).item(), ieee_sqrt(1.0 - ap - sg**2).item(), sg.item()]
         self.ddim_coef = coef
 
     @torch.no_grad()

@@ -27,6 +27,12 @@ import torch
 # ----------------------------------------------------------------------------- schedules
 
 
+def ieee_sqrt(t: torch.Tensor) -> torch.Tensor:
+    """Square root rounded as IEEE 754 prescribes (numpy's), in t's dtype: torch's CPU sqrt rounds as the host's vector math library's code path
+    for the CPU does, and the DDIM tables below are pinned bit for bit."""
+    return torch.from_numpy(np.sqrt(t.detach().cpu().numpy()))
+
+
 def ddpm_schedule(timesteps: int = 1000, linear_start: float = 1e-4, linear_end: float = 2e-2, v_posterior: float = 0.0):
     """fp64 numpy tables cast to fp32, as ddpm.py:137-176 (beta_schedule='linear')."""
     betas = (torch.linspace(linear_start**0.5, linear_end**0.5, timesteps, dtype=torch.float64) ** 2).numpy()
@@ -66,13 +72,13 @@ def ddim_schedule(alphas_cumprod: torch.Tensor, num_ddpm: int, S: int, eta: floa
     # util.py:69 mixes an fp32 tensor with a float64 array: ``ndarray / Tensor`` dispatches to
     # Tensor.__rtruediv__ = reciprocal() * other, so 1/(1-a) is rounded in fp32, the rest is float64
     recip_one_minus_a = (1 - a).reciprocal().double()
-    sig = eta * torch.sqrt(recip_one_minus_a * (1 - a_prev) * (1 - a.double() / a_prev))
+    sig = eta * ieee_sqrt(recip_one_minus_a * (1 - a_prev) * (1 - a.double() / a_prev))
     return {
         "ddim_timesteps": tau,
         "ddim_alphas": a,
         "ddim_alphas_prev": a_prev,
         "ddim_sigmas": sig,
-        "ddim_sqrt_one_minus_alphas": torch.sqrt(1.0 - a),  # ddim.py:57, fp32
+        "ddim_sqrt_one_minus_alphas": ieee_sqrt(1.0 - a),  # ddim.py:57, fp32
     }
 
 
@@ -89,10 +95,10 @@ def ddim_step_coeffs(sched: dict) -> np.ndarray:
         a_prev = torch.full((1,), float(sched["ddim_alphas_prev"][i]))
         sigma = torch.full((1,), float(sched["ddim_sigmas"][i]))
         s1m = torch.full((1,), float(sched["ddim_sqrt_one_minus_alphas"][i]))
-        out[i, 0] = a_t.sqrt().item()
+        out[i, 0] = ieee_sqrt(a_t).item()
         out[i, 1] = s1m.item()
-        out[i, 2] = a_prev.sqrt().item()
-        out[i, 3] = (1.0 - a_prev - sigma**2).sqrt().item()
+        out[i, 2] = ieee_sqrt(a_prev).item()
+        out[i, 3] = ieee_sqrt(1.0 - a_prev - sigma**2).item()
         out[i, 4] = sigma.item()
     return out
 

@@ -1,9 +1,13 @@
 import os
 import sys
 
-import numpy as np
-import pytest
-import torch
+# torch's CPU exp / sin / cos / sqrt round as the code branch MKL picks for the host CPU does.  The bit-exact fixtures (the timestep embedding,
+# the stress weights' checksums) were recorded on MKL's AVX-512 branch: pin it (MKL conditional numerical reproducibility) before torch loads MKL.
+os.environ.setdefault("MKL_CBWR", "AVX512")
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

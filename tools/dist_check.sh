@@ -4,7 +4,7 @@
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$ROOT"
 DRM_BENCH_DIST=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-  bench.py --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null > /tmp/dist_check.out
+  bench.py --gpus 1 --steps 4 --warmup 1 --full --no-cpu-baseline 2>/dev/null > /tmp/dist_check.out
 python3 - <<'PY'
 import json
 L = [l for l in open('/tmp/dist_check.out') if l.strip()]

@@ -9,7 +9,7 @@ OUT="$ROOT/gpurun_out/prof_obsnet"
 rm -rf "$OUT"; mkdir -p "$OUT"
 ARGS="--workload obsnet --precision $prec --no-cpu-baseline --no-parity-check --no-strict-fp32 --no-secondary"
 cd "$ROOT"
-python3 bench.py $ARGS --steps 10 --warmup 3 > $OUT/${tag}_obsnet_${prec}_bench.log 2>&1
+python3 bench.py $ARGS --full --steps 10 --warmup 3 > $OUT/${tag}_obsnet_${prec}_bench.log 2>&1
 grep "^{\"metric\"" $OUT/${tag}_obsnet_${prec}_bench.log | tail -1 > $OUT/${tag}_obsnet_${prec}_bench.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $OUT/stats -- python3 $ROOT/bench.py $ARGS --steps 5 --warmup 2 --no-profile > $OUT/stats.log 2>&1
