@@ -80,7 +80,7 @@ std::atomic<int> g_op_precision{PREC_FP32};
 // packs one conv weight for the op precision `prec`; `slot` = 64-float scale slot (2^k, 2^-k), `scratch` = 1 uint
 int pack_for_ops(int prec, const float* w, float* dst, float* slot, float* scratch, int cout, int cin, int taps, int coutp, int cinp, hipStream_t s,
                  bool mx_site = false) {
-  if (prec != PREC_FP32 && cinp % 32 == 0)
+  if (conv_split_weights(prec, cinp))
     return launch_pack_conv_weight_split(w, dst, slot, reinterpret_cast<unsigned*>(scratch), cout, cin, taps, coutp, cinp, s,
                                          prec == PREC_F16MX && mx_site, prec == PREC_BF16);
   return launch_pack_conv_weight(w, dst, cout, cin, taps, coutp, cinp, s);
@@ -208,10 +208,12 @@ int drm_op_norm_act_conv(const float* x, const float* gamma, const float* beta, 
       float* gp = ar.alloc<float>(cinp);
       float* bpn = ar.alloc<float>(cinp);
       ConvArgs a;
+      a.C0 = cinp; a.N = N; a.H = H; a.W = W; a.taps = taps; a.Cout = coutp; a.out_nchw = 1; a.cout_valid = Cout;
+      const ConvPlan p = plan_conv(a, op_prec);
       if (ar.dry) {
         xa.mom_valid = false;
         DRM_TRY(ensure_moments(c, xa));
-        if (!gamma) DRM_TRY(raw_input_guard(c, a, &xa, 0, cinp, nullptr, nullptr, cinp));
+        if (!gamma) DRM_TRY(raw_input_guard(c, a, p, &xa, 0, cinp, nullptr, nullptr, cinp));
         return DRM_OK;
       }
       DRM_TRY(launch_pack_input(x, nullptr, nullptr, xa.p, N, H, W, Cin, 0, cinp, s));
@@ -220,7 +222,7 @@ int drm_op_norm_act_conv(const float* x, const float* gamma, const float* beta, 
       if (!gamma) {
         xa.mom_valid = false;
         DRM_TRY(ensure_moments(c, xa));
-        DRM_TRY(raw_input_guard(c, a, &xa, 0, cinp, nullptr, nullptr, cinp));
+        DRM_TRY(raw_input_guard(c, a, p, &xa, 0, cinp, nullptr, nullptr, cinp));
       }
       if (gamma) {
         DRM_HIP_CHECK(hipMemcpyAsync(gp, gamma, Cin * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -232,11 +234,11 @@ int drm_op_norm_act_conv(const float* x, const float* gamma, const float* beta, 
         DRM_TRY(launch_nchw_to_nhwc(residual, resn, N, H, W, Cout, s));
         a.res = resn;
       }
-      a.src0 = xa.p; a.C0 = cinp; a.N = N; a.H = H; a.W = W; a.silu = silu;
-      a.w = wp; a.bias = bp; a.taps = taps; a.Cout = coutp;
+      a.src0 = xa.p; a.silu = silu;
+      a.w = wp; a.bias = bp;
       a.emb = emb; a.emb_stride = Cout;
-      a.out = out; a.out_nchw = 1; a.cout_valid = Cout; a.cin_real = Cin;
-      return run_conv(c, a, wb, 0);
+      a.out = out; a.cin_real = Cin;
+      return run_conv(c, a, p, wb, 0);
     });
   });
 }

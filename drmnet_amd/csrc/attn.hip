@@ -655,11 +655,17 @@ size_t attention_conv_workspace_floats(int N, int T, int C) {
   const size_t Z = (size_t)(C > T ? C : T);
   return 2 * (size_t)N * T * C + (size_t)N * (2 * C + T + Z) + 6 * (size_t)N + 64;
 }
-bool attention_conv_applicable(int T, int C, int H, int W, int terms) {
-  return terms != 0 && T % 256 == 0 && C % 128 == 0 && T % 128 == 0 && H % 16 == 0 && W % 16 == 0;
+// S = alpha q k^T (cin = C, cout = T) and O = P v (cin = T, cout = C) of nb images: 1x1 convs with per-image weights (k, v^T)
+static ConvArgs attention_gemm(int nb, int H, int W, int cin, int cout) {
+  ConvArgs a;
+  a.C0 = cin; a.N = nb; a.H = H; a.W = W; a.taps = 1; a.Cout = cout;
+  a.w_img_stride_f4 = (long long)cin * cout / 4; a.prof_kind = PROF_KINDS;  // (inside the core's profiler scope)
+  return a;
 }
-
-int launch_conv_split(const ConvArgs& a, hipStream_t s);
+bool attention_conv_planned(int H, int W, int C, int precision) {
+  return plan_conv(attention_gemm(1, H, W, C, H * W), precision).kernel == CONV_PIPELINE &&
+         plan_conv(attention_gemm(1, H, W, H * W, C), precision).kernel == CONV_PIPELINE;
+}
 
 // (for attn_flash.hip: the per-image factor tables and the row-major pre-split image of q / k)
 void launch_attn_scales(const double2* mom, int N, int C, int T, float alpha, float* q_tab, float* p_tab, float* zero_tab, float* qk_inv, float* k_scale,
@@ -676,10 +682,10 @@ int launch_pack_attn_rows(const float* src, long long img_stride, int ld, const 
 
 // qkv [N][T][3C] (+ its fused per-channel statistics), scores workspace [N][T][T], out [N][T][C], ws: attention_conv_workspace_floats
 // proj_guard (optional): receives the (scale, shift, inverse) tables that guard proj_out's read of `out`
-int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* scores, float* out, float* ws, int N, int H, int W, int C, int terms,
+int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* scores, float* out, float* ws, int N, int H, int W, int C, int precision,
                           hipStream_t s, ConvArgs* proj_guard) {
   const int T = H * W;
-  DRM_REQUIRE(attention_conv_applicable(T, C, H, W, terms) && qkv_mom, "attention on the conv pipeline: shape");
+  DRM_REQUIRE(attention_conv_planned(H, W, C, precision) && qkv_mom, "attention on the conv pipeline: shape");
   const size_t Z = (size_t)(C > T ? C : T);
   float* wk = ws;                           // [N] packed k:   Cout = T, Cin = C
   float* wv = wk + (size_t)N * T * C;       // [N] packed v^T: Cout = C, Cin = T
@@ -702,27 +708,29 @@ int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* score
   }
   const unsigned pb = (unsigned)std::min<size_t>(((size_t)T * C / 8 + 255) / 256, 4096);
   hipLaunchKernelGGL(pack_attn_weight_kernel<true>, dim3(pb, N), dim3(256), 0, s, qkv + C, (long long)T * 3 * C, 3 * C, k_scale,
-                     reinterpret_cast<float4*>(wk), T, C, terms == 4 ? 1 : 0);
+                     reinterpret_cast<float4*>(wk), T, C, precision == PREC_BF16 ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(pack_attn_weight_kernel<false>, dim3(pb, N), dim3(256), 0, s, qkv + 2 * C, (long long)T * 3 * C, 3 * C, v_scale,
-                     reinterpret_cast<float4*>(wv), C, T, terms == 4 ? 1 : 0);
+                     reinterpret_cast<float4*>(wv), C, T, precision == PREC_BF16 ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   const int NB = attention_group(N, T);
   for (int n0 = 0; n0 < N; n0 += NB) {  // one pass per image group (scores = the group's [nb, T, T] buffer)
     const int nb = std::min(NB, N - n0);
-    ConvArgs a;  // S = alpha q k^T
-    a.src0 = qkv + (size_t)n0 * T * 3 * C; a.C0 = C; a.ld0 = 3 * C; a.N = nb; a.H = H; a.W = W;
-    a.gn_scale = q_tab + (size_t)n0 * C; a.gn_shift = zero_tab + (size_t)n0 * Z; a.silu = 0;
-    a.w = wk + (size_t)n0 * T * C; a.w_img_stride_f4 = (long long)T * C / 4; a.w_inv_img = k_inv + n0; a.in_inv = qk_inv + n0;
-    a.taps = 1; a.Cout = T; a.out = scores; a.terms = terms; a.prof_kind = PROF_KINDS;  // (inside the scope above)
-    DRM_TRY(launch_conv_split(a, s));
+    ConvArgs a = attention_gemm(nb, H, W, C, T);  // S = alpha q k^T
+    a.src0 = qkv + (size_t)n0 * T * 3 * C; a.ld0 = 3 * C;
+    a.gn_scale = q_tab + (size_t)n0 * C; a.gn_shift = zero_tab + (size_t)n0 * Z;
+    a.w = wk + (size_t)n0 * T * C; a.w_inv_img = k_inv + n0; a.in_inv = qk_inv + n0; a.out = scores;
+    const ConvPlan qk_plan = plan_conv(a, precision);
+    a.terms = qk_plan.terms;
+    DRM_TRY(launch_conv(a, qk_plan, s));
     DRM_TRY(launch_softmax_rows(scores, (long long)nb * T, T, s));
-    ConvArgs b;  // O = P v
-    b.src0 = scores; b.C0 = T; b.N = nb; b.H = H; b.W = W;
-    b.gn_scale = p_tab + (size_t)n0 * T; b.gn_shift = zero_tab + (size_t)n0 * Z; b.silu = 0;
-    b.w = wv + (size_t)n0 * T * C; b.w_img_stride_f4 = (long long)T * C / 4; b.w_inv_img = v_inv + n0; b.in_inv = pv_inv + n0;
-    b.taps = 1; b.Cout = C; b.out = out + (size_t)n0 * T * C; b.terms = terms; b.prof_kind = PROF_KINDS;
-    DRM_TRY(launch_conv_split(b, s));
+    ConvArgs b = attention_gemm(nb, H, W, T, C);  // O = P v
+    b.src0 = scores;
+    b.gn_scale = p_tab + (size_t)n0 * T; b.gn_shift = zero_tab + (size_t)n0 * Z;
+    b.w = wv + (size_t)n0 * T * C; b.w_inv_img = v_inv + n0; b.in_inv = pv_inv + n0; b.out = out + (size_t)n0 * T * C;
+    const ConvPlan pv_plan = plan_conv(b, precision);
+    b.terms = pv_plan.terms;
+    DRM_TRY(launch_conv(b, pv_plan, s));
   }
   return DRM_OK;
 }

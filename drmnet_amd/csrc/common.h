@@ -78,7 +78,7 @@ struct ConvArgs {
   float* out = nullptr;             // NHWC [N,H,W,Cout], or NCHW [N,cout_valid,H,W] if out_nchw
   int out_nchw = 0, cout_valid = 0;
   int cin_real = 0;                 // un-padded Cin for FLOP accounting (0 = C0 + C1)
-  int ksplit = 1;                      // split-K factor (conv_split_ksplit); > 1: split k writes its raw partial sums to out + k * split_stride
+  int ksplit = 1;                      // split-K factor (plan_conv); > 1: split k writes its raw partial sums to out + k * split_stride
   size_t split_stride = 0;             // floats between the split-K slabs (0 unless ksplit > 1)
   float* split_ws = nullptr;           // fused split-K: slab workspace ([ksplit] slabs of split_stride floats); the workgroup that arrives LAST at an output tile
   unsigned* tile_ticket = nullptr;     // (arrival counter per output tile, zero before the launch) sums the slabs in slab order and runs the full epilogue into `out`
@@ -90,7 +90,7 @@ struct ConvArgs {
 #endif
   double2* stat_out = nullptr;         // optional [N][Cout] (sum, sum of squares) of the OUTPUT, accumulated atomically (must be zeroed)
   float* pool_out = nullptr;           // optional: the 2x2 average pool of the output, NHWC [N][H/2][W/2][Cout] (Downsample, openaimodel.py:154-160), written by the
-  double2* pool_stat = nullptr;        // same epilogue, with its [N][Cout] (sum, sum of squares) (zeroed) -- conv_split_pool_applicable says which launches can
+  double2* pool_stat = nullptr;        // same epilogue, with its [N][Cout] (sum, sum of squares) (zeroed) -- plan_conv says which launches can
   const float* w_inv_scale = nullptr;  // split-precision path: device scalar 2^-k undoing the weight pre-scaling
   int ld0 = 0;                         // channel stride of src0's pixels when it is a channel slice of a wider tensor (0 = C0)
   long long w_img_stride_f4 = 0;       // split 1x1 path: every image has its own packed weight set this many float4 apart (attention GEMMs)
@@ -99,17 +99,36 @@ struct ConvArgs {
   const float* in_inv = nullptr;       // split-precision path: [N] per-image 2^-k undoing the input staging factor (launch_act_pow2_scale)
   GnFold gnf;                          // sparse launches (engine.hip gn_params): gn_scale / gn_shift (and a guard table set) are finalised by this launch's own prologue
 };
-int launch_conv(const ConvArgs& a, hipStream_t s);
+// One decision per conv launch: plan_conv (conv_split2.hip) picks the kernel and its instantiation, the split-K form, and whether the 2x2 pool and
+// the GroupNorm finalise fold into the launch; launch_conv carries it out.  The engine plans every conv once, in sizing and real passes alike.
+enum ConvKernel : unsigned char { CONV_NONE, CONV_IGEMM, CONV_PIPELINE };  // NONE: per-image weights outside the pipeline's rule
+enum ConvTile : unsigned char { TILE_256x256, TILE_256x192, TILE_256x128, TILE_128x128, TILE_256x64, TILE_128x64, TILE_128x32 };  // GEMM rows x channels
+// split-K finish: by the workgroup that arrives last at an output tile (SK instantiation, ConvArgs::tile_ticket), or by a second launch
+// (splitk_reduce_small_kernel) that sums the slabs
+enum SplitFinish : unsigned char { SPLIT_NONE, SPLIT_IN_LAUNCH, SPLIT_REDUCE };
+struct ConvPlan {
+  ConvKernel kernel = CONV_NONE;  // conv_igemm_kernel (conv.hip) or conv_split2_kernel
+  int terms = 0;                  // ConvArgs::terms of a pipeline launch
+  ConvTile tile = TILE_128x32;
+  int th = 0, tw = 0;             // pixel tile of one image (the kernel's TH x TW)
+  bool ragged = false;            // pipeline: edge tiles masked (RAG instantiations); conv_igemm_kernel masks them always
+  int kc = 32;                    // conv_igemm_kernel: channels per K step (8: input channels that are not whole 32-chunks)
+  int ksplit = 1;
+  SplitFinish finish = SPLIT_NONE;
+  size_t tickets = 0;             // SPLIT_IN_LAUNCH: the zeroed arrival counters to allocate (ConvArgs::tile_ticket)
+  bool pool = false;              // the epilogue writes the 2x2 average pool (ConvArgs::pool_out / pool_stat)
+  bool gn_fold = false;           // the prologue finalises the input's GroupNorm tables (ConvArgs::gnf)
+  bool split() const { return kernel == CONV_PIPELINE && terms != 0; }  // split-precision operands: an un-normalised input needs its range guard
+};
+// `a`: the shape fields (N, H, W, C0, C1, taps, Cout, mx_site, out_nchw, w_img_stride_f4).  want_pool: a Downsample follows this conv;
+// gn_foldable: the input's GroupNorm tables may be finalised by this launch
+ConvPlan plan_conv(const ConvArgs& a, int precision, bool want_pool = false, bool gn_foldable = false);
+// the weight image a conv with `cin` (padded) input channels reads in `precision`: the pre-split one (launch_pack_conv_weight_split) or plain fp32
+bool conv_split_weights(int precision, int cin);
+// the one launch entry of every conv: validates `a` against the plan; a split-K launch takes its slabs at a.split_ws
+int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
 // index of the pixel-tile family {TH, TW} that wastes the fewest GEMM rows on an H x W map (ties: the first = larger tile)
 int conv_tile_family(int H, int W, const int (*fam)[2], int n_fam);
-// split-precision (fp16 hi/lo x 3 MFMA, fp32-accurate) variant; a.w = pre-split weights (conv_split.hip)
-int launch_conv_split(const ConvArgs& a, hipStream_t s);
-int conv_split_ksplit(const ConvArgs& a);  // split-K factor the split kernels want for this launch (1 = none)
-bool conv_split_fused_finish(const ConvArgs& a);  // a split-K launch of this shape finishes its tiles itself (ConvArgs::split_ws / tile_ticket); else launch_splitk_reduce follows
-// deterministic second half of a split-K conv on maps of at most 256 pixels: out = sum of the slabs at `partial` (+ bias, emb, residual), statistics into a.stat_out
-int launch_splitk_reduce(const ConvArgs& a, const float* partial, hipStream_t s);
-bool conv_split_pool_applicable(const ConvArgs& a);  // this launch (shape fields set) can write ConvArgs::pool_out / pool_stat from its epilogue
-bool conv_split_fuses_stats();  // true when the active split kernel accumulates ConvArgs::stat_out in its epilogue
 size_t packed_conv_weight_split_floats(int taps, int CoutP, int CinP);
 // mx: the f16mx image (fp16 hi planes + e4m3 planes of hi and lo) for the 3x3 convs that run with ConvArgs::terms == 2
 int launch_pack_conv_weight_split(const float* w, float* packed, float* scales, unsigned* scratch, int Cout, int Cin, int taps, int CoutP,
@@ -118,6 +137,8 @@ int launch_pack_conv_weight_split(const float* w, float* packed, float* scales, 
 // PREC_BF16: bf16 operands, fp32 accumulate (v_mfma_f32_32x32x16_bf16): BASELINE configs[2] as written; reduced precision like PREC_F16
 enum Precision { PREC_FP32 = 0, PREC_F16X3 = 1, PREC_F16 = 2, PREC_F16MX = 3, PREC_BF16 = 4 };
 inline bool precision_valid(int p) { return p >= PREC_FP32 && p <= PREC_BF16; }
+// ConvArgs::terms of the pipeline kernel in a mode (PREC_F16MX: 3, and 2 on its mx_site launches)
+inline int precision_terms(int p) { return p == PREC_F16 ? 1 : (p == PREC_BF16 ? 4 : (p == PREC_FP32 ? 0 : 3)); }
 // repack PyTorch conv weight [Cout][Cin][kh][kw] -> [taps][CinP/4][CoutP][4] (zero padded)
 int launch_pack_conv_weight(const float* w, float* packed, int Cout, int Cin, int taps, int CoutP, int CinP, hipStream_t s);
 size_t packed_conv_weight_floats(int taps, int CoutP, int CinP);
@@ -146,8 +167,8 @@ int launch_erode_mask(const unsigned char* mask, int H, int W, int k, unsigned c
 int launch_attention(const float* qkv, float* scores, float* out, int N, int T, int C, hipStream_t s, int terms = 0, const double2* qkv_mom = nullptr,
                      float* ws = nullptr, ConvArgs* proj_guard = nullptr);
 size_t attention_small_workspace_floats(int N, int T, int C);
-// split-precision attention core on the fused 1x1 conv pipeline (per-image weights = k, v^T); T = H*W must be a multiple of 256
-bool attention_conv_applicable(int T, int C, int H, int W, int terms);
+// split-precision attention core on the fused 1x1 conv pipeline (per-image weights = k, v^T): whether plan_conv takes both GEMMs
+bool attention_conv_planned(int H, int W, int C, int precision);
 // single-kernel form (attn_flash.hip): the long-sequence level (T >= 1024, C = 384), no score matrix in HBM
 bool attention_flash_applicable(int T, int C, int terms);
 size_t attention_flash_workspace_floats(int N, int T, int C);
@@ -157,7 +178,7 @@ int attention_group(int N, int T);
 size_t attention_scores_floats(int N, int T);
 size_t attention_conv_workspace_floats(int N, int T, int C);
 struct ConvArgs;
-int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* scores, float* out, float* ws, int N, int H, int W, int C, int terms,
+int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* scores, float* out, float* ws, int N, int H, int W, int C, int precision,
                           hipStream_t s, ConvArgs* proj_guard = nullptr);
 
 // boundary maps and the envmap warp (transform.hip)

@@ -285,9 +285,9 @@ static int launch_variant(const ConvArgs& a, hipStream_t s) {
 }
 
 template <int TAPS, int TH, int TW, int KC>
-static int dispatch_bn(const ConvArgs& a, hipStream_t s) {
-  if (a.Cout % 128 == 0) return launch_variant<TAPS, TH, TW, 2, 2, 2, 2, KC>(a, s);
-  if (a.Cout % 64 == 0) return launch_variant<TAPS, TH, TW, 2, 2, 2, 1, KC>(a, s);
+static int launch_igemm_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.tile == TILE_128x128) return launch_variant<TAPS, TH, TW, 2, 2, 2, 2, KC>(a, s);
+  if (p.tile == TILE_128x64) return launch_variant<TAPS, TH, TW, 2, 2, 2, 1, KC>(a, s);
   return launch_variant<TAPS, TH, TW, 4, 1, 1, 1, KC>(a, s);
 }
 
@@ -309,31 +309,22 @@ int conv_tile_family(int H, int W, const int (*fam)[2], int n_fam) {
 }
 
 template <int TAPS, int KC>
-static int dispatch_tile(const ConvArgs& a, hipStream_t s) {
-  static const int fam[4][2] = {{8, 16}, {8, 8}, {4, 8}, {4, 4}};
-  switch (conv_tile_family(a.H, a.W, fam, 4)) {
-    case 0: return dispatch_bn<TAPS, 8, 16, KC>(a, s);
-    case 1: return dispatch_bn<TAPS, 8, 8, KC>(a, s);
-    case 2: return dispatch_bn<TAPS, 4, 8, KC>(a, s);
-    default: return dispatch_bn<TAPS, 4, 4, KC>(a, s);
-  }
+static int launch_igemm_family(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.th == 8 && p.tw == 16) return launch_igemm_tile<TAPS, 8, 16, KC>(a, p, s);
+  if (p.th == 8 && p.tw == 8) return launch_igemm_tile<TAPS, 8, 8, KC>(a, p, s);
+  if (p.th == 4 && p.tw == 8) return launch_igemm_tile<TAPS, 4, 8, KC>(a, p, s);
+  return launch_igemm_tile<TAPS, 4, 4, KC>(a, p, s);
 }
 
-int launch_conv(const ConvArgs& a, hipStream_t s) {
-  const int Ctot = a.C0 + a.C1;
-  DRM_REQUIRE(a.taps == 9 || a.taps == 1, "conv taps must be 9 or 1");
+// the CONV_IGEMM plans of launch_conv (conv_split2.hip)
+int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   DRM_REQUIRE(a.Cout % 32 == 0, "conv Cout must be padded to a multiple of 32");
-  DRM_REQUIRE(Ctot % 8 == 0, "conv Cin must be padded to a multiple of 8");
-  DRM_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv shape");
-  DRM_REQUIRE(!a.up0 || (a.H % 2 == 0 && a.W % 2 == 0), "upsampled source needs even output size");
+  DRM_REQUIRE((a.C0 + a.C1) % 8 == 0, "conv Cin must be padded to a multiple of 8");
   DRM_REQUIRE((a.gn_scale == nullptr) == (a.gn_shift == nullptr), "gn scale/shift must come together");
-  if (Ctot % 32 == 0 && a.C0 % 32 == 0) {
-    if (a.taps == 9) return dispatch_tile<9, 32>(a, s);
-    return dispatch_tile<1, 32>(a, s);
-  }
+  if (p.kc == 32) return a.taps == 9 ? launch_igemm_family<9, 32>(a, p, s) : launch_igemm_family<1, 32>(a, p, s);
   DRM_REQUIRE(a.C0 % 8 == 0, "conv C0 must be a multiple of 8");
   DRM_REQUIRE(a.taps == 9, "1x1 conv needs Cin % 32 == 0");
-  return dispatch_tile<9, 8>(a, s);
+  return launch_igemm_family<9, 8>(a, p, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// Split-precision arithmetic of the fused GroupNorm+SiLU+conv implicit GEMM -- entry point + weight pre-split (the kernel: conv_split2.hip):
+// Split-precision arithmetic of the fused GroupNorm+SiLU+conv implicit GEMM -- weight pre-split (the kernel and its planner: conv_split2.hip):
 // fp32-accurate products on the gfx950 f16 matrix cores.
 //
 // Every fp32 operand x is split as x = hi + lo with hi = fp16(x), lo = fp16(x - hi) (22 significant bits together),
@@ -15,25 +15,11 @@
 //     halves stay in the fp16 normal range; the epilogue multiplies by the inverse scale (exact).
 // LDS images: A = [hi|lo][slab s][lane-half h][pixel][8 halfs], B = [hi|lo][s][h][cout][8 halfs]; one ds_read_b128 per
 // operand fragment (lane (r,h) of slab s needs channels 16s + 8h .. +7 of row/col r).
-// This file holds the dispatcher and the weight pre-split / packing kernels; the conv kernel is conv_split2.hip.
+// This file holds the weight pre-split / packing kernels.
 #include "common.h"
 #include "profiler.h"
 
 namespace drm {
-
-int launch_conv_split2(const ConvArgs& a, hipStream_t s);
-
-// the split kernels accumulate ConvArgs::stat_out (GroupNorm statistics of their output) in the epilogue
-bool conv_split_fuses_stats() { return true; }
-
-int launch_conv_split(const ConvArgs& a, hipStream_t s) {
-  const int Ctot = a.C0 + a.C1;
-  DRM_REQUIRE(a.taps == 9 || a.taps == 1, "conv taps must be 9 or 1");
-  DRM_REQUIRE(a.Cout % 32 == 0 && Ctot % 32 == 0 && a.C0 % 32 == 0, "split conv needs channels % 32 == 0");
-  DRM_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv shape");
-  DRM_REQUIRE(!a.up0 || (a.H % 2 == 0 && a.W % 2 == 0), "upsampled source needs even output size");
-  return launch_conv_split2(a, s);  // LDS-DMA weight ring, 256-pixel tiles (conv_split2.hip)
-}
 
 // ------------------------------------------------------------------------------------------------
 // weight pre-split: PyTorch [Cout][Cin][taps] fp32 -> [tap][chunk][hl][s][h][CoutP][8] fp16, scaled by 2^k

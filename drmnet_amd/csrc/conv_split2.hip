@@ -359,7 +359,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
   // split-K: this split's partial slab.  Fused form (a.split_ws): the slabs live in their own workspace and a.out is the real output; two-launch
   // form: a.out is the workspace and splitk_reduce_kernel follows.
   constexpr bool FUSE = SK;
-  static_assert(!SK || (WM == 4 && WN == 1 && MT == 1 && NT == 1 && !RAG), "split-K launches use the 128-row x 32-channel tiles (conv_split_ksplit)");
+  static_assert(!SK || (WM == 4 && WN == 1 && MT == 1 && NT == 1 && !RAG), "split-K launches use the 128-row x 32-channel tiles (plan_conv)");
   const bool fused = FUSE && ks > 1 && a.split_ws != nullptr;
   float* const out_s = (fused ? a.split_ws : a.out) + (size_t)split * a.split_stride;  // (split_stride = 0 without split-K)
   const bool has_gn = a.gn_scale != nullptr;
@@ -1328,7 +1328,7 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
   using C = S2Cfg<TAPS, TH, TW, WM, WN, MT, NT, R, TPS, TERMS>;
   auto kern = conv_split2_kernel<TAPS, TH, TW, WM, WN, MT, NT, R, TPS, TERMS, RAG, SK, POOL>;
   DRM_REQUIRE(RAG || (a.H % TH == 0 && a.W % TW == 0), "conv tile does not divide the map");
-  DRM_REQUIRE(POOL == (a.pool_out != nullptr), "pooled output: only launches conv_split_pool_applicable accepts");
+  DRM_REQUIRE(POOL == (a.pool_out != nullptr), "pooled output: only launches plan_conv pools");
   DRM_REQUIRE(!POOL || (a.pool_stat && a.stat_out && a.ksplit <= 1 && !a.out_nchw), "pooled output: needs both statistics tables, no split-K");
   const size_t lds_bytes = (size_t)(C::LDS_F4 + (POOL ? C::ST_F4 : 0)) * sizeof(float4);
   static_assert((C::LDS_F4 + (POOL ? C::ST_F4 : 0)) * 16 <= 160 * 1024, "LDS budget");
@@ -1409,164 +1409,185 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
   return DRM_OK;
 }
 
-constexpr long long S2_MIN_WIDE_TILES = 176;  // 256 x 128 tiles are used from this many workgroups on (of 256 CUs)
-
-// Deep levels (maps of at most 128 pixels: the 8x16 and 4x8 levels of a batch-32 step): too few GEMM rows for the 128-channel-wide tiles to fill
-// the chip, and the narrow tiles that do fill it re-stage (GroupNorm + SiLU + split) every activation tile once per 32 or 64 output channels.
-// Split-K over the WIDE tiles instead: every split writes its slab, splitk_reduce_small_kernel finishes (two-launch form).  Returns the
-// split factor (1 = not this form).
-inline int conv_split_wide_ksplit(const ConvArgs& a) {
-#ifdef DRM_NO_WIDE_SPLIT
-  return 1;
-#else
-  // (1x1 convs of these levels on the same form measured neutral: 5.86 -> 5.54 ms of 1x1 time per step, given back by the reduction launches)
-  if (a.taps != 9) return 1;
-  if (a.out_nchw || a.w_img_stride_f4 != 0 || a.Cout % 128 != 0) return 1;
-  const int hw = a.H * a.W;
-  if (hw > 128 || !((a.H % 8 == 0 && a.W % 16 == 0) || (a.H % 4 == 0 && a.W % 8 == 0))) return 1;
-  const long long rows = (long long)a.N * hw;
-  if (rows < 1024) return 1;  // (sparse launches keep the narrow tiles: a batch-1 step would fill half a wide tile)
-  const int bm = (a.taps == 1 || (a.H % 8 == 0 && a.W % 16 == 0)) ? 256 : 128;  // (3x3 on 4x8 maps: 128-pixel x 128-channel tiles on 4 waves, dispatch_s2_bn)
-  const long long tiles = ((rows + bm - 1) / bm) * (a.Cout / 128);
-  if (tiles >= S2_MIN_WIDE_TILES) return 1;
-  const int nch = (a.C0 + a.C1) / 32;
-  const long long ks = std::min<long long>(std::min<long long>(8, nch / 2), std::max<long long>(1, 256 / tiles));
-  return (int)std::max<long long>(ks, 1);
-#endif
+static int no_form(const ConvPlan& p) {  // (a plan that names a form no unit instantiates: a planner bug)
+  set_error("conv plan: form " + std::to_string((int)p.tile) + " on " + std::to_string(p.th) + "x" + std::to_string(p.tw) + (p.ragged ? " ragged" : "") +
+            " pixel tiles, terms " + std::to_string(p.terms) + ", is not instantiated");
+  return DRM_ERR_STATE;
 }
 
-// 256-pixel x {128, 64}-channel tiles on 8 waves, 128-pixel x {64, 32}-channel tiles on 4 waves
-template <int TAPS, int TH, int TW, int TH4, int TW4, int TERMS>
-static int dispatch_s2_bn(const ConvArgs& a, hipStream_t s) {
-  // Deep U-Net levels (4x8 .. 8x16 maps) have few GEMM rows: with 256x128 tiles they launch far fewer workgroups than
-  // the chip has CUs.  Shrink the tile (128 rows, then 64 / 32 channels) until the grid covers the 256 CUs.
-  const long long rows = (long long)a.N * a.H * a.W;
-  auto wgs = [&](int bm, int bn) { return ((rows + bm - 1) / bm) * (a.Cout / bn); };
-  // 3x3: one barrier per kernel ROW (3 taps, 48 KB of weights per step, double-buffered); 1x1: one tap per step, ring of 4.
-  // 256-row tiles on 4x8 / 4x4 maps keep the one-tap ring (their multi-image halo tiles leave no room for 96 KB of weights).
-  constexpr int TPS = (TAPS == 9) ? 3 : 1;
-  constexpr int RG = (TAPS == 9) ? 2 : 4;
-  constexpr bool big_ok = (TAPS == 1) || (TH >= 8);
-  if constexpr (TAPS == 1 && TH == 16 && TW == 16 && TERMS == 3) {
-    // 1x1 on big maps with Cout a multiple of 256: 256 output channels per tile (64 x 128 per wave, weight ring of 2).  The 1x1 form pays
-    // its activation staging and its barrier once per 24 MFMAs of a wave; here per 48 (the 64x128-map skip convs: 11-15 % faster).  The
-    // 1x1 kernel has the registers for it (176 -> 256 VGPRs, 2 spilled); the 3x3 kernel does not.
-    if (a.Cout % 256 == 0 && wgs(256, 256) >= 512) return launch_s2<TAPS, TH, TW, 4, 2, 2, 4, 2, 1, TERMS>(a, s);
-    // ... and 192 channels per tile (64 x 96 per wave, ring of 3) for Cout = 384 / 1152 / 1536 ...: qkv 512->1536 @16x32 and the 32x64-map skip
-    // convs 12-16 % faster
-    if (a.Cout % 192 == 0 && wgs(256, 192) >= 512) return launch_s2<TAPS, TH, TW, 4, 2, 2, 3, 3, 1, TERMS>(a, s);
-  }
-  // (one round of 128-wide tiles on >= 176 of the 256 CUs beats two rounds of the less efficient 64-wide ones: qkv 640->1920 @8x16 27 %,
-  //  512->1536 @8x16 24 %, 3x3 384->384 @16x32 12 % faster than with the old "fill every CU" rule)
-  if constexpr (TAPS == 9 && TH == 16 && TW == 16 && (TERMS == 3 || TERMS == 2)) {
-    // 3x3 with 192 output channels per tile (64 x 96 per wave; one-tap weight ring of 3: the three-tap groups would not fit next to the
-    // halo tile) for Cout = 384 on big maps: 12 fragment reads per 18 MFMA products instead of 8 per 12 -- 5 % faster there.  Fits since
-    // the scalar-base DMA addressing took the kernel from 256 to 207 VGPRs.
-    if (a.Cout % 192 == 0 && wgs(256, 192) >= 512) return launch_s2<TAPS, TH, TW, 4, 2, 2, 3, 3, 1, TERMS>(a, s);
-  }
-  if (a.Cout % 128 == 0 && (wgs(256, 128) >= S2_MIN_WIDE_TILES || (a.ksplit > 1 && !a.split_ws && conv_split_wide_ksplit(a) > 1))) {
-    if constexpr (TAPS == 9 && TH == 16 && TW == 16) {  // (conv_split_pool_applicable: exactly the launches that reach this line on 16 x 16 tiles)
-      if (a.pool_out) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS, false, false, true>(a, s);
-    }
-    if constexpr (big_ok) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS>(a, s);
-    else return launch_s2<TAPS, TH4, TW4, 2, 2, 2, 2, 3, 1, TERMS>(a, s);
-  }
-  if (a.Cout % 64 == 0 && wgs(256, 64) >= 256) {
-    if constexpr (big_ok) return launch_s2<TAPS, TH, TW, 4, 2, 2, 1, RG, TPS, TERMS>(a, s);
-    else return launch_s2<TAPS, TH4, TW4, 2, 2, 2, 1, RG, TPS, TERMS>(a, s);
-  }
-  constexpr int RS = RG;  // ([r4] a ring of 4 three-tap groups on these sparse-launch tiles: 5.31 vs 5.38 ms on the batch-1 step, later 5.06 vs 5.08 -- not adopted)
-  // ([r4] 128 x 32 tiles from 512 workgroups on -- two workgroups per CU on the batch-1 step's top level instead of one: 4.74 vs 4.755 ms there,
-  //  780 vs 800 steps/s at batch 32 -- not adopted: co-resident workgroups do not hide what a sparse launch waits for)
-  if (a.Cout % 64 == 0 && wgs(128, 64) >= 256) return launch_s2<TAPS, TH4, TW4, 2, 2, 2, 1, RS, TPS, TERMS>(a, s);
-  if (a.ksplit > 1 && a.split_ws) return launch_s2<TAPS, TH4, TW4, 4, 1, 1, 1, RS, TPS, TERMS, false, true>(a, s);  // (conv_split_ksplit: only ever here)
-  return launch_s2<TAPS, TH4, TW4, 4, 1, 1, 1, RS, TPS, TERMS>(a, s);
-}
-
-// Maps that are not a whole number of tiles (any H, W the reference accepts other than the shipped sizes): 128-row tiles on 4 waves,
-// 64 or 32 channels wide, in three pixel-tile families, edge tiles masked (RAG instantiations; no split-K, no per-image weights).
+// The instantiations of one (TAPS, TERMS) unit on one pixel tile, by GEMM tile.  3x3: one barrier per kernel ROW (3 taps, 48 KB of weights per
+// step, double-buffered); 1x1: one tap per step, ring of 4.  3x3 256-row tiles of 4-row pixel tiles (4x8 / 4x4 maps) do not exist: their
+// multi-image halo tiles leave no room for 96 KB of weights.
 template <int TAPS, int TH, int TW, int TERMS>
-static int dispatch_s2_ragged(const ConvArgs& a, hipStream_t s) {
-  constexpr int TPS = (TAPS == 9) ? 3 : 1;
-  constexpr int RG = (TAPS == 9) ? 2 : 4;
-  if (a.Cout % 64 == 0) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS, true>(a, s);
-  return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS, true>(a, s);
+static int launch_s2_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  constexpr int TPS = (TAPS == 9) ? 3 : 1, RG = (TAPS == 9) ? 2 : 4;
+  constexpr bool T16 = TH == 16 && TW == 16, ROWS256 = TAPS == 1 || TH >= 8;
+  if (p.ragged) {
+    if constexpr (TERMS != 0 && !T16 && !(TH == 4 && TW == 8)) {  // (the ragged families; fp32 runs ragged maps on conv_igemm_kernel)
+      if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS, true>(a, s);
+      if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS, true>(a, s);
+    }
+  } else if (p.tile == TILE_256x256) {
+    if constexpr (TAPS == 1 && T16 && TERMS == 3) return launch_s2<TAPS, TH, TW, 4, 2, 2, 4, 2, 1, TERMS>(a, s);
+  } else if (p.tile == TILE_256x192) {
+    if constexpr (T16 && (TERMS == 3 || (TAPS == 9 && TERMS == 2))) return launch_s2<TAPS, TH, TW, 4, 2, 2, 3, 3, 1, TERMS>(a, s);
+  } else if (p.tile == TILE_256x128 && p.pool) {
+    if constexpr (TAPS == 9 && T16) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS, false, false, true>(a, s);
+  } else if (p.tile == TILE_256x128) {
+    if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS>(a, s);
+  } else if (p.tile == TILE_128x128) {
+    if constexpr (!ROWS256) return launch_s2<TAPS, TH, TW, 2, 2, 2, 2, 3, 1, TERMS>(a, s);
+  } else if (p.tile == TILE_256x64) {
+    if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 1, RG, TPS, TERMS>(a, s);
+  } else if constexpr (!T16) {  // 128-row tiles
+    if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS>(a, s);
+    if (p.tile == TILE_128x32 && p.finish == SPLIT_IN_LAUNCH) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS, false, true>(a, s);
+    if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS>(a, s);
+  }
+  return no_form(p);
 }
-
-static bool s2_exact(const ConvArgs& a) { return a.H % 4 == 0 && a.W % 4 == 0; }
 
 template <int TAPS, int TERMS>
-int dispatch_s2_tile(const ConvArgs& a, hipStream_t s) {
-  if (a.H % 16 == 0 && a.W % 16 == 0) return dispatch_s2_bn<TAPS, 16, 16, 8, 16, TERMS>(a, s);
-  if (a.H % 8 == 0 && a.W % 16 == 0) return dispatch_s2_bn<TAPS, 8, 16, 8, 16, TERMS>(a, s);
-  if (a.H % 8 == 0 && a.W % 8 == 0) return dispatch_s2_bn<TAPS, 8, 8, 8, 8, TERMS>(a, s);
-  if (a.H % 4 == 0 && a.W % 8 == 0) return dispatch_s2_bn<TAPS, 4, 8, 4, 8, TERMS>(a, s);
-  if (a.H % 4 == 0 && a.W % 4 == 0) return dispatch_s2_bn<TAPS, 4, 4, 4, 4, TERMS>(a, s);
-  DRM_REQUIRE(a.w_img_stride_f4 == 0 && a.ksplit <= 1, "per-image weights / split-K need a map that is a whole number of tiles");
-  if constexpr (TERMS == 0) {
-    set_error("fp32 mode: ragged maps run on conv_igemm_kernel");
-    return DRM_ERR_INVALID;
-  } else {
-  static const int fam[3][2] = {{8, 16}, {8, 8}, {4, 4}};
-  switch (conv_tile_family(a.H, a.W, fam, 3)) {
-    case 0: return dispatch_s2_ragged<TAPS, 8, 16, TERMS>(a, s);
-    case 1: return dispatch_s2_ragged<TAPS, 8, 8, TERMS>(a, s);
-    default: return dispatch_s2_ragged<TAPS, 4, 4, TERMS>(a, s);
-  }
-  }
+int dispatch_s2(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.th == 16 && p.tw == 16) return launch_s2_tile<TAPS, 16, 16, TERMS>(a, p, s);
+  if (p.th == 8 && p.tw == 16) return launch_s2_tile<TAPS, 8, 16, TERMS>(a, p, s);
+  if (p.th == 8 && p.tw == 8) return launch_s2_tile<TAPS, 8, 8, TERMS>(a, p, s);
+  if (p.th == 4 && p.tw == 8) return launch_s2_tile<TAPS, 4, 8, TERMS>(a, p, s);
+  if (p.th == 4 && p.tw == 4) return launch_s2_tile<TAPS, 4, 4, TERMS>(a, p, s);
+  return no_form(p);
 }
 
 // Build units: this file is compiled once per (TAPS, TERMS) pair with -DDRM_S2_UNIT=<10 * TAPS + TERMS> (the kernel instantiations of that pair,
 // in parallel: drmnet_amd/build.py) and once without (the host-side rest below, which only declares them).
 #ifdef DRM_S2_UNIT
-template int dispatch_s2_tile<DRM_S2_UNIT / 10, DRM_S2_UNIT % 10>(const ConvArgs&, hipStream_t);
+template int dispatch_s2<DRM_S2_UNIT / 10, DRM_S2_UNIT % 10>(const ConvArgs&, const ConvPlan&, hipStream_t);
 #else
-extern template int dispatch_s2_tile<9, 0>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<1, 0>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<9, 1>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<1, 1>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<9, 4>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<1, 4>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<9, 2>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<9, 3>(const ConvArgs&, hipStream_t);
-extern template int dispatch_s2_tile<1, 3>(const ConvArgs&, hipStream_t);
+extern template int dispatch_s2<9, 0>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<1, 0>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<9, 1>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<1, 1>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<9, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<1, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<9, 2>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<9, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<1, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
+int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s);  // (conv.hip)
 
-// Who finishes a split-K conv.  Maps of at least 128 pixels: the launch itself -- the workgroup that arrives last at an output tile sums the slabs in
-// slab order and runs the full epilogue (SK instantiation; the hand-off costs ~10 us whatever the shape).  Smaller maps: splitk_reduce_small_kernel
-// in a second launch (5.8 us on the 4x8 maps of the batch-32 step, where the fused finish measured 1 % slower on the whole step; at batch 1 the maps
-// of 128 .. 1024 pixels are where the second launch cost 12 .. 22 us: 6.64 -> 6.0 ms per step with the fused finish).
-// ([r4] with the agent-scope hand-off the fused finish was tried on the smaller maps too: batch 1 4.79 vs 4.755 ms, batch 32 759 vs 763 steps/s -- the second launch stays)
-// mirrors dispatch_s2_tile / dispatch_s2_bn: a 3x3 launch on 16 x 16 pixel tiles that takes the 128-channel-wide 8-wave variant without split-K
-bool conv_split_pool_applicable(const ConvArgs& a) {
-  if (a.taps != 9 || a.out_nchw || a.w_img_stride_f4 != 0 || a.H % 16 != 0 || a.W % 16 != 0 || a.Cout % 128 != 0 || (a.C0 + a.C1) % 32 != 0 || a.C0 % 32 != 0) return false;
-  const long long rows = (long long)a.N * a.H * a.W;
+constexpr long long S2_MIN_WIDE_TILES = 176;  // 256 x 128 tiles are used from this many workgroups on (of 256 CUs)
+// On sparse launches (few images) the conv finalises its input's GroupNorm tables in its own prologue (ConvArgs::gnf, gn_fold.h) and no
+// gn_finalize launch is made: at batch 1 a ~5 us launch per GroupNorm was 111 launches = a tenth of the DRMNet step.
+constexpr int GN_FOLD_MAX_N = 4;
+
+bool conv_split_weights(int precision, int cin) { return precision != PREC_FP32 && cin % 32 == 0; }
+
+ConvPlan plan_conv(const ConvArgs& a, int precision, bool want_pool, bool gn_foldable) {
+  ConvPlan p;
+  const int Ctot = a.C0 + a.C1, hw = a.H * a.W;
+  const bool split = precision != PREC_FP32, chunks = Ctot % 32 == 0 && a.C0 % 32 == 0;
+  const long long rows = (long long)a.N * hw;
   auto wgs = [&](int bm, int bn) { return ((rows + bm - 1) / bm) * (a.Cout / bn); };
-  if ((a.terms == 3 || a.terms == 2) && a.Cout % 192 == 0 && wgs(256, 192) >= 512) return false;  // (the 192-wide variant goes first there)
-  return wgs(256, 128) >= S2_MIN_WIDE_TILES;
-}
-
-bool conv_split_fused_finish(const ConvArgs& a) { return a.H * a.W >= 128 && conv_split_wide_ksplit(a) <= 1; }
-
-// Split-K factor for a launch (1 = none).  Mirrors dispatch_s2_bn: only the 128-row x 32-channel fallback tiles qualify, when
-// their grid leaves most of the 256 CUs idle and the reduction is long.
-int conv_split_ksplit(const ConvArgs& a) {
-  if (a.out_nchw || !s2_exact(a) || a.w_img_stride_f4 != 0) return 1;
-  if (const int wide = conv_split_wide_ksplit(a); wide > 1) return wide;
-  // (1x1 convs too [r3]: on the deep, small maps a K = 768 .. 1536 reduction is 24 .. 48 serial one-chunk steps of a handful of workgroups --
-  //  30 us at batch 1 whatever the map; split, they are ~5 chunks each plus the small-map reduction)
-  const long long rows = (long long)a.N * a.H * a.W;
-  auto wgs = [&](int bm, int bn) { return ((rows + bm - 1) / bm) * (a.Cout / bn); };
-  if (a.Cout % 128 == 0 && wgs(256, 128) >= S2_MIN_WIDE_TILES) return 1;
-  if (a.Cout % 64 == 0 && wgs(256, 64) >= 256) return 1;
-  if (a.Cout % 64 == 0 && wgs(128, 64) >= 256) return 1;
-  const long long tiles = wgs(128, 32);
-  const int nch = (a.C0 + a.C1) / 32;
+  if (a.w_img_stride_f4 != 0) {
+    // per-image weights (the attention GEMMs, attn.hip): split modes, one image per tile (maps of whole 16 x 16 tiles), 128-channel multiples
+    if (!split || a.H % 16 != 0 || a.W % 16 != 0 || a.Cout % 128 != 0 || Ctot % 128 != 0) return p;
+  }
+  // The pipeline kernel (LDS-DMA weight ring, persistent tiles, fused output statistics) takes every conv whose channel counts are whole 32-chunks:
+  // the split modes on any map, exact fp32 (TERMS = 0) on maps that are a whole number of 4x4 tiles.  The rest -- odd channel counts of the
+  // per-module entry points, ragged maps in fp32 -- runs on conv_igemm_kernel (conv.hip): 128-row tiles, edge tiles masked.
+  if (!chunks || (!split && (a.H % 4 != 0 || a.W % 4 != 0))) {
+    static const int fam[4][2] = {{8, 16}, {8, 8}, {4, 8}, {4, 4}};
+    const int f = conv_tile_family(a.H, a.W, fam, 4);
+    p.kernel = CONV_IGEMM;
+    p.th = fam[f][0]; p.tw = fam[f][1];
+    p.tile = a.Cout % 128 == 0 ? TILE_128x128 : (a.Cout % 64 == 0 ? TILE_128x64 : TILE_128x32);
+    p.kc = chunks ? 32 : 8;
+    return p;
+  }
+  p.kernel = CONV_PIPELINE;
+  p.terms = (precision == PREC_F16MX && a.mx_site) ? 2 : precision_terms(precision);
+  p.gn_fold = gn_foldable && a.N <= GN_FOLD_MAX_N;
+  // pixel-tile family: 256-row tiles of TH x TW pixels per image, 128-row tiles of TH4 x TW4
+  static const int whole[5][4] = {{16, 16, 8, 16}, {8, 16, 8, 16}, {8, 8, 8, 8}, {4, 8, 4, 8}, {4, 4, 4, 4}};
+  const int* fw = nullptr;
+  for (const auto& f : whole)
+    if (!fw && a.H % f[0] == 0 && a.W % f[1] == 0) fw = f;
+  if (!fw) {
+    // Maps that are not a whole number of tiles (any H, W the reference accepts other than the shipped sizes): 128-row tiles on 4 waves,
+    // 64 or 32 channels wide, in three pixel-tile families, edge tiles masked (no split-K, no per-image weights)
+    static const int fam[3][2] = {{8, 16}, {8, 8}, {4, 4}};
+    const int f = conv_tile_family(a.H, a.W, fam, 3);
+    p.th = fam[f][0]; p.tw = fam[f][1];
+    p.ragged = true;
+    p.tile = a.Cout % 64 == 0 ? TILE_128x64 : TILE_128x32;
+    return p;
+  }
+  // Split-K.  Deep levels (maps of at most 128 pixels: the 8x16 and 4x8 levels of a batch-32 step): too few GEMM rows for the 128-channel-wide
+  // tiles to fill the chip, and the narrow tiles that do fill it re-stage (GroupNorm + SiLU + split) every activation tile once per 32 or 64 output
+  // channels.  Split-K over the WIDE tiles instead: every split writes its slab, splitk_reduce_small_kernel finishes (two-launch form).
+  // (1x1 convs of these levels on the same form measured neutral: 5.86 -> 5.54 ms of 1x1 time per step, given back by the reduction launches)
+  int wide = 1;
+  if (a.taps == 9 && !a.out_nchw && a.w_img_stride_f4 == 0 && a.Cout % 128 == 0 && hw <= 128 &&
+      ((a.H % 8 == 0 && a.W % 16 == 0) || (a.H % 4 == 0 && a.W % 8 == 0)) && rows >= 1024) {  // (sparse launches keep the narrow tiles: a batch-1 step would fill half a wide tile)
+    const int bm = (a.taps == 1 || (a.H % 8 == 0 && a.W % 16 == 0)) ? 256 : 128;  // (3x3 on 4x8 maps: 128-pixel x 128-channel tiles on 4 waves)
+    const long long tiles = ((rows + bm - 1) / bm) * (a.Cout / 128);
+    if (tiles < S2_MIN_WIDE_TILES) wide = (int)std::max<long long>(std::min<long long>(std::min<long long>(8, Ctot / 32 / 2), std::max<long long>(1, 256 / tiles)), 1);
+  }
+  // Deep U-Net levels (4x8 .. 8x16 maps) have few GEMM rows: with 256x128 tiles they launch far fewer workgroups than the chip has CUs.  Shrink
+  // the tile (128 rows, then 64 / 32 channels) until the grid covers the 256 CUs.
+  const bool t16 = fw[0] == 16 && fw[1] == 16, rows256 = a.taps == 1 || fw[0] >= 8;
+  auto tile = [&](ConvTile t, bool r256) {
+    p.tile = t;
+    p.th = r256 ? fw[0] : fw[2];
+    p.tw = r256 ? fw[1] : fw[3];
+  };
+  if (a.taps == 1 && t16 && p.terms == 3 && a.Cout % 256 == 0 && wgs(256, 256) >= 512) {
+    // 1x1 on big maps with Cout a multiple of 256: 256 output channels per tile (64 x 128 per wave, weight ring of 2).  The 1x1 form pays
+    // its activation staging and its barrier once per 24 MFMAs of a wave; here per 48 (the 64x128-map skip convs: 11-15 % faster).  The
+    // 1x1 kernel has the registers for it (176 -> 256 VGPRs, 2 spilled); the 3x3 kernel does not.
+    tile(TILE_256x256, true);
+  } else if (t16 && (p.terms == 3 || (a.taps == 9 && p.terms == 2)) && a.Cout % 192 == 0 && wgs(256, 192) >= 512) {
+    // 192 output channels per tile (64 x 96 per wave, one-tap weight ring of 3).  1x1 for Cout = 384 / 1152 / 1536 ...: qkv 512->1536 @16x32 and
+    // the 32x64-map skip convs 12-16 % faster.  3x3 (f16x3, f16mx; the three-tap groups would not fit next to the halo tile) for Cout = 384 on
+    // big maps: 12 fragment reads per 18 MFMA products instead of 8 per 12 -- 5 % faster there.  Fits since the scalar-base DMA addressing took
+    // the kernel from 256 to 207 VGPRs.
+    tile(TILE_256x192, true);
+  } else if (a.Cout % 128 == 0 && (wgs(256, 128) >= S2_MIN_WIDE_TILES || wide > 1)) {
+    // (one round of 128-wide tiles on >= 176 of the 256 CUs beats two rounds of the less efficient 64-wide ones: qkv 640->1920 @8x16 27 %,
+    //  512->1536 @8x16 24 %, 3x3 384->384 @16x32 12 % faster than with the old "fill every CU" rule)
+    tile(rows256 ? TILE_256x128 : TILE_128x128, rows256);
+    // the Downsample behind a 3x3 conv on 16 x 16 pixel tiles, from its epilogue (split modes)
+    p.pool = want_pool && split && a.taps == 9 && t16 && !a.out_nchw;
+  } else if (a.Cout % 64 == 0 && wgs(256, 64) >= 256) {
+    tile(rows256 ? TILE_256x64 : TILE_128x64, rows256);
+  } else if (a.Cout % 64 == 0 && wgs(128, 64) >= 256) {
+    // ([r4] 128 x 32 tiles from 512 workgroups on -- two workgroups per CU on the batch-1 step's top level instead of one: 4.74 vs 4.755 ms there,
+    //  780 vs 800 steps/s at batch 32 -- not adopted: co-resident workgroups do not hide what a sparse launch waits for)
+    tile(TILE_128x64, false);
+  } else {
+    // ([r4] a ring of 4 three-tap groups on these sparse-launch tiles: 5.31 vs 5.38 ms on the batch-1 step, later 5.06 vs 5.08 -- not adopted)
+    tile(TILE_128x32, false);
+  }
+  // Split-K factor: the wide split above, else only the 128-row x 32-channel tiles qualify, when their grid leaves most of the 256 CUs idle and
+  // the reduction is long.  (1x1 convs too [r3]: on the deep, small maps a K = 768 .. 1536 reduction is 24 .. 48 serial one-chunk steps of a
+  // handful of workgroups -- 30 us at batch 1 whatever the map; split, they are ~5 chunks each plus the small-map reduction.)
   // ([r4] with the cheaper hand-off: splits of >= 2 chunks up to 1024 workgroups measured 5.13 vs 5.08 ms on the batch-1 step -- not adopted)
-  const long long ks = std::min<long long>(std::min<long long>(8, nch / 4), 640 / std::max<long long>(tiles, 1));
-  return (int)std::max<long long>(ks, 1);
+  p.ksplit = wide;
+  if (wide == 1 && p.tile == TILE_128x32 && !a.out_nchw && a.w_img_stride_f4 == 0)
+    p.ksplit = (int)std::max<long long>(std::min<long long>(std::min<long long>(8, Ctot / 32 / 4), 640 / std::max<long long>(wgs(128, 32), 1)), 1);
+  if (p.ksplit > 1) {
+    // Who finishes a split-K conv.  Maps of at least 128 pixels: the launch itself -- the workgroup that arrives last at an output tile sums the
+    // slabs in slab order and runs the full epilogue (SK instantiation; the hand-off costs ~10 us whatever the shape).  Smaller maps:
+    // splitk_reduce_small_kernel in a second launch (5.8 us on the 4x8 maps of the batch-32 step, where the fused finish measured 1 % slower on
+    // the whole step; at batch 1 the maps of 128 .. 1024 pixels are where the second launch cost 12 .. 22 us: 6.64 -> 6.0 ms per step with the
+    // fused finish).  ([r4] with the agent-scope hand-off the fused finish was tried on the smaller maps too: batch 1 4.79 vs 4.755 ms, batch 32
+    // 759 vs 763 steps/s -- the second launch stays)
+    p.finish = (hw >= 128 && wide == 1) ? SPLIT_IN_LAUNCH : SPLIT_REDUCE;
+    // one arrival counter per output tile (128 GEMM rows x 32 channels; an upper bound over the pixel-tile families)
+    if (p.finish == SPLIT_IN_LAUNCH) p.tickets = ((size_t)a.N * hw / 128 + (size_t)hw / 16 + 2) * (size_t)(a.Cout / 32);
+  }
+  return p;
 }
 
-// Second launch of a split-K conv on the smallest maps (H * W < 128: conv_split_fused_finish says which): out = sum of the slabs in slab order (already
+// Second launch of a split-K conv on the smallest maps (H * W < 128, or the wide split: plan_conv says which): out = sum of the slabs in slab order (already
 // un-scaled by their launch) + bias (+ emb[n] + residual), and the per-(image, channel) sums / sums of squares of the result for the next GroupNorm.
 // The whole image sits in ONE block per 16 channel quads -- 16 quads x 16 pixel lanes, the lanes of a channel fold in LDS in lane order and the
 // block's sums ARE the statistics: no partial table, no ticket, no fence, no atomics; 5.8 us at batch 32 on the 4x8 maps.  Larger maps finish inside
@@ -1626,7 +1647,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* 
   }
 }
 
-int launch_splitk_reduce(const ConvArgs& a, const float* partial, hipStream_t s) {
+static int launch_splitk_reduce(const ConvArgs& a, const float* partial, hipStream_t s) {
   const int HW = a.H * a.W;
   DRM_REQUIRE(a.ksplit > 1 && a.split_stride % 4 == 0 && a.Cout % 4 == 0 && HW <= 256, "split-K reduction arguments (maps of more than 256 pixels finish inside the conv launch)");
   hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((a.Cout / 4 + 15) / 16, a.N), dim3(256), 0, s, reinterpret_cast<const float4*>(partial),
@@ -1635,26 +1656,34 @@ int launch_splitk_reduce(const ConvArgs& a, const float* partial, hipStream_t s)
   return DRM_OK;
 }
 
-int launch_conv_split2(const ConvArgs& a, hipStream_t s) {
-  if (a.terms == 0) {  // exact fp32 operands on the same pipeline (DRM_PREC_FP32; maps that are a whole number of tiles)
-    DRM_REQUIRE(a.H % 4 == 0 && a.W % 4 == 0, "fp32 mode: maps that are not a whole number of 4x4 tiles run on conv_igemm_kernel");
-    if (a.taps == 9) return dispatch_s2_tile<9, 0>(a, s);
-    return dispatch_s2_tile<1, 0>(a, s);
-  }
-  if (a.terms == 1) {  // plain fp16 operands, one MFMA per product (DRM_PREC_F16)
-    if (a.taps == 9) return dispatch_s2_tile<9, 1>(a, s);
-    return dispatch_s2_tile<1, 1>(a, s);
-  }
-  if (a.terms == 4) {  // plain bf16 operands, one MFMA per product (DRM_PREC_BF16)
-    if (a.taps == 9) return dispatch_s2_tile<9, 4>(a, s);
-    return dispatch_s2_tile<1, 4>(a, s);
-  }
-  if (a.terms == 2) {  // fp16 hi*hi + block-scaled fp8 cross terms (DRM_PREC_F16MX): the GroupNorm-fed 3x3 convs only
-    DRM_REQUIRE(a.taps == 9 && a.gn_scale && !a.in_inv && a.w_img_stride_f4 == 0, "f16mx: 3x3 convs on a GroupNorm-ed input only");
-    return dispatch_s2_tile<9, 2>(a, s);
-  }
-  if (a.taps == 9) return dispatch_s2_tile<9, 3>(a, s);
-  return dispatch_s2_tile<1, 3>(a, s);
+int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  DRM_REQUIRE(a.taps == 9 || a.taps == 1, "conv taps must be 9 or 1");
+  DRM_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv shape");
+  DRM_REQUIRE(!a.up0 || (a.H % 2 == 0 && a.W % 2 == 0), "upsampled source needs even output size");
+  DRM_REQUIRE(a.ksplit == p.ksplit && (p.ksplit == 1 || a.split_ws), "split-K launch without its slab workspace");
+  if (p.kernel == CONV_IGEMM) return launch_igemm(a, p, s);
+  DRM_REQUIRE(p.kernel == CONV_PIPELINE, "no conv kernel takes this shape (per-image weights: split modes, maps of whole 16x16 tiles, 128-channel multiples)");
+  DRM_REQUIRE(a.Cout % 32 == 0 && (a.C0 + a.C1) % 32 == 0 && a.C0 % 32 == 0, "split conv needs channels % 32 == 0");
+  DRM_REQUIRE(a.terms == p.terms, "ConvArgs::terms differs from the plan");
+  DRM_REQUIRE(p.terms != 2 || (a.taps == 9 && a.gn_scale && !a.in_inv && a.w_img_stride_f4 == 0), "f16mx: 3x3 convs on a GroupNorm-ed input only");
+  auto run = [&](const ConvArgs& x) -> int {
+    switch (p.terms) {
+      case 0: return a.taps == 9 ? dispatch_s2<9, 0>(x, p, s) : dispatch_s2<1, 0>(x, p, s);  // exact fp32 operands (DRM_PREC_FP32)
+      case 1: return a.taps == 9 ? dispatch_s2<9, 1>(x, p, s) : dispatch_s2<1, 1>(x, p, s);  // plain fp16 operands, one MFMA per product (DRM_PREC_F16)
+      case 2: return dispatch_s2<9, 2>(x, p, s);  // fp16 hi*hi + block-scaled fp8 cross terms (DRM_PREC_F16MX): the GroupNorm-fed 3x3 convs only
+      case 3: return a.taps == 9 ? dispatch_s2<9, 3>(x, p, s) : dispatch_s2<1, 3>(x, p, s);  // fp16 hi / lo, three MFMAs per product
+      case 4: return a.taps == 9 ? dispatch_s2<9, 4>(x, p, s) : dispatch_s2<1, 4>(x, p, s);  // plain bf16 operands (DRM_PREC_BF16)
+    }
+    return no_form(p);
+  };
+  if (p.finish != SPLIT_REDUCE) return run(a);
+  // smallest maps: every split writes its own slab, a fixed-order second launch sums them and applies bias / emb / residual / statistics
+  ConvArgs part = a;
+  part.out = a.split_ws;
+  part.split_ws = nullptr;
+  part.bias = nullptr; part.emb = nullptr; part.res = nullptr; part.stat_out = nullptr;
+  DRM_TRY(run(part));
+  return launch_splitk_reduce(a, a.split_ws, s);
 }
 #endif  // DRM_S2_UNIT
 

@@ -142,27 +142,23 @@ struct Ctx {
   int precision = PREC_FP32;
   bool dry() const { return ar->dry; }
   bool split() const { return precision == PREC_F16X3 || precision == PREC_F16 || precision == PREC_F16MX || precision == PREC_BF16; }
-  // ConvArgs::terms of the pipeline kernel (PREC_F16MX: 3, and 2 on its mx_site launches)
-  int terms() const { return precision == PREC_F16 ? 1 : (precision == PREC_BF16 ? 4 : (precision == PREC_FP32 ? 0 : 3)); }
-  bool mx() const { return precision == PREC_F16MX; }
+  int terms() const { return precision_terms(precision); }
 };
 Act new_act(Ctx& c, int C, int H, int W);
 int ensure_moments(Ctx& c, Act& a);
-// pool (optional): the Downsample that follows this block -- when the out_layers conv can write the 2x2 average pool of `out` and its statistics from
-// its own epilogue (conv_split_pool_applicable) it does, and *pooled is set; otherwise the caller runs launch_avgpool2
+// pool (optional): the Downsample that follows this block -- when the out_layers conv's plan writes the 2x2 average pool of `out` and its statistics
+// from its own epilogue (ConvPlan::pool) it does, and *pooled is set; otherwise the caller runs launch_avgpool2
 int run_resblock(Ctx& c, const float* wbuf, const ResLayer& r, Act& x0, Act* x1, const float* emb_all, int emb_stride, Act& out, Act* pool = nullptr,
                  bool* pooled = nullptr);
 int run_attention(Ctx& c, const float* wbuf, const AttnLayer& a, Act& x, Act& out);
-// dispatches to the fp32 or the split-precision conv kernel; scale_off = the conv's pre-scaling slot in wbuf
+// launches a planned conv; scale_off = the conv's pre-scaling slot in wbuf
 // `stats_for` (optional): the activation this conv completes -- its GroupNorm statistics are then accumulated in the epilogue
-// `splitk_ws`: the partial-slab workspace plan_splitk returned for this launch (null = no split-K)
-int run_conv(Ctx& c, ConvArgs& a, const float* wbuf, size_t scale_off, Act* stats_for = nullptr, float* splitk_ws = nullptr);
-float* plan_splitk(Ctx& c, ConvArgs& a);  // sets a.ksplit / a.split_stride from the shape fields of `a`; allocates the slabs
+int run_conv(Ctx& c, ConvArgs& a, const ConvPlan& p, const float* wbuf, size_t scale_off, Act* stats_for = nullptr);
 // split-precision range guard for an un-normalised conv input (see engine.hip)
-int raw_input_guard(Ctx& c, ConvArgs& a, Act* x0, int lo0, int hi0, Act* x1, const unsigned* absmax_bits, int Ctab, int absmax_parts = 1);
+int raw_input_guard(Ctx& c, ConvArgs& a, const ConvPlan& p, Act* x0, int lo0, int hi0, Act* x1, const unsigned* absmax_bits, int Ctab, int absmax_parts = 1);
 // ensure_moments on both sources + gn_finalize into (scale, shift)
 // guard_for (optional): a split conv reading (x0 | x1) un-normalised gets its range-guard tables from the same launch
 int gn_params(Ctx& c, Act& x0, Act* x1, const float* gamma, const float* beta, float* scale, float* shift, ConvArgs* guard_for = nullptr,
-              ConvArgs* fold_into = nullptr);  // fold_into: the consumer conv finalises the tables itself on sparse launches (ConvArgs::gnf)
+              ConvArgs* fold_into = nullptr);  // fold_into: the consumer conv finalises the tables itself (ConvPlan::gn_fold)
 
 }  // namespace drm

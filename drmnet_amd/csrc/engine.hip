@@ -231,12 +231,10 @@ int UNet::build(const drm_unet_desc& d) {
   }
   scratch_off = wbuf_floats;
   wbuf_floats += 64;
-#ifndef DRM_NO_DIRECT_ENDS  // (A/B builds: tools/build_variant.sh)
   if (stem_direct_applicable(d.in_channels, mc)) {
     stem_direct_w = (long long)wbuf_floats;
     wbuf_floats += (stem_weight_floats() + 63) & ~size_t(63);
   }
-#endif
   // fused embedding projection
   embcat_w = wbuf_floats;
   wbuf_floats += ((size_t)emb_total * emb_dim + 63) & ~size_t(63);
@@ -261,7 +259,7 @@ int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
     DRM_REQUIRE(ptrs[i] != nullptr, "null parameter pointer for " + p.name);
     if (p.kind == PK_COPY) {
       DRM_HIP_CHECK(hipMemcpyAsync(wbuf + p.dst, ptrs[i], p.count * sizeof(float), hipMemcpyDeviceToDevice, s));
-    } else if (precision != PREC_FP32 && p.cinp % 32 == 0) {  // both fp16 modes use the pre-split, pre-scaled image
+    } else if (conv_split_weights(precision, p.cinp)) {
       DRM_TRY(launch_pack_conv_weight_split(ptrs[i], wbuf + p.dst, wbuf + p.scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), p.cout,
                                             p.cin, p.taps, p.coutp, p.cinp, s, precision == PREC_F16MX && p.mx_site, precision == PREC_BF16));
     } else {
@@ -296,73 +294,40 @@ int ensure_moments(Ctx& c, Act& a) {
   return DRM_OK;
 }
 
-// split-K factor the launch will use and the partial-slab workspace it then needs (allocated in sizing and real passes alike)
-// The pipeline kernel (conv_split2.hip: LDS-DMA weight ring, persistent tiles, fused output statistics) takes every conv whose channel counts
-// are whole 32-chunks: the two fp16 modes on any map, exact fp32 (TERMS = 0) on maps that are a whole number of 4x4 tiles.  The rest -- odd
-// channel counts of the per-module entry points, ragged maps in fp32 -- runs on conv_igemm_kernel (conv.hip).
-static bool on_pipeline(const Ctx& c, const ConvArgs& a) {
-  return (a.C0 + a.C1) % 32 == 0 && a.C0 % 32 == 0 && (c.split() || (a.H % 4 == 0 && a.W % 4 == 0));
-}
-
-float* plan_splitk(Ctx& c, ConvArgs& a) {
-  a.ksplit = 1;
-  if (!on_pipeline(c, a)) return nullptr;
-  a.ksplit = conv_split_ksplit(a);
-  if (a.ksplit <= 1) return nullptr;
+// a.ksplit of the plan and, for a split-K plan, its workspace (allocated in sizing and real passes alike): a.split_stride, the slabs at
+// a.split_ws and, for the in-launch finish, the zeroed arrival counters at a.tile_ticket -- from the pass's statistics pool, else zeroed here
+static void splitk_workspace(Ctx& c, ConvArgs& a, const ConvPlan& p) {
+  a.ksplit = p.ksplit;
+  if (p.ksplit <= 1) return;
   a.split_stride = (size_t)a.N * a.H * a.W * a.Cout;
-  a.tile_ticket = nullptr;
-  if (conv_split_fused_finish(a)) {
-    // one arrival counter per output tile (128 GEMM rows x 32 channels; an upper bound over the pixel-tile families), zeroed: from the pass's
-    // statistics pool, else here -- the workgroup that arrives last at a tile sums the slabs and runs the full epilogue (conv_split2.hip)
-    const size_t hw = (size_t)a.H * a.W;
-    const size_t tickets = ((size_t)a.N * hw / 128 + hw / 16 + 2) * (size_t)(a.Cout / 32);
+  if (p.finish == SPLIT_IN_LAUNCH) {
     bool zeroed = false;
-    a.tile_ticket = reinterpret_cast<unsigned*>(c.ar->alloc_stats(tickets * sizeof(unsigned), &zeroed));
-    if (!zeroed && !c.dry()) (void)hipMemsetAsync(a.tile_ticket, 0, tickets * sizeof(unsigned), c.s);
+    a.tile_ticket = reinterpret_cast<unsigned*>(c.ar->alloc_stats(p.tickets * sizeof(unsigned), &zeroed));
+    if (!zeroed && !c.dry()) (void)hipMemsetAsync(a.tile_ticket, 0, p.tickets * sizeof(unsigned), c.s);
   }
-  return c.ar->alloc<float>(a.split_stride * a.ksplit);
+  a.split_ws = c.ar->alloc<float>(a.split_stride * a.ksplit);
 }
 
-int run_conv(Ctx& c, ConvArgs& a, const float* Wb, size_t scale_off, Act* stats_for, float* splitk_ws) {
-  if (on_pipeline(c, a)) {
+int run_conv(Ctx& c, ConvArgs& a, const ConvPlan& p, const float* Wb, size_t scale_off, Act* stats_for) {
+  if (p.kernel == CONV_PIPELINE) {
     a.w_inv_scale = c.split() ? Wb + scale_off + 1 : nullptr;  // (fp32 weights are packed unscaled)
-    a.terms = (c.mx() && a.mx_site) ? 2 : c.terms();
-    if (!splitk_ws) {
-      a.ksplit = 1;
-      a.split_stride = 0;
-    }
-    double2* stat = nullptr;
-    if (stats_for && !a.out_nchw && conv_split_fuses_stats()) {
+    a.terms = p.terms;
+    if (stats_for && !a.out_nchw) {  // (the pipeline accumulates the output's statistics in its epilogue)
       if (!stats_for->mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(stats_for->mom, 0, (size_t)c.N * stats_for->C * sizeof(double2), c.s));
-      stat = stats_for->mom;
+      a.stat_out = stats_for->mom;
       stats_for->mom_valid = true;
       stats_for->mom_sums = true;
     }
-    if (a.ksplit > 1 && !a.tile_ticket) {
-      // smallest maps: every split writes its own slab, a fixed-order second launch sums them and applies bias / emb / residual / statistics
-      ConvArgs part = a;
-      part.out = splitk_ws;
-      part.bias = nullptr; part.emb = nullptr; part.res = nullptr; part.stat_out = nullptr;
-      DRM_TRY(launch_conv_split(part, c.s));
-      ConvArgs red = a;
-      red.stat_out = stat;
-      return launch_splitk_reduce(red, splitk_ws, c.s);
-    }
-    // (other split-K launches: the workgroup that arrives last at an output tile sums the slabs in slab order and applies bias / emb /
-    //  residual / statistics itself -- one launch, no atomics on the data path)
-    a.split_ws = a.ksplit > 1 ? splitk_ws : nullptr;
-    a.stat_out = stat;
-    return launch_conv_split(a, c.s);
   }
-  return launch_conv(a, c.s);
+  return launch_conv(a, p, c.s);
 }
 
 // Split-precision convs on an UN-normalised input (skip_connection, proj_out, stem): stage it through a per-image power of two
 // derived from a rigorous bound of max |x| (gn.hip act_pow2_scale_kernel) so nothing saturates or underflows fp16; the factor rides
 // on the (scale, shift) tables the staging path applies anyway and is undone per image in the epilogue.  Bound source: the
 // per-channel sum-of-squares tables of x0 (channels [lo0, hi0)) and x1, or an absmax word per image.  No-op in fp32 mode.
-int raw_input_guard(Ctx& c, ConvArgs& a, Act* x0, int lo0, int hi0, Act* x1, const unsigned* absmax_bits, int Ctab, int absmax_parts) {
-  if (!c.split() || Ctab % 32 != 0) return DRM_OK;  // (channel counts that are not whole 32-chunks run on the exact-fp32 kernel)
+int raw_input_guard(Ctx& c, ConvArgs& a, const ConvPlan& p, Act* x0, int lo0, int hi0, Act* x1, const unsigned* absmax_bits, int Ctab, int absmax_parts) {
+  if (!p.split()) return DRM_OK;
   float* sc = c.ar->alloc<float>((size_t)c.N * Ctab);
   float* sh = c.ar->alloc<float>((size_t)c.N * Ctab);
   float* inv = c.ar->alloc<float>((size_t)c.N);
@@ -378,17 +343,14 @@ int raw_input_guard(Ctx& c, ConvArgs& a, Act* x0, int lo0, int hi0, Act* x1, con
   return DRM_OK;
 }
 
-// fold_into: the split-pipeline conv that stages through (scale, shift) -- its shape fields already set.  On sparse launches (few images) that
-// launch finalises the tables in its own prologue (ConvArgs::gnf, gn_fold.h) and no gn_finalize launch is made: at batch 1 a ~5 us launch per
-// GroupNorm was 111 launches = a tenth of the DRMNet step.
-constexpr int GN_FOLD_MAX_N = 4;
+// fold_into: the conv whose plan finalises the tables in its own prologue (ConvPlan::gn_fold: ConvArgs::gnf, gn_fold.h) -- no gn_finalize launch
 int gn_params(Ctx& c, Act& x0, Act* x1, const float* gamma, const float* beta, float* scale, float* shift, ConvArgs* guard_for, ConvArgs* fold_into) {
   DRM_TRY(ensure_moments(c, x0));
   if (x1) DRM_TRY(ensure_moments(c, *x1));
   // the same launch can also produce the range-guard tables of a split conv that reads (x0 | x1) un-normalised (skip_connection)
   const int Ctot = x0.C + (x1 ? x1->C : 0);
   float *gs = nullptr, *gh = nullptr, *gi = nullptr;
-  if (guard_for && c.split() && Ctot % 32 == 0) {
+  if (guard_for) {
     gs = c.ar->alloc<float>((size_t)c.N * Ctot);
     gh = c.ar->alloc<float>((size_t)c.N * Ctot);
     gi = c.ar->alloc<float>((size_t)c.N);
@@ -399,7 +361,7 @@ int gn_params(Ctx& c, Act& x0, Act* x1, const float* gamma, const float* beta, f
   if (c.dry()) return DRM_OK;
   auto inv = [](const Act& a) { return a.mom_sums ? 1.0 / ((double)(a.H >> a.up) * (a.W >> a.up)) : 1.0; };
   auto cnt = [](const Act& t) { return t.mom_sums ? 0.0 : (double)(t.H >> t.up) * (t.W >> t.up); };
-  if (fold_into && c.N <= GN_FOLD_MAX_N && on_pipeline(c, *fold_into)) {
+  if (fold_into) {
     GnFold& f = fold_into->gnf;
     f.mom0 = x0.mom; f.C0 = x0.C; f.inv0 = inv(x0); f.cnt0 = cnt(x0);
     f.mom1 = x1 ? x1->mom : nullptr; f.C1 = x1 ? x1->C : 0; f.inv1 = x1 ? inv(*x1) : 1.0; f.cnt1 = x1 ? cnt(*x1) : 0.0;
@@ -435,53 +397,50 @@ int run_resblock(Ctx& c, const float* Wb, const ResLayer& r, Act& x0, Act* x1, c
   ConvArgs a;  // in_layers conv: GroupNorm(x0 | x1) -> SiLU -> 3x3 + emb
   a.src0 = x0.p; a.src1 = x1 ? x1->p : nullptr; a.C0 = C0; a.C1 = C1; a.up0 = x0.up;
   a.N = c.N; a.H = H; a.W = W; a.taps = 9; a.Cout = r.cout; a.mx_site = 1;
-  DRM_TRY(gn_params(c, x0, x1, Wb + r.n1_w, Wb + r.n1_b, sc1, sh1, r.has_skip ? &k : nullptr, &a));
-  float* ws1 = plan_splitk(c, a);
+  const ConvPlan pa = plan_conv(a, c.precision, false, true);
+  ConvPlan pk;
+  if (r.has_skip) {
+    k.C0 = C0; k.C1 = C1; k.N = c.N; k.H = H; k.W = W; k.taps = 1; k.Cout = r.cout;
+    pk = plan_conv(k, c.precision);
+  }
+  DRM_TRY(gn_params(c, x0, x1, Wb + r.n1_w, Wb + r.n1_b, sc1, sh1, pk.split() ? &k : nullptr, pa.gn_fold ? &a : nullptr));
+  splitk_workspace(c, a, pa);
   if (!c.dry()) {
     a.gn_scale = sc1; a.gn_shift = sh1; a.silu = 1;
     a.w = Wb + r.c1_w; a.bias = Wb + r.c1_b;
     a.emb = emb_all ? emb_all + r.emb_off : nullptr; a.emb_stride = emb_stride;
     a.out = h1.p;
-    DRM_TRY(run_conv(c, a, Wb, r.c1_s, &h1, ws1));
+    DRM_TRY(run_conv(c, a, pa, Wb, r.c1_s, &h1));
   }
   ConvArgs b;  // out_layers conv: GroupNorm(h1) -> SiLU -> 3x3 + residual
   b.src0 = h1.p; b.C0 = r.cout; b.N = c.N; b.H = H; b.W = W; b.taps = 9; b.Cout = r.cout; b.mx_site = 1;
-  DRM_TRY(gn_params(c, h1, nullptr, Wb + r.n2_w, Wb + r.n2_b, sc2, sh2, nullptr, &b));
-  float* ws2 = plan_splitk(c, b);
-  // the Downsample behind this block, from this conv's epilogue (decided on shapes and mode only: the sizing pass decides the same)
-  b.terms = (c.mx() && b.mx_site) ? 2 : c.terms();
-#ifdef DRM_NO_POOL_FUSION  // (A/B builds)
-  pool = nullptr;
-#endif
-  const bool fuse_pool = pool && b.ksplit <= 1 && c.split() && conv_split_fuses_stats() && conv_split_pool_applicable(b);
-  if (pooled) *pooled = fuse_pool;
-  if (fuse_pool) {
+  const ConvPlan pb = plan_conv(b, c.precision, pool != nullptr, true);  // (the Downsample behind this block, from this conv's epilogue)
+  DRM_TRY(gn_params(c, h1, nullptr, Wb + r.n2_w, Wb + r.n2_b, sc2, sh2, nullptr, pb.gn_fold ? &b : nullptr));
+  splitk_workspace(c, b, pb);
+  if (pooled) *pooled = pb.pool;
+  if (pb.pool) {
     pool->mom_valid = true;
     pool->mom_sums = true;
   }
-  float* wsk = nullptr;
-  if (r.has_skip) {
-    k.C0 = C0; k.C1 = C1; k.N = c.N; k.H = H; k.W = W; k.taps = 1; k.Cout = r.cout;
-    wsk = plan_splitk(c, k);
-  }
+  if (r.has_skip) splitk_workspace(c, k, pk);
   if (!c.dry()) {
     const float* res = x0.p;
     if (r.has_skip) {
       k.src0 = x0.p; k.src1 = x1 ? x1->p : nullptr; k.up0 = x0.up;
       k.w = Wb + r.sk_w; k.bias = Wb + r.sk_b;
       k.out = out.p;
-      DRM_TRY(run_conv(c, k, Wb, r.sk_s, nullptr, wsk));
+      DRM_TRY(run_conv(c, k, pk, Wb, r.sk_s, nullptr));
       res = out.p;
     }
     b.gn_scale = sc2; b.gn_shift = sh2; b.silu = 1;
     b.w = Wb + r.c2_w; b.bias = Wb + r.c2_b;
     b.res = res; b.out = out.p;
-    if (fuse_pool) {
+    if (pb.pool) {
       if (!pool->mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(pool->mom, 0, (size_t)c.N * pool->C * sizeof(double2), c.s));
       b.pool_out = pool->p;
       b.pool_stat = pool->mom;
     }
-    DRM_TRY(run_conv(c, b, Wb, r.c2_s, &out, ws2));
+    DRM_TRY(run_conv(c, b, pb, Wb, r.c2_s, &out));
   }
   c.ar->release(mark);
   return DRM_OK;
@@ -496,7 +455,8 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
   float* sh = c.ar->alloc<float>((size_t)c.N * C);
   ConvArgs a;  // qkv: GroupNorm(x) -> 1x1
   a.C0 = C; a.N = c.N; a.H = H; a.W = W; a.taps = 1; a.Cout = 3 * C;
-  DRM_TRY(gn_params(c, x, nullptr, Wb + l.n_w, Wb + l.n_b, sc, sh, nullptr, &a));
+  const ConvPlan pa = plan_conv(a, c.precision, false, true);
+  DRM_TRY(gn_params(c, x, nullptr, Wb + l.n_w, Wb + l.n_b, sc, sh, nullptr, pa.gn_fold ? &a : nullptr));
   Act qkv_act = new_act(c, 3 * C, H, W);  // its per-channel sums (fused into the qkv conv's epilogue) bound |v| >= |attention output|
   float* qkv = qkv_act.p;
   const bool flash = c.split() && attention_flash_applicable(T, C, c.terms());  // the long-sequence level: one kernel, no score matrix (attn_flash.hip)
@@ -504,33 +464,34 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
   float* att = c.ar->alloc<float>((size_t)c.N * T * C);
   // the T >= 256 levels: both GEMMs on the conv pipeline -- except on sparse launches (the 16x16 level of a batch-1 step: six launches, 51 us, where
   // the short-sequence form -- qk_small, softmax, P v -- takes three and ~25 us)
-  const bool on_conv = flash || (c.split() && attention_conv_applicable(T, C, H, W, c.terms()) && (long long)c.N * T > 1024);
+  const bool on_conv = flash || (attention_conv_planned(H, W, C, c.precision) && (long long)c.N * T > 1024);
   // (the short-sequence form in the split modes: per-image guard factors + proj_out's guard tables, from one attn_scales launch)
   const bool small_guard = !on_conv && c.split() && C % 32 == 0;
   float* aws = flash ? c.ar->alloc<float>(attention_flash_workspace_floats(c.N, T, C))
                : on_conv ? c.ar->alloc<float>(attention_conv_workspace_floats(c.N, T, C))
                : small_guard ? c.ar->alloc<float>(attention_small_workspace_floats(c.N, T, C)) : nullptr;
   ConvArgs p;  // proj_out: 1x1 conv on the raw attention output, a convex combination of v rows: max |att| <= max |v|
-  float* wsq = plan_splitk(c, a);
+  splitk_workspace(c, a, pa);
   p.C0 = C; p.N = c.N; p.H = H; p.W = W; p.taps = 1; p.Cout = C;
-  float* wsp = plan_splitk(c, p);
+  const ConvPlan pp = plan_conv(p, c.precision);
+  splitk_workspace(c, p, pp);
   if (!c.dry()) {
     a.src0 = x.p;
     a.gn_scale = sc; a.gn_shift = sh; a.silu = 0;
     a.w = Wb + l.qkv_w; a.bias = Wb + l.qkv_b; a.out = qkv;
-    DRM_TRY(run_conv(c, a, Wb, l.qkv_s, &qkv_act, wsq));
+    DRM_TRY(run_conv(c, a, pa, Wb, l.qkv_s, &qkv_act));
     if (flash) DRM_TRY(launch_attention_flash(qkv, qkv_act.mom, att, aws, c.N, T, C, c.terms(), c.s, &p));
-    else if (on_conv) DRM_TRY(launch_attention_conv(qkv, qkv_act.mom, scores, att, aws, c.N, H, W, C, c.terms(), c.s, &p));
+    else if (on_conv) DRM_TRY(launch_attention_conv(qkv, qkv_act.mom, scores, att, aws, c.N, H, W, C, c.precision, c.s, &p));
     else DRM_TRY(launch_attention(qkv, scores, att, c.N, T, C, c.s, c.split() ? c.terms() : 0, small_guard ? qkv_act.mom : nullptr, aws, small_guard ? &p : nullptr));
   } else {
     qkv_act.mom_valid = true;  // sizing pass: the table is filled by the conv epilogue, no stand-alone moments launch
     qkv_act.mom_sums = true;
   }
-  if (!on_conv && !small_guard) DRM_TRY(raw_input_guard(c, p, &qkv_act, 2 * C, 3 * C, nullptr, nullptr, C));  // (the attention cores of the split modes hand p its guard tables)
+  if (!on_conv && !small_guard) DRM_TRY(raw_input_guard(c, p, pp, &qkv_act, 2 * C, 3 * C, nullptr, nullptr, C));  // (the attention cores of the split modes hand p its guard tables)
   if (!c.dry()) {
     p.src0 = att;
     p.w = Wb + l.proj_w; p.bias = Wb + l.proj_b; p.res = x.p; p.out = out.p;
-    DRM_TRY(run_conv(c, p, Wb, l.proj_s, &out, wsp));
+    DRM_TRY(run_conv(c, p, pp, Wb, l.proj_s, &out));
   }
   c.ar->release(mark);
   return DRM_OK;
@@ -624,11 +585,12 @@ int UNet::forward(const float* x, int Cx, const float* cond, int Cc, const int32
     h->mom_sums = true;
   } else {
     ConvArgs a;  // stem conv: raw network input
-    DRM_TRY(raw_input_guard(c, a, nullptr, 0, 0, nullptr, amax, in_cp, amax_parts));
+    a.C0 = in_cp; a.N = N; a.H = H; a.W = W; a.taps = 9; a.Cout = mc;
+    const ConvPlan pa = plan_conv(a, precision);
+    DRM_TRY(raw_input_guard(c, a, pa, nullptr, 0, 0, nullptr, amax, in_cp, amax_parts));
     if (!c.dry()) {
-      a.src0 = xin.p; a.C0 = in_cp; a.N = N; a.H = H; a.W = W;
-      a.w = Wb + stem_w; a.bias = Wb + stem_b; a.taps = 9; a.Cout = mc; a.out = h->p; a.cin_real = desc.in_channels;
-      DRM_TRY(run_conv(c, a, Wb, stem_s, h));
+      a.src0 = xin.p; a.w = Wb + stem_w; a.bias = Wb + stem_b; a.out = h->p; a.cin_real = desc.in_channels;
+      DRM_TRY(run_conv(c, a, pa, Wb, stem_s, h));
     }
   }
   hs.push_back(h);
@@ -704,7 +666,7 @@ int UNet::forward(const float* x, int Cx, const float* cond, int Cc, const int32
       a.gn_scale = sc; a.gn_shift = sh; a.silu = 1;
       a.w = Wb + oc_w; a.bias = Wb + oc_b; a.taps = 9; a.Cout = out_cp;
       a.out = out; a.out_nchw = 1; a.cout_valid = desc.out_channels;
-      DRM_TRY(run_conv(c, a, Wb, oc_s));
+      DRM_TRY(run_conv(c, a, plan_conv(a, precision), Wb, oc_s));
     } else {
       DRM_TRY(launch_encoder_head(h->p, sc, sh, Wb + oc_w, Wb + oc_b, out, N, h->H * h->W, final_ch, desc.out_channels, s));
     }

@@ -1,13 +1,14 @@
 """CPU-only checks of the C-ABI library: it loads, exports every symbol include/drmnet_hip.h declares,
 and its parameter table equals the reference state_dict() layout (no compute calls)."""
 import ctypes as C
+import json
 import os
 import re
 
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import GOLD, ROOT
 from drmnet_amd import _lib
 from oracle import unet as ou
 
@@ -85,3 +86,28 @@ def test_workspace_query_rejects_bad_shapes():
 
     m = UNetModel(**ou.TINY_UNET_CFG)
     assert m.workspace_bytes(1, 10, 10) == 0  # 10x10 is not divisible down to a 4x4 map
+
+
+# the dry sizing pass makes every conv's split-K, ticket-table and attention-workspace decision on the CPU: its answers are pinned to the recorded
+# table (tests/golden/workspace_bytes.json) so a change of any of those decisions shows without a GPU
+WS_NETS = [("illnet", ou.ILLNET_CFG, "unet"), ("refnet", ou.REFNET_CFG, "encoder"), ("obsnet", ou.OBSNET_CFG, "unet"), ("tiny_unet", ou.TINY_UNET_CFG, "unet")]
+WS_SIZES = [(1, 128, 128), (32, 128, 256), (128, 128, 256), (2, 96, 160)]
+WS_TINY_SIZES = [(3, 4, 4), (2, 12, 20), (1, 44, 20), (5, 24, 40), (2, 36, 68)]  # (test_gpu_sizes.py)
+
+
+def workspace_table():
+    from drmnet_amd.unet import EncoderUNetModel, UNetModel
+
+    out = {}
+    for name, cfg, kind in WS_NETS:
+        m = (UNetModel if kind == "unet" else EncoderUNetModel)(**cfg)
+        for prec in m.PRECISIONS:
+            m.set_precision(prec)
+            for n, h, w in WS_TINY_SIZES if name == "tiny_unet" else WS_SIZES:
+                out[f"{name} {prec} {n}x{h}x{w}"] = m.workspace_bytes(n, h, w)
+    return out
+
+
+def test_workspace_bytes_match_the_recorded_sizing():
+    with open(os.path.join(GOLD, "workspace_bytes.json")) as f:
+        assert workspace_table() == json.load(f)
