@@ -570,4 +570,16 @@ int drm_resize(const float* x, float* out, int planes, int IH, int IW, int OH, i
   return guarded([&]() -> int { return launch_resize(x, out, planes, IH, IW, OH, OW, mode, static_cast<hipStream_t>(stream)); });
 }
 
+// ------------------------------------------------------------------------------------------------ forward model (render.hip)
+
+int drm_render_refmap(const float* z, const float* envmap, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_refmap(z, envmap, out, B, R, EH, EW, quad, subpixel, flip, static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream) {
+  return guarded([&]() -> int { return launch_brdf_eval(z, z_rows, n, v, l, out, (long long)N, static_cast<hipStream_t>(stream)); });
+}
+
 }  // extern "C"

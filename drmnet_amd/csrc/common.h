@@ -191,6 +191,11 @@ int launch_mirmap2envmap(const float* mir, const float* basis, float* out, int B
 int launch_hdr2ldr(const float* x, const unsigned char* mask, int HW, float alpha, float gamma, float* out, hipStream_t s);
 int launch_resize(const float* x, float* out, int planes, int IH, int IW, int OH, int OW, int mode, hipStream_t s);
 
+// reflectance-map forward model (render.hip): z [B][6] canonical principled rows, env [B][EH][EW][3] or null (white), out [B][3][R][R]
+int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s);
+// principled eval (f times n.l) of N (n, v, l) triples; z [1 or N][6]; out [N][3]
+int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s);
+
 // misc kernels (misc.hip)
 // absmax_bits (optional): [N][pack_input_absmax_parts(H, W)] words, every one written: max |element| of one block of a packed image as fp32 bits
 int pack_input_absmax_parts(int H, int W);

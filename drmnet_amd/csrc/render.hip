@@ -1,0 +1,274 @@
+// The forward model DRMNet inverts: a reflectance map of one sphere lit only by a lat-long environment map, seen through the principled
+// BSDF subset of the shipped configs, under a direct-lighting integral.  Replaces the reference's Mitsuba 3 renders on the inference side
+// (paths relative to the reference root):
+//   RefMapSensor (camera at +z, up +y, orthographic over the sphere)   utils/mitsuba3_utils.py:14-89
+//   MitsubaRefMapRenderer.rendering (sphere + envmap, "direct")        utils/mitsuba3_utils.py:324-430
+//   get_bsdf / eval_bsdf / visualize_bsdf ("principled")             utils/mitsuba3_utils.py:528-640
+//   DRMNet.instantiate_brdf_model (basis_r0), reconstruct            models/drmnet.py:328-347, 943-953
+// The BSDF is Mitsuba 3's principled with spec_tint, sheen, clearcoat, anisotropic, spec_trans and flatness at 0: a GGX specular lobe with
+// Smith G and the exact dielectric / Schlick metallic Fresnel mix, plus the retro-reflective Disney diffuse.  A pixel is the box-filtered
+// mean over its footprint of P(n) = integral over {l : n.l > 0} of L(l) f(v, l) (n.l) dl, with v = +z and n the sphere normal the sensor
+// sees.  The integral is a deterministic stratified quadrature per lobe: a Q x Q midpoint grid of (u1, u2) mapped to the GGX visible
+// normals seen from v (Heitz 2018: weight F G1(l), bounded, so the heavy GGX tail needs no extra strata) for the specular lobe and to
+// cosine-weighted directions for the diffuse one, at S x S sub-pixel normals.  One wave
+// owns one pixel: its lanes split the Q^2 grid, keep their partial sums in a fixed order and meet in a fixed butterfly, so a render is
+// bitwise reproducible (no atomics).
+#include "common.h"
+
+namespace drm {
+
+namespace {
+
+constexpr float kPi = 3.14159265358979323846f;
+constexpr int kRenderWaves = 4;  // pixels (one wave each) per 256-thread workgroup
+
+struct V3 {
+  float x, y, z;
+};
+__host__ __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
+__host__ __device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__host__ __device__ __forceinline__ V3 axpy(float s, V3 a, V3 b) { return v3(s * a.x + b.x, s * a.y + b.y, s * a.z + b.z); }
+// |a x b|^2: sin^2 of the angle between unit vectors without the cancellation of 1 - cos^2 near 0
+__host__ __device__ __forceinline__ float cross_sq(V3 a, V3 b) {
+  const float cx = a.y * b.z - a.z * b.y, cy = a.z * b.x - a.x * b.z, cz = a.x * b.y - a.y * b.x;
+  return cx * cx + cy * cy + cz * cz;
+}
+__host__ __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+
+// canonical row (metallic, base colour R G B, roughness, specular), clipped to [0, 1] as get_bsdf / _render_scene clip
+struct Principled {
+  float m, c[3], r, alpha, a2, eta;
+};
+__host__ __device__ __forceinline__ Principled principled(const float* z) {
+  Principled p;
+  p.m = clip01(z[0]);
+  p.c[0] = clip01(z[1]);
+  p.c[1] = clip01(z[2]);
+  p.c[2] = clip01(z[3]);
+  p.r = clip01(z[4]);
+  p.alpha = fmaxf(0.001f, p.r * p.r);
+  p.a2 = p.alpha * p.alpha;
+  p.eta = 2.0f / (1.0f - sqrtf(0.08f * clip01(z[5]))) - 1.0f;  // Mitsuba's specular -> eta; >= 1, so no total internal reflection
+  return p;
+}
+
+// The BSDF terms are templates: the quadrature runs them in fp32; drm_brdf_eval runs them in fp64, since near a narrow peak (alpha down
+// to 0.001) the value is ill-conditioned in the half vector: fp32 rounding of h alone would move D by more than 1e-5.
+// GGX D with 1 - (n.h)^2 passed as s2 = |n x h|^2; 0 where D (n.h) <= 1e-20 (Mitsuba's cut-off)
+template <typename T>
+__host__ __device__ __forceinline__ T ggx_d(T a2, T nh, T s2) {
+  const T t = s2 + a2 * nh * nh;
+  const T d = a2 / (T(kPi) * t * t);
+  return d * nh > T(1e-20) ? d : T(0);
+}
+// Smith G1 of GGX for a direction w: c = n.w, s2 = |n x w|^2, wh = w.h; 0 on the back of the microfacet, 1 at normal incidence
+template <typename T>
+__host__ __device__ __forceinline__ T ggx_g1(T a2, T c, T s2, T wh) {
+  if (wh * c <= T(0)) return T(0);
+  if (s2 == T(0)) return T(1);
+  return T(2) / (T(1) + sqrt(T(1) + a2 * s2 / (c * c)));
+}
+// exact unpolarised dielectric Fresnel at cos cd, relative index eta >= 1 (0 when index-matched)
+template <typename T>
+__host__ __device__ __forceinline__ T fresnel_dielectric(T cd, T eta) {
+  if (eta == T(1)) return T(0);
+  const T ct = sqrt(fmax(T(1) - (T(1) - cd * cd) / (eta * eta), T(0)));
+  const T as = (cd - eta * ct) / (cd + eta * ct);
+  const T ap = (ct - eta * cd) / (ct + eta * cd);
+  return T(0.5) * (as * as + ap * ap);
+}
+template <typename T>
+__host__ __device__ __forceinline__ T schlick_weight(T c) {
+  const T t = fmin(fmax(T(1) - c, T(0)), T(1));
+  const T t2 = t * t;
+  return t2 * t2 * t;
+}
+// Disney diffuse term without c / pi: (1 - F_l / 2)(1 - F_v / 2) + R_r (F_l + F_v + F_l F_v (R_r - 1)), R_r = 2 r cd^2
+template <typename T>
+__host__ __device__ __forceinline__ T diffuse_shape(T r, T cl, T cv, T cd) {
+  const T fl = schlick_weight(cl), fv = schlick_weight(cv), rr = T(2) * r * cd * cd;
+  return (T(1) - T(0.5) * fl) * (T(1) - T(0.5) * fv) + rr * (fl + fv + fl * fv * (rr - T(1)));
+}
+
+// Mitsuba's eval (f times n.l) per channel, in fp64; n, v (toward the viewer), l (toward the light) unit vectors
+__host__ __device__ __forceinline__ void principled_eval(const Principled& p, const float* n, const float* v, const float* l, float out[3]) {
+  out[0] = out[1] = out[2] = 0.0f;
+  const double nx = n[0], ny = n[1], nz = n[2];
+  const double cv = nx * v[0] + ny * v[1] + nz * v[2], cl = nx * l[0] + ny * l[1] + nz * l[2];
+  if (!(cv > 0.0 && cl > 0.0)) return;
+  double hx = (double)v[0] + l[0], hy = (double)v[1] + l[1], hz = (double)v[2] + l[2];
+  const double inv = 1.0 / sqrt(hx * hx + hy * hy + hz * hz);
+  hx *= inv; hy *= inv; hz *= inv;
+  const double nh = nx * hx + ny * hy + nz * hz;  // > 0: v and l are both above the surface
+  const double cd = hx * v[0] + hy * v[1] + hz * v[2], lh = hx * l[0] + hy * l[1] + hz * l[2];
+  const double a2 = (double)p.alpha * p.alpha, m = p.m;
+  // sin^2 as 1 - cos^2 (in fp64 the cancellation costs nothing, and this is the definition's form for inputs that are unit only to fp32)
+  const double D = ggx_d(a2, nh, 1.0 - nh * nh);
+  const double G = ggx_g1(a2, cv, 1.0 - cv * cv, cd) * ggx_g1(a2, cl, 1.0 - cl * cl, lh);
+  const double k = D * G / (4.0 * cv);
+  const double fd = (1.0 - m) * fresnel_dielectric(cd, (double)p.eta), sw = schlick_weight(cd);
+  const double kd = (1.0 - m) * cl * diffuse_shape((double)p.r, cl, cv, cd) / kPi;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) out[ch] = (float)((fd + m * (p.c[ch] + (1.0 - p.c[ch]) * sw)) * k + kd * p.c[ch]);
+}
+
+// radiance toward w: bilinear in the texel grid of an EH x EW map whose texel (i, j) looks along theta = (i + 1/2) pi / EH,
+// psi = (j + 1/2) 2 pi / EW, w = (sin theta sin psi, cos theta, -sin theta cos psi); wraps in psi, clamps in theta.  env [EH][EW][3].
+__host__ __device__ __forceinline__ void env_lookup(const float* __restrict__ env, int EH, int EW, V3 w, float L[3]) {
+  const float u = atan2f(w.x, -w.z) * (0.5f / kPi);
+  const float t = acosf(fminf(fmaxf(w.y, -1.0f), 1.0f)) * (1.0f / kPi);
+  const float x = u * (float)EW - 0.5f;
+  const float y = fminf(fmaxf(t * (float)EH - 0.5f, 0.0f), (float)(EH - 1));
+  const float xf = floorf(x), yf = floorf(y);
+  const float fx = x - xf, fy = y - yf;
+  int j0 = (int)xf % EW;
+  if (j0 < 0) j0 += EW;
+  const int j1 = j0 + 1 == EW ? 0 : j0 + 1;
+  const int i0 = (int)yf, i1 = i0 + 1 < EH ? i0 + 1 : EH - 1;
+  const float* r0 = env + (size_t)i0 * EW * 3;
+  const float* r1 = env + (size_t)i1 * EW * 3;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float top = (1.0f - fx) * r0[j0 * 3 + ch] + fx * r0[j1 * 3 + ch];
+    const float bot = (1.0f - fx) * r1[j0 * 3 + ch] + fx * r1[j1 * 3 + ch];
+    L[ch] = (1.0f - fy) * top + fy * bot;
+  }
+}
+
+// RefMapSensor: the normal seen at film position (px, py) in [0, 1]^2 (from the left / from the top); flip mirrors x
+__host__ __device__ __forceinline__ V3 sensor_normal(float px, float py, int flip) {
+  const float a = (2.0f * px - 1.0f) * (0.5f * kPi), b = (1.0f - 2.0f * py) * (0.5f * kPi);
+  const float cb = cosf(b);
+  const float nx = cb * sinf(a);
+  return v3(flip ? -nx : nx, sinf(b), cb * cosf(a));
+}
+
+// one lane's share of pixel (i, j): every sub-pixel, the grid points q = lane, lane + lanes, ... of both lobes, summed in that order
+// into acc (unnormalised).  env == nullptr: white environment (L = 1).
+__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, int EH, int EW, int R, int i, int j,
+                                                        int Q, int S, int flip, int lane, int lanes, float acc[3]) {
+  const V3 v = v3(0.0f, 0.0f, 1.0f);
+  const float invQ = 1.0f / (float)Q;
+  const bool diffuse = p.m < 1.0f;
+  for (int sy = 0; sy < S; ++sy) {
+    for (int sx = 0; sx < S; ++sx) {
+      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
+      const float cv = n.z;  // n.v for v = +z
+      // orthonormal frame (t, bt, n) (Duff et al. 2017; n.z > 0 on the whole film); v = (-n.x, -n.y, n.z) in it
+      const float ka = -1.0f / (1.0f + n.z), kb = n.x * n.y * ka;
+      const V3 t = v3(1.0f + n.x * n.x * ka, kb, -n.x), bt = v3(kb, 1.0f + n.y * n.y * ka, -n.y);
+      // visible-normal sampling frame: V = normalize(alpha v_t, alpha v_b, v_n), T1 = normalize(z x V) (x if V = z), T2 = V x T1
+      float Vx = -p.alpha * n.x, Vy = -p.alpha * n.y, Vz = cv;
+      const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
+      Vx *= vinv; Vy *= vinv; Vz *= vinv;
+      const float lensq = Vx * Vx + Vy * Vy;
+      const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
+      const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
+      const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
+      const float vs = 0.5f * (1.0f + Vz);
+      for (int q = lane; q < Q * Q; q += lanes) {
+        const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
+        const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
+        float L[3] = {1.0f, 1.0f, 1.0f};
+        // specular lobe: h from the GGX distribution of visible normals (Heitz 2018) seen from v, l = reflect(v, h); weight F G1(l)
+        {
+          const float rs = sqrtf(u1), t1 = rs * cp;
+          const float t2 = (1.0f - vs) * sqrtf(1.0f - t1 * t1) + vs * rs * sp;
+          const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
+          const float hx = p.alpha * (t1 * T1x + t2 * T2x + tz * Vx), hy = p.alpha * (t1 * T1y + t2 * T2y + tz * Vy);
+          const float hz = fmaxf(t2 * T2z + tz * Vz, 0.0f);
+          const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
+          const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
+          const V3 h = axpy(nh, n, axpy(hy * hinv, bt, v3(hx * hinv * t.x, hx * hinv * t.y, hx * hinv * t.z)));
+          const float vh = dot3(v, h);
+          const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
+          const float cl = dot3(n, l);
+          if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
+            const float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh);
+            const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
+            if (env) env_lookup(env, EH, EW, l, L);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
+          }
+        }
+        // diffuse lobe: cosine-weighted l; weight pi diff / (n.l) = (1 - m) c shape
+        if (diffuse) {
+          const float rs = sqrtf(u1), cl = sqrtf(1.0f - u1);
+          const V3 l = axpy(cl, n, axpy(rs * sp, bt, v3(rs * cp * t.x, rs * cp * t.y, rs * cp * t.z)));
+          V3 h = v3(l.x, l.y, l.z + 1.0f);
+          const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
+          const float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd);
+          if (env) env_lookup(env, EH, EW, l, L);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
+        }
+      }
+    }
+  }
+}
+
+// grid: ceil(B R^2 / 4) workgroups of 4 waves; wave = pixel (b, i, j); out [B][3][R][R]
+__global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restrict__ z, const float* __restrict__ env, float* __restrict__ out, int B,
+                                                            int R, int EH, int EW, int Q, int S, int flip) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)B * R * R) return;  // (wave-uniform)
+  const int b = (int)(pix / ((long long)R * R));
+  const int rem = (int)(pix - (long long)b * R * R);
+  const int i = rem / R, j = rem - (rem / R) * R;
+  const Principled p = principled(z + 6 * (size_t)b);
+  const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  pixel_lane_sum(p, e, EH, EW, R, i, j, Q, S, flip, lane, 64, acc);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], o);
+  }
+  if (lane == 0) {
+    const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(((size_t)b * 3 + c) * R + i) * R + j] = acc[c] * scale;
+  }
+}
+
+// one thread per element: out[k] = eval(z[k or 0], n[k], v[k], l[k])
+__global__ __launch_bounds__(256) void brdf_eval_kernel(const float* __restrict__ z, int z_rows, const float* __restrict__ n, const float* __restrict__ v,
+                                                        const float* __restrict__ l, float* __restrict__ out, long long N) {
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < N; k += (long long)gridDim.x * blockDim.x) {
+    const Principled p = principled(z + (z_rows == 1 ? 0 : 6 * k));
+    float f[3];
+    principled_eval(p, n + 3 * k, v + 3 * k, l + 3 * k, f);
+    out[3 * k] = f[0];
+    out[3 * k + 1] = f[1];
+    out[3 * k + 2] = f[2];
+  }
+}
+
+}  // namespace
+
+int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {
+  DRM_REQUIRE(z && out, "render_refmap: null pointer");
+  DRM_REQUIRE(B > 0 && R > 0 && R <= 8192, "render_refmap: B >= 1 rows of R x R pixels, 1 <= R <= 8192");
+  DRM_REQUIRE(quad >= 1 && quad <= 1024 && subpixel >= 1 && subpixel <= 16, "render_refmap: quad in [1, 1024], subpixel in [1, 16]");
+  DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), "render_refmap: envmap must be EH x EW with EH, EW >= 1");
+  const long long blocks = ((long long)B * R * R + kRenderWaves - 1) / kRenderWaves;
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: B R^2 too large for one launch");
+  hipLaunchKernelGGL(refmap_render_kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, out, B, R, env ? EH : 1, env ? EW : 1, quad,
+                     subpixel, flip ? 1 : 0);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s) {
+  DRM_REQUIRE(N >= 0, "brdf_eval: N >= 0");
+  if (N == 0) return DRM_OK;
+  DRM_REQUIRE(z && n && v && l && out, "brdf_eval: null pointer");
+  DRM_REQUIRE(z_rows == 1 || (long long)z_rows == N, "brdf_eval: z has 1 or N rows");
+  const long long blocks = std::min<long long>((N + 255) / 256, 65536);
+  hipLaunchKernelGGL(brdf_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, s, z, z_rows, n, v, l, out, N);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+}  // namespace drm

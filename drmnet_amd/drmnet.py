@@ -5,8 +5,9 @@ inference path touches (scripts/estimate.py:84-100):
   __init__ params (configs/drmnet/eval_drmnet.yaml), ema_scope :242-258, init_from_ckpt :260-277,
   apply_model :376-388, get_brdf_out :390-396, forward :452-456, get_schedule :458-501,
   check_convergence :747-750, p_mean_variance :752-770, p_sample (stub) :772-780,
-  p_sample_loop :782-847, get_input_for_predict :1011-1045, decode_first_stage, r0toenvmap :931-941.
-Training (p_losses, get_input, caches, log_images, Mitsuba rendering) is out of scope.
+  p_sample_loop :782-847, get_input_for_predict :1011-1045, decode_first_stage, r0toenvmap :931-941, and the forward model on
+  csrc/render.hip: basis_r0 :328-347, rendering_refmaps :667-696, get_visualized_brdf_grid :916-929, reconstruct :943-953.
+Training (p_losses, get_input, caches, log_images, the training-data renders) is out of scope.
 
 The module is a plain ``nn.Module`` (pytorch_lightning is not needed for inference); ``state_dict()`` has the
 reference's keys, so ``drmnet.ckpt`` loads with ``init_from_ckpt``.
@@ -17,6 +18,7 @@ import ctypes as C
 import math
 from typing import List, Optional, Tuple, Union
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -40,7 +42,7 @@ class DRMNet(nn.Module):
                  conditioning_key: Optional[str] = None, scale_factor: float = 1.0, scale_by_std: bool = False, delta: float = 0.0125,
                  gamma: float = 0.9, epsilon: float = 0.001, brdf_param_names=("specular",), z0=(1.0,), model_emb_z: bool = True,
                  emb_z_crossattn: bool = False, refmap_input_scaler: Optional[float] = None, first_stage_config=None,
-                 cond_stage_config="__is_first_stage__", basis_r0: Optional[torch.Tensor] = None, cond_stage_forward: Optional[str] = None,
+                 cond_stage_config="__is_first_stage__", basis_r0: Union[torch.Tensor, str, None] = None, cond_stage_forward: Optional[str] = None,
                  **training_only):
         # (the leading four parameters keep the reference's positional order, models/drmnet.py:79-85: DRMNet(ill, ref, renderer_cfg, 250))
         super().__init__()
@@ -99,14 +101,69 @@ class DRMNet(nn.Module):
         return self.z0.device
 
     def instantiate_brdf_model(self, config, basis_r0=None):
-        """Reference renders basis_r0 (white envmap, BRDF z0) through Mitsuba (drmnet.py:328-347). Out of scope here:
-        basis_r0 is an optional input (ones by default) -- see DESIGN.md.  For the shipped z0 = [1, 1, 1, 1, 0, 1] (white, fully metallic,
-        roughness 0: Schlick F0 = base colour = 1) under the white environment the rendered quantity is analytically 1 on the sphere, so ones is
-        its noise-free value; any other z0 needs the rendered basis (first screen)."""
+        """The reference renders basis_r0 (white envmap, BRDF z0) at construction (drmnet.py:328-347).  Here basis_r0 is ones by default
+        (None), a tensor the caller supplies, or "render": the basis rendered from z0 by csrc/render.hip on first GPU use (r0toenvmap,
+        reconstruct or render_basis_r0()) -- construction never touches the GPU.  For the shipped z0 = [1, 1, 1, 1, 0, 1] (white, fully
+        metallic, roughness 0) the rendered basis is 1 on the sphere up to the grazing rim, so ones is its noise-free value; any other z0
+        needs the rendered basis (first screen)."""
         self.renderer = instantiate_from_config(config) if config is not None else None
-        if basis_r0 is None:
+        self._basis_pending = isinstance(basis_r0, str)
+        if self._basis_pending and basis_r0 != "render":
+            raise ValueError(f'basis_r0 must be None, a tensor or "render", got {basis_r0!r}')
+        if basis_r0 is None or self._basis_pending:
             basis_r0 = torch.ones(3, self.image_size, self.image_size)
         self.register_buffer("basis_r0", basis_r0.float(), persistent=False)
+
+    def _renderer(self):
+        """The reflectance-map renderer: the configured one, else one at image_size made on first use."""
+        from .render import RefMapRenderer
+
+        if self.renderer is None:
+            self.renderer = RefMapRenderer(self.image_size, brdf_param_names=self.brdf_param_names)
+        if not isinstance(self.renderer, RefMapRenderer):
+            raise NotImplementedError(f"rendering needs drmnet_amd.render.RefMapRenderer, not {type(self.renderer).__name__}")
+        return self.renderer
+
+    @torch.no_grad()
+    def render_basis_r0(self) -> torch.Tensor:
+        """drmnet.py:328-347: basis_r0 = the reflectance map of z0 under a white environment at image_size x image_size ([3, S, S]),
+        rendered on the model's GPU and stored in the basis_r0 buffer."""
+        if not self.z0.is_cuda:
+            raise RuntimeError("render_basis_r0 renders on the GPU: move the model there first (drmnet_amd has no CPU path)")
+        basis = self._renderer().render(self.z0[None], self.brdf_param_names, None, res=self.image_size)[0]
+        self.basis_r0 = basis.contiguous()
+        self._basis_pending = False
+        return self.basis_r0
+
+    @torch.no_grad()
+    def rendering_refmaps(self, envmaps, z: torch.Tensor, brdf_param_names=None, transform: bool = True, view_from=None,
+                          new_scene: bool = False) -> torch.Tensor:
+        """drmnet.py:667-696: envmaps [B, H, W, 3], z [L, B, P] -> reflectance maps [L, B, 3, R, R], every (list, batch) item under
+        envmaps[b] -- one drm_render_refmap launch for all of them.  Envmap names (the training path) and view_from are not implemented."""
+        assert len(envmaps) == z.size(1)
+        if isinstance(envmaps, (list, tuple)) or view_from is not None:
+            raise NotImplementedError("rendering_refmaps: envmap names (training data) and view_from are not modelled; pass envmaps [B, H, W, 3]")
+        r = self._renderer()
+        L, B = z.shape[0], z.shape[1]
+        env = envmaps[None].expand(L, *envmaps.shape).reshape(L * B, *envmaps.shape[1:])
+        out = r.render(z.reshape(L * B, -1), brdf_param_names or self.brdf_param_names, env)
+        if not new_scene:
+            r._envmap = envmaps[-1].to(out.device)  # the scene keeps the last map it was given, as the reference's does
+        return out.reshape(L, B, *out.shape[1:])
+
+    def reconstruct(self, Lr_0: torch.Tensor, z: torch.Tensor, brdf_param_names=None, transform: bool = True) -> torch.Tensor:
+        """drmnet.py:943-953: the estimate re-rendered -- Lr_0 (network space, [B, 3, S, S]) rescaled, warped to an envmap through
+        basis_r0 (r0toenvmap), and rendered back through z [B, P] -> [B, 3, R, R]."""
+        r0 = self.ds.rescale(Lr_0)
+        envmap = self.r0toenvmap(r0, (self.image_size, self.image_size * 2))
+        return self.rendering_refmaps(envmap, z[None], new_scene=True, brdf_param_names=brdf_param_names, transform=transform)[0]
+
+    def get_visualized_brdf_grid(self, zs: torch.Tensor, brdf_param_names=None) -> np.ndarray:
+        """drmnet.py:916-929: visualize_bsdf (128 x 128 spheres) of every row of zs [B, P], stacked -> [B * 128, 448, 3]."""
+        from .render import get_bsdf, visualize_bsdf
+
+        rows = [visualize_bsdf(get_bsdf(z, brdf_param_names or self.brdf_param_names), imsize=(128, 128))[0] for z in zs]
+        return np.concatenate(rows, axis=0)
 
     def ema_scope(self, context=None):
         """models/drmnet.py:242-258 -- ``with model.ema_scope(): ...`` samples with the EMA weights of both networks (and of the
@@ -484,4 +541,6 @@ class DRMNet(nn.Module):
 
         if envshape is None:
             envshape = (self.image_size, self.image_size * 2)
+        if self._basis_pending:
+            self.render_basis_r0()
         return ops.mirmap2envmap(r0, envshape, basis=self.basis_r0.to(r0.device), channels_last=True)

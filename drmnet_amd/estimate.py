@@ -6,7 +6,8 @@
 `estimate()` keeps the reference's signature and statement order (scripts/estimate.py:29-107); every stage runs on the GPU:
 mask erosion + refmap_mask_make (csrc/refmap.hip), ObsNet DDIM inpainting and the DRMNet reverse loop (device loops behind
 the C ABI).  The keyword-only `hooks` let tests inject the random draws the reference takes from torch's global generator.
-Rendering the estimated BRDF (Mitsuba, scripts/estimate.py:146-148) is out of scope: the BRDF parameters are printed / saved.
+`main` writes the reference's two images (sample_env.png, and sample_brdf.png through visualize_bsdf on csrc/render.hip) and also saves
+and prints the BRDF parameters.
 """
 from __future__ import annotations
 
@@ -106,6 +107,16 @@ def estimate_batch(DRMNet_model, ObsNet_model, input_imgs: torch.Tensor, input_n
     return Lr0, zK_est, K
 
 
+def save_brdf_png(path, zK, brdf_param_names) -> None:
+    """scripts/estimate.py:146-148: the estimated BRDF's visualize_bsdf figure, tone-mapped (hdr2ldr), with its sphere mask as alpha."""
+    from . import file_io
+    from .render import get_bsdf, visualize_bsdf
+    from .transform import hdr2ldr
+
+    fig, mask = visualize_bsdf(get_bsdf(zK, brdf_param_names))
+    file_io.save_png(path, hdr2ldr(fig), mask=mask)
+
+
 def main(argv=None):
     # Provenance: this entry point deliberately mirrors the reference's command line (scripts/estimate.py:105-142: the same options, defaults, mask
     # rule and output files -- SURVEY 2 #20 keeps it as the user-facing surface); everything it calls is this package's own code over the HIP library.
@@ -144,6 +155,7 @@ def main(argv=None):
     envmap_est = drmnet_model.r0toenvmap(Lr0_sample[None], (drmnet_model.image_size, drmnet_model.image_size * 2))[0]  # [H, W, 3]
     args.output_dir.mkdir(exist_ok=True)
     file_io.save_png(args.output_dir / "sample_env.png", hdr2ldr(envmap_est.cpu().numpy()))
+    save_brdf_png(args.output_dir / "sample_brdf.png", zK_est, drmnet_model.brdf_param_names)
     np.save(args.output_dir / "sample_brdf.npy", zK_est.cpu().numpy())
     print("estimated BRDF parameters", dict(zip(drmnet_model.brdf_param_names, zK_est.tolist())))
 

@@ -40,7 +40,8 @@ class IdentityFirstStage(nn.Module):
 
 
 class NullRenderer:
-    """Stand-in for the Mitsuba renderers (training data / basis_r0 render; out of scope)."""
+    """Stand-in for the Mitsuba mesh renderer of the training data (MitsubaOrthoRenderer; out of scope).  The reflectance-map
+    renderer is drmnet_amd.render.RefMapRenderer."""
 
     def __init__(self, refmap_res: int = 128, **kwargs):
         self.image_size = (refmap_res, refmap_res)

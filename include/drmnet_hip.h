@@ -343,6 +343,27 @@ int drm_hdr2ldr(const float* x, const uint8_t* mask, int HW, float alpha, float 
 #define DRM_RESIZE_BICUBIC_AA 2
 int drm_resize(const float* x, float* out, int planes, int IH, int IW, int OH, int OW, int mode, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The forward model DRMNet inverts: reflectance maps of a sphere lit by an environment map (csrc/render.hip).
+ * ------------------------------------------------------------------------------------------- */
+/* A BSDF row is canonical: z[6] = (metallic, base colour R, G, B, roughness, specular), each clipped to [0, 1] by the kernels.  The BSDF is
+ * Mitsuba 3's "principled" with every other parameter 0 (GGX alpha = max(0.001, roughness^2), eta = 2 / (1 - sqrt(0.08 specular)) - 1).
+ *
+ * Replaces MitsubaRefMapRenderer.rendering (utils/mitsuba3_utils.py:324-430: sphere, "envmap" emitter, "direct" integrator, RefMapSensor
+ * :14-89 at +z looking at -z, box filter) and the basis_r0 render of DRMNet.instantiate_brdf_model (models/drmnet.py:328-347).
+ *   z [B][6]; envmap [B][EH][EW][3] channels-last lat-long maps (texel (i, j) looks along theta = (i + 1/2) pi / EH, psi = (j + 1/2) 2 pi / EW,
+ *   (sin theta sin psi, cos theta, -sin theta cos psi); bilinear, wraps in psi, clamps in theta), or NULL for a white environment (L = 1).
+ *   out [B][3][R][R]: pixel (i, j) is the mean over its footprint of the radiance the sphere reflects toward +z at the normal
+ *   n = (cos b sin a, sin b, cos b cos a), a = (2 px - 1) pi / 2, b = (1 - 2 py) pi / 2 (flip != 0 negates n.x).
+ *   The integral is a deterministic quadrature: subpixel x subpixel normals per pixel, a quad x quad stratified grid per lobe
+ *   (GGX-sampled half vectors for the specular lobe, cosine-weighted directions for the diffuse one); bitwise reproducible.
+ *   quad in [1, 1024] (32 by default in the Python layer), subpixel in [1, 16] (2). */
+int drm_render_refmap(const float* z, const float* envmap, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, void* stream);
+/* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
+ * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
+ * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
+int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
