@@ -310,18 +310,16 @@ int drm_op_attention_block(const float* x, const float* const* params, float* ou
       auto off = [&](float* p) { return (size_t)(p - wb); };
       float* nw = ar.alloc<float>(C); float* nb = ar.alloc<float>(C);
       float* qw = ar.alloc<float>(packed_conv_weight_floats(1, 3 * C, C)); float* qb = ar.alloc<float>(3 * C);
-      float* pw = ar.alloc<float>(packed_conv_weight_floats(1, C, C)); float* pb = ar.alloc<float>(C);
-      float* s1 = ar.alloc<float>(64); float* s2 = ar.alloc<float>(64); float* scratch = ar.alloc<float>(64);
+      float* fw = ar.alloc<float>((size_t)3 * C * C);  // raw [3C][C] qkv weight with proj_out folded into its v rows, as UNet::load forms it
+      float* s1 = ar.alloc<float>(64); float* scratch = ar.alloc<float>(64);
       Act a = new_act(c, C, H, W);
       Act o = new_act(c, C, H, W);
       if (!ar.dry) {
-        l.n_w = off(nw); l.n_b = off(nb); l.qkv_w = off(qw); l.qkv_b = off(qb); l.proj_w = off(pw); l.proj_b = off(pb); l.qkv_s = off(s1); l.proj_s = off(s2);
+        l.n_w = off(nw); l.n_b = off(nb); l.qkv_w = off(qw); l.qkv_b = off(qb); l.qkv_s = off(s1);
         DRM_HIP_CHECK(hipMemcpyAsync(nw, params[0], C * sizeof(float), hipMemcpyDeviceToDevice, s));
         DRM_HIP_CHECK(hipMemcpyAsync(nb, params[1], C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DRM_TRY(pack_for_ops(op_prec, params[2], qw, s1, scratch, 3 * C, C, 1, 3 * C, C, s));
-        DRM_HIP_CHECK(hipMemcpyAsync(qb, params[3], 3 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DRM_TRY(pack_for_ops(op_prec, params[4], pw, s2, scratch, C, C, 1, C, C, s));
-        DRM_HIP_CHECK(hipMemcpyAsync(pb, params[5], C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DRM_TRY(launch_fold_attn_params(params[2], params[3], params[4], params[5], fw, qb, C, s));
+        DRM_TRY(pack_for_ops(op_prec, fw, qw, s1, scratch, 3 * C, C, 1, 3 * C, C, s));
         DRM_TRY(launch_nchw_to_nhwc(x, a.p, N, H, W, C, s));
       }
       DRM_TRY(run_attention(c, wb, l, a, o));

@@ -4,8 +4,10 @@
 //     S = (q * C^-1/4) . (k * C^-1/4)^T   -> fp32 softmax over keys -> out = P . v        out: [N][T][C]
 // Round-1 structure: two batched MFMA GEMMs (fp32 v_mfma_f32_32x32x2_f32, 64x64 tiles) around a row softmax,
 // with the [N][T][T] score matrix in a workspace.  Attention is <= 4 % (IllNet) / 9 % (ObsNet) of the FLOPs
-// (SURVEY.md 8a), so the fused flash-style kernel is a later-round item; the GroupNorm, qkv and proj_out
-// projections and the residual add run in conv.hip (taps = 1).
+// (SURVEY.md 8a), so the fused flash-style kernel is a later-round item; the GroupNorm and the qkv projection run
+// on the conv kernels (taps = 1).  proj_out is folded into the v rows of that projection when the parameters are
+// loaded (conv_split.hip fold_attn_params_kernel), so the core's last kernel finishes the block: it adds the
+// block's input x and accumulates the per-channel (sum, sum of squares) of the result for the next GroupNorm.
 #include <algorithm>
 
 #include "common.h"
@@ -20,10 +22,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 //   BT = true : B given as [Ncols][K] row-major (ldb)  -> C = A . B^T   (Q . K^T)
 //   BT = false: B given as [K][Ncols] row-major (ldb)  -> C = A . B     (P . V)
 // 64x64 tile, 4 waves (2x2), one 32x32 accumulator per wave, K chunk 32.
+// R (optional, laid out like C) is added to the result; stat (optional, [batch][Ncols], zeroed) then receives the per-column (sum, sum of
+// squares) of what was written, one fp64 atomic per (wave, column, moment).
 template <bool BT>
 __global__ __launch_bounds__(256) void bgemm64_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ Cm, int M,
                                                       int Ncols, int K, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
-                                                      float alpha) {
+                                                      float alpha, const float* __restrict__ R = nullptr, double2* __restrict__ stat = nullptr) {
   constexpr int KG = 8, LD = 65;  // LD: padded row stride (float4 units) to spread LDS banks on the staging writes
   __shared__ float4 As[KG * LD];
   __shared__ float4 Bs[KG * LD];
@@ -109,10 +113,27 @@ __global__ __launch_bounds__(256) void bgemm64_kernel(const float* __restrict__ 
     __syncthreads();
   }
   const int col = n0 + wn * 32 + r;
+  if (R) R += (size_t)blockIdx.z * sC;
+  double s1 = 0.0, s2 = 0.0;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int row = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-    if (row < M && col < Ncols) Cm[(size_t)row * ldc + col] = alpha * acc[e];
+    if (row < M && col < Ncols) {
+      float v = alpha * acc[e];
+      if (R) v += R[(size_t)row * ldc + col];
+      Cm[(size_t)row * ldc + col] = v;
+      s1 += (double)v;
+      s2 += (double)v * (double)v;
+    }
+  }
+  if (stat) {
+    s1 += __shfl_xor(s1, 32);
+    s2 += __shfl_xor(s2, 32);
+    if (h == 0 && col < Ncols) {
+      double* d = reinterpret_cast<double*>(stat + (size_t)blockIdx.z * Ncols + col);
+      atomicAdd(d, s1);
+      atomicAdd(d + 1, s2);
+    }
   }
 }
 
@@ -347,12 +368,15 @@ __global__ __launch_bounds__(256) void qk_small_kernel(const float* __restrict__
 // it first takes the maximum and the sum of exp of its 32 score rows (eight lanes per row), then its four waves split the keys: a lane loads
 // eight consecutive scores of "its" row and eight v values of "its" channel per 16-key step straight into the MFMA operand layout, applies
 // expf(s - max) / sum * 2^12 to the scores and the per-image power of two to v (attn_scales_kernel), no LDS and no barrier in the loop; the four
-// partial tiles meet in LDS and are added in wave order (deterministic).
+// partial tiles meet in LDS and are added in wave order (deterministic).  The epilogue finishes the attention block: it adds the block's input
+// R (laid out like O) and folds the tile's per-channel (sum, sum of squares) of the result through LDS into stat ([images][C], zeroed): one fp64
+// atomic per (workgroup, channel, moment).
 constexpr int PV_UNR = 2;
 template <int TERMS>
 __global__ __launch_bounds__(256) void pv_small_kernel(const float* __restrict__ S, const float* __restrict__ V, float* __restrict__ O, int T, int C, int ldv,
                                                        long long sS, long long sV, long long sO, float alpha, float a_scale,
-                                                       const float* __restrict__ v_scale_img, const float* __restrict__ v_inv_img) {
+                                                       const float* __restrict__ v_scale_img, const float* __restrict__ v_inv_img,
+                                                       const float* __restrict__ R, double2* __restrict__ stat) {
   __shared__ float part[4][32 * 33];
   __shared__ float row_max[32], row_inv[32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -361,6 +385,7 @@ __global__ __launch_bounds__(256) void pv_small_kernel(const float* __restrict__
   S += (size_t)blockIdx.z * sS;
   V += (size_t)blockIdx.z * sV;
   O += (size_t)blockIdx.z * sO;
+  R += (size_t)blockIdx.z * sO;
   const float v_scale = v_scale_img ? v_scale_img[blockIdx.z] : 1.0f;
   if (v_inv_img) alpha *= v_inv_img[blockIdx.z];
   {  // row softmax statistics: row = tid >> 3, eight lanes per row over whole rows (T % 32 == 0)
@@ -442,7 +467,22 @@ __global__ __launch_bounds__(256) void pv_small_kernel(const float* __restrict__
   for (int j = 0; j < 4; ++j) {
     const int idx = tid + 256 * j, row = idx >> 5, col = idx & 31;
     const float v = ((part[0][row * 33 + col] + part[1][row * 33 + col]) + part[2][row * 33 + col]) + part[3][row * 33 + col];
-    if (m0 + row < T && c0 + col < C) O[(size_t)(m0 + row) * C + c0 + col] = alpha * v;
+    float o = 0.f;
+    if (m0 + row < T && c0 + col < C) {
+      o = alpha * v + R[(size_t)(m0 + row) * C + c0 + col];
+      O[(size_t)(m0 + row) * C + c0 + col] = o;
+    }
+    part[0][row * 33 + col] = o;  // (this thread's own entry: read above by nobody else)
+  }
+  __syncthreads();
+  if (tid < 64) {  // lanes 0 .. 31: the column sums, lanes 32 .. 63: the sums of squares
+    const int col = tid & 31, sq = tid >> 5;
+    double acc2 = 0.0;
+    for (int row = 0; row < 32; ++row) {
+      const double o = (double)part[0][row * 33 + col];
+      acc2 += sq ? o * o : o;
+    }
+    if (c0 + col < C) atomicAdd(reinterpret_cast<double*>(stat + (size_t)blockIdx.z * C + c0 + col) + sq, acc2);
   }
 }
 
@@ -481,14 +521,15 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ S
 // ------------------------------------------------------------------------------------------------------------------------------
 
 // per image: power-of-two factors of q, k, v from the per-channel sums of squares of the qkv tensor (bound * 2^k in [2^14, 2^15))
-// and everything the two conv launches read: tables [N][C] (2^kq), [N][T] (2^12), zeros, and the epilogue / weight factors
+// and everything the two conv launches read: tables [N][C] (2^kq), [N][T] (2^12), zeros, and the epilogue / weight factors.  v here is the
+// folded v' = (Wp Wv) xn + (Wp bv + bp): the block's output minus its input is a convex combination of v' rows, bounded like them.
 __global__ __launch_bounds__(256) void attn_scales_kernel(const double2* __restrict__ mom, int C, int T, float alpha, float* __restrict__ q_tab,
                                                           float* __restrict__ p_tab, float* __restrict__ zero_tab, float* __restrict__ qk_inv,
                                                           float* __restrict__ k_scale, float* __restrict__ k_inv, float* __restrict__ pv_inv,
-                                                          float* __restrict__ v_scale, float* __restrict__ v_inv, float* __restrict__ o_tab,
+                                                          float* __restrict__ v_scale, float* __restrict__ v_inv,
                                                           float* __restrict__ q_scale /* [N] 2^kq, or null */) {
   __shared__ double red[3][4];
-  __shared__ float s_q, s_v;
+  __shared__ float s_q;
   const int n = blockIdx.x, t = threadIdx.x;
   double m[3] = {0.0, 0.0, 0.0};
   for (int c = t; c < 3 * C; c += 256) m[c / C] = fmax(m[c / C], mom[(size_t)n * 3 * C + c].y);
@@ -514,7 +555,6 @@ __global__ __launch_bounds__(256) void attn_scales_kernel(const double2* __restr
       iv[j] = ldexpf(1.0f, -k);
     }
     s_q = sc[0];
-    s_v = sc[2];
     qk_inv[n] = alpha * iv[0];
     if (q_scale) q_scale[n] = sc[0];
     k_scale[n] = sc[1];
@@ -524,11 +564,8 @@ __global__ __launch_bounds__(256) void attn_scales_kernel(const double2* __restr
     v_inv[n] = iv[2];
   }
   __syncthreads();
-  const float sq = s_q, sv = s_v;
-  for (int c = t; c < C; c += 256) {
-    q_tab[(size_t)n * C + c] = sq;
-    o_tab[(size_t)n * C + c] = sv;  // the attention output is a convex combination of v rows: the same bound guards proj_out's input
-  }
+  const float sq = s_q;
+  for (int c = t; c < C; c += 256) q_tab[(size_t)n * C + c] = sq;
   for (int c = t; c < T; c += 256) p_tab[(size_t)n * T + c] = 4096.0f;  // probabilities <= 1: 2^12 keeps the small ones normal in fp16
   const int Z = C > T ? C : T;
   for (int c = t; c < Z; c += 256) zero_tab[(size_t)n * Z + c] = 0.f;
@@ -653,7 +690,7 @@ size_t attention_scores_floats(int N, int T) { return (size_t)attention_group(N,
 
 size_t attention_conv_workspace_floats(int N, int T, int C) {
   const size_t Z = (size_t)(C > T ? C : T);
-  return 2 * (size_t)N * T * C + (size_t)N * (2 * C + T + Z) + 6 * (size_t)N + 64;
+  return 2 * (size_t)N * T * C + (size_t)N * (C + T + Z) + 6 * (size_t)N + 64;
 }
 // S = alpha q k^T (cin = C, cout = T) and O = P v (cin = T, cout = C) of nb images: 1x1 convs with per-image weights (k, v^T)
 static ConvArgs attention_gemm(int nb, int H, int W, int cin, int cout) {
@@ -669,9 +706,9 @@ bool attention_conv_planned(int H, int W, int C, int precision) {
 
 // (for attn_flash.hip: the per-image factor tables and the row-major pre-split image of q / k)
 void launch_attn_scales(const double2* mom, int N, int C, int T, float alpha, float* q_tab, float* p_tab, float* zero_tab, float* qk_inv, float* k_scale,
-                        float* k_inv, float* pv_inv, float* v_scale, float* v_inv, float* o_tab, float* q_scale, hipStream_t s) {
+                        float* k_inv, float* pv_inv, float* v_scale, float* v_inv, float* q_scale, hipStream_t s) {
   hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, mom, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale, v_inv,
-                     o_tab, q_scale);
+                     q_scale);
 }
 int launch_pack_attn_rows(const float* src, long long img_stride, int ld, const float* scale, float* dst, int rows, int cin, int N, hipStream_t s, bool bf16) {
   const unsigned pb = (unsigned)std::min<size_t>(((size_t)rows * cin / 8 + 255) / 256, 4096);
@@ -680,32 +717,26 @@ int launch_pack_attn_rows(const float* src, long long img_stride, int ld, const 
   return DRM_OK;
 }
 
-// qkv [N][T][3C] (+ its fused per-channel statistics), scores workspace [N][T][T], out [N][T][C], ws: attention_conv_workspace_floats
-// proj_guard (optional): receives the (scale, shift, inverse) tables that guard proj_out's read of `out`
-int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* scores, float* out, float* ws, int N, int H, int W, int C, int precision,
-                          hipStream_t s, ConvArgs* proj_guard) {
+// qkv [N][T][3C] (+ its fused per-channel statistics), x [N][T][C], scores workspace [N][T][T], out = x + P v [N][T][C], out_stat [N][C] (zeroed),
+// ws: attention_conv_workspace_floats.  The residual add and the output statistics are the P v launch's own epilogue (ConvArgs::res / stat_out).
+int launch_attention_conv(const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat, float* ws, int N, int H,
+                          int W, int C, int precision, hipStream_t s) {
   const int T = H * W;
-  DRM_REQUIRE(attention_conv_planned(H, W, C, precision) && qkv_mom, "attention on the conv pipeline: shape");
+  DRM_REQUIRE(attention_conv_planned(H, W, C, precision) && qkv_mom && x && out_stat, "attention on the conv pipeline: shape");
   const size_t Z = (size_t)(C > T ? C : T);
   float* wk = ws;                           // [N] packed k:   Cout = T, Cin = C
   float* wv = wk + (size_t)N * T * C;       // [N] packed v^T: Cout = C, Cin = T
   float* q_tab = wv + (size_t)N * T * C;    // [N][C]
   float* p_tab = q_tab + (size_t)N * C;     // [N][T]
   float* zero_tab = p_tab + (size_t)N * T;  // [N][max(C, T)]
-  float* o_tab = zero_tab + (size_t)N * Z;  // [N][C]
-  float* vec = o_tab + (size_t)N * C;       // 6 x [N]
+  float* vec = zero_tab + (size_t)N * Z;    // 6 x [N]
   float *qk_inv = vec, *k_scale = vec + N, *k_inv = vec + 2 * N, *pv_inv = vec + 3 * N, *v_scale = vec + 4 * N, *v_inv = vec + 5 * N;
   const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
   prof_tag(N, T, 1, C, C);
-  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 4 * C + 4.0 * T * T), s);  // one scope for the whole core
+  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C + 4.0 * T * T), s);  // one scope for the whole core (q, k, v, x in, out)
   hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, qkv_mom, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv,
-                     v_scale, v_inv, o_tab, nullptr);
+                     v_scale, v_inv, nullptr);
   DRM_HIP_CHECK(hipGetLastError());
-  if (proj_guard) {
-    proj_guard->gn_scale = o_tab;
-    proj_guard->gn_shift = zero_tab;
-    proj_guard->in_inv = v_inv;
-  }
   const unsigned pb = (unsigned)std::min<size_t>(((size_t)T * C / 8 + 255) / 256, 4096);
   hipLaunchKernelGGL(pack_attn_weight_kernel<true>, dim3(pb, N), dim3(256), 0, s, qkv + C, (long long)T * 3 * C, 3 * C, k_scale,
                      reinterpret_cast<float4*>(wk), T, C, precision == PREC_BF16 ? 1 : 0);
@@ -724,7 +755,8 @@ int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* score
     a.terms = qk_plan.terms;
     DRM_TRY(launch_conv(a, qk_plan, s));
     DRM_TRY(launch_softmax_rows(scores, (long long)nb * T, T, s));
-    ConvArgs b = attention_gemm(nb, H, W, T, C);  // O = P v
+    ConvArgs b = attention_gemm(nb, H, W, T, C);  // out = x + P v, and its statistics
+    b.res = x + (size_t)n0 * T * C; b.stat_out = out_stat + (size_t)n0 * C;
     b.src0 = scores;
     b.gn_scale = p_tab + (size_t)n0 * T; b.gn_shift = zero_tab + (size_t)n0 * Z;
     b.w = wv + (size_t)n0 * T * C; b.w_inv_img = v_inv + n0; b.in_inv = pv_inv + n0; b.out = out + (size_t)n0 * T * C;
@@ -737,21 +769,21 @@ int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* score
 
 size_t attention_small_workspace_floats(int N, int T, int C) {
   const size_t Z = (size_t)(C > T ? C : T);
-  return (size_t)N * (2 * C + T + Z) + 7 * (size_t)N + 64;
+  return (size_t)N * (C + T + Z) + 7 * (size_t)N + 64;
 }
 
 // Short-sequence form (T <= 256 off the conv pipeline, and every level of a sparse launch): S by qk_small_kernel, row softmax, P v by the 64x64-tile
 // GEMM.  qkv_mom + ws (attention_small_workspace_floats): the split modes stage q, k and v through their per-image powers of two (attn_scales_kernel --
-// the same range guard as the conv-pipeline form: |v| or |q| beyond fp16's range is exact), and proj_guard receives the guard tables of proj_out's
-// input (|attention output| <= max |v|) from the same launch.
-int launch_attention(const float* qkv, float* scores, float* out, int N, int T, int C, hipStream_t s, int terms, const double2* qkv_mom, float* ws,
-                     ConvArgs* proj_guard) {
+// the same range guard as the conv-pipeline form: |v| or |q| beyond fp16's range is exact).  The P v kernel of either form adds x and accumulates
+// out_stat (zeroed by the caller).
+int launch_attention(const float* qkv, const float* x, float* scores, float* out, double2* out_stat, int N, int T, int C, hipStream_t s, int terms,
+                     const double2* qkv_mom, float* ws) {
   bool split = terms != 0;
-  DRM_REQUIRE(C % 4 == 0 && T > 0 && N > 0, "attention shape");
+  DRM_REQUIRE(C % 4 == 0 && T > 0 && N > 0 && x && out_stat, "attention shape");
   const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
   const int tb = (T + 63) / 64;
   prof_tag(N, T, 1, C, C);
-  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 4 * C + 4.0 * T * T), s);
+  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C + 4.0 * T * T), s);
   // S = q k^T needs whole 32-chunks of C only (rows beyond T are masked); P v needs them of T: the 4x4 level (T = 16) of a 128x128 input keeps
   // the exact-fp32 form for P v and takes the split form for S like every other level
   const bool split_qk = split && (C % 32 == 0);
@@ -763,17 +795,11 @@ int launch_attention(const float* qkv, float* scores, float* out, int N, int T, 
     float* q_tab = ws;                        // [N][C]
     float* p_tab = q_tab + (size_t)N * C;     // [N][T]
     float* zero_tab = p_tab + (size_t)N * T;  // [N][max(C, T)]
-    float* o_tab = zero_tab + (size_t)N * Z;  // [N][C]
-    float* vec = o_tab + (size_t)N * C;       // 7 x [N]
+    float* vec = zero_tab + (size_t)N * Z;    // 7 x [N]
     qk_inv = vec; k_scale = vec + N; k_inv = vec + 2 * N; float* pv_inv = vec + 3 * N; v_scale = vec + 4 * N; v_inv = vec + 5 * N; q_scale = vec + 6 * N;
     hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, qkv_mom, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale,
-                       v_inv, o_tab, q_scale);
+                       v_inv, q_scale);
     DRM_HIP_CHECK(hipGetLastError());
-    if (proj_guard) {
-      proj_guard->gn_scale = o_tab;
-      proj_guard->gn_shift = zero_tab;
-      proj_guard->in_inv = v_inv;
-    }
   }
   const int NB = attention_group(N, T), t32 = (T + 31) / 32;
   const long long sq = (long long)T * 3 * C;  // image stride of qkv
@@ -782,6 +808,8 @@ int launch_attention(const float* qkv, float* scores, float* out, int N, int T, 
     const int nb = std::min(NB, N - n0);
     const float* qg = qkv + (size_t)n0 * sq;
     float* og = out + (size_t)n0 * T * C;
+    const float* xg = x + (size_t)n0 * T * C;
+    double2* sg = out_stat + (size_t)n0 * C;
     if (split_qk && terms == 4)
       hipLaunchKernelGGL(qk_small_kernel<4>, dim3(t32, t32, nb), dim3(256), 0, s, qg, qg + C, scores, T, C, 3 * C, sq, (long long)T * T, alpha, at(q_scale, n0), at(k_scale, n0), at(qk_inv, n0), at(k_inv, n0));
     else if (split_qk && terms == 1)
@@ -794,16 +822,16 @@ int launch_attention(const float* qkv, float* scores, float* out, int N, int T, 
     if (!split) DRM_TRY(launch_softmax_rows(scores, (long long)nb * T, T, s));  // (the split P v applies the row softmax while it stages the scores)
     if (split && terms == 4)
       hipLaunchKernelGGL(pv_small_kernel<4>, dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
-                         (long long)T * C, 1.0f, 1.0f, at(v_scale, n0), at(v_inv, n0));
+                         (long long)T * C, 1.0f, 1.0f, at(v_scale, n0), at(v_inv, n0), xg, sg);
     else if (split && terms == 1)  // probabilities are scaled by 2^12 before the fp16 conversion (largest 4096, smallest normal 2^-26)
       hipLaunchKernelGGL(pv_small_kernel<1>, dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
-                         (long long)T * C, 1.0f / 4096.0f, 4096.0f, at(v_scale, n0), at(v_inv, n0));
+                         (long long)T * C, 1.0f / 4096.0f, 4096.0f, at(v_scale, n0), at(v_inv, n0), xg, sg);
     else if (split)
       hipLaunchKernelGGL(pv_small_kernel<3>, dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
-                         (long long)T * C, 1.0f / 4096.0f, 4096.0f, at(v_scale, n0), at(v_inv, n0));
+                         (long long)T * C, 1.0f / 4096.0f, 4096.0f, at(v_scale, n0), at(v_inv, n0), xg, sg);
     else
       hipLaunchKernelGGL(bgemm64_kernel<false>, dim3((C + 63) / 64, tb, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, T, T, 3 * C, C,
-                         (long long)T * T, sq, (long long)T * C, 1.0f);
+                         (long long)T * T, sq, (long long)T * C, 1.0f, xg, sg);
     DRM_HIP_CHECK(hipGetLastError());
   }
   return DRM_OK;

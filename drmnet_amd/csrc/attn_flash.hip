@@ -94,12 +94,13 @@ __device__ __forceinline__ void fa_static_for(std::integer_sequence<int, I...>, 
 
 // q / k images: [C/32 chunks][8 planes: hi seg 0..3, lo seg 0..3][T rows][8 halfs] per image (pack_attn_weight_kernel<true> of attn.hip; seg =
 // slab * 2 + lane half); v image: [T/32 key chunks][8 planes][C channels][8 halfs] with the keys of a half-plane in accumulator order
-// (pack_attn_v_perm_kernel below).  out [N][T][C] fp32.  s_scale[n] = alpha 2^-kq 2^-kk, o_scale[n] = 2^-kv.
+// (pack_attn_v_perm_kernel below).  out = res + O [N][T][C] fp32 (res: the attention block's input; v carries the folded proj_out).
+// s_scale[n] = alpha 2^-kq 2^-kk, o_scale[n] = 2^-kv.
 // grid: N * T / 128 workgroups of 256 threads.
 template <int C, int TERMS>
 __global__ __launch_bounds__(256, 1) void attn_flash_kernel(const float4* __restrict__ qimg, const float4* __restrict__ kimg, const float4* __restrict__ vimg,
-                                                            float* __restrict__ out, const float* __restrict__ qk_inv, const float* __restrict__ k_inv,
-                                                            const float* __restrict__ v_inv, int N, int T) {
+                                                            const float* __restrict__ res, float* __restrict__ out, const float* __restrict__ qk_inv,
+                                                            const float* __restrict__ k_inv, const float* __restrict__ v_inv, int N, int T) {
   constexpr int CB = C / 32;                // channel blocks of O^T
   constexpr int NCH = C / 32;               // k / q chunk steps per key tile
   constexpr int NSL = FA_KT / 16;           // v slab steps per key tile
@@ -366,13 +367,17 @@ __global__ __launch_bounds__(256, 1) void attn_flash_kernel(const float4* __rest
   // ---- epilogue: O^T / (l FA_PSCALE 2^kv) (FA_PSCALE = 2^8, the staging factor of the probabilities): this lane's query, channels c * 32 + 8 g4 + 4 h + {0..3} per register group
   const float l = l_run + __shfl_xor(l_run, 32);
   const float fo = v_inv[n] / (FA_PSCALE * l);
-  float* op = out + ((size_t)n * T + q0 + wave * 32 + r) * C;
+  const size_t row_off = ((size_t)n * T + q0 + wave * 32 + r) * C;
+  float* op = out + row_off;
+  const float* rp = res + row_off;
 #pragma unroll
   for (int c = 0; c < CB; ++c)
 #pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4)
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const float4 x = *reinterpret_cast<const float4*>(rp + c * 32 + 8 * g4 + 4 * h);
       *reinterpret_cast<float4*>(op + c * 32 + 8 * g4 + 4 * h) =
-          make_float4(O[c][4 * g4] * fo, O[c][4 * g4 + 1] * fo, O[c][4 * g4 + 2] * fo, O[c][4 * g4 + 3] * fo);
+          make_float4(x.x + O[c][4 * g4] * fo, x.y + O[c][4 * g4 + 1] * fo, x.z + O[c][4 * g4 + 2] * fo, x.w + O[c][4 * g4 + 3] * fo);
+    }
 }
 
 // v[n] ([T keys][ld] fp32, channel c at column c) * scale[n] -> the v^T image of attn_flash_kernel: [T/32 key chunks][8 planes: hi seg 0..3, lo seg
@@ -418,38 +423,33 @@ bool attention_flash_applicable(int T, int C, int terms) { return (terms == 3 ||
 
 size_t attention_flash_workspace_floats(int N, int T, int C) {
   const size_t Z = (size_t)(C > T ? C : T);
-  return 3 * (size_t)N * T * C + (size_t)N * (2 * C + T + Z) + 7 * (size_t)N + 64;
+  return 3 * (size_t)N * T * C + (size_t)N * (C + T + Z) + 7 * (size_t)N + 64;
 }
 
 // (attn.hip)
 void launch_attn_scales(const double2* mom, int N, int C, int T, float alpha, float* q_tab, float* p_tab, float* zero_tab, float* qk_inv, float* k_scale,
-                        float* k_inv, float* pv_inv, float* v_scale, float* v_inv, float* o_tab, float* q_scale, hipStream_t s);
+                        float* k_inv, float* pv_inv, float* v_scale, float* v_inv, float* q_scale, hipStream_t s);
 int launch_pack_attn_rows(const float* src, long long img_stride, int ld, const float* scale, float* dst, int rows, int cin, int N, hipStream_t s, bool bf16);
 
-// qkv [N][T][3C] (+ its fused per-channel statistics), out [N][T][C], ws: attention_flash_workspace_floats.
-// proj_guard (optional): receives the (scale, shift, inverse) tables that guard proj_out's read of `out`, as launch_attention_conv does
-int launch_attention_flash(const float* qkv, const double2* qkv_mom, float* out, float* ws, int N, int T, int C, int terms, hipStream_t s, ConvArgs* proj_guard) {
-  DRM_REQUIRE(attention_flash_applicable(T, C, terms) && qkv_mom, "single-kernel attention: shape");
+// qkv [N][T][3C] (+ its fused per-channel statistics), x [N][T][C], out = x + P v [N][T][C], ws: attention_flash_workspace_floats.
+// The statistics of `out` are NOT accumulated here (the kernel runs one wave per SIMD on the whole register file, its epilogue has no LDS left
+// to reduce in): the caller takes them with the stand-alone moments launch.
+int launch_attention_flash(const float* qkv, const double2* qkv_mom, const float* x, float* out, float* ws, int N, int T, int C, int terms, hipStream_t s) {
+  DRM_REQUIRE(attention_flash_applicable(T, C, terms) && qkv_mom && x, "single-kernel attention: shape");
   const size_t Z = (size_t)(C > T ? C : T);
   float* wq = ws;                           // three pre-split images, T * C * 4 bytes per image each
   float* wk = wq + (size_t)N * T * C;
   float* wv = wk + (size_t)N * T * C;
-  float* q_tab = wv + (size_t)N * T * C;    // [N][C]   (tables of the conv-pipeline form: only o_tab / zero_tab / v_inv are read here, by proj_out)
+  float* q_tab = wv + (size_t)N * T * C;    // [N][C]   (tables of the conv-pipeline form, written by the shared scales kernel; only the [N] factors are read here)
   float* p_tab = q_tab + (size_t)N * C;     // [N][T]
   float* zero_tab = p_tab + (size_t)N * T;  // [N][max(C, T)]
-  float* o_tab = zero_tab + (size_t)N * Z;  // [N][C]
-  float* vec = o_tab + (size_t)N * C;       // 7 x [N]
+  float* vec = zero_tab + (size_t)N * Z;    // 7 x [N]
   float *qk_inv = vec, *k_scale = vec + N, *k_inv = vec + 2 * N, *pv_inv = vec + 3 * N, *v_scale = vec + 4 * N, *v_inv = vec + 5 * N, *q_scale = vec + 6 * N;
   const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
   prof_tag(N, T, 1, C, C);
-  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 4 * C), s);  // algorithmic bytes: q, k, v in, o out
-  launch_attn_scales(qkv_mom, N, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale, v_inv, o_tab, q_scale, s);
+  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C), s);  // algorithmic bytes: q, k, v, x in, out
+  launch_attn_scales(qkv_mom, N, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale, v_inv, q_scale, s);
   DRM_HIP_CHECK(hipGetLastError());
-  if (proj_guard) {
-    proj_guard->gn_scale = o_tab;
-    proj_guard->gn_shift = zero_tab;
-    proj_guard->in_inv = v_inv;
-  }
   const long long sq = (long long)T * 3 * C;
   DRM_TRY(launch_pack_attn_rows(qkv, sq, 3 * C, q_scale, wq, T, C, N, s, terms == 4));
   DRM_TRY(launch_pack_attn_rows(qkv + C, sq, 3 * C, k_scale, wk, T, C, N, s, terms == 4));
@@ -466,7 +466,7 @@ int launch_attention_flash(const float* qkv, const double2* qkv_mom, float* out,
       attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)(N * (T / FA_QT))), dim3(256), lds_bytes, s, reinterpret_cast<const float4*>(wq), reinterpret_cast<const float4*>(wk),
-                       reinterpret_cast<const float4*>(wv), out, qk_inv, k_inv, v_inv, N, T);
+                       reinterpret_cast<const float4*>(wv), x, out, qk_inv, k_inv, v_inv, N, T);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;
   };

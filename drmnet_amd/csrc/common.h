@@ -141,6 +141,10 @@ inline bool precision_valid(int p) { return p >= PREC_FP32 && p <= PREC_BF16; }
 inline int precision_terms(int p) { return p == PREC_F16 ? 1 : (p == PREC_BF16 ? 4 : (p == PREC_FP32 ? 0 : 3)); }
 // repack PyTorch conv weight [Cout][Cin][kh][kw] -> [taps][CinP/4][CoutP][4] (zero padded)
 int launch_pack_conv_weight(const float* w, float* packed, int Cout, int Cin, int taps, int CoutP, int CinP, hipStream_t s);
+// attention parameter fold (conv_split.hip): raw qkv [3C][C] / [3C] and proj_out [C][C] / [C] -> w_out [3C][C], b_out [3C] whose v rows hold
+// Wp Wv and Wp bv + bp (fp64 products, rounded once); what every attention block's qkv conv is packed from
+int launch_fold_attn_params(const float* qkv_w, const float* qkv_b, const float* proj_w, const float* proj_b, float* w_out, float* b_out, int C,
+                            hipStream_t s);
 size_t packed_conv_weight_floats(int taps, int CoutP, int CinP);
 
 // GroupNorm statistics (gn.hip)
@@ -157,29 +161,31 @@ int launch_gn_finalize(const double2* mom0, int C0, double inv0, const double2* 
                        const float* beta, int N, float* scale, float* shift, hipStream_t s, double cnt0 = 0.0, double cnt1 = 0.0,
                        float* guard_scale = nullptr, float* guard_shift = nullptr, float* guard_inv = nullptr);
 
-// attention (attn.hip): qkv [N][T][3C] -> out [N][T][C]; scores workspace [N][T][T]
+// attention (attn.hip): qkv [N][T][3C] (v thirds = proj_out folded into v: launch_fold_attn_params), x [N][T][C] the block's input
+// -> out = x + softmax(q k^T) v [N][T][C] and out_stat [N][C] += per-channel (sum, sum of squares) of out (zeroed by the caller);
+// scores workspace [N][T][T]
 size_t refmap_workspace_bytes(long long n, int res, float thr);
 int launch_refmap_mask_make(const float* colors, const float* normals, long long n, int C, int res, float thr, int min_points, float* refmap,
                             unsigned char* refmask, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_erode_mask(const unsigned char* mask, int H, int W, int k, unsigned char* out, hipStream_t s);
 // terms: 0 = fp32 MFMA, 3 = fp16 hi/lo split, 1 = plain fp16 operands
-// qkv_mom + ws (attention_small_workspace_floats floats): per-image range guard of q, k, v in the split modes; proj_guard then receives proj_out's guard tables
-int launch_attention(const float* qkv, float* scores, float* out, int N, int T, int C, hipStream_t s, int terms = 0, const double2* qkv_mom = nullptr,
-                     float* ws = nullptr, ConvArgs* proj_guard = nullptr);
+// qkv_mom + ws (attention_small_workspace_floats floats): per-image range guard of q, k, v in the split modes
+int launch_attention(const float* qkv, const float* x, float* scores, float* out, double2* out_stat, int N, int T, int C, hipStream_t s, int terms = 0,
+                     const double2* qkv_mom = nullptr, float* ws = nullptr);
 size_t attention_small_workspace_floats(int N, int T, int C);
 // split-precision attention core on the fused 1x1 conv pipeline (per-image weights = k, v^T): whether plan_conv takes both GEMMs
 bool attention_conv_planned(int H, int W, int C, int precision);
-// single-kernel form (attn_flash.hip): the long-sequence level (T >= 1024, C = 384), no score matrix in HBM
+// single-kernel form (attn_flash.hip): the long-sequence level (T >= 1024, C = 384), no score matrix in HBM; adds x, leaves out's statistics
+// to the caller (one wave per SIMD on the whole register file: no room for the reduction)
 bool attention_flash_applicable(int T, int C, int terms);
 size_t attention_flash_workspace_floats(int N, int T, int C);
-int launch_attention_flash(const float* qkv, const double2* qkv_mom, float* out, float* ws, int N, int T, int C, int terms, hipStream_t s, ConvArgs* proj_guard);
+int launch_attention_flash(const float* qkv, const double2* qkv_mom, const float* x, float* out, float* ws, int N, int T, int C, int terms, hipStream_t s);
 // images per attention pass and the score workspace that takes ([group, T, T] floats: independent of the batch beyond one group)
 int attention_group(int N, int T);
 size_t attention_scores_floats(int N, int T);
 size_t attention_conv_workspace_floats(int N, int T, int C);
-struct ConvArgs;
-int launch_attention_conv(const float* qkv, const double2* qkv_mom, float* scores, float* out, float* ws, int N, int H, int W, int C, int precision,
-                          hipStream_t s, ConvArgs* proj_guard = nullptr);
+int launch_attention_conv(const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat, float* ws, int N, int H,
+                          int W, int C, int precision, hipStream_t s);
 
 // boundary maps and the envmap warp (transform.hip)
 int launch_map_chain(const float* x, float* out, long long per_image, int B, const int32_t* ops, const float* args, int n_ops, const float* lo,

@@ -2,7 +2,7 @@
 //
 // Replaces, per call, the reference's  GroupNorm32 -> SiLU -> conv_nd  chains of ResBlock.in_layers /
 // out_layers (openaimodel.py:201-205,225-232,263,274), the stem/head convs (:534,:703-707), the 1x1
-// skip_connection (:241) and the k=1 Conv1d qkv / proj_out of AttentionBlock (:306,:314), including the
+// skip_connection (:241) and the k=1 Conv1d qkv of AttentionBlock (:306; proj_out :314 is folded into its v rows at load time), including the
 // th.cat of U-Net skips (:762) and the nearest x2 Upsample (:116), neither of which is ever materialised:
 // the A-tile loader reads two NHWC sources and an (y>>1, x>>1) address.
 //

@@ -8,7 +8,7 @@
 // matrix rate, at unchanged HBM traffic (activations stay fp32 in HBM; the split happens once per staged element, in
 // registers, right after the GroupNorm affine + SiLU).
 //   * activations: values a GroupNorm has just normalised are O(1) and are split as they are; an UN-normalised input (skip_connection,
-//     proj_out, stem, attention q / k / v) is first multiplied by a per-image power of two chosen from a rigorous bound of max |x|
+//     stem, attention q / k / v) is first multiplied by a per-image power of two chosen from a rigorous bound of max |x|
 //     (engine.hip raw_input_guard, gn.hip act_pow2_scale_kernel), so that nothing reaches fp16's limit and hi AND lo stay in the normal
 //     range; the epilogue multiplies by the inverse power of two (exact).  A clamp to +-65504 in front of the split is the last resort.
 //   * weights: pre-split at load time after an exact power-of-two scaling that moves max|w| to [8192, 16384), so the lo
@@ -126,6 +126,39 @@ int launch_pack_conv_weight_split(const float* w, float* packed, float* scales /
                        reinterpret_cast<unsigned char*>(packed), scales, Cout, Cin, taps, CoutP, CinP);
     DRM_HIP_CHECK(hipGetLastError());
   }
+  return DRM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Attention parameter fold (single head): proj_out is linear and every softmax row sums to one, so
+//     Wp (sum_s P[t,s] v_s) + bp = sum_s P[t,s] ((Wp Wv) xn_s + (Wp bv + bp))
+// and the block needs no proj_out conv when the v rows of the qkv conv hold Wp Wv and Wp bv + bp.  Formed once per parameter set from the
+// raw tensors, products accumulated in fp64 and rounded once to fp32; the q and k rows pass through.  The result is an ordinary
+// [3C][C] conv weight + [3C] bias for the packers above.   grid (ceil((C + 1) / 256), C): column C of a row is its bias.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fold_attn_params_kernel(const float* __restrict__ qkv_w, const float* __restrict__ qkv_b,
+                                                               const float* __restrict__ proj_w, const float* __restrict__ proj_b,
+                                                               float* __restrict__ w_out, float* __restrict__ b_out, int C) {
+  const int co = blockIdx.y, ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci > C) return;
+  const bool is_bias = ci == C;
+  const float* wv = qkv_w + (size_t)2 * C * C + (is_bias ? 0 : ci);
+  const float* bv = qkv_b + 2 * C;
+  const float* pr = proj_w + (size_t)co * C;
+  double acc = is_bias ? (double)proj_b[co] : 0.0;
+  for (int m = 0; m < C; ++m) acc += (double)pr[m] * (double)(is_bias ? bv[m] : wv[(size_t)m * C]);
+  for (int part = 0; part < 3; ++part) {
+    const size_t row = (size_t)part * C + co;
+    if (is_bias) b_out[row] = part == 2 ? (float)acc : qkv_b[row];
+    else w_out[row * C + ci] = part == 2 ? (float)acc : qkv_w[row * C + ci];
+  }
+}
+
+int launch_fold_attn_params(const float* qkv_w, const float* qkv_b, const float* proj_w, const float* proj_b, float* w_out, float* b_out, int C,
+                            hipStream_t s) {
+  DRM_REQUIRE(C > 0 && qkv_w && qkv_b && proj_w && proj_b && w_out && b_out, "attention parameter fold: arguments");
+  hipLaunchKernelGGL(fold_attn_params_kernel, dim3((unsigned)(C / 256 + 1), (unsigned)C), dim3(256), 0, s, qkv_w, qkv_b, proj_w, proj_b, w_out, b_out, C);
+  DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
 

@@ -66,7 +66,9 @@ struct Act {  // NHWC activation (+ cached per-channel moments for GroupNorm)
   bool mom_zeroed = false;  // table comes from the pass's pre-zeroed statistics pool
 };
 
-enum ParamKind { PK_COPY, PK_CONV };
+// PK_FOLDED: a tensor of an attention block that the fold launched at the block's qkv.weight slot consumes (qkv.bias, proj_out.*): load() copies
+// nothing for it on its own; proj_out.* have no storage in the packed buffer at all
+enum ParamKind { PK_COPY, PK_CONV, PK_FOLDED };
 
 struct ParamSlot {
   std::string name;
@@ -77,6 +79,7 @@ struct ParamSlot {
   int cout = 0, cin = 0, taps = 0, coutp = 0, cinp = 0;  // PK_CONV
   size_t scale_dst = 0;    // PK_CONV: 2 floats (2^k, 2^-k) of the split-precision weight pre-scaling
   bool mx_site = false;    // PK_CONV: a GroupNorm-fed 3x3 conv of a res block (PREC_F16MX packs the f16mx image for it)
+  bool attn_fold = false;  // PK_CONV: qkv.weight of an attention block -- packed from the fold of this and the next three tensors (qkv.bias, proj_out.*)
 };
 
 struct ResLayer {
@@ -88,7 +91,7 @@ struct ResLayer {
 };
 struct AttnLayer {
   int ch = 0;
-  size_t n_w = 0, n_b = 0, qkv_w = 0, qkv_b = 0, proj_w = 0, proj_b = 0, qkv_s = 0, proj_s = 0;
+  size_t n_w = 0, n_b = 0, qkv_w = 0, qkv_b = 0, qkv_s = 0;  // qkv: proj_out folded into the v rows (launch_fold_attn_params)
 };
 struct Layer {
   enum Kind { RES, ATTN, DOWN, UP } kind;

@@ -129,10 +129,16 @@ void UNet::add_attn(Layer& l, const std::string& px, int ch) {
   a.ch = ch;
   a.n_w = add_copy(px + ".norm.weight", {ch});
   a.n_b = add_copy(px + ".norm.bias", {ch});
+  // proj_out is folded into the v rows of qkv when a parameter set is loaded (load(): launch_fold_attn_params over these four tensors); the
+  // manifest keeps all of them, the packed buffer only the folded qkv
   a.qkv_w = add_conv(px + ".qkv.weight", 3 * ch, ch, 1, 3 * ch, ch, true, &a.qkv_s);
+  params.back().attn_fold = true;
   a.qkv_b = add_copy(px + ".qkv.bias", {3 * ch});
-  a.proj_w = add_conv(px + ".proj_out.weight", ch, ch, 1, ch, ch, true, &a.proj_s);
-  a.proj_b = add_copy(px + ".proj_out.bias", {ch});
+  params.back().kind = PK_FOLDED;
+  ParamSlot pw; pw.name = px + ".proj_out.weight"; pw.shape = {ch, ch, 1}; pw.kind = PK_FOLDED; pw.count = (size_t)ch * ch;
+  params.push_back(pw);
+  ParamSlot pb; pb.name = px + ".proj_out.bias"; pb.shape = {ch}; pb.kind = PK_FOLDED; pb.count = (size_t)ch;
+  params.push_back(pb);
 }
 
 int UNet::build(const drm_unet_desc& d) {
@@ -254,16 +260,41 @@ int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
   float* wbuf = wsets[set];
   loaded[set] = false;
   DRM_HIP_CHECK(hipMemsetAsync(wbuf, 0, wbuf_floats * sizeof(float), s));
+  // staging for the folded attention parameters ([3C][C] weight + [3C] bias of the widest block): reused block after block in stream order,
+  // freed when the last pack has run
+  struct Staging {
+    float* p = nullptr;
+    hipStream_t s;
+    ~Staging() {
+      if (p) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(p);
+      }
+    }
+  } fold{nullptr, s};
+  size_t fold_floats = 0;
+  for (const ParamSlot& p : params)
+    if (p.attn_fold) fold_floats = std::max(fold_floats, (size_t)p.cout * p.cin + (size_t)p.cout);
+  if (fold_floats) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fold.p), fold_floats * sizeof(float)));
   for (size_t i = 0; i < params.size(); ++i) {
     const ParamSlot& p = params[i];
     DRM_REQUIRE(ptrs[i] != nullptr, "null parameter pointer for " + p.name);
+    if (p.kind == PK_FOLDED) continue;  // (consumed at the block's qkv.weight slot)
+    const float* w = ptrs[i];
+    if (p.attn_fold) {
+      DRM_REQUIRE(i + 3 < params.size() && ptrs[i + 1] && ptrs[i + 2] && ptrs[i + 3], "attention block parameters of " + p.name);
+      float* fb = fold.p + (size_t)p.cout * p.cin;
+      DRM_TRY(launch_fold_attn_params(ptrs[i], ptrs[i + 1], ptrs[i + 2], ptrs[i + 3], fold.p, fb, p.cin, s));
+      DRM_HIP_CHECK(hipMemcpyAsync(wbuf + params[i + 1].dst, fb, (size_t)p.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+      w = fold.p;
+    }
     if (p.kind == PK_COPY) {
-      DRM_HIP_CHECK(hipMemcpyAsync(wbuf + p.dst, ptrs[i], p.count * sizeof(float), hipMemcpyDeviceToDevice, s));
+      DRM_HIP_CHECK(hipMemcpyAsync(wbuf + p.dst, w, p.count * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else if (conv_split_weights(precision, p.cinp)) {
-      DRM_TRY(launch_pack_conv_weight_split(ptrs[i], wbuf + p.dst, wbuf + p.scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), p.cout,
+      DRM_TRY(launch_pack_conv_weight_split(w, wbuf + p.dst, wbuf + p.scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), p.cout,
                                             p.cin, p.taps, p.coutp, p.cinp, s, precision == PREC_F16MX && p.mx_site, precision == PREC_BF16));
     } else {
-      DRM_TRY(launch_pack_conv_weight(ptrs[i], wbuf + p.dst, p.cout, p.cin, p.taps, p.coutp, p.cinp, s));
+      DRM_TRY(launch_pack_conv_weight(w, wbuf + p.dst, p.cout, p.cin, p.taps, p.coutp, p.cinp, s));
     }
   }
   if (stem_direct_w >= 0) DRM_TRY(launch_pack_stem_weight(ptrs[stem_param], wbuf + stem_direct_w, desc.model_channels, desc.in_channels, precision == PREC_FP32, s));
@@ -322,7 +353,7 @@ int run_conv(Ctx& c, ConvArgs& a, const ConvPlan& p, const float* Wb, size_t sca
   return launch_conv(a, p, c.s);
 }
 
-// Split-precision convs on an UN-normalised input (skip_connection, proj_out, stem): stage it through a per-image power of two
+// Split-precision convs on an UN-normalised input (skip_connection, stem): stage it through a per-image power of two
 // derived from a rigorous bound of max |x| (gn.hip act_pow2_scale_kernel) so nothing saturates or underflows fp16; the factor rides
 // on the (scale, shift) tables the staging path applies anyway and is undone per image in the epilogue.  Bound source: the
 // per-channel sum-of-squares tables of x0 (channels [lo0, hi0)) and x1, or an absmax word per image.  No-op in fp32 mode.
@@ -446,6 +477,7 @@ int run_resblock(Ctx& c, const float* Wb, const ResLayer& r, Act& x0, Act* x1, c
   return DRM_OK;
 }
 
+// GroupNorm(x) -> qkv 1x1 conv (proj_out folded into its v rows) -> attention core, whose last kernel adds x and leaves out's statistics
 int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out) {
   DRM_REQUIRE(!x.up && x.C == l.ch, "attention input");
   DRM_TRY(arena_ok(c));
@@ -457,43 +489,54 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
   a.C0 = C; a.N = c.N; a.H = H; a.W = W; a.taps = 1; a.Cout = 3 * C;
   const ConvPlan pa = plan_conv(a, c.precision, false, true);
   DRM_TRY(gn_params(c, x, nullptr, Wb + l.n_w, Wb + l.n_b, sc, sh, nullptr, pa.gn_fold ? &a : nullptr));
-  Act qkv_act = new_act(c, 3 * C, H, W);  // its per-channel sums (fused into the qkv conv's epilogue) bound |v| >= |attention output|
+  Act qkv_act = new_act(c, 3 * C, H, W);  // its per-channel sums (fused into the qkv conv's epilogue) bound |q|, |k|, |v| for the split cores
   float* qkv = qkv_act.p;
   const bool flash = c.split() && attention_flash_applicable(T, C, c.terms());  // the long-sequence level: one kernel, no score matrix (attn_flash.hip)
   float* scores = flash ? nullptr : c.ar->alloc<float>(attention_scores_floats(c.N, T));  // one image group at a time (attn.hip attention_group)
-  float* att = c.ar->alloc<float>((size_t)c.N * T * C);
+  // Sizing contract: what drm_*_workspace_bytes answers per network, shape and mode is a recorded table (tests/golden/workspace_bytes.json) that
+  // callers size long-lived buffers by.  The fold removed the proj_out stage -- its input tensor, its [N][C] guard table, its split-K slabs and
+  // tickets -- and the block still reserves their share of the arena and of the statistics pool, untouched, in the order they were taken, so
+  // every recorded answer stands.  (Dropping the reservation means re-recording that table; nothing here reads these bytes.)
+  (void)c.ar->alloc<float>((size_t)c.N * T * C);
+  const size_t proj_tab = (size_t)c.N * C;
   // the T >= 256 levels: both GEMMs on the conv pipeline -- except on sparse launches (the 16x16 level of a batch-1 step: six launches, 51 us, where
   // the short-sequence form -- qk_small, softmax, P v -- takes three and ~25 us)
   const bool on_conv = flash || (attention_conv_planned(H, W, C, c.precision) && (long long)c.N * T > 1024);
-  // (the short-sequence form in the split modes: per-image guard factors + proj_out's guard tables, from one attn_scales launch)
+  // (the short-sequence form in the split modes: per-image guard factors from one attn_scales launch)
   const bool small_guard = !on_conv && c.split() && C % 32 == 0;
-  float* aws = flash ? c.ar->alloc<float>(attention_flash_workspace_floats(c.N, T, C))
-               : on_conv ? c.ar->alloc<float>(attention_conv_workspace_floats(c.N, T, C))
-               : small_guard ? c.ar->alloc<float>(attention_small_workspace_floats(c.N, T, C)) : nullptr;
-  ConvArgs p;  // proj_out: 1x1 conv on the raw attention output, a convex combination of v rows: max |att| <= max |v|
+  float* aws = flash ? c.ar->alloc<float>(attention_flash_workspace_floats(c.N, T, C) + proj_tab)
+               : on_conv ? c.ar->alloc<float>(attention_conv_workspace_floats(c.N, T, C) + proj_tab)
+               : small_guard ? c.ar->alloc<float>(attention_small_workspace_floats(c.N, T, C) + proj_tab) : nullptr;
   splitk_workspace(c, a, pa);
-  p.C0 = C; p.N = c.N; p.H = H; p.W = W; p.taps = 1; p.Cout = C;
-  const ConvPlan pp = plan_conv(p, c.precision);
-  splitk_workspace(c, p, pp);
+  {  // (the sizing contract above: the split-K share of a C -> C 1x1 conv on this map)
+    ConvArgs p;
+    p.C0 = C; p.N = c.N; p.H = H; p.W = W; p.taps = 1; p.Cout = C;
+    const ConvPlan pp = plan_conv(p, c.precision);
+    if (pp.ksplit > 1) {
+      bool zeroed = false;
+      if (pp.finish == SPLIT_IN_LAUNCH) (void)c.ar->alloc_stats(pp.tickets * sizeof(unsigned), &zeroed);
+      (void)c.ar->alloc<float>((size_t)c.N * T * C * pp.ksplit);
+    }
+  }
   if (!c.dry()) {
     a.src0 = x.p;
     a.gn_scale = sc; a.gn_shift = sh; a.silu = 0;
     a.w = Wb + l.qkv_w; a.bias = Wb + l.qkv_b; a.out = qkv;
     DRM_TRY(run_conv(c, a, pa, Wb, l.qkv_s, &qkv_act));
-    if (flash) DRM_TRY(launch_attention_flash(qkv, qkv_act.mom, att, aws, c.N, T, C, c.terms(), c.s, &p));
-    else if (on_conv) DRM_TRY(launch_attention_conv(qkv, qkv_act.mom, scores, att, aws, c.N, H, W, C, c.precision, c.s, &p));
-    else DRM_TRY(launch_attention(qkv, scores, att, c.N, T, C, c.s, c.split() ? c.terms() : 0, small_guard ? qkv_act.mom : nullptr, aws, small_guard ? &p : nullptr));
-  } else {
-    qkv_act.mom_valid = true;  // sizing pass: the table is filled by the conv epilogue, no stand-alone moments launch
-    qkv_act.mom_sums = true;
-  }
-  if (!on_conv && !small_guard) DRM_TRY(raw_input_guard(c, p, pp, &qkv_act, 2 * C, 3 * C, nullptr, nullptr, C));  // (the attention cores of the split modes hand p its guard tables)
-  if (!c.dry()) {
-    p.src0 = att;
-    p.w = Wb + l.proj_w; p.bias = Wb + l.proj_b; p.res = x.p; p.out = out.p;
-    DRM_TRY(run_conv(c, p, pp, Wb, l.proj_s, &out));
+    if (!flash && !out.mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(out.mom, 0, (size_t)c.N * C * sizeof(double2), c.s));
+    if (flash) DRM_TRY(launch_attention_flash(qkv, qkv_act.mom, x.p, out.p, aws, c.N, T, C, c.terms(), c.s));
+    else if (on_conv) DRM_TRY(launch_attention_conv(qkv, qkv_act.mom, x.p, scores, out.p, out.mom, aws, c.N, H, W, C, c.precision, c.s));
+    else DRM_TRY(launch_attention(qkv, x.p, scores, out.p, out.mom, c.N, T, C, c.s, c.split() ? c.terms() : 0, small_guard ? qkv_act.mom : nullptr, aws));
   }
   c.ar->release(mark);
+  if (flash) {  // (the single-kernel form leaves the statistics of its output to the stand-alone moments launch; its partial table takes the
+                //  place of the block's temporaries, which are dead in stream order)
+    out.mom_valid = false;
+    DRM_TRY(ensure_moments(c, out));
+  } else {
+    out.mom_valid = true;
+    out.mom_sums = true;
+  }
   return DRM_OK;
 }
 

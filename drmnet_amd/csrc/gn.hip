@@ -106,8 +106,8 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double2* __restr
   gn_finalize_image(f, blockIdx.x, threadIdx.x, 256, scratch);  // (gn_fold.h: the same code runs in the prologue of sparse conv launches)
 }
 
-// Range guard of the split-precision path for UN-normalised conv inputs (ResBlock skip_connection, AttentionBlock proj_out, the
-// stem: openaimodel.py:241, :314, :534).  The fp16 hi/lo split keeps 22 bits only while the staged values sit inside fp16's
+// Range guard of the split-precision path for UN-normalised conv inputs (ResBlock skip_connection, the
+// stem: openaimodel.py:241, :534).  The fp16 hi/lo split keeps 22 bits only while the staged values sit inside fp16's
 // normal range, so such a tensor is staged through an exact power-of-two factor per image, undone in the epilogue:
 //   bound[n] = a rigorous upper bound of max |x| over image n  --  sqrt(max_c sum_pixels x^2), from the per-channel (sum, sum of
 //              squares) tables the GroupNorm fusion already keeps, or an explicit absmax word;
