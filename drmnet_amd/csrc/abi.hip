@@ -88,10 +88,16 @@ int pack_for_ops(int prec, const float* w, float* dst, float* slot, float* scrat
 
 size_t unet_ws(UNet& net, int N, int H, int W) {
   Arena a;
-  a.dry = true;
-  const int Cx = net.desc.kind == 0 ? net.desc.out_channels : net.desc.in_channels / 2;
-  if (net.forward(nullptr, Cx, nullptr, net.desc.in_channels - Cx, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, a, nullptr) != DRM_OK) return 0;
+  if (net.dry_forward(N, H, W, a) != DRM_OK) return 0;
   return a.peak + 256;
+}
+
+// the tail of the DDIM / DDPM chain entry points: the caller's workspace as the arena, then the chain over it
+template <typename Body>
+int run_chain(drm_unet* net, const ChainIO& io, void* workspace, size_t workspace_bytes, Body&& chain) {
+  Arena ar;
+  DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, io.N, io.H, io.W)));
+  return chain(ar);
 }
 
 }  // namespace
@@ -406,9 +412,10 @@ int drm_ddim_sample(drm_unet* net, float* x, const float* cond, const int64_t* t
                     const float* noise, uint64_t seed, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
   return guarded([&]() -> int {
     DRM_REQUIRE(net && x && cond, "null argument");
-    Arena ar;
-    DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, N, H, W)));
-    return ddim_sample(&net->net, x, cond, timesteps, coef, S, num_steps, noise, seed, N, H, W, ar, static_cast<hipStream_t>(stream));
+    const ChainIO io{x, cond, noise, seed, N, H, W};
+    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
+      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, ChainLog{}, drm_sampler_options{}, ar, static_cast<hipStream_t>(stream));
+    });
   });
 }
 
@@ -418,13 +425,11 @@ int drm_ddim_sample_logged(drm_unet* net, float* x, const float* cond, const int
   return guarded([&]() -> int {
     DRM_REQUIRE(net && x && cond, "null argument");
     DRM_REQUIRE(log_every_t > 0 && log_x && log_pred_x0 && log_slots > 0, "ddim intermediates: log_every_t, both log buffers and their slot count");
-    Arena ar;
-    DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, N, H, W)));
-    int logged = 0;
-    const int rc = ddim_sample(&net->net, x, cond, timesteps, coef, S, num_steps, noise, seed, N, H, W, ar, static_cast<hipStream_t>(stream), log_every_t, log_x,
-                               log_pred_x0, log_slots, &logged);
-    if (n_logged) *n_logged = logged;
-    return rc;
+    const ChainIO io{x, cond, noise, seed, N, H, W};
+    const ChainLog log{log_every_t, log_x, log_pred_x0, log_slots, n_logged};
+    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
+      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, log, drm_sampler_options{}, ar, static_cast<hipStream_t>(stream));
+    });
   });
 }
 
@@ -432,16 +437,11 @@ int drm_ddpm_sample(drm_unet* net, float* x, float* pred_x0, const float* cond, 
                     const float* noise, uint64_t seed, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
   return guarded([&]() -> int {
     DRM_REQUIRE(net && x && cond, "null argument");
-    Arena ar;
-    DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, N, H, W)));
-    return ddpm_sample(&net->net, x, pred_x0, cond, coef, T_start, clip_denoised, noise, seed, N, H, W, ar, static_cast<hipStream_t>(stream));
+    const ChainIO io{x, cond, noise, seed, N, H, W};
+    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
+      return ddpm_sample(&net->net, io, pred_x0, coef, T_start, clip_denoised, drm_sampler_options{}, ar, static_cast<hipStream_t>(stream));
+    });
   });
-}
-
-static MaskBlend to_blend(const drm_mask_blend* b) {
-  MaskBlend m;
-  m.mask = b->mask; m.mask_channels = b->mask_channels; m.x0 = b->x0; m.qcoef = b->qcoef; m.qnoise = b->qnoise; m.when = b->when;
-  return m;
 }
 
 int drm_ddim_sample_ex(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
@@ -450,16 +450,12 @@ int drm_ddim_sample_ex(drm_unet* net, float* x, const float* cond, const int64_t
   return guarded([&]() -> int {
     DRM_REQUIRE(net && x && cond && opt, "null argument");
     DRM_REQUIRE(log_every_t <= 0 || (log_x && log_pred_x0 && log_slots > 0), "ddim intermediates: both log buffers and their slot count");
-    Arena ar;
-    DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, N, H, W)));
-    MaskBlend mb;
-    if (opt->blend) mb = to_blend(opt->blend);
-    int logged = 0;
-    const int rc = ddim_sample(&net->net, x, cond, timesteps, coef, S, num_steps, noise, seed, N, H, W, ar, static_cast<hipStream_t>(stream),
-                               log_every_t > 0 ? log_every_t : 0, log_every_t > 0 ? log_x : nullptr, log_every_t > 0 ? log_pred_x0 : nullptr, log_slots, &logged,
-                               opt->blend ? &mb : nullptr, opt->uncond, opt->guidance_scale, opt->noise_dropout, opt->dropout_keep);
-    if (n_logged) *n_logged = logged;
-    return rc;
+    const ChainIO io{x, cond, noise, seed, N, H, W};
+    ChainLog log{0, nullptr, nullptr, log_slots, n_logged};  // (log_every_t <= 0: no intermediates, whatever the buffers)
+    if (log_every_t > 0) log = ChainLog{log_every_t, log_x, log_pred_x0, log_slots, n_logged};
+    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
+      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, log, *opt, ar, static_cast<hipStream_t>(stream));
+    });
   });
 }
 
@@ -469,12 +465,10 @@ int drm_ddpm_sample_ex(drm_unet* net, float* x, float* pred_x0, const float* con
   return guarded([&]() -> int {
     DRM_REQUIRE(net && x && cond && opt, "null argument");
     DRM_REQUIRE(opt->uncond == nullptr, "drm_ddpm_sample_ex: classifier-free guidance exists on the DDIM chain only (ddim.py:225-232; ddpm.py p_sample has none)");
-    Arena ar;
-    DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, N, H, W)));
-    MaskBlend mb;
-    if (opt->blend) mb = to_blend(opt->blend);
-    return ddpm_sample(&net->net, x, pred_x0, cond, coef, T_start, clip_denoised, noise, seed, N, H, W, ar, static_cast<hipStream_t>(stream), opt->blend ? &mb : nullptr,
-                       opt->noise_dropout, opt->dropout_keep);
+    const ChainIO io{x, cond, noise, seed, N, H, W};
+    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
+      return ddpm_sample(&net->net, io, pred_x0, coef, T_start, clip_denoised, *opt, ar, static_cast<hipStream_t>(stream));
+    });
   });
 }
 

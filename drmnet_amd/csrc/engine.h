@@ -128,6 +128,7 @@ class UNet {
   std::map<std::tuple<int, int, int, int>, size_t> stats_pool_cache;  // (N, H, W, precision) -> bytes of the statistics pool (split-K tickets live in it)
   int forward(const float* x, int Cx, const float* cond, int Cc, const int32_t* rows, const float* t_emb, const int64_t* t, const float* tf,
               float* out, int N, int H, int W, Arena& ar, hipStream_t s);
+  int dry_forward(int N, int H, int W, Arena& probe);  // the sizing walk: makes `probe` a dry arena and runs forward over it with no tensors
   ~UNet();
 
  private:

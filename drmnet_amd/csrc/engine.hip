@@ -542,6 +542,12 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
 
 // ------------------------------------------------------------------------------------------------ forward
 
+int UNet::dry_forward(int N, int H, int W, Arena& probe) {
+  probe.dry = true;
+  const int Cx = desc.kind == 0 ? desc.out_channels : desc.in_channels / 2;  // (forward only checks that the two parts sum to in_channels)
+  return forward(nullptr, Cx, nullptr, desc.in_channels - Cx, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, probe, nullptr);
+}
+
 int UNet::forward(const float* x, int Cx, const float* cond, int Cc, const int32_t* rows, const float* t_emb, const int64_t* t,
                   const float* tf, float* out, int N, int H, int W, Arena& ar, hipStream_t s) {
   DRM_REQUIRE(ar.dry || loaded[active], "drm_unet_forward before drm_unet_load_params (weight set " + std::to_string(active) + ")");
@@ -569,8 +575,7 @@ int UNet::forward(const float* x, int Cx, const float* cond, int Cc, const int32
     auto it = stats_pool_cache.find(key);
     if (it == stats_pool_cache.end()) {
       Arena probe;
-      probe.dry = true;
-      DRM_TRY(forward(nullptr, Cx, nullptr, Cc, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, probe, s));
+      DRM_TRY(dry_forward(N, H, W, probe));
       it = stats_pool_cache.emplace(key, probe.st_off).first;
     }
     ar.st_cap = it->second;

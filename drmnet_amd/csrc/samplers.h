@@ -54,21 +54,24 @@ class DrmnetSampler {
 size_t sampler_workspace_bytes(UNet* net, int N, int H, int W);
 void set_graph_replay(bool on);   // DDIM / DDPM chains: replay one captured hipGraph of a step (default off)
 long long graph_launches();       // hipGraphLaunch calls made so far (tests / bench read it)
-// mask / x0 blending of a DDIM / DDPM chain (drm_mask_blend of the C ABI; see mask_blend_kernel)
-struct MaskBlend {
-  const float* mask = nullptr;    // [N, mask_channels, H, W] device
-  int mask_channels = 1;          // 1 (broadcast) or out_channels
-  const float* x0 = nullptr;      // [N, C, H, W] device
-  const float* qcoef = nullptr;   // [steps][2] host: (sqrt(a_bar), sqrt(1 - a_bar)) of q_sample for the blend of chain step j
-  const float* qnoise = nullptr;  // [steps][N, C, H, W] device or null (Philox)
-  int when = 0;                   // 0 = before the step's network forward, 1 = after its update
+// a DDIM / DDPM chain's tensors and shape
+struct ChainIO {
+  float* x;            // [N,C,H,W] device: in = x_T, out = the chain's last x
+  const float* cond;   // [N,Cc,H,W] device
+  const float* noise;  // [steps][N,C,H,W] device, or null: Philox(seed)
+  uint64_t seed;
+  int N, H, W;
 };
-// log_every_t > 0 with log_x / log_pred ([log_slots][N,3,H,W] each): the reference's intermediates (ddim.py:198-200), *n_logged = slots written
-int ddim_sample(UNet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps, const float* noise,
-                uint64_t seed, int N, int H, int W, Arena& ar, hipStream_t s, int log_every_t = 0, float* log_x = nullptr, float* log_pred = nullptr,
-                int log_slots = 0, int* n_logged = nullptr, const MaskBlend* blend = nullptr, const float* uncond = nullptr, float guidance_scale = 1.0f,
-                float drop_p = 0.f, const float* drop_keep = nullptr);
-int ddpm_sample(UNet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip, const float* noise,
-                uint64_t seed, int N, int H, int W, Arena& ar, hipStream_t s, const MaskBlend* blend = nullptr, float drop_p = 0.f, const float* drop_keep = nullptr);
+// the reference's intermediates (ddim.py:198-200): every_t > 0 with x / pred ([slots][N,C,H,W] each), *n_logged = slots written
+struct ChainLog {
+  int every_t;
+  float *x, *pred;
+  int slots;
+  int* n_logged;
+};
+// opt: drm_sampler_options of the C ABI (mask / x0 blending: see mask_blend_kernel; uncond + guidance_scale: DDIM only; noise dropout)
+int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const float* coef, int S, int num_steps, const ChainLog& log,
+                const drm_sampler_options& opt, Arena& ar, hipStream_t s);
+int ddpm_sample(UNet* net, const ChainIO& io, float* pred_x0, const float* coef, int T_start, int clip, const drm_sampler_options& opt, Arena& ar, hipStream_t s);
 
 }  // namespace drm

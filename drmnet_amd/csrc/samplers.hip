@@ -307,10 +307,8 @@ static StepBuffers step_buffers(Arena& ar, int n, int zd, int mc, size_t chw) {
 size_t DrmnetSampler::part_need(int nmax, int H, int W) const {
   for (const auto& e : part_need_memo)
     if (e.n == nmax && e.H == H && e.W == W) return e.bytes;
-  Arena p1; p1.dry = true;
-  Arena p2; p2.dry = true;
-  if (illnet->forward(nullptr, 3, nullptr, 3, nullptr, nullptr, nullptr, nullptr, nullptr, nmax, H, W, p1, nullptr) != DRM_OK) return ~size_t(0);
-  if (refnet->forward(nullptr, 3, nullptr, 3, nullptr, nullptr, nullptr, nullptr, nullptr, nmax, H, W, p2, nullptr) != DRM_OK) return ~size_t(0);
+  Arena p1, p2;
+  if (illnet->dry_forward(nmax, H, W, p1) != DRM_OK || refnet->dry_forward(nmax, H, W, p2) != DRM_OK) return ~size_t(0);
   const size_t need = (std::max(p1.peak, p2.peak) + 255) & ~size_t(255);
   if (part_need_memo.size() >= 64) part_need_memo.clear();
   part_need_memo.push_back({nmax, H, W, need});
@@ -324,10 +322,8 @@ size_t DrmnetSampler::workspace_bytes(int N, int H, int W) const {
   ar.alloc<int32_t>((size_t)N);  // rows
   ar.alloc_bytes(0);
   const size_t base = (ar.peak + 255) & ~size_t(255);
-  Arena a1; a1.dry = true;
-  Arena a2; a2.dry = true;
-  if (illnet->forward(nullptr, 3, nullptr, 3, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, a1, nullptr) != DRM_OK) return 0;
-  if (refnet->forward(nullptr, 3, nullptr, 3, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, a2, nullptr) != DRM_OK) return 0;
+  Arena a1, a2;
+  if (illnet->dry_forward(N, H, W, a1) != DRM_OK || refnet->dry_forward(N, H, W, a2) != DRM_OK) return 0;
   size_t need = std::max(a1.peak, a2.peak);
   for (int np = 2; np <= std::min(std::min(parts, (int)PART_MAX), N / std::max(part_min, 1)); ++np) {  // the batch parts' workspace slices (step)
     const size_t pn = part_need((N + np - 1) / np, H, W);
@@ -472,8 +468,7 @@ int DrmnetSampler::sample(const float* LrK, const float* cond, const float* nois
 
 size_t sampler_workspace_bytes(UNet* net, int N, int H, int W) {
   Arena a;
-  a.dry = true;
-  if (net->forward(nullptr, 3, nullptr, 3, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, a, nullptr) != DRM_OK) return 0;
+  if (net->dry_forward(N, H, W, a) != DRM_OK) return 0;
   const size_t chw = (size_t)net->desc.out_channels * H * W;
   // U-Net arena + eps [N,C,H,W] + timesteps [N] + the per-step scalar table (<= 4096 steps) and its counter
   // (+ the mask-blend (a, b) pair per step, same bound)
@@ -597,7 +592,7 @@ static int upload_step_table(const std::vector<float>& rows, float* tab, int* co
 }
 
 // uploads the blend's per-step (a, b) pairs behind the step table (same stream, pageable source: hipMemcpyAsync returns after staging it)
-static int upload_blend_table(const MaskBlend* blend, int steps, float* qtab, hipStream_t s) {
+static int upload_blend_table(const drm_mask_blend* blend, int steps, float* qtab, hipStream_t s) {
   DRM_REQUIRE(blend->mask && blend->x0 && blend->qcoef, "mask blending needs mask, x0 and the per-step q_sample coefficients");
   DRM_REQUIRE(blend->mask_channels >= 1 && (blend->when == 0 || blend->when == 1), "mask blending: mask_channels >= 1, when = 0 (before the forward) or 1 (after the update)");
   DRM_HIP_CHECK(hipMemcpyAsync(qtab, blend->qcoef, (size_t)steps * 2 * sizeof(float), hipMemcpyHostToDevice, s));
@@ -605,15 +600,25 @@ static int upload_blend_table(const MaskBlend* blend, int steps, float* qtab, hi
   return DRM_OK;
 }
 
-int ddim_sample(UNet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps, const float* noise,
-                uint64_t seed, int N, int H, int W, Arena& ar, hipStream_t caller, int log_every_t, float* log_x, float* log_pred, int log_slots,
-                int* n_logged, const MaskBlend* blend, const float* uncond, float guidance_scale, float drop_p, const float* drop_keep) {
-  DRM_REQUIRE(net && net->desc.kind == 0, "ddim needs a UNetModel");
-  DRM_REQUIRE(S >= 1 && timesteps && coef, "ddim schedule");
-  DRM_REQUIRE(S <= MAX_TABLE_STEPS, "ddim: at most " + std::to_string(MAX_TABLE_STEPS) + " steps (the workspace budgets the step table for that many)");
+// What chain_run hands the samplers' update callables: the chain's stream and the workspace buffers of a step.
+struct Chain {
+  hipStream_t s;
+  float *e, *e_u, *tf, *tab;  // eps [N,C,H,W] (e_u: the unconditional branch, with opt.uncond), timesteps [N], the step table
+  int* counter;
+  int Cx, Cc;
+  size_t n, mark;  // elements of x; the arena mark a network forward starts from
+};
+
+// The fixed-length chains' shared driver: workspace, option checks, the two device tables, and `steps` replayable steps of
+//   step_begin -> blend (when 0) -> forward -> update(chain) -> blend (when 1) -> step_advance.
+// fill(rows) writes the STEP_ROW floats of every step; update(chain) launches what follows the conditional forward.
+template <typename Fill, typename Update>
+static int chain_run(const std::string& name, UNet* net, const ChainIO& io, int steps, const drm_sampler_options& opt, Arena& ar, hipStream_t caller,
+                     Fill&& fill, Update&& update) {
+  const drm_mask_blend* blend = opt.blend;
+  const int N = io.N, H = io.H, W = io.W;
   const int Cx = net->desc.out_channels, Cc = net->desc.in_channels - Cx;
   const size_t n = (size_t)N * Cx * H * W;
-  const int steps = (num_steps > 0 && num_steps < S) ? num_steps : S;
   hipStream_t s;
   DRM_TRY(chain_stream(caller, steps, &s));
   float* e = ar.alloc<float>(n);
@@ -621,31 +626,20 @@ int ddim_sample(UNet* net, float* x, const float* cond, const int64_t* timesteps
   float* tab = ar.alloc<float>((size_t)steps * STEP_ROW);
   int* counter = ar.alloc<int>(1);
   float* qtab = blend ? ar.alloc<float>((size_t)steps * 2) : nullptr;
-  float* e_u = uncond ? ar.alloc<float>(n) : nullptr;
-  if (ar.failed) { set_error("ddim: workspace too small"); return DRM_ERR_WORKSPACE; }
-  DRM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "noise_dropout: 0 <= p < 1");
+  float* e_u = opt.uncond ? ar.alloc<float>(n) : nullptr;
+  if (ar.failed) { set_error(name + ": workspace too small"); return DRM_ERR_WORKSPACE; }
+  DRM_REQUIRE(opt.noise_dropout >= 0.f && opt.noise_dropout < 1.f, "noise_dropout: 0 <= p < 1");
   DRM_REQUIRE(!blend || blend->mask_channels == 1 || blend->mask_channels == Cx, "mask blending: the mask has 1 or out_channels channels");
   std::vector<float> rows((size_t)steps * STEP_ROW, 0.f);
-  int logged = 0;
-  DRM_REQUIRE(!log_x || log_pred, "ddim: the intermediates log needs both buffers");
-  for (int j = 0; j < steps; ++j) {
-    const int index = S - 1 - j;
-    rows[(size_t)j * STEP_ROW] = (float)timesteps[index];
-    for (int k = 0; k < 5; ++k) rows[(size_t)j * STEP_ROW + 1 + k] = coef[5 * index + k];
-    // the reference appends (img, pred_x0) after the step of `index` when index % log_every_t == 0 or at the first step (ddim.py:198-200)
-    if (log_x && log_every_t > 0 && (index % log_every_t == 0 || index == S - 1)) {
-      DRM_REQUIRE(logged < log_slots, "ddim: the intermediates log has too few slots");
-      rows[(size_t)j * STEP_ROW + 7] = (float)(++logged);
-    }
-  }
-  if (n_logged) *n_logged = logged;
+  DRM_TRY(fill(rows.data()));
   DRM_TRY(upload_step_table(rows, tab, counter, s));
   if (blend) DRM_TRY(upload_blend_table(blend, steps, qtab, s));
   const size_t mark = ar.mark();
   const size_t hw = (size_t)H * W;
+  const Chain c{s, e, e_u, tf, tab, counter, Cx, Cc, n, mark};
   auto blend_now = [&]() -> int {
-    hipLaunchKernelGGL(mask_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, blend->x0, blend->mask, blend->mask_channels, Cx, hw, blend->qnoise, n,
-                       qtab, counter, seed);
+    hipLaunchKernelGGL(mask_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, io.x, blend->x0, blend->mask, blend->mask_channels, Cx, hw, blend->qnoise, n,
+                       qtab, counter, io.seed);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;
   };
@@ -654,15 +648,8 @@ int ddim_sample(UNet* net, float* x, const float* cond, const int64_t* timesteps
     DRM_HIP_CHECK(hipGetLastError());
     if (blend && blend->when == 0) DRM_TRY(blend_now());
     ar.release(mark);
-    DRM_TRY(net->forward(x, Cx, cond, Cc, nullptr, nullptr, nullptr, tf, e, N, H, W, ar, s));
-    if (uncond) {
-      ar.release(mark);
-      DRM_TRY(net->forward(x, Cx, uncond, Cc, nullptr, nullptr, nullptr, tf, e_u, N, H, W, ar, s));
-      hipLaunchKernelGGL(cfg_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, e, e_u, guidance_scale, n);
-      DRM_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ddim_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, e, noise, n, tab, counter, seed, log_x, log_pred, drop_p, drop_keep);
-    DRM_HIP_CHECK(hipGetLastError());
+    DRM_TRY(net->forward(io.x, Cx, io.cond, Cc, nullptr, nullptr, nullptr, tf, e, N, H, W, ar, s));
+    DRM_TRY(update(c));
     if (blend && blend->when == 1) DRM_TRY(blend_now());
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, counter);
     DRM_HIP_CHECK(hipGetLastError());
@@ -670,49 +657,60 @@ int ddim_sample(UNet* net, float* x, const float* cond, const int64_t* timesteps
   });
 }
 
-int ddpm_sample(UNet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip, const float* noise,
-                uint64_t seed, int N, int H, int W, Arena& ar, hipStream_t caller, const MaskBlend* blend, float drop_p, const float* drop_keep) {
+int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const float* coef, int S, int num_steps, const ChainLog& log,
+                const drm_sampler_options& opt, Arena& ar, hipStream_t caller) {
+  DRM_REQUIRE(net && net->desc.kind == 0, "ddim needs a UNetModel");
+  DRM_REQUIRE(S >= 1 && timesteps && coef, "ddim schedule");
+  DRM_REQUIRE(S <= MAX_TABLE_STEPS, "ddim: at most " + std::to_string(MAX_TABLE_STEPS) + " steps (the workspace budgets the step table for that many)");
+  const int steps = (num_steps > 0 && num_steps < S) ? num_steps : S;
+  auto fill = [&](float* rows) -> int {
+    int logged = 0;
+    DRM_REQUIRE(!log.x || log.pred, "ddim: the intermediates log needs both buffers");
+    for (int j = 0; j < steps; ++j) {
+      const int index = S - 1 - j;
+      rows[(size_t)j * STEP_ROW] = (float)timesteps[index];
+      for (int k = 0; k < 5; ++k) rows[(size_t)j * STEP_ROW + 1 + k] = coef[5 * index + k];
+      // the reference appends (img, pred_x0) after the step of `index` when index % log_every_t == 0 or at the first step (ddim.py:198-200)
+      if (log.x && log.every_t > 0 && (index % log.every_t == 0 || index == S - 1)) {
+        DRM_REQUIRE(logged < log.slots, "ddim: the intermediates log has too few slots");
+        rows[(size_t)j * STEP_ROW + 7] = (float)(++logged);
+      }
+    }
+    if (log.n_logged) *log.n_logged = logged;
+    return DRM_OK;
+  };
+  return chain_run("ddim", net, io, steps, opt, ar, caller, fill, [&](const Chain& c) -> int {
+    const dim3 grid((unsigned)((c.n + 255) / 256));
+    if (opt.uncond) {
+      ar.release(c.mark);
+      DRM_TRY(net->forward(io.x, c.Cx, opt.uncond, c.Cc, nullptr, nullptr, nullptr, c.tf, c.e_u, io.N, io.H, io.W, ar, c.s));
+      hipLaunchKernelGGL(cfg_combine_kernel, grid, dim3(256), 0, c.s, c.e, c.e_u, opt.guidance_scale, c.n);
+      DRM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ddim_update_kernel, grid, dim3(256), 0, c.s, io.x, c.e, io.noise, c.n, c.tab, c.counter, io.seed, log.x, log.pred, opt.noise_dropout,
+                       opt.dropout_keep);
+    DRM_HIP_CHECK(hipGetLastError());
+    return DRM_OK;
+  });
+}
+
+int ddpm_sample(UNet* net, const ChainIO& io, float* pred_x0, const float* coef, int T_start, int clip, const drm_sampler_options& opt, Arena& ar,
+                hipStream_t caller) {
   DRM_REQUIRE(net && net->desc.kind == 0, "ddpm needs a UNetModel");
   DRM_REQUIRE(T_start >= 1 && coef, "ddpm schedule");
   DRM_REQUIRE(T_start <= MAX_TABLE_STEPS, "ddpm: at most " + std::to_string(MAX_TABLE_STEPS) + " steps (the workspace budgets the step table for that many)");
-  hipStream_t s;
-  DRM_TRY(chain_stream(caller, T_start, &s));
-  const int Cx = net->desc.out_channels, Cc = net->desc.in_channels - Cx;
-  const size_t n = (size_t)N * Cx * H * W;
-  float* e = ar.alloc<float>(n);
-  float* tf = ar.alloc<float>((size_t)N);
-  float* tab = ar.alloc<float>((size_t)T_start * STEP_ROW);
-  int* counter = ar.alloc<int>(1);
-  float* qtab = blend ? ar.alloc<float>((size_t)T_start * 2) : nullptr;
-  if (ar.failed) { set_error("ddpm: workspace too small"); return DRM_ERR_WORKSPACE; }
-  DRM_REQUIRE(!blend || blend->mask_channels == 1 || blend->mask_channels == Cx, "mask blending: the mask has 1 or out_channels channels");
-  std::vector<float> rows((size_t)T_start * STEP_ROW, 0.f);
-  for (int j = 0; j < T_start; ++j) {
-    const int t = T_start - 1 - j;
-    rows[(size_t)j * STEP_ROW] = (float)t;
-    for (int k = 0; k < 5; ++k) rows[(size_t)j * STEP_ROW + 1 + k] = coef[5 * t + k];
-    rows[(size_t)j * STEP_ROW + 6] = t != 0 ? 1.f : 0.f;  // no noise at t == 0 (ddpm.py:1161)
-  }
-  DRM_TRY(upload_step_table(rows, tab, counter, s));
-  if (blend) DRM_TRY(upload_blend_table(blend, T_start, qtab, s));
-  const size_t mark = ar.mark();
-  const size_t hw = (size_t)H * W;
-  auto blend_now = [&]() -> int {
-    hipLaunchKernelGGL(mask_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, blend->x0, blend->mask, blend->mask_channels, Cx, hw, blend->qnoise, n,
-                       qtab, counter, seed);
-    DRM_HIP_CHECK(hipGetLastError());
+  auto fill = [&](float* rows) -> int {
+    for (int j = 0; j < T_start; ++j) {
+      const int t = T_start - 1 - j;
+      rows[(size_t)j * STEP_ROW] = (float)t;
+      for (int k = 0; k < 5; ++k) rows[(size_t)j * STEP_ROW + 1 + k] = coef[5 * t + k];
+      rows[(size_t)j * STEP_ROW + 6] = t != 0 ? 1.f : 0.f;  // no noise at t == 0 (ddpm.py:1161)
+    }
     return DRM_OK;
   };
-  return run_steps(T_start, s, [&]() -> int {
-    hipLaunchKernelGGL(step_begin_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tab, counter, tf, N);
-    DRM_HIP_CHECK(hipGetLastError());
-    if (blend && blend->when == 0) DRM_TRY(blend_now());
-    ar.release(mark);
-    DRM_TRY(net->forward(x, Cx, cond, Cc, nullptr, nullptr, nullptr, tf, e, N, H, W, ar, s));
-    hipLaunchKernelGGL(ddpm_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, pred_x0, e, noise, n, tab, counter, clip, seed, drop_p, drop_keep);
-    DRM_HIP_CHECK(hipGetLastError());
-    if (blend && blend->when == 1) DRM_TRY(blend_now());
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, counter);
+  return chain_run("ddpm", net, io, T_start, opt, ar, caller, fill, [&](const Chain& c) -> int {
+    hipLaunchKernelGGL(ddpm_update_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, c.s, io.x, pred_x0, c.e, io.noise, c.n, c.tab, c.counter, clip, io.seed,
+                       opt.noise_dropout, opt.dropout_keep);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;
   });

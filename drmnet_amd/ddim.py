@@ -1,4 +1,4 @@
-"""``DDIMSampler`` -- same surface as ldm/models/diffusion/ddim.py:16-259, loop executed by drm_ddim_sample.
+"""``DDIMSampler`` -- same surface as ldm/models/diffusion/ddim.py:16-259, loop executed by drm_ddim_sample_ex.
 
 Schedule construction restates make_ddim_timesteps / make_ddim_sampling_parameters
 (ldm/modules/diffusionmodules/util.py:46-74) including the reference's mixed fp32/fp64 rounding sequence
@@ -155,46 +155,29 @@ class DDIMSampler(object):
             coef[:, 4] = (torch.from_numpy(coef[:, 4]) * float(temperature)).numpy()
         S = len(ts)
         steps = S if not num_steps else min(int(num_steps), S)
-        blend = keep = None
+        blend = uc = None
         if mask is not None:
             # q_sample(x0, ts) at the step's own t (ddpm.py:1052-1058: sqrt_alphas_cumprod[t] x0 + sqrt_one_minus_alphas_cumprod[t] noise)
             sa = self.model.sqrt_alphas_cumprod.detach().cpu().float().numpy()
             s1 = self.model.sqrt_one_minus_alphas_cumprod.detach().cpu().float().numpy()
             q = np.array([[sa[int(ts[S - 1 - j])], s1[int(ts[S - 1 - j])]] for j in range(steps)], dtype=np.float32)
-            blend, keep = _lib.make_mask_blend(mask, x0, q, mask_noise, 0, tuple(img.shape))
+            blend = _lib.make_mask_blend(mask, x0, q, mask_noise, 0, tuple(img.shape))
+        if guided:
+            uc = unconditional_conditioning[0] if isinstance(unconditional_conditioning, (list, tuple)) else unconditional_conditioning
+        opt, keep = _lib.make_sampler_options(tuple(img.shape), steps, blend=blend, uncond=uc, guidance_scale=unconditional_guidance_scale,
+                                              noise_dropout=noise_dropout, dropout_keep=dropout_keep)
         log_every_t = int(log_every_t) if log_every_t else 0
         slots = sum(1 for j in range(steps) if log_every_t > 0 and ((S - 1 - j) % log_every_t == 0 or j == 0))
         inter = {"x_inter": [x_start], "pred_x0": [x_start]}
+        log_x = torch.empty((slots,) + tuple(img.shape), dtype=torch.float32, device=dev) if slots else None
+        log_p = torch.empty_like(log_x) if slots else None
+        n_logged = C.c_int32(0)
         with torch.cuda.device(dev):
-            if blend is not None or guided or noise_dropout > 0.0:
-                uc = None
-                if guided:
-                    uc = unconditional_conditioning[0] if isinstance(unconditional_conditioning, (list, tuple)) else unconditional_conditioning
-                opt, keep_o = _lib.make_sampler_options(tuple(img.shape), steps, blend=None if blend is None else (blend, keep), uncond=uc,
-                                                        guidance_scale=unconditional_guidance_scale, noise_dropout=noise_dropout, dropout_keep=dropout_keep)
-                log_x = torch.empty((max(slots, 1),) + tuple(img.shape), dtype=torch.float32, device=dev)
-                log_p = torch.empty_like(log_x)
-                n_logged = C.c_int32(0)
-                _lib.check(L.drm_ddim_sample_ex(h, img.data_ptr(), c.data_ptr(), ts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                coef.ctypes.data_as(C.POINTER(C.c_float)), S, int(num_steps or 0), _lib.ptr(noise), seed, C.byref(opt),
-                                                log_every_t if slots else 0, log_x.data_ptr(), log_p.data_ptr(), slots, C.byref(n_logged), n, hh, ww,
-                                                ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+            _lib.check(L.drm_ddim_sample_ex(h, img.data_ptr(), c.data_ptr(), ts.ctypes.data_as(C.POINTER(C.c_int64)), coef.ctypes.data_as(C.POINTER(C.c_float)), S,
+                                            int(num_steps or 0), _lib.ptr(noise), seed, C.byref(opt), log_every_t if slots else 0, _lib.ptr(log_x), _lib.ptr(log_p),
+                                            slots, C.byref(n_logged), n, hh, ww, ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+            if any(k is not None for k in keep) or noise_dropout > 0.0:
                 torch.cuda.current_stream(dev).synchronize()  # (the options' tensors stay alive until the chain has run)
-                del keep_o
-                inter["x_inter"] += [log_x[k] for k in range(n_logged.value)]
-                inter["pred_x0"] += [log_p[k] for k in range(n_logged.value)]
-            elif slots == 0:
-                _lib.check(L.drm_ddim_sample(h, img.data_ptr(), c.data_ptr(), ts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                             coef.ctypes.data_as(C.POINTER(C.c_float)), S, int(num_steps or 0), _lib.ptr(noise), seed, n, hh, ww,
-                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
-            else:
-                log_x = torch.empty((slots,) + tuple(img.shape), dtype=torch.float32, device=dev)
-                log_p = torch.empty_like(log_x)
-                n_logged = C.c_int32(0)
-                _lib.check(L.drm_ddim_sample_logged(h, img.data_ptr(), c.data_ptr(), ts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                    coef.ctypes.data_as(C.POINTER(C.c_float)), S, int(num_steps or 0), _lib.ptr(noise), seed, log_every_t,
-                                                    log_x.data_ptr(), log_p.data_ptr(), slots, C.byref(n_logged), n, hh, ww, ws.data_ptr(), ws.numel(),
-                                                    _lib.stream_ptr(dev)))
-                inter["x_inter"] += [log_x[k] for k in range(n_logged.value)]
-                inter["pred_x0"] += [log_p[k] for k in range(n_logged.value)]
+        inter["x_inter"] += [log_x[k] for k in range(n_logged.value)]
+        inter["pred_x0"] += [log_p[k] for k in range(n_logged.value)]
         return img, inter

@@ -301,7 +301,7 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def _ddpm_loop(self, cond, shape, x_T=None, timesteps=None, start_T=None, noise=None, seed=None, mask=None, x0=None, mask_noise=None, blend_when=1,
                    temperature=1.0, noise_dropout=0.0, dropout_keep=None):
-        """The ancestral chain on the device (drm_ddpm_sample).  mask / x0: the known-region blending of the reference's two loops --
+        """The ancestral chain on the device (drm_ddpm_sample_ex).  mask / x0: the known-region blending of the reference's two loops --
         ``blend_when`` 1 = LatentDiffusion.p_sample_loop (after p_sample, q_sample(x0, t): ddpm.py:1300-1302), 0 = ObsNetDiffusion.p_sample_loop (before
         p_sample, x0 itself at t == 0, else q_sample(x0, t - 1): models/obsnet.py:545-547); ``mask_noise`` [T,N,C,H,W] injects q_sample's draws.
         ``temperature`` scales the step noise (ddpm.py:1157: the exp(0.5 logvar) column); ``noise_dropout`` is p_sample's F.dropout on it (ddpm.py:1158-1159;
@@ -335,31 +335,25 @@ class LatentDiffusion(DDPM):
             coef[:, 4] = (torch.from_numpy(coef[:, 4]) * float(temperature)).numpy()
         if not 0.0 <= noise_dropout < 1.0:
             raise ValueError("noise_dropout: 0 <= p < 1")
-        if mask is not None or noise_dropout > 0.0:
-            blend = None
-            if mask is not None:
-                sa = self.sqrt_alphas_cumprod.detach().cpu().float().numpy()
-                s1 = self.sqrt_one_minus_alphas_cumprod.detach().cpu().float().numpy()
-                q = np.zeros((T, 2), dtype=np.float32)
-                for j in range(T):
-                    t = T - 1 - j
-                    if blend_when == 1:
-                        q[j] = (sa[t], s1[t])
-                    else:
-                        q[j] = (1.0, 0.0) if t == 0 else (sa[t - 1], s1[t - 1])
-                blend = _lib.make_mask_blend(mask, x0, q, mask_noise, blend_when, tuple(img.shape))
-            opt, keep = _lib.make_sampler_options(tuple(img.shape), T, blend=blend, noise_dropout=noise_dropout, dropout_keep=dropout_keep)
-            with torch.cuda.device(dev):
-                _lib.check(L.drm_ddpm_sample_ex(h, img.data_ptr(), pred_x0.data_ptr(), c.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), T,
-                                                int(bool(self.clip_denoised)), _lib.ptr(noise), seed, C.byref(opt), n, hh, ww, ws.data_ptr(), ws.numel(),
-                                                _lib.stream_ptr(dev)))
-            torch.cuda.current_stream(dev).synchronize()  # (the options' tensors stay alive until the chain has run)
-            del keep
-            return img, pred_x0
+        blend = None
+        if mask is not None:
+            sa = self.sqrt_alphas_cumprod.detach().cpu().float().numpy()
+            s1 = self.sqrt_one_minus_alphas_cumprod.detach().cpu().float().numpy()
+            q = np.zeros((T, 2), dtype=np.float32)
+            for j in range(T):
+                t = T - 1 - j
+                if blend_when == 1:
+                    q[j] = (sa[t], s1[t])
+                else:
+                    q[j] = (1.0, 0.0) if t == 0 else (sa[t - 1], s1[t - 1])
+            blend = _lib.make_mask_blend(mask, x0, q, mask_noise, blend_when, tuple(img.shape))
+        opt, keep = _lib.make_sampler_options(tuple(img.shape), T, blend=blend, noise_dropout=noise_dropout, dropout_keep=dropout_keep)
         with torch.cuda.device(dev):
-            _lib.check(L.drm_ddpm_sample(h, img.data_ptr(), pred_x0.data_ptr(), c.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), T,
-                                         int(bool(self.clip_denoised)), _lib.ptr(noise), seed, n, hh, ww, ws.data_ptr(), ws.numel(),
-                                         _lib.stream_ptr(dev)))
+            _lib.check(L.drm_ddpm_sample_ex(h, img.data_ptr(), pred_x0.data_ptr(), c.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), T,
+                                            int(bool(self.clip_denoised)), _lib.ptr(noise), seed, C.byref(opt), n, hh, ww, ws.data_ptr(), ws.numel(),
+                                            _lib.stream_ptr(dev)))
+        if any(k is not None for k in keep) or noise_dropout > 0.0:
+            torch.cuda.current_stream(dev).synchronize()  # (the options' tensors stay alive until the chain has run)
         return img, pred_x0
 
     @torch.no_grad()

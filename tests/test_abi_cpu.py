@@ -111,3 +111,23 @@ def workspace_table():
 def test_workspace_bytes_match_the_recorded_sizing():
     with open(os.path.join(GOLD, "workspace_bytes.json")) as f:
         assert workspace_table() == json.load(f)
+
+
+# the chains' workspace on top of the network's: recorded from the two hand-written chain drivers before they became one (ObsNet and the tiny U-Net,
+# the networks the chains run on), so the shared driver's allocations and the chain's sizing walk are pinned without a GPU
+def sampler_workspace_table():
+    from drmnet_amd.unet import UNetModel
+
+    out = {}
+    for name, cfg, sizes in (("obsnet", ou.OBSNET_CFG, WS_SIZES), ("tiny_unet", ou.TINY_UNET_CFG, WS_TINY_SIZES)):
+        m = UNetModel(**cfg)
+        for prec in m.PRECISIONS:
+            m.set_precision(prec)
+            for n, h, w in sizes:
+                out[f"{name} {prec} {n}x{h}x{w}"] = int(_lib.lib().drm_sampler_workspace_bytes(m._h, n, h, w))
+    return out
+
+
+def test_sampler_workspace_bytes_match_the_recorded_sizing():
+    with open(os.path.join(GOLD, "sampler_workspace_bytes.json")) as f:
+        assert sampler_workspace_table() == json.load(f)

@@ -343,3 +343,52 @@ def test_graph_replayed_chain_equals_eager_chain(dev, precision):
         assert torch.equal(d_e, d_g)
     finally:
         ops.set_graph_replay(False)
+
+
+def test_plain_chain_entry_points_equal_the_host_classes(dev):
+    """drm_ddim_sample / drm_ddim_sample_logged / drm_ddpm_sample (the entry points without drm_sampler_options; the host classes go through the _ex
+    ones) called as INTEGRATION.md binds them: bit for bit what DDIMSampler / p_sample_loop return for the same inputs -- the final state, pred_x0,
+    and every logged slot and their count."""
+    import ctypes as C
+
+    from drmnet_amd import _lib
+    from drmnet_amd.ddim import DDIMSampler
+
+    L = _lib.lib()
+    m = tiny_obsnet(dev).set_precision("f16x3")
+    h = m.model.diffusion_model.engine_handle()
+
+    def tail(x):  # N, H, W, workspace, its size, stream
+        n, _, hh, ww = x.shape
+        ws = torch.empty(int(L.drm_sampler_workspace_bytes(h, n, hh, ww)), dtype=torch.uint8, device=dev)
+        return n, hh, ww, ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)
+
+    g = gold("ddim_trace_eta1")
+    cond, x_T, noise = (torch.from_numpy(g[k]).to(dev) for k in ("cond", "x_T", "noise"))
+    s = DDIMSampler(m)
+    want_x, want = s.sample(50, cond.shape[0], (3, 16, 16), cond, eta=1.0, x_T=x_T, verbose=False, noise=noise, log_every_t=10)
+    slots = len(want["x_inter"]) - 1
+    assert slots == 6  # index 49 (the first step), 40, 30, 20, 10, 0
+    ts = np.ascontiguousarray(np.asarray(s.ddim_timesteps, dtype=np.int64))
+    sched = (ts.ctypes.data_as(C.POINTER(C.c_int64)), s.ddim_coef.ctypes.data_as(C.POINTER(C.c_float)), 50, 0, noise.data_ptr(), 0)
+    with torch.cuda.device(dev):
+        x = x_T.clone()
+        _lib.check(L.drm_ddim_sample(h, x.data_ptr(), cond.data_ptr(), *sched, *tail(x)))
+        assert torch.equal(x, want_x)
+        x = x_T.clone()
+        log_x = torch.empty((slots,) + tuple(x.shape), dtype=torch.float32, device=dev)
+        log_p = torch.empty_like(log_x)
+        n_logged = C.c_int32(0)
+        _lib.check(L.drm_ddim_sample_logged(h, x.data_ptr(), cond.data_ptr(), *sched, 10, log_x.data_ptr(), log_p.data_ptr(), slots, C.byref(n_logged), *tail(x)))
+        assert n_logged.value == slots and torch.equal(x, want_x)
+        for k in range(slots):
+            assert torch.equal(log_x[k], want["x_inter"][1 + k]) and torch.equal(log_p[k], want["pred_x0"][1 + k]), k
+
+        g = gold("ddpm_trace")
+        cond, x_T, noise = (torch.from_numpy(g[k]).to(dev) for k in ("cond", "x_T", "noise"))
+        want_p, want = m.p_sample_loop(cond, tuple(x_T.shape), return_intermediates=True, x_T=x_T, verbose=False, start_T=6, noise=noise)
+        coef = m.ddpm_coef_table()
+        x, pred = x_T.clone(), torch.empty_like(x_T)
+        _lib.check(L.drm_ddpm_sample(h, x.data_ptr(), pred.data_ptr(), cond.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), 6, int(bool(m.clip_denoised)),
+                                     noise.data_ptr(), 0, *tail(x)))
+        assert torch.equal(x, want["x_inter"][-1]) and torch.equal(pred, want_p)
