@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DRM_LIB_PATH") or os.path.join(_HERE, "csrc", "libdrmnet_hip.so")
 ABI_VERSION = 3
 MAX_LEVELS = 8
+LOSS_WORKSPACE_BYTES = 2048  # DRM_LOSS_WORKSPACE_BYTES
 
 # every symbol include/drmnet_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -30,7 +31,7 @@ SYMBOLS = [
     "drm_refmap_workspace_bytes", "drm_refmap_mask_make", "drm_erode_mask",
     "drm_unet_load_params_set", "drm_unet_use_set", "drm_set_graph_replay", "drm_graph_launches",
     "drm_map_chain", "drm_masked_log_range", "drm_luminance_scale", "drm_mirmap2envmap", "drm_hdr2ldr", "drm_resize", "drm_profile_variants",
-    "drm_render_refmap", "drm_brdf_eval",
+    "drm_render_refmap", "drm_brdf_eval", "drm_render_refmap_views", "drm_validation_losses",
 ]
 
 
@@ -183,6 +184,9 @@ def lib() -> C.CDLL:
     L.drm_profile_variants.restype = C.c_size_t
     L.drm_render_refmap.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.drm_brdf_eval.argtypes = [fp, i32, fp, fp, fp, fp, C.c_int64, vp]
+    L.drm_render_refmap_views.argtypes = [fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_validation_losses.argtypes = [fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
+                                        fp, vp]
     if L.drm_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libdrmnet_hip.so ABI version {L.drm_abi_version()} != {ABI_VERSION}: rebuild with `python -m drmnet_amd.build`")
     _lib = L

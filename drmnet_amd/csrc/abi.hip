@@ -570,8 +570,26 @@ int drm_render_refmap(const float* z, const float* envmap, float* out, int B, in
   });
 }
 
+int drm_render_refmap_views(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
+                            int subpixel, int flip, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_refmap_views(z, L, envmap, view, out, B, R, EH, EW, quad, subpixel, flip, static_cast<hipStream_t>(stream));
+  });
+}
+
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream) {
   return guarded([&]() -> int { return launch_brdf_eval(z, z_rows, n, v, l, out, (long long)N, static_cast<hipStream_t>(stream)); });
+}
+
+// ------------------------------------------------------------------------------------------------ validation losses (losses.hip)
+
+int drm_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
+                          const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double l_refmap_weight,
+                          double l_refcode_weight, int B, int64_t per_row, int P, void* workspace, size_t workspace_bytes, float* out, void* stream) {
+  return guarded([&]() -> int {
+    return launch_validation_losses(model_out, Lr_k, Lr_km1, K, z_out, z_k, z_K, reversed_k, z0, gamma, loss_type, l_refmap_weight, l_refcode_weight, B,
+                                    (long long)per_row, P, static_cast<double*>(workspace), workspace_bytes, out, static_cast<hipStream_t>(stream));
+  });
 }
 
 }  // extern "C"

@@ -199,6 +199,14 @@ int launch_resize(const float* x, float* out, int planes, int IH, int IW, int OH
 
 // reflectance-map forward model (render.hip): z [B][6] canonical principled rows, env [B][EH][EW][3] or null (white), out [B][3][R][R]
 int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s);
+// the same kernel on L stacked sets of rows: z [L][B][6], out [L][B][3][R][R]; row (l, b) under env[b], seen through view[b] ([B][9] row-major
+// rotations, or null: +z)
+int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
+                               int subpixel, int flip, hipStream_t s);
+// validation losses (losses.hip): see drm_validation_losses
+int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
+                             const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,
+                             double w_refcode, int B, long long per_row, int P, double* ws, size_t ws_bytes, float* out, hipStream_t s);
 // principled eval (f times n.l) of N (n, v, l) triples; z [1 or N][6]; out [N][3]
 int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s);
 

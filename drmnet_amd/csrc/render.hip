@@ -143,10 +143,35 @@ __host__ __device__ __forceinline__ V3 sensor_normal(float px, float py, int fli
   return v3(flip ? -nx : nx, sinf(b), cb * cosf(a));
 }
 
+// the view rotation of one row: directions of the quadrature live in the frame whose viewer is +z; the environment is read at Rot l
+// (row-major Rot).  on == false: the view from +z, l is used as it is (not multiplied by the identity: 0 * l.y + ... would turn -0 into +0
+// in front of atan2f, and the +z renders must not move).  The kernel is compiled with and without the view (VIEW): a launch without view
+// matrices runs the instantiation that holds no rotation at all, at the register count (and occupancy) the +z renderer always had.
+struct ViewRot {
+  float m[9];
+  bool on;
+};
+__host__ __device__ __forceinline__ ViewRot view_rot(const float* view) {
+  ViewRot r;
+  r.on = false;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    r.m[k] = view ? view[k] : (k % 4 == 0 ? 1.0f : 0.0f);
+    r.on = r.on || r.m[k] != (k % 4 == 0 ? 1.0f : 0.0f);
+  }
+  return r;
+}
+template <bool VIEW>
+__host__ __device__ __forceinline__ V3 to_world(const ViewRot& r, V3 l) {
+  if (!VIEW || !r.on) return l;
+  return v3(r.m[0] * l.x + r.m[1] * l.y + r.m[2] * l.z, r.m[3] * l.x + r.m[4] * l.y + r.m[5] * l.z, r.m[6] * l.x + r.m[7] * l.y + r.m[8] * l.z);
+}
+
 // one lane's share of pixel (i, j): every sub-pixel, the grid points q = lane, lane + lanes, ... of both lobes, summed in that order
 // into acc (unnormalised).  env == nullptr: white environment (L = 1).
-__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, int EH, int EW, int R, int i, int j,
-                                                        int Q, int S, int flip, int lane, int lanes, float acc[3]) {
+template <bool VIEW>
+__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
+                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3]) {
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
@@ -186,7 +211,7 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
           if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
             const float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh);
             const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-            if (env) env_lookup(env, EH, EW, l, L);
+            if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
 #pragma unroll
             for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
           }
@@ -198,7 +223,7 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
           V3 h = v3(l.x, l.y, l.z + 1.0f);
           const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
           const float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd);
-          if (env) env_lookup(env, EH, EW, l, L);
+          if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
 #pragma unroll
           for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
         }
@@ -207,19 +232,23 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
   }
 }
 
-// grid: ceil(B R^2 / 4) workgroups of 4 waves; wave = pixel (b, i, j); out [B][3][R][R]
-__global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restrict__ z, const float* __restrict__ env, float* __restrict__ out, int B,
-                                                            int R, int EH, int EW, int Q, int S, int flip) {
+// grid: ceil(L B R^2 / 4) workgroups of 4 waves; wave = pixel (row, i, j), row = l B + b lit by env[b] and seen through view[b];
+// z [L][B][6], out [L][B][3][R][R].  Every row runs the same per-lane order whatever L is, so a stacked render equals its rows rendered alone.
+template <bool VIEW>
+__global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
+                                                            float* __restrict__ out, int rows, int B, int R, int EH, int EW, int Q, int S, int flip) {
   const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (pix >= (long long)B * R * R) return;  // (wave-uniform)
-  const int b = (int)(pix / ((long long)R * R));
-  const int rem = (int)(pix - (long long)b * R * R);
+  if (pix >= (long long)rows * R * R) return;  // (wave-uniform)
+  const int row = (int)(pix / ((long long)R * R));
+  const int rem = (int)(pix - (long long)row * R * R);
   const int i = rem / R, j = rem - (rem / R) * R;
-  const Principled p = principled(z + 6 * (size_t)b);
+  const int b = __builtin_amdgcn_readfirstlane(row % B);  // (a wave is one pixel: the map and the view matrix are fetched through scalar loads)
+  const Principled p = principled(z + 6 * (size_t)row);
   const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+  const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
   float acc[3] = {0.0f, 0.0f, 0.0f};
-  pixel_lane_sum(p, e, EH, EW, R, i, j, Q, S, flip, lane, 64, acc);
+  pixel_lane_sum<VIEW>(p, e, rot, EH, EW, R, i, j, Q, S, flip, lane, 64, acc);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
@@ -228,7 +257,7 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
   if (lane == 0) {
     const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[(((size_t)b * 3 + c) * R + i) * R + j] = acc[c] * scale;
+    for (int c = 0; c < 3; ++c) out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale;
   }
 }
 
@@ -247,17 +276,25 @@ __global__ __launch_bounds__(256) void brdf_eval_kernel(const float* __restrict_
 
 }  // namespace
 
-int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {
+int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
+                               int subpixel, int flip, hipStream_t s) {
   DRM_REQUIRE(z && out, "render_refmap: null pointer");
-  DRM_REQUIRE(B > 0 && R > 0 && R <= 8192, "render_refmap: B >= 1 rows of R x R pixels, 1 <= R <= 8192");
+  DRM_REQUIRE(L > 0 && B > 0 && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
+              "render_refmap: L >= 1 stacks of B >= 1 rows of R x R pixels, 1 <= R <= 8192");
   DRM_REQUIRE(quad >= 1 && quad <= 1024 && subpixel >= 1 && subpixel <= 16, "render_refmap: quad in [1, 1024], subpixel in [1, 16]");
   DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), "render_refmap: envmap must be EH x EW with EH, EW >= 1");
-  const long long blocks = ((long long)B * R * R + kRenderWaves - 1) / kRenderWaves;
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: B R^2 too large for one launch");
-  hipLaunchKernelGGL(refmap_render_kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, out, B, R, env ? EH : 1, env ? EW : 1, quad,
-                     subpixel, flip ? 1 : 0);
+  const long long blocks = ((long long)L * B * R * R + kRenderWaves - 1) / kRenderWaves;
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: L B R^2 too large for one launch");
+  // (a view only turns the environment: under a white one it changes nothing and is not read)
+  const bool with_view = env && view;
+  hipLaunchKernelGGL(with_view ? refmap_render_kernel<true> : refmap_render_kernel<false>, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env,
+                     with_view ? view : nullptr, out, L * B, B, R, env ? EH : 1, env ? EW : 1, quad, subpixel, flip ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
+}
+
+int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {
+  return launch_render_refmap_views(z, 1, env, nullptr, out, B, R, EH, EW, quad, subpixel, flip, s);
 }
 
 int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s) {

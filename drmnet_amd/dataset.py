@@ -11,6 +11,7 @@ dataset object for the matching ``rescale``.  GPU tensors only: there is no torc
 from __future__ import annotations
 
 import math
+from pathlib import Path
 from typing import List, Optional, Tuple
 
 import torch
@@ -118,3 +119,96 @@ class BaseDataset(torch.utils.data.Dataset):
 
     def rescale(self, x: torch.Tensor):
         return self._run(x, self._inverse)
+
+
+class ParametricRefmapDataset(BaseDataset):
+    """The reference's synthetic validation / test (and training) items (dataset/parametricrefmap.py:16-220): item ``idx`` is environment map
+    ``envs[idx]`` with a BRDF code, a point of the schedule and a view drawn from a generator seeded per index -- ``val`` and ``test`` items
+    are the same in every epoch, ``train`` items move with ``set_current_epoch``.  The draws keep the reference's order (zK, normalized_k,
+    the azimuth out of 64, the unused theta draw, the mask draw) so that an index names the same item as there; ``view_from`` lies on the
+    horizontal circle.  With a model attached (``ds.model = drmnet``) whose ``_z0`` exists, ``K, k, zk, zkm1`` come from its
+    ``get_schedule`` (``zkm1`` is NaN where K == 0).  ``return_envmap`` adds the map, read with file_io.load_exr.
+
+    ``datalist``: the text file naming one ``<name>.exr`` per line; default the reference's ``data/datalists/<data_root name>/envs_<split>.txt``
+    (relative to the working directory).  ``refmap_cache_root`` / ``return_cache`` are accepted and unused: no .pt refmap cache is read, every
+    map is rendered by DRMNet.get_input.  ``mask_root`` (the sparse masks of ObsNet's data, read through OpenCV) is not implemented."""
+
+    def __init__(self, size: int, split: str, data_root: str, zdim: int, transform_func: str = "log", clamp_before_exp: float = 0,
+                 return_envmap: bool = False, mask_root: Optional[str] = None, mask_area_min_rate: float = 0.002, epoch_bias: int = 0,
+                 epoch_cycle: int = 1000, preload_envmap: bool = False, return_cache: bool = False, refmap_cache_root: Optional[str] = None,
+                 datalist: Optional[str] = None):
+        super().__init__(size, transform_func=transform_func, clamp_before_exp=clamp_before_exp)
+        assert split in ["train", "val", "test"]
+        if mask_root is not None:
+            raise NotImplementedError("mask_root: the sparse masks belong to ObsNet's training data and need OpenCV")
+        self.split = split
+        self.root = Path(data_root)
+        self.data_name = self.root.name
+        with open(datalist if datalist is not None else f"data/datalists/{self.data_name}/envs_{split}.txt", "r") as f:
+            self.envs = f.read().splitlines()
+        self.with_mask = False
+        self.zdim = zdim
+        self.return_envmap = return_envmap
+        self.generator = torch.Generator()
+        self.current_epoch = 0
+        self.model = None
+        self.return_cache = return_cache
+        self.refmap_cache_root = refmap_cache_root
+        self.epoch_bias = epoch_bias
+        self.epoch_cycle = epoch_cycle
+        self.preload_envmap = preload_envmap
+        if self.return_envmap and preload_envmap:
+            self.envmaps = {env[:-4]: self._load(env[:-4]) for env in self.envs}
+
+    def _load(self, env_name: str) -> torch.Tensor:
+        from . import file_io
+
+        return file_io.load_exr(self.root / f"{env_name}.exr", as_torch=True)
+
+    def __len__(self):
+        return len(self.envs)
+
+    def set_current_epoch(self, epoch):
+        self.current_epoch = epoch
+
+    def set_generator(self, idx: int, epoch: Optional[int] = None):
+        """parametricrefmap.py:84-99: train items are keyed by (epoch, idx); val and test items by idx alone, through one and two draws of
+        a generator seeded with idx (so the two splits differ on the same index)."""
+        draw = lambda: torch.empty((), dtype=torch.int64).random_(generator=self.generator).item()
+        if self.split == "train":
+            epoch = (epoch or self.current_epoch) + self.epoch_bias
+            if epoch >= self.epoch_cycle:
+                epoch = epoch % self.epoch_cycle
+            self.generator.manual_seed(epoch * len(self) + idx)
+        elif self.split == "val":
+            self.generator.manual_seed(idx)
+            self.generator.manual_seed(draw())
+        else:
+            self.generator.manual_seed(idx)
+            draw()
+            self.generator.manual_seed(draw())
+
+    @torch.no_grad()
+    def __getitem__(self, idx: int):
+        env_name = self.envs[idx][:-4]
+        self.set_generator(idx)
+        rand = lambda *shape: torch.rand(shape, generator=self.generator)
+        zK = rand(self.zdim)
+        normalized_k = rand()
+        phi = (rand() * 64).int() / 64 * torch.pi * 2 - torch.pi
+        theta = (rand() * 0 + 0.5) * torch.pi  # (the reference draws and discards it: every view is on the horizontal circle)
+        rand()  # the mask draw
+        # thetaphi2xyz(normal = +y, tangent = +z): cos(theta) y + sin(theta) cos(phi) z + sin(theta) sin(phi) x, summed in that order
+        y, z, x = torch.tensor([0.0, 1.0, 0.0]), torch.tensor([0.0, 0.0, 1.0]), torch.tensor([1.0, 0.0, 0.0])
+        view_from = torch.cos(theta) * y
+        view_from += torch.sin(theta) * torch.cos(phi) * z
+        view_from += torch.sin(theta) * torch.sin(phi) * x
+        data = {"zK": zK, "envmap_name": env_name, "normalized_k": normalized_k, "view_from": view_from}
+        z0 = getattr(self.model, "_z0", None) if self.model is not None else None
+        if z0 is not None:
+            K, k, zk, zkm1 = self.model.get_schedule(zK, z0=z0, normalized_k=normalized_k, return_zkm1=True)
+            data.update(K=K, k=k, zk=zk, zkm1=zkm1 if K > 0 else torch.full_like(zkm1, torch.nan))
+        if self.return_envmap:
+            data["envmap"] = self.envmaps[env_name] if self.preload_envmap else self._load(env_name)
+        data["tag"] = env_name
+        return data

@@ -5,9 +5,12 @@ inference path touches (scripts/estimate.py:84-100):
   __init__ params (configs/drmnet/eval_drmnet.yaml), ema_scope :242-258, init_from_ckpt :260-277,
   apply_model :376-388, get_brdf_out :390-396, forward :452-456, get_schedule :458-501,
   check_convergence :747-750, p_mean_variance :752-770, p_sample (stub) :772-780,
-  p_sample_loop :782-847, get_input_for_predict :1011-1045, decode_first_stage, r0toenvmap :931-941, and the forward model on
-  csrc/render.hip: basis_r0 :328-347, rendering_refmaps :667-696, get_visualized_brdf_grid :916-929, reconstruct :943-953.
-Training (p_losses, get_input, caches, log_images, the training-data renders) is out of scope.
+  p_sample_loop :782-847, get_input_for_predict :1011-1045, decode_first_stage, r0toenvmap :931-941, the forward model on
+  csrc/render.hip: basis_r0 :328-347, rendering_refmaps :667-696, get_visualized_brdf_grid :916-929, reconstruct :943-953,
+and for the validation pass of ``python main.py --base ...`` without ``-t`` (drmnet_amd.validate):
+  get_loss :398-411, p_losses :413-450 (eval mode, losses on csrc/losses.hip), get_input :503-651, shared_step :707-710,
+  validation_step :731-740.
+Training (backward, the EMA update, train_with_zk_gt), log_images and the .pt refmap cache are out of scope.
 
 The module is a plain ``nn.Module`` (pytorch_lightning is not needed for inference); ``state_dict()`` has the
 reference's keys, so ``drmnet.ckpt`` loads with ``init_from_ckpt``.
@@ -27,15 +30,25 @@ from .config import instantiate_from_config
 from .wrappers import DiffusionWrapper, IdentityFirstStage, LitEma, ZEmbDiffusionWrapper, ema_weights, load_checkpoint
 
 
-# Constructor / YAML keys of the reference (models/drmnet.py:79-240) that steer only training, logging or dataset caches: accepted so that
-# configs/drmnet/*.yaml load unchanged, never read.  Any other unknown key is an error.
+# Constructor / YAML keys of the reference (models/drmnet.py:79-240) beyond the sampling path: accepted so that configs/drmnet/*.yaml load
+# unchanged.  Those the validation pass reads (_VALIDATION_DEFAULTS) are kept in ``validation_params``; the rest steer only training, logging
+# or the refmap cache and are never read.  Any other unknown key is an error.
 _TRAINING_ONLY = frozenset({
     "loss_type", "monitor", "scheduler_config", "cond_stage_trainable", "l_refmap_weight", "l_refcode_weight", "sigma",
     "train_with_zk_gt", "train_with_zk_gt_switch_epoch", "cache_refmap", "refmap_cache_root", "envmap_dir",
 })
 
 
+# the reference's defaults (models/drmnet.py:85, 104-106, 121) of the keys get_input / p_losses read
+_VALIDATION_DEFAULTS = {"loss_type": "l1", "sigma": 0.01, "l_refmap_weight": 1.0, "l_refcode_weight": 1.0, "envmap_dir": None}
+
+
 class DRMNet(nn.Module):
+    """The reference's constructor surface.  ``loss_type``, ``sigma``, ``l_refmap_weight``, ``l_refcode_weight`` and ``envmap_dir`` are kept
+    in the dict ``validation_params`` under their own names (not as attributes of those names: the module keeps the attribute surface of the
+    sampling path it had).  ``cache_refmap`` / ``refmap_cache_root`` stay accepted and unused: a reflectance map is one deterministic kernel
+    launch here, cheaper than reading a .pt file back, so nothing is cached."""
+
     def __init__(self, illnet_config, refnet_config, renderer_config=None, max_timesteps: int = 250, *, ckpt_path: Optional[str] = None,
                  init_from_ckpt_verbose: bool = True, ignore_keys=(), use_ema: bool = True, input_key: str = "LrK", sigma_for_cond_xK: float = 0.0,
                  image_size: int = 128, channels: int = 3, log_every_k: int = 5, parameterization: str = "residual", concat_mode: bool = False,
@@ -68,6 +81,7 @@ class DRMNet(nn.Module):
         self.image_size, self.channels, self.scale_factor = image_size, channels, scale_factor
         self.brdf_param_names = list(brdf_param_names)
         self.refmap_input_scaler = refmap_input_scaler
+        self.validation_params = {k: training_only.get(k, d) for k, d in _VALIDATION_DEFAULTS.items()}
         self.concat_mode = concat_mode
         self._z0 = torch.tensor(list(z0), dtype=torch.float32)
         self.zdim = len(self._z0)
@@ -138,18 +152,29 @@ class DRMNet(nn.Module):
     @torch.no_grad()
     def rendering_refmaps(self, envmaps, z: torch.Tensor, brdf_param_names=None, transform: bool = True, view_from=None,
                           new_scene: bool = False) -> torch.Tensor:
-        """drmnet.py:667-696: envmaps [B, H, W, 3], z [L, B, P] -> reflectance maps [L, B, 3, R, R], every (list, batch) item under
-        envmaps[b] -- one drm_render_refmap launch for all of them.  Envmap names (the training path) and view_from are not implemented."""
+        """drmnet.py:667-696: envmaps [B, H, W, 3], z [L, B, P], view_from [B, 3] or None (+z) -> reflectance maps [L, B, 3, R, R], every
+        (list, batch) item under envmaps[b] seen from view_from[b] -- one drm_render_refmap_views launch; the L rows of an item read the same
+        map (no copies).  Envmap names (a list of str) are read from ``envmap_dir``."""
         assert len(envmaps) == z.size(1)
-        if isinstance(envmaps, (list, tuple)) or view_from is not None:
-            raise NotImplementedError("rendering_refmaps: envmap names (training data) and view_from are not modelled; pass envmaps [B, H, W, 3]")
+        if isinstance(envmaps, (list, tuple)):
+            envmaps = self._load_envmaps(list(envmaps)).to(z.device if z.is_cuda else self.device)
         r = self._renderer()
-        L, B = z.shape[0], z.shape[1]
-        env = envmaps[None].expand(L, *envmaps.shape).reshape(L * B, *envmaps.shape[1:])
-        out = r.render(z.reshape(L * B, -1), brdf_param_names or self.brdf_param_names, env)
-        if not new_scene:
-            r._envmap = envmaps[-1].to(out.device)  # the scene keeps the last map it was given, as the reference's does
-        return out.reshape(L, B, *out.shape[1:])
+        out = r.render(z, brdf_param_names or self.brdf_param_names, envmaps, view_from=view_from)
+        if not new_scene:  # the scene keeps the last map and view it was given, as the reference's does
+            r._envmap = envmaps[-1].to(out.device)
+            if view_from is not None:
+                r._view_from = torch.as_tensor(view_from)[-1].detach().to("cpu", torch.float32)
+        return out
+
+    def _load_envmaps(self, names) -> torch.Tensor:
+        """envmap_dir/<name>.exr for every name, stacked [n, H, W, 3] on the host (drmnet.py:551-555, 685-689)."""
+        from pathlib import Path
+
+        from . import file_io
+
+        root = self.validation_params["envmap_dir"]
+        assert root is not None, "envmap_dir was needed, but was not specified"
+        return torch.stack([file_io.load_exr(Path(root) / f"{name}.exr", as_torch=True) for name in names])
 
     def reconstruct(self, Lr_0: torch.Tensor, z: torch.Tensor, brdf_param_names=None, transform: bool = True) -> torch.Tensor:
         """drmnet.py:943-953: the estimate re-rendered -- Lr_0 (network space, [B, 3, S, S]) rescaled, warped to an envmap through
@@ -505,6 +530,135 @@ class DRMNet(nn.Module):
                 if active.numel() == 0:
                     break
         return Lr_k, zK, K, intermediates
+
+    # ------------------------------------------------------------------ the validation pass (forward process + losses)
+    def get_loss(self, pred: torch.Tensor, target: torch.Tensor, mean=True):
+        """drmnet.py:398-411 on torch tensors (the validation pass itself reduces on the device through ops.validation_losses)."""
+        loss_type = self.validation_params["loss_type"]
+        if loss_type == "l1":
+            loss = (target - pred).abs()
+        elif loss_type == "l2":
+            loss = (target - pred) ** 2
+        else:
+            raise NotImplementedError(f"unknown loss type '{loss_type}'")
+        return loss.mean() if mean else loss
+
+    @torch.no_grad()
+    def p_losses(self, Lr_k, Lr_km1, z_k, z_K, K, k, illnet_cond, refnet_cond, *, noise=None, seed=None):
+        """drmnet.py:413-450 in eval mode: the forward noise (sigma > 0: ``noise`` [B, 3, H, W] if given, else the library's Philox stream
+        keyed by ``seed``, drawn from torch's generator when None), one pass of both networks at each row's own reversed_k = K - k - 1, and
+        the three losses from drm_validation_losses.  Returns (loss, {"val/loss_refmap", "val/loss_refcode", "val/loss"}), 0-dim device
+        tensors.  There is no backward on this engine: training mode raises."""
+        from . import ops
+
+        if self.training:
+            raise NotImplementedError("p_losses in training mode: the HIP engine has no backward (validation only)")
+        vp = self.validation_params
+        Lr_k = _lib.require_gpu_tensor(Lr_k, "Lr_k")
+        dev = Lr_k.device
+        K, k = K.to(dev), k.to(dev)
+        reversed_k = K - k - 1
+        if vp["sigma"] > 0:
+            if noise is None:
+                if seed is None:
+                    seed = int(torch.randint(0, 2**62, (1,)).item())
+                noise = ops.randn(Lr_k.shape, seed, 0, dev)
+            Lr_k = Lr_k + vp["sigma"] * _lib.require_gpu_tensor(noise, "noise")
+        model_out, z_out = self(Lr_k, illnet_cond, refnet_cond, reversed_k.long())
+        out = ops.validation_losses(model_out, Lr_k, Lr_km1.to(dev), K, z_out, z_k.to(dev), z_K.to(dev), reversed_k, self.z0, self.gamma,
+                                    vp["loss_type"], vp["l_refmap_weight"], vp["l_refcode_weight"])
+        return out[2], {"val/loss_refmap": out[0], "val/loss_refcode": out[1], "val/loss": out[2]}
+
+    @torch.no_grad()
+    def get_input(self, batch, return_Lr_zero=False, return_envmap=False, return_envmap_name=False, return_view_from=False,
+                  bs: Optional[int] = None):
+        """drmnet.py:503-651: the first ``bs`` items of a ParametricRefmapDataset batch -> [K, k, Lr_K, Lr_k, Lr_km1, zK, zk, illnet_c,
+        refnet_c(, Lr_0)(, envmap)(, envmap_name)(, view_from)].  A reflectance map the batch brings ("LrK", "Lrk", "Lrkm1", "r0") with a
+        finite [b, 0, 0, 0] is used as it is; every other one is rendered from its code of the stack (zK, zk, zkm1[, z0]) under
+        batch["envmap"][b] (read from envmap_dir/<name>.exr where missing or NaN-marked) seen from batch["view_from"][b], all of them in one
+        drm_render_refmap_views launch (a NaN code, zkm1 where K == 0, gives a NaN map).  Then the exposure scale of LrK (``normalizing_scale``) is applied to every map, then
+        ``ds.transform``.  Nothing is written to a refmap cache."""
+        from . import ops
+
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("get_input runs on the GPU: move the model there first (drmnet_amd has no CPU path)")
+        zK = batch["zK"]
+        bs = min(len(zK), bs) if bs is not None else len(zK)
+        self.batch_size = bs
+        zK = zK[:bs].to(dev, torch.float32)
+        envmap_name = list(batch["envmap_name"][:bs])
+        view_from = batch.get("view_from")[:bs]
+        K, k = batch["K"][:bs].to(dev), batch["k"][:bs].to(dev)
+        zk, zkm1 = batch["zk"][:bs].to(dev, torch.float32), batch["zkm1"][:bs].to(dev, torch.float32)
+        keys, codes = ["LrK", "Lrk", "Lrkm1"], [zK, zk, zkm1]
+        if return_Lr_zero:
+            keys.append("r0")
+            codes.append(self.z0[None].expand(bs, -1))
+        stacked_z = torch.stack(codes)  # [L, B, P]
+        res = self._renderer().refmap_res
+        given = [batch[key][:bs].to(dev, torch.float32) if key in batch else None for key in keys]
+        not_cached = torch.stack([torch.ones(bs, dtype=torch.bool, device=dev) if r is None else torch.isnan(r[:, 0, 0, 0]) for r in given])
+        envmap = None
+        if bool(not_cached.any()):
+            rows = torch.nonzero(not_cached.any(dim=0)).flatten().tolist()  # the batch items with something to render
+            have = batch["envmap"][:bs] if "envmap" in batch else None
+            load = [b for b in rows if have is None or bool(torch.isnan(have[b, 0, 0, 0]))]
+            loaded = self._load_envmaps([envmap_name[b] for b in load]) if load else None
+            if have is None:
+                envmap = torch.full((bs, *loaded.shape[1:]), float("nan"))
+            else:
+                envmap = have.clone() if load else have
+            for b, em in zip(load, loaded if load else ()):
+                envmap[b] = em.to(envmap.device)
+            envmap = envmap.to(dev, torch.float32)
+            all_rows = len(rows) == bs
+            pick = None if all_rows else torch.tensor(rows, device=dev)
+            rendered = self._renderer().render(stacked_z if all_rows else stacked_z[:, pick], self.brdf_param_names,
+                                               envmap if all_rows else envmap[pick], res=res,
+                                               view_from=view_from if all_rows else torch.as_tensor(view_from)[rows])
+            stacked_Lr = []
+            for l, r in enumerate(given):
+                full = rendered[l] if all_rows else torch.full((bs, 3, res, res), float("nan"), device=dev).index_copy_(0, pick, rendered[l])
+                # a code that is not a number (zkm1 where K == 0) has no reflectance map: NaN, as the item's Lrkm1 says, not a render of clipped NaNs
+                full = torch.where(torch.isnan(stacked_z[l]).any(dim=-1)[:, None, None, None], float("nan"), full)
+                stacked_Lr.append(full if r is None else torch.where(not_cached[l][:, None, None, None], full, r))
+        else:
+            stacked_Lr = given
+        if self.refmap_input_scaler is not None:
+            self.normalizing_scale = ops.luminance_scale(stacked_Lr[0].contiguous(), self.refmap_input_scaler)
+            stacked_Lr = [ops.map_chain(Lr.contiguous(), [("img_mul", 0.0)], scale=self.normalizing_scale) for Lr in stacked_Lr]
+        stacked_Lr = [self.get_first_stage_encoding(self.encode_first_stage(self.ds.transform(Lr))) for Lr in stacked_Lr]
+        Lr_K, Lr_k, Lr_km1 = stacked_Lr[:3]
+        cond_LrK = Lr_K if self.sigma_for_cond_xK <= 0 else self.sigma_for_cond_xK * torch.randn_like(Lr_K) + Lr_K
+        illnet_c = [cond_LrK]
+        out = [K, k, Lr_K, Lr_k, Lr_km1, zK, zk, illnet_c, illnet_c]
+        if return_Lr_zero:
+            out.append(stacked_Lr[3])
+        if return_envmap:
+            out.append(envmap)
+        if return_envmap_name:
+            out.append(batch["envmap_name"][:bs])
+        if return_view_from:
+            out.append(view_from)
+        return out
+
+    def shared_step(self, batch, *, seed=None):
+        """drmnet.py:707-710 (``seed`` keys the forward noise of p_losses)."""
+        K, k, Lr_K, Lr_k, Lr_km1, zK, zk, illnet_c, refnet_c = self.get_input(batch)
+        return self.p_losses(Lr_k, Lr_km1, zk, zK, K, k, illnet_c, refnet_c, seed=seed)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx, *, seed=None):
+        """drmnet.py:731-740: the losses on the live weights and, under ema_scope, on the EMA weights (keys + "_ema").  The reference logs
+        the two dicts; there is no logger here, so the merged six-key dict is returned (0-dim device tensors).  ``seed``: the forward noise
+        of the live pass is keyed by it, that of the EMA pass by seed + 1 (the reference draws twice from one generator)."""
+        _, loss_dict = self.shared_step(batch, seed=seed)
+        with self.ema_scope():
+            _, loss_dict_ema = self.shared_step(batch, seed=None if seed is None else seed + 1)
+        merged = dict(loss_dict)
+        merged.update({key + "_ema": v for key, v in loss_dict_ema.items()})
+        return merged
 
     # ------------------------------------------------------------------ estimate.py glue
     @torch.no_grad()

@@ -117,6 +117,45 @@ def randn(shape, seed: int, offset: int = 0, device="cuda"):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ validation losses (csrc/losses.hip)
+
+LOSS_TYPES = {"l1": 0, "l2": 1}
+
+
+@torch.no_grad()
+def validation_losses(model_out, Lr_k, Lr_km1, K, z_out, z_k, z_K, reversed_k, z0, gamma: float, loss_type: str = "l2", l_refmap_weight: float = 1.0,
+                      l_refcode_weight: float = 1.0) -> torch.Tensor:
+    """models/drmnet.py:432-450 in eval mode (drm_validation_losses): model_out, Lr_k (as the networks saw it), Lr_km1 [B, 3, H, W]; K,
+    reversed_k [B] int32; z_out, z_k, z_K [B, P]; z0 [P] -> fp32 [3] on the device = (loss_refmap, loss_refcode, loss).  Rows with K == 0 are
+    selected out of loss_refmap.  Two launches, no host synchronisation; fp64 sums in a fixed order."""
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError(f"unknown loss type '{loss_type}'")
+    model_out = _lib.require_gpu_tensor(model_out, "model_out")
+    dev = model_out.device
+    B = model_out.shape[0]
+    maps = [model_out] + [_lib.require_gpu_tensor(t, n) for t, n in ((Lr_k, "Lr_k"), (Lr_km1, "Lr_km1"))]
+    if any(t.shape != model_out.shape for t in maps):
+        raise RuntimeError(f"model_out, Lr_k and Lr_km1 must share one shape, got {[tuple(t.shape) for t in maps]}")
+    codes = [_lib.require_gpu_tensor(t, n) for t, n in ((z_out, "z_out"), (z_k, "z_k"), (z_K, "z_K"))]
+    P = codes[0].shape[-1]
+    if any(tuple(t.shape) != (B, P) for t in codes):
+        raise RuntimeError(f"z_out, z_k and z_K must be [B={B}, P], got {[tuple(t.shape) for t in codes]}")
+    ints = [_lib.require_gpu_tensor(t.to(torch.int32), n, torch.int32) for t, n in ((K, "K"), (reversed_k, "reversed_k"))]
+    if any(tuple(t.shape) != (B,) for t in ints):
+        raise RuntimeError(f"K and reversed_k must be [B={B}]")
+    z0 = _lib.require_gpu_tensor(z0.to(dev, torch.float32), "z0")
+    if z0.numel() != P:
+        raise RuntimeError(f"z0 must have {P} entries")
+    ws = torch.empty(_lib.LOSS_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_validation_losses(maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(), ints[0].data_ptr(), codes[0].data_ptr(),
+                                                    codes[1].data_ptr(), codes[2].data_ptr(), ints[1].data_ptr(), z0.data_ptr(), float(gamma),
+                                                    LOSS_TYPES[loss_type], float(l_refmap_weight), float(l_refcode_weight), B,
+                                                    model_out.numel() // B, P, ws.data_ptr(), ws.numel() * 8, out.data_ptr(), _lib.stream_ptr(dev)))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ boundary maps (csrc/transform.hip)
 
 MAP_CODES = {"log_p1": 0, "log10": 1, "lowerbound": 2, "unit_to_signed": 3, "norm_log": 4, "exp_m1": 5, "exp10": 6, "signed_to_unit": 7,

@@ -57,13 +57,34 @@ def _device(*tensors) -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def view_rotation(view_from) -> torch.Tensor:
+    """view_from [B, 3] (or [3]) -> the row-major rotations [B, 3, 3] drm_render_refmap_views reads: the reference's
+    look_at(origin=view_from, target=0, up=+y) (utils/mitsuba3_utils.py:394-396) with columns (right, up', back), back = v / |v|,
+    right = normalize(+y x back), up' = back x right.  [0, 0, d > 0] gives the identity exactly; a view along +-y has no right vector and is
+    a ValueError.  Built on the host (a [B, 3] input on the GPU is brought over: view positions are per-item metadata)."""
+    v = torch.as_tensor(view_from).detach().to("cpu", torch.float32).reshape(-1, 3)
+    back = v / torch.linalg.norm(v, dim=-1, keepdim=True)
+    right = torch.stack([back[:, 2], torch.zeros_like(back[:, 0]), -back[:, 0]], dim=-1)  # +y x back
+    length = torch.linalg.norm(right, dim=-1, keepdim=True)
+    if not bool(torch.isfinite(back).all()) or bool((length < 1e-6).any()):
+        raise ValueError("view_from must be a non-zero position off the +-y axis (look_at with up = +y has no right vector there)")
+    right = right / length
+    up = torch.linalg.cross(back, right, dim=-1)
+    return torch.stack([right, up, back], dim=-1).contiguous()
+
+
 @torch.no_grad()
 def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD,
-           subpixel: int = SUBPIXEL, flip: bool = False) -> torch.Tensor:
-    """One launch of drm_render_refmap: z [B, P], envmaps [B, H, W, 3] (or None: white) -> reflectance maps [B, 3, res, res]."""
+           subpixel: int = SUBPIXEL, flip: bool = False, view_from=None) -> torch.Tensor:
+    """One launch of drm_render_refmap_views: z [B, P] or [L, B, P], envmaps [B, H, W, 3] (or None: white), view_from [B, 3] (or None: +z)
+    -> reflectance maps [B, 3, res, res] or [L, B, 3, res, res].  The L rows of a batch item read the same map: nothing is expanded."""
     dev = _device(z, envmaps)
-    rows = canonical_rows(torch.as_tensor(z).to(dev), brdf_param_names).reshape(-1, 6).contiguous()
-    B = rows.shape[0]
+    z = torch.as_tensor(z).to(dev)
+    if z.dim() not in (2, 3):
+        raise ValueError(f"z must be [B, P] or [L, B, P], got {tuple(z.shape)}")
+    stacked = z.dim() == 3
+    L, B = (z.shape[0], z.shape[1]) if stacked else (1, z.shape[0])
+    rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
     env, EH, EW = None, 0, 0
     if envmaps is not None:
         env = envmaps.to(dev, torch.float32)
@@ -71,19 +92,25 @@ def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] =
             raise ValueError(f"envmaps must be [B={B}, H, W, 3], got {tuple(env.shape)}")
         env = env.contiguous()
         EH, EW = int(env.shape[1]), int(env.shape[2])
-    out = torch.empty((B, 3, res, res), dtype=torch.float32, device=dev)
+    view = None
+    if view_from is not None:
+        view = view_rotation(view_from)
+        if view.shape[0] != B:
+            raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
+        view = view.to(dev)
+    out = torch.empty((L * B, 3, res, res), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().drm_render_refmap(rows.data_ptr(), _lib.ptr(env), out.data_ptr(), B, int(res), EH, EW, int(quad), int(subpixel),
-                                                int(bool(flip)), _lib.stream_ptr(dev)))
-    return out
+        _lib.check(_lib.lib().drm_render_refmap_views(rows.data_ptr(), L, _lib.ptr(env), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad),
+                                                      int(subpixel), int(bool(flip)), _lib.stream_ptr(dev)))
+    return out.reshape(L, B, 3, res, res) if stacked else out
 
 
 class RefMapRenderer:
     """MitsubaRefMapRenderer (utils/mitsuba3_utils.py:324-430) on drm_render_refmap: the sphere seen from +z under the scene's
     environment map, ``direct`` integration, box-filtered pixels.  The integral is a deterministic quadrature (``quad`` x ``quad``
     points per lobe at ``subpixel`` x ``subpixel`` normals per pixel), so ``spp`` and ``denoise`` are accepted and ignored: there is
-    no Monte-Carlo noise to average or denoise.  Other views (``init_view_from`` off the +z axis, ``view_from``) and the normal /
-    depth outputs are not implemented.  Construction does not touch the GPU."""
+    no Monte-Carlo noise to average or denoise.  A per-call ``view_from`` turns the environment (render.view_rotation); a scene whose own
+    sensor is off the +z axis (``init_view_from``) and the normal / depth outputs are not implemented.  Construction does not touch the GPU."""
 
     def __init__(self, refmap_res: int, spp: int = 1024, envmap_size=(1000, 2000), denoise: Optional[str] = None, return_normal: bool = False,
                  return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
@@ -102,18 +129,20 @@ class RefMapRenderer:
         self.quad, self.subpixel = int(quad), int(subpixel)
         self.flip = False
         self._envmap: Optional[torch.Tensor] = None  # the scene's map; None = the initial all-zero bitmap of envmap_size
+        self._view_from: Optional[torch.Tensor] = None  # the scene's view; None = the sensor's own (+z)
 
-    def render(self, z, brdf_param_names=None, envmaps=None, *, res: Optional[int] = None, flip: Optional[bool] = None) -> torch.Tensor:
-        """Batched form: z [B, P], envmaps [B, H, W, 3] or None (white) -> [B, 3, R, R] in one launch."""
+    def render(self, z, brdf_param_names=None, envmaps=None, *, res: Optional[int] = None, flip: Optional[bool] = None, view_from=None) -> torch.Tensor:
+        """Batched form: z [B, P] or [L, B, P], envmaps [B, H, W, 3] or None (white), view_from [B, 3] or None (+z) -> [(L,) B, 3, R, R] in
+        one launch."""
         return render(z, brdf_param_names or self.brdf_param_names, envmaps, res=res or self.refmap_res, quad=self.quad, subpixel=self.subpixel,
-                      flip=self.flip if flip is None else flip)
+                      flip=self.flip if flip is None else flip, view_from=view_from)
 
     def rendering(self, z, brdf_param_names, envmap: Optional[torch.Tensor] = None, view_from=None, flip: Optional[bool] = None, sensor=0,
                   spp: int = 0, new_scene: bool = False, channel_first: bool = False) -> torch.Tensor:
         """utils/mitsuba3_utils.py:416-430: one reflectance map [R, R, 3] ([3, R, R] with channel_first).  ``envmap`` [H, W, 3] replaces
-        the scene's map (``new_scene``: for this call only); None reuses it.  ``flip`` mirrors the sensor (kept for later calls)."""
-        if view_from is not None:
-            raise NotImplementedError("view_from: only the view from +z is modelled")
+        the scene's map (``new_scene``: for this call only); None reuses it.  ``view_from`` [3] moves the viewer and, like the map, stays
+        with the scene for later calls (the reference updates the scene's sensor, :394-396).  ``flip`` mirrors the sensor (kept for later
+        calls)."""
         if not (isinstance(sensor, int) and sensor == 0):
             raise NotImplementedError("only the scene's own sensor (sensor=0) is modelled")
         if envmap is not None:
@@ -123,6 +152,7 @@ class RefMapRenderer:
             if envmap is None:
                 raise ValueError("new_scene needs an envmap")
             env = envmap.to(dev)
+            view = view_from
         else:
             if flip is not None:
                 self.flip = bool(flip)
@@ -131,8 +161,12 @@ class RefMapRenderer:
             if self._envmap is None:
                 self._envmap = torch.zeros(*self.envmap_size, 3, device=dev)
             env = self._envmap
+            if view_from is not None:
+                self._view_from = torch.as_tensor(view_from).detach().to("cpu", torch.float32).reshape(3)
+            view = self._view_from
         z = torch.as_tensor(z).reshape(1, -1)
-        img = self.render(z, brdf_param_names, env[None], flip=flip if new_scene else None)[0]
+        img = self.render(z, brdf_param_names, env[None], flip=flip if new_scene else None,
+                          view_from=None if view is None else torch.as_tensor(view).reshape(1, 3))[0]
         return img if channel_first else img.permute(1, 2, 0)
 
 

@@ -1,0 +1,105 @@
+"""Validation of a DRMNet checkpoint, the reference's ``python main.py --base <yaml>`` without ``-t`` (main.py:685, trainer.validate) on the
+MI355X path.
+
+    python -m drmnet_amd.validate --base configs/drmnet/eval_drmnet.yaml --data_root data/LavalIndoor+PolyHaven_2k [--split val]
+        [--datalist envs_val.txt] [--batch_size 20] [--limit N] [--precision auto] [--seed 0] [--ckpt drmnet.ckpt]
+
+Every batch goes through ``DRMNet.validation_step``: the forward process renders the reflectance maps of (zK, zk, zkm1) under the item's
+environment map and view (csrc/render.hip), both networks run once on the live and once on the EMA weights, and the losses are reduced on
+the device (csrc/losses.hip).  One JSON line is printed: the epoch means of ``val/loss_refmap``, ``val/loss_refcode``, ``val/loss`` and their
+``_ema`` twins, weighted by batch size as Lightning's ``on_epoch`` reduction weights them, plus the item and batch counts.
+
+The dataset is the ``data.params.validation`` node of the YAML when it has one (a copy of the reference's training YAML works unchanged);
+otherwise it is a ParametricRefmapDataset built from the flags, with the transform of the YAML's ``predict`` node.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from pathlib import Path
+from typing import Optional
+
+import torch
+
+QUADRATURE_NOTE = ("the reflectance maps are rendered with a fixed 32 x 32 quadrature per lobe without importance sampling or prefiltering of the "
+                   "environment map: it is unvalidated for small, very bright lights in 1000 x 2000 maps")
+
+
+def collate(items):
+    """torch's default_collate (main.py:366-371 without the mesh entry this dataset never has)."""
+    from torch.utils.data import default_collate
+
+    return default_collate(items)
+
+
+@torch.no_grad()
+def validate(model, dataset, batch_size: int, limit: Optional[int] = None, precision: Optional[str] = None, seed: int = 0) -> dict:
+    """One validation epoch of ``model`` (on the GPU) over the first ``limit`` items of ``dataset`` in order, ``batch_size`` at a time.  The
+    dataset is attached both ways as main.py does (``dataset.model``, ``model.ds``).  ``precision``: DRMNet.set_precision mode, None leaves the
+    model as it is.  ``seed``: batch i keys its forward noise by seed + 2 i (live) and seed + 2 i + 1 (EMA).  Returns the batch-size-weighted
+    epoch means as floats, plus "items", "batches" and the per-batch dicts under "per_batch" (each with its "batch_size")."""
+    if precision is not None:
+        model.set_precision(precision)
+    dataset.model = model
+    model.ds = dataset
+    n = len(dataset) if limit is None else min(len(dataset), int(limit))
+    per_batch = []
+    for i, start in enumerate(range(0, n, batch_size)):
+        batch = collate([dataset[j] for j in range(start, min(start + batch_size, n))])
+        out = model.validation_step(batch, i, seed=seed + 2 * i)
+        per_batch.append((model.batch_size, out))  # (device scalars: nothing waits for the GPU inside the loop)
+    rows = [dict({k: float(v) for k, v in out.items()}, batch_size=bs) for bs, out in per_batch]
+    result = {k: sum(r[k] * r["batch_size"] for r in rows) / n for k in rows[0] if k != "batch_size"} if rows else {}
+    result.update(items=n, batches=len(rows), per_batch=rows)
+    return result
+
+
+def build_dataset(config: dict, args):
+    """The YAML's data.params.validation node; without one, a ParametricRefmapDataset from the flags."""
+    from .config import instantiate_from_config
+    from .dataset import ParametricRefmapDataset
+
+    params = (config.get("data") or {}).get("params") or {}
+    if "validation" in params and args.data_root is None:
+        return instantiate_from_config(params["validation"])
+    if args.data_root is None:
+        raise SystemExit("validate: the config has no data.params.validation node, so --data_root is needed")
+    base = dict((params.get("predict") or {}).get("params") or {})
+    model_params = config["model"]["params"]
+    return ParametricRefmapDataset(size=base.get("size", model_params.get("image_size", 128)), split=args.split, data_root=str(args.data_root),
+                                   zdim=len(model_params.get("z0", [1.0])), transform_func=base.get("transform_func", "log"),
+                                   clamp_before_exp=base.get("clamp_before_exp", 0), return_envmap=True, datalist=args.datalist)
+
+
+def make_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m drmnet_amd.validate", description="Validation losses of a DRMNet checkpoint on the GPU. Note: " + QUADRATURE_NOTE + ".")
+    p.add_argument("--base", type=Path, required=True, help="the model config (the reference's eval or training YAML)")
+    p.add_argument("--data_root", type=Path, default=None, help="directory of the <name>.exr environment maps (overrides the YAML's validation node)")
+    p.add_argument("--split", choices=["train", "val", "test"], default="val")
+    p.add_argument("--datalist", type=str, default=None, help="text file naming one <name>.exr per line (default data/datalists/<data_root name>/envs_<split>.txt)")
+    p.add_argument("--batch_size", type=int, default=20)
+    p.add_argument("--limit", type=int, default=None, help="validate the first N items only")
+    p.add_argument("--precision", default="auto", help="conv arithmetic of both networks (DRMNet.set_precision)")
+    p.add_argument("--seed", type=int, default=0, help="keys the forward noise")
+    p.add_argument("--ckpt", type=Path, default=None, help="checkpoint to load instead of the YAML's ckpt_path")
+    return p
+
+
+def main(argv=None) -> dict:
+    from .config import instantiate_from_config, load_config
+
+    args = make_parser().parse_args(argv)
+    config = load_config(args.base)
+    model_cfg = {"target": config["model"]["target"], "params": dict(config["model"].get("params") or {})}
+    if args.ckpt is not None:
+        model_cfg["params"]["ckpt_path"] = str(args.ckpt)
+    model = instantiate_from_config(model_cfg).cuda()
+    dataset = build_dataset(config, args)
+    result = validate(model, dataset, args.batch_size, limit=args.limit, precision=args.precision, seed=args.seed)
+    result.pop("per_batch")
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -359,10 +359,44 @@ int drm_resize(const float* x, float* out, int planes, int IH, int IW, int OH, i
  *   (GGX-sampled half vectors for the specular lobe, cosine-weighted directions for the diffuse one); bitwise reproducible.
  *   quad in [1, 1024] (32 by default in the Python layer), subpixel in [1, 16] (2). */
 int drm_render_refmap(const float* z, const float* envmap, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, void* stream);
+/* The same kernel on L stacked sets of B rows, each batch item under its own view: what DRMNet.get_input / rendering_refmaps ask of the
+ * renderer (models/drmnet.py:559-569, 667-705: a Python loop of MitsubaRefMapRenderer.rendering(z, envmap, view_from) calls, one scene
+ * update and one render per (stack, batch) item) in one launch.  drm_render_refmap is this entry with L = 1 and view = NULL.
+ *   z [L][B][6]; out [L][B][3][R][R]; row (l, b) is lit by envmap[b] and seen through view[b]: the L rows of a batch item index the same map,
+ *   nothing is expanded.  envmap [B][EH][EW][3] or NULL (white; the view is then not read).
+ *   view [B][9] or NULL: row-major rotations Rot.  Every light direction l of the quadrature (in the frame whose viewer is +z) is looked up
+ *   in the environment at Rot l.  For the reference's look_at(origin = v, target = 0, up = +y) (utils/mitsuba3_utils.py:394-396) the columns
+ *   of Rot are (right, up', back): back = v / |v|, right = normalize(+y x back), up' = back x right.  NULL and an exact identity skip the
+ *   rotation (they are not multiplied by it), so the view from +z is the drm_render_refmap result bit for bit.
+ *   Every row is summed in the per-lane order of drm_render_refmap whatever L is: a stacked render equals its rows rendered one by one. */
+int drm_render_refmap_views(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
+                            int subpixel, int flip, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The validation losses (csrc/losses.hip).
+ * ------------------------------------------------------------------------------------------- */
+/* DRMNet.p_losses after the two networks, in eval mode (models/drmnet.py:432-450 with get_loss :398-411 and get_brdf_out :390-396): two
+ * launches, no host synchronisation, nothing materialised.
+ *   model_out, Lr_k (the noised input of the networks), Lr_km1 [B][per_row] fp32 (per_row = 3 H W); K, reversed_k int32[B];
+ *   z_out, z_k, z_K [B][P] fp32; z0 fp32[P]; loss_type DRM_LOSS_L1 (|d|) or DRM_LOSS_L2 (d^2).
+ *   out fp32[3] on the device = (loss_refmap, loss_refcode, loss):
+ *     loss_refmap  = mean of f(model_out - (Lr_km1 - Lr_k)) over the rows with K != 0.  Rows are selected, not weighted: a NaN in a row with
+ *                    K == 0 (the dataset marks its zkm1 / Lrkm1 so) does not reach the result; no selected row gives NaN (torch's empty mean)
+ *     zk_out       = clamp(z0 + gamma^reversed_k (z_out - z0), 0, 1), the power as exp(reversed_k ln gamma) in fp64 cast to fp32
+ *     loss_refcode = (mean f(zk_out - z_k) + mean f(clamp(z_out, 0, 1) - z_K)) / 2
+ *     loss         = l_refmap_weight loss_refmap + l_refcode_weight loss_refcode
+ *   Element arithmetic and sums are fp64, combined in a fixed order without atomics (two calls are bitwise equal); the three results are
+ *   rounded to fp32 once.  workspace: DRM_LOSS_WORKSPACE_BYTES of device memory, contents irrelevant. */
+#define DRM_LOSS_L1 0
+#define DRM_LOSS_L2 1
+#define DRM_LOSS_WORKSPACE_BYTES 2048
+int drm_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
+                          const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double l_refmap_weight,
+                          double l_refcode_weight, int B, int64_t per_row, int P, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
 #ifdef __cplusplus
 }

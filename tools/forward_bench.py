@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Timings behind DESIGN.md's forward-process paragraph (one MI355X).
+
+    python tools/forward_bench.py render [--libs - drmnet_amd/csrc/_ab/libdrmnet_hip_parent.so]
+        L x B stacked rows at R = 128 through drm_render_refmap_views (maps indexed per row) against the same L B rows through
+        drm_render_refmap with the maps expanded L times, per library, alternating ("-" = the product library; a library without the
+        stacked entry point, e.g. the parent commit's built with tools/build_variant.sh, runs the expanded form only).
+    python tools/forward_bench.py step [--batch 20]
+        one DRMNet.validation_step at full width (synthetic weights, 128 x 128, 128 x 256 maps) split into forward process (renders +
+        transforms), networks and loss by device events.  Run it under `rocprofv3 --kernel-trace --stats -- python ...` for the kernel table.
+"""
+import argparse
+import ctypes as C
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return ms
+
+
+def bench_render(args):
+    from drmnet_amd import _lib
+
+    dev = torch.device("cuda:0")
+    L, B, R = args.stack, args.batch, 128
+    libs = []
+    for path in args.libs:
+        lib = C.CDLL(_lib.LIB_PATH if path == "-" else os.path.join(ROOT, path))
+        libs.append((path, lib, hasattr(lib, "drm_render_refmap_views")))
+    g = torch.Generator().manual_seed(1)
+    z = torch.rand((L, B, 6), generator=g).to(dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    vp = C.c_void_p
+    for EH, EW in ((128, 256), (1000, 2000)):
+        env = (torch.rand((B, EH, EW, 3), generator=g) + 0.05).to(dev)
+        out = torch.empty((L, B, 3, R, R), device=dev)
+        results = {}
+        for rep in range(args.rounds):
+            for name, lib, has_views in libs:
+                def expanded():
+                    e = env[None].expand(L, *env.shape).reshape(L * B, *env.shape[1:])  # (the copy is part of what is timed)
+                    assert lib.drm_render_refmap(vp(z.data_ptr()), vp(e.data_ptr()), vp(out.data_ptr()), L * B, R, EH, EW, 32, 2, 0, stream) == 0
+
+                def stacked():
+                    assert lib.drm_render_refmap_views(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0, stream) == 0
+
+                results.setdefault((name, "expanded + drm_render_refmap"), []).extend(timed(expanded, args.reps))
+                if has_views:
+                    results.setdefault((name, "drm_render_refmap_views"), []).extend(timed(stacked, args.reps))
+        # every form of every library renders the same bits
+        ref = None
+        for name, lib, has_views in libs:
+            e = env[None].expand(L, *env.shape).reshape(L * B, *env.shape[1:])
+            forms = [("expanded", lambda: lib.drm_render_refmap(vp(z.data_ptr()), vp(e.data_ptr()), vp(out.data_ptr()), L * B, R, EH, EW, 32, 2, 0, stream))]
+            if has_views:
+                forms.append(("stacked", lambda: lib.drm_render_refmap_views(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0, stream)))
+            for form, call in forms:
+                out.zero_()
+                assert call() == 0
+                torch.cuda.synchronize()
+                ref = out.clone() if ref is None else ref
+                print(f"maps {EH}x{EW}  [{name}] {form}: bitwise equal to the first form: {torch.equal(out, ref)}", flush=True)
+            del e
+        for (name, form), ms in results.items():
+            ms = sorted(ms)
+            print(f"maps {EH}x{EW} L={L} B={B} R={R}  [{name}] {form}: median {ms[len(ms) // 2]:.2f} ms  min {ms[0]:.2f}  max {ms[-1]:.2f}  (n={len(ms)})", flush=True)
+        del env
+
+
+def bench_step(args):
+    from drmnet_amd import synth
+    from drmnet_amd.config import load_config
+    from drmnet_amd.dataset import BaseDataset
+    from drmnet_amd.drmnet import DRMNet
+
+    dev = torch.device("cuda:0")
+    params = dict(load_config(os.path.join(ROOT, "configs/drmnet/eval_drmnet.yaml"))["model"]["params"], ckpt_path=None, use_ema=False)
+    m = DRMNet(**params)
+    synth.load_synth(m.illnet_model.diffusion_model, synth.SEED_ILLNET)
+    synth.load_synth(m.refnet_model.diffusion_model, synth.SEED_REFNET)
+    zman = [(k, tuple(v.shape)) for k, v in m.illnet_model.z_emb_layer.state_dict().items()]
+    m.illnet_model.z_emb_layer.load_state_dict(synth.synth_state_dict(zman, synth.SEED_ZEMB))
+    m.ds = BaseDataset(128, "log", clamp_before_exp=20)
+    m = m.to(dev).set_precision(args.precision)
+    B = args.batch
+    g = torch.Generator().manual_seed(2)
+    zK = torch.rand((B, 6), generator=g)
+    K, k, zk, zkm1 = m.get_schedule(zK, z0=m._z0, normalized_k=torch.rand((B,), generator=g), return_zkm1=True)
+    phi = torch.rand((B,), generator=g) * 6.2831853
+    batch = {"zK": zK, "K": K, "k": k, "zk": zk, "zkm1": zkm1, "envmap_name": [f"e{i}" for i in range(B)],
+             "view_from": torch.stack([torch.sin(phi), torch.zeros(B), torch.cos(phi)], dim=-1),
+             "envmap": (torch.rand((B, 128, 256, 3), generator=g) + 0.05).to(dev)}
+    parts = {}
+
+    def step():
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        marks[0].record()
+        K_, k_, Lr_K, Lr_k, Lr_km1, zK_, zk_, ic, rc = m.get_input(batch)
+        marks[1].record()
+        reversed_k = K_ - k_ - 1
+        noised = Lr_k + 0.02 * torch.randn_like(Lr_k)
+        model_out, z_out = m(noised, ic, rc, reversed_k.long())
+        marks[2].record()
+        from drmnet_amd import ops
+
+        out = ops.validation_losses(model_out, noised, Lr_km1, K_, z_out, zk_, zK_, reversed_k, m.z0, m.gamma, "l2", 10.0, 0.1)
+        marks[3].record()
+        marks[3].synchronize()
+        for name, i in (("forward process (renders + transforms)", 0), ("networks", 1), ("loss", 2)):
+            parts.setdefault(name, []).append(marks[i].elapsed_time(marks[i + 1]))
+        return out
+
+    step()
+    parts.clear()
+    t0 = time.time()
+    for _ in range(args.reps):
+        out = step()
+    wall = (time.time() - t0) / args.reps * 1e3
+    for name, ms in parts.items():
+        ms = sorted(ms)
+        print(f"validation step B={B} {args.precision}: {name}: median {ms[len(ms) // 2]:.2f} ms (min {ms[0]:.2f}, max {ms[-1]:.2f}, n={len(ms)})")
+    print(f"validation step B={B} {args.precision}: wall {wall:.1f} ms per pass of one weight set; losses {out.tolist()}", flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["render", "step"])
+    ap.add_argument("--libs", nargs="*", default=["-"])
+    ap.add_argument("--stack", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--precision", default="f16mx")
+    a = ap.parse_args()
+    {"render": bench_render, "step": bench_step}[a.what](a)
