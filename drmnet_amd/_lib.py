@@ -18,6 +18,13 @@ LIB_PATH = os.environ.get("DRM_LIB_PATH") or os.path.join(_HERE, "csrc", "libdrm
 ABI_VERSION = 3
 MAX_LEVELS = 8
 LOSS_WORKSPACE_BYTES = 2048  # DRM_LOSS_WORKSPACE_BYTES
+DIFFUSION_LOSS_MAX_PARTS = 32  # DRM_DIFFUSION_LOSS_MAX_PARTS
+
+
+def diffusion_loss_workspace_bytes(B: int) -> int:
+    """DRM_DIFFUSION_LOSS_WORKSPACE_BYTES(B)"""
+    return int(B) * DIFFUSION_LOSS_MAX_PARTS * 2 * 8
+
 
 # every symbol include/drmnet_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -32,6 +39,7 @@ SYMBOLS = [
     "drm_unet_load_params_set", "drm_unet_use_set", "drm_set_graph_replay", "drm_graph_launches",
     "drm_map_chain", "drm_masked_log_range", "drm_luminance_scale", "drm_mirmap2envmap", "drm_hdr2ldr", "drm_resize", "drm_profile_variants",
     "drm_render_refmap", "drm_brdf_eval", "drm_render_refmap_views", "drm_validation_losses",
+    "drm_obs_forward_process", "drm_diffusion_losses",
 ]
 
 
@@ -187,6 +195,8 @@ def lib() -> C.CDLL:
     L.drm_render_refmap_views.argtypes = [fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.drm_validation_losses.argtypes = [fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]
+    L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_diffusion_losses.argtypes = [fp, fp, fp, vp, fp, fp, i32, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t, fp, fp, vp]
     if L.drm_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libdrmnet_hip.so ABI version {L.drm_abi_version()} != {ABI_VERSION}: rebuild with `python -m drmnet_amd.build`")
     _lib = L

@@ -592,4 +592,26 @@ int drm_validation_losses(const float* model_out, const float* Lr_k, const float
   });
 }
 
+// ------------------------------------------------------------------------------------------------ ObsNet forward process and losses (obs_forward.hip)
+
+int drm_obs_forward_process(const float* x, const float* mask, const int32_t* t, const float* sqrt_alphas_cumprod,
+                            const float* sqrt_one_minus_alphas_cumprod, int T, float noisy_observe, int padding_mode, const float* e_observe,
+                            const float* e_padding, const float* e_q, uint64_t seed, float* cond, float* x_noisy, float* noise, int B, int C, int H,
+                            int W, int mask_H, int mask_W, void* stream) {
+  return guarded([&]() -> int {
+    return launch_obs_forward_process(x, mask, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, T, noisy_observe, padding_mode, e_observe, e_padding,
+                                      e_q, seed, cond, x_noisy, noise, B, C, H, W, mask_H, mask_W, static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_diffusion_losses(const float* model_out, const float* target, const float* invmask, const int32_t* t, const float* logvar,
+                         const float* lvlb_weights, int T, int loss_type, double l_simple_weight, double original_elbo_weight, int B,
+                         int64_t per_row, int C, void* workspace, size_t workspace_bytes, float* out, float* loss_simple_rows, void* stream) {
+  return guarded([&]() -> int {
+    return launch_diffusion_losses(model_out, target, invmask, t, logvar, lvlb_weights, T, loss_type, l_simple_weight, original_elbo_weight, B,
+                                   (long long)per_row, C, static_cast<double*>(workspace), workspace_bytes, out, loss_simple_rows,
+                                   static_cast<hipStream_t>(stream));
+  });
+}
+
 }  // extern "C"

@@ -207,6 +207,13 @@ int launch_render_refmap_views(const float* z, int L, const float* env, const fl
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,
                              double w_refcode, int B, long long per_row, int P, double* ws, size_t ws_bytes, float* out, hipStream_t s);
+// ObsNet's forward process and diffusion losses (obs_forward.hip): see drm_obs_forward_process / drm_diffusion_losses
+int launch_obs_forward_process(const float* x, const float* mask, const int32_t* t, const float* sqrt_ac, const float* sqrt_1mac, int T,
+                               float noisy_observe, int padding_mode, const float* e_obs, const float* e_pad, const float* e_q, uint64_t seed,
+                               float* cond, float* x_noisy, float* noise, int B, int C, int H, int W, int mask_H, int mask_W, hipStream_t s);
+int launch_diffusion_losses(const float* model_out, const float* target, const float* invmask, const int32_t* t, const float* logvar,
+                            const float* lvlb, int T, int loss_type, double w_simple, double w_elbo, int B, long long per_row, int C, double* ws,
+                            size_t ws_bytes, float* out, float* rows_out, hipStream_t s);
 // principled eval (f times n.l) of N (n, v, l) triples; z [1 or N][6]; out [N][3]
 int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s);
 

@@ -131,7 +131,8 @@ class ParametricRefmapDataset(BaseDataset):
 
     ``datalist``: the text file naming one ``<name>.exr`` per line; default the reference's ``data/datalists/<data_root name>/envs_<split>.txt``
     (relative to the working directory).  ``refmap_cache_root`` / ``return_cache`` are accepted and unused: no .pt refmap cache is read, every
-    map is rendered by DRMNet.get_input.  ``mask_root`` (the sparse masks of ObsNet's data, read through OpenCV) is not implemented."""
+    map is rendered by DRMNet.get_input.  ``mask_root`` (the sparse masks of ObsNet's data, read through OpenCV) is not implemented here:
+    MaskedRefmapDataset below restates it without OpenCV."""
 
     def __init__(self, size: int, split: str, data_root: str, zdim: int, transform_func: str = "log", clamp_before_exp: float = 0,
                  return_envmap: bool = False, mask_root: Optional[str] = None, mask_area_min_rate: float = 0.002, epoch_bias: int = 0,
@@ -197,7 +198,7 @@ class ParametricRefmapDataset(BaseDataset):
         normalized_k = rand()
         phi = (rand() * 64).int() / 64 * torch.pi * 2 - torch.pi
         theta = (rand() * 0 + 0.5) * torch.pi  # (the reference draws and discards it: every view is on the horizontal circle)
-        rand()  # the mask draw
+        mask_draw = rand().item()
         # thetaphi2xyz(normal = +y, tangent = +z): cos(theta) y + sin(theta) cos(phi) z + sin(theta) sin(phi) x, summed in that order
         y, z, x = torch.tensor([0.0, 1.0, 0.0]), torch.tensor([0.0, 0.0, 1.0]), torch.tensor([1.0, 0.0, 0.0])
         view_from = torch.cos(theta) * y
@@ -210,5 +211,71 @@ class ParametricRefmapDataset(BaseDataset):
             data.update(K=K, k=k, zk=zk, zkm1=zkm1 if K > 0 else torch.full_like(zkm1, torch.nan))
         if self.return_envmap:
             data["envmap"] = self.envmaps[env_name] if self.preload_envmap else self._load(env_name)
+        self._add_mask(data, mask_draw)
         data["tag"] = env_name
         return data
+
+    def _add_mask(self, data: dict, mask_draw: float) -> None:
+        """what the item's fifth draw selects (parametricrefmap.py:119-131); nothing without masks"""
+
+
+def _nearest_indices(src: int, dst: int) -> torch.Tensor:
+    """OpenCV's INTER_NEAREST source index of every destination index: min(floor(dst_index * src / dst), src - 1), the scale src / dst taken in
+    double precision as cv::resize takes it."""
+    scale = float(src) / float(dst)
+    return torch.tensor([min(int(math.floor(i * scale)), src - 1) for i in range(dst)], dtype=torch.long)
+
+
+class MaskedRefmapDataset(ParametricRefmapDataset):
+    """ParametricRefmapDataset with the sparse observation masks of ObsNet's data (dataset/parametricrefmap.py:45-52, :119-131), the items
+    ObsNetDiffusion.get_input reads for cond_key "masked_LrK".  The parent's fifth draw u picks mask ``int(u * mask_len)`` of the list; a mask
+    with fewer than ``H W mask_area_min_rate`` non-zero pixels is passed over for the next index (modulo ``mask_len``); the mask is resized to
+    ``size x size`` by the nearest rule and stored under "mask" as ``mask / 255`` (float64, as numpy divides a uint8 array).  Every other
+    entry of an item is the parent's, draw for draw.
+
+    ``mask_list``: the text file naming one mask image per line, relative to ``mask_root/<train|test>`` (``val`` items read the ``train``
+    directory, as in the reference); default ``data/datalists/<mask_root name>/sparsemaskannotations_<split>.txt``.
+
+    The reference reads and resizes through OpenCV (cv2.imread(..., -1), cv2.resize(..., INTER_NEAREST)), which this project does not depend
+    on.  Here Pillow reads the file -- single-channel 8-bit images only, anything else is an error rather than a guess at what imread would
+    return -- and the resize is OpenCV's documented nearest rule, source index = min(floor(dst_index * src / dst), src - 1) per axis.  That
+    rule is restated from OpenCV's documentation and source, NOT checked against a run of OpenCV: it is not installed where this was written."""
+
+    def __init__(self, size: int, split: str, data_root: str, zdim: int, mask_root: str, mask_area_min_rate: float = 0.002,
+                 mask_list: Optional[str] = None, **kwargs):
+        super().__init__(size, split, data_root, zdim, mask_root=None, mask_area_min_rate=mask_area_min_rate, **kwargs)
+        if mask_root is None:
+            raise ValueError("MaskedRefmapDataset needs mask_root")
+        self.with_mask = True
+        self.mask_root = Path(mask_root)
+        self.mask_name = self.mask_root.name
+        self.t = "train" if split in ("train", "val") else "test"
+        with open(mask_list if mask_list is not None else f"data/datalists/{self.mask_name}/sparsemaskannotations_{split}.txt", "r") as f:
+            self.mask_annotations = f.read().splitlines()
+        self.mask_len = len(self.mask_annotations)
+        if self.mask_len == 0:
+            raise ValueError("MaskedRefmapDataset: the mask list is empty")
+        self.mask_area_min_rate = mask_area_min_rate
+
+    def _read_mask(self, idx: int):
+        import numpy as np
+        from PIL import Image
+
+        path = self.mask_root / self.t / self.mask_annotations[idx]
+        with Image.open(path) as im:
+            if im.mode != "L":
+                raise ValueError(f"{path}: a mask must be a single-channel 8-bit image (Pillow mode 'L'), got mode {im.mode!r}")
+            return np.array(im, dtype=np.uint8)
+
+    def _add_mask(self, data: dict, mask_draw: float) -> None:
+        mask_idx = int(mask_draw * self.mask_len)
+        for _ in range(self.mask_len):
+            mask = self._read_mask(mask_idx)
+            height, width = mask.shape[:2]
+            if mask.astype(bool).sum() >= height * width * self.mask_area_min_rate:  # don't use the masks with too small region
+                break
+            mask_idx = (mask_idx + 1) % self.mask_len
+        else:
+            raise ValueError(f"no mask of {self.mask_root / self.t} covers {self.mask_area_min_rate} of its image")  # (the reference loops forever)
+        rows, cols = _nearest_indices(height, self.size).numpy(), _nearest_indices(width, self.size).numpy()
+        data["mask"] = mask[rows][:, cols] / 255

@@ -6,6 +6,13 @@ Mirrors (inference half only; training, VQ/KL first stages, patch fold/unfold ar
   LatentDiffusion.__init__/apply_model/p_mean_variance/p_sample/sample/decode_first_stage
                                                                   ddpm.py:439-488, :916-1023, :1079-1167, :1315-1350, :731-789
   ObsNetDiffusion.__init__/p_sample_loop/sample_log/get_cond_for_predict   models/obsnet.py:35-137, :500-583, :656-704
+and for the validation pass of ``python main.py --base ...`` without ``-t`` (drmnet_amd.validate):
+  DDPM.get_loss, lvlb_weights, logvar                              ddpm.py:296-309, :179-187, :133
+  ObsNetDiffusion.get_input (cond_key "masked_LrK") / shared_step / forward / p_losses (eval mode)
+                                                                  models/obsnet.py:139-413, :415-429, :453-498
+  validation_step                                                 ddpm.py:373-379
+with the forward process and the loss reduction on csrc/obs_forward.hip.  The object-image branch of get_input (cond_key "raw_refmap", the
+Mitsuba mesh renderer) and the .pt caches stay out of scope.
 ``state_dict()`` keys equal the reference's (schedule buffers, ``model.diffusion_model.*``, ``model_ema.*``).
 """
 from __future__ import annotations
@@ -40,14 +47,20 @@ def extract_into_tensor(a, t, x_shape):
     return a[t].reshape((t.shape[0],) + (1,) * (len(x_shape) - 1))
 
 
-# Constructor / YAML keys of the reference that steer only training, logging or the out-of-scope renderers (ldm/models/diffusion/ddpm.py:60-135,
-# :442-512; models/obsnet.py:38-137).  They are ACCEPTED, so configs/**.yaml and reference-style constructor calls load unchanged, and never
-# read: nothing on the sampling path depends on them.  Any other unknown key is an error.
+# Constructor / YAML keys of the reference beyond the sampling path (ldm/models/diffusion/ddpm.py:60-135, :442-512; models/obsnet.py:38-137).
+# They are ACCEPTED, so configs/**.yaml and reference-style constructor calls load unchanged.  Those the validation pass reads
+# (_VALIDATION_DEFAULTS) are kept in ``validation_params``; the rest steer only training, logging, the caches or the out-of-scope mesh renderer
+# and are never read.  Any other unknown key is an error.
 _TRAINING_ONLY = frozenset({
     "loss_type", "monitor", "original_elbo_weight", "l_simple_weight", "scheduler_config", "use_positional_encodings", "logvar_init", "cosine_s",
     "first_stage_key", "cond_stage_trainable", "masked_loss", "obj_img_key", "cache_data", "refmap_cache_root", "objimg_cache_root", "envmap_dir",
     "img_renderer_config",
 })
+
+
+# the reference's defaults (ddpm.py:64, :80-88, :447; models/obsnet.py:53, :60) of the keys get_input / p_losses read
+_VALIDATION_DEFAULTS = {"loss_type": "l2", "l_simple_weight": 1.0, "original_elbo_weight": 0.0, "logvar_init": 0.0, "masked_loss": True,
+                        "first_stage_key": "image", "envmap_dir": None}
 
 
 def _drop_training_only(kwargs: dict, who: str) -> None:
@@ -57,7 +70,9 @@ def _drop_training_only(kwargs: dict, who: str) -> None:
 
 
 class DDPM(nn.Module):
-    """The noise schedule + the wrapped eps-network (ddpm.py:59-231), inference half."""
+    """The noise schedule + the wrapped eps-network (ddpm.py:59-231), without training.  ``loss_type``, ``l_simple_weight``,
+    ``original_elbo_weight``, ``logvar_init``, ``masked_loss``, ``first_stage_key`` and ``envmap_dir`` are kept in the dict ``validation_params``
+    under their own names (not as attributes of those names: the module keeps the attribute surface of the sampling path it had)."""
 
     def __init__(self, unet_config, timesteps=1000, beta_schedule="linear", *, ckpt_path=None, ignore_keys=(), load_only_unet=False, use_ema=True,
                  image_size=256, channels=3, log_every_t=100, clip_denoised=True, linear_start=1e-4, linear_end=2e-2, given_betas=None,
@@ -69,6 +84,7 @@ class DDPM(nn.Module):
         if learn_logvar:
             raise NotImplementedError("learn_logvar is training-only")
         self.parameterization = parameterization
+        self.validation_params = {k: training_only.get(k, d) for k, d in _VALIDATION_DEFAULTS.items()}
         self.image_size, self.channels = image_size, channels
         self.clip_denoised, self.log_every_t, self.v_posterior = clip_denoised, log_every_t, v_posterior
         self.cond_stage_model = None
@@ -80,6 +96,8 @@ class DDPM(nn.Module):
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=list(ignore_keys), only_model=load_only_unet)
         self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps, linear_start=linear_start, linear_end=linear_end)
+        # ddpm.py:133: a plain tensor attribute there (learn_logvar raises above); here a buffer outside state_dict(), so that it follows .to()
+        self.register_buffer("logvar", torch.full(fill_value=float(self.validation_params["logvar_init"]), size=(self.num_timesteps,)), persistent=False)
 
     @property
     def device(self):
@@ -115,6 +133,12 @@ class DDPM(nn.Module):
         )
         for name, table in tables:
             self.register_buffer(name, torch.tensor(table, dtype=torch.float32))
+        # ddpm.py:179-187 ("eps"): the weight of the variational bound's term t, in fp32 from the fp32 buffers as the reference computes it;
+        # posterior_variance[0] is 0, so entry 0 takes entry 1.  persistent=False: not in state_dict(), as there
+        lvlb_weights = self.betas**2 / (2 * self.posterior_variance * torch.tensor(alpha, dtype=torch.float32) * (1 - self.alphas_cumprod))
+        lvlb_weights[0] = lvlb_weights[1]
+        self.register_buffer("lvlb_weights", lvlb_weights, persistent=False)
+        assert not torch.isnan(self.lvlb_weights).all()
 
     def ema_scope(self, context=None):
         """ldm/models/diffusion/ddpm.py:189-202 -- ``with model.ema_scope(): ...`` samples with the EMA weights (wrappers.ema_weights)."""
@@ -137,6 +161,17 @@ class DDPM(nn.Module):
         noise = torch.randn_like(x_start) if noise is None else noise
         return (extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
+
+    def get_loss(self, pred, target, mean=True):
+        """ddpm.py:296-309 on torch tensors (the validation pass itself reduces on the device through ops.diffusion_losses)."""
+        loss_type = self.validation_params["loss_type"]
+        if loss_type == "l1":
+            loss = (target - pred).abs()
+        elif loss_type == "l2":
+            loss = (target - pred) ** 2
+        else:
+            raise NotImplementedError(f"unknown loss type '{loss_type}'")
+        return loss.mean() if mean else loss
 
 
 class LatentDiffusion(DDPM):
@@ -258,6 +293,14 @@ class LatentDiffusion(DDPM):
                 return self.cond_stage_model.encode(c)
             return self.cond_stage_model(c)
         return getattr(self.cond_stage_model, self.cond_stage_forward)(c)
+
+    @torch.no_grad()
+    def encode_first_stage(self, x):
+        return self.first_stage_model.encode(x)
+
+    def get_first_stage_encoding(self, encoder_posterior):
+        assert isinstance(encoder_posterior, torch.Tensor)
+        return self.scale_factor * encoder_posterior
 
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
         return self.first_stage_model.decode(1.0 / self.scale_factor * z)
@@ -424,6 +467,154 @@ class ObsNetDiffusion(LatentDiffusion):
         else:
             samples, intermediates = self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         return samples, intermediates
+
+    # ------------------------------------------------------------------ the validation pass (forward process + losses)
+    def _refmap_renderer(self):
+        from .render import RefMapRenderer
+
+        if not isinstance(self.renderer, RefMapRenderer) or not self.renderer.brdf_param_names:
+            raise NotImplementedError("rendering LrK needs a renderer_config of drmnet_amd.render.RefMapRenderer with brdf_param_names, got "
+                                      f"{type(self.renderer).__name__}")
+        return self.renderer
+
+    def _load_envmaps(self, names) -> torch.Tensor:
+        """envmap_dir/<name>.exr for every name, stacked [n, H, W, 3] on the host (models/obsnet.py:157-169)."""
+        from pathlib import Path
+
+        from . import file_io
+
+        root = self.validation_params["envmap_dir"]
+        assert root is not None, "envmap_dir is needed, but not set"
+        return torch.stack([file_io.load_exr(Path(root) / f"{name}.exr", as_torch=True) for name in names])
+
+    @torch.no_grad()
+    def get_input(self, batch, k, return_first_stage_outputs=False, force_c_encode=False, cond_key=None, return_original_cond=False, bs=None, *,
+                  noise=None, seed=None):
+        """models/obsnet.py:139-413 for cond_key "masked_LrK" (any other key raises, as :373 does for the shipped "raw_refmap" configs: the
+        reference compares against " raw_refmap" with a leading space, and that branch needs the Mitsuba object-image renderer): the first ``bs``
+        items of a MaskedRefmapDataset batch -> [LrK_z, c, mask(, LrK, LrK_rec)(, cond)].  Rows whose ``batch[k]`` has a NaN [b, 0, 0, 0], or every
+        row when the batch has no ``k``, are rendered from zK under batch["envmap"][b] (read from envmap_dir/<name>.exr where missing or NaN-marked)
+        seen from batch["view_from"][b], all of them in one drm_render_refmap_views launch.  Then ``ds.transform(LrK, dynamic_normalize=True,
+        mask=mask)`` and one drm_obs_forward_process launch: c = mask LrK + noisy_observe e1 + (1 - mask) e2.  The reference's in-place
+        ``cond += ...`` also lands in c (IdentityFirstStage.encode returns its argument); restated explicitly: c and cond are the padded tensor.
+        The .pt caches are neither read nor written.
+
+        Keyword-only, not in the reference: ``noise`` = {"observe": e1, "padding": e2} injects the draws (parity runs); one that is not injected
+        comes from the library's Philox stream keyed by ``seed`` (drawn from torch's generator when None), e1 and e2 from the first two of its
+        three ranges (p_losses takes the third)."""
+        from . import ops
+
+        cond_key = cond_key if cond_key is not None else self.cond_stage_key
+        if cond_key != "masked_LrK":
+            raise NotImplementedError(f'cond_key {cond_key!r}: only "masked_LrK" is implemented (the reference itself raises for "raw_refmap", '
+                                      "models/obsnet.py:373)")
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("get_input runs on the GPU: move the model there first (drmnet_amd has no CPU path)")
+        zK = batch["zK"]
+        bs = min(len(zK), bs) if bs is not None else len(zK)
+        self.batch_size = bs
+        zK = zK[:bs].to(dev, torch.float32)
+        envmap_name = list(batch["envmap_name"][:bs])
+        view_from = batch.get("view_from")[:bs]
+        given = batch[k][:bs].to(dev, torch.float32) if k in batch else None
+        not_cached = torch.ones(bs, dtype=torch.bool) if given is None else torch.isnan(given[:, 0, 0, 0]).cpu()
+        if bool(not_cached.any()):
+            renderer = self._refmap_renderer()
+            rows = torch.nonzero(not_cached).flatten().tolist()
+            have = batch["envmap"][:bs] if "envmap" in batch else None
+            load = [b for b in rows if have is None or bool(torch.isnan(have[b, 0, 0, 0]))]
+            loaded = self._load_envmaps([envmap_name[b] for b in load]) if load else None
+            maps = [loaded[load.index(b)] if b in load else have[b] for b in rows]
+            envmap = torch.stack([m.to(dev, torch.float32) for m in maps])
+            rendered = renderer.render(zK[rows], None, envmap, view_from=torch.as_tensor(view_from)[rows])
+            if given is None:
+                LrK = rendered
+            else:
+                LrK = given.clone().index_copy_(0, torch.tensor(rows, device=dev), rendered)
+        else:
+            LrK = given
+        mask = batch["mask"][:bs, None].to(dev, torch.float32).contiguous()  # [BS, 1, H, W]
+        LrK = self.ds.transform(LrK.contiguous(), dynamic_normalize=True, mask=mask)
+        LrK_z = self.get_first_stage_encoding(self.encode_first_stage(LrK)).detach()
+        if self.model.conditioning_key is not None:
+            if tuple(mask.shape[-2:]) != (self.image_size, self.image_size):  # :396 (default mode: nearest); a no-op on the shipped configs
+                mask = ops.resize(mask, (self.image_size, self.image_size), "nearest")
+            if self.padding_mode not in ("noise", "zeros"):
+                raise NotImplementedError()
+            noise = noise or {}
+            if seed is None:
+                seed = int(torch.randint(0, 2**62, (1,)).item())
+            cond = ops.obs_forward_process(LrK, mask, None, None, None, self.noisy_observe, self.padding_mode, e_observe=noise.get("observe"),
+                                           e_padding=noise.get("padding"), seed=seed, want_q=False)[0]
+            c = self.get_learned_conditioning(cond)
+        else:
+            cond = c = None
+        out = [LrK_z, c, mask]
+        if return_first_stage_outputs:
+            out.extend([LrK, self.decode_first_stage(LrK_z)])
+        if return_original_cond:
+            out.append(cond)
+        return out
+
+    def _draw_t(self, n, seed):
+        """forward's draw of the steps (models/obsnet.py:421): torch's global generator as in the reference, or a CPU generator seeded by ``seed``"""
+        if seed is None:
+            return torch.randint(0, self.num_timesteps, (n,), device=self.device).long()
+        return torch.randint(0, self.num_timesteps, (n,), generator=torch.Generator().manual_seed(int(seed))).long().to(self.device)
+
+    def shared_step(self, batch, *, seed=None, noise=None, t=None, **kwargs):
+        """models/obsnet.py:415-418.  ``seed`` keys the steps t and the three noise draws; ``noise`` = {"observe", "padding", "q"} and ``t``
+        inject them instead (parity runs)."""
+        noise = noise or {}
+        x, c, mask = self.get_input(batch, self.validation_params["first_stage_key"], noise=noise, seed=seed)
+        return self(x, c, mask, noise.get("q"), t=t, seed=seed)
+
+    def forward(self, x, c, mask, *args, t=None, seed=None, **kwargs):
+        """models/obsnet.py:420-429: t ~ randint(0, num_timesteps) per row unless ``t`` is given (``seed``: from a CPU generator seeded by it)."""
+        if t is None:
+            t = self._draw_t(x.shape[0], seed)
+        if self.model.conditioning_key is not None:
+            assert c is not None
+        return self.p_losses(x, c, mask, t, *args, seed=seed, **kwargs)
+
+    @torch.no_grad()
+    def p_losses(self, x_start, cond, mask, t, noise=None, *, seed=None):
+        """models/obsnet.py:453-498 in eval mode: q_sample at each row's t (``noise`` [B, 3, H, W] if given, else the q-noise range of the
+        library's Philox stream keyed by ``seed``, drawn from torch's generator when None), one pass of the network, and the three losses from
+        drm_diffusion_losses.  Returns (loss, {"val/loss_simple", "val/loss_vlb", "val/loss"}), 0-dim device tensors.  There is no backward on
+        this engine: training mode raises."""
+        from . import ops
+
+        if self.training:
+            raise NotImplementedError("p_losses in training mode: the HIP engine has no backward (validation only)")
+        vp = self.validation_params
+        x_start = _lib.require_gpu_tensor(x_start, "x_start")
+        dev = x_start.device
+        t = t.to(dev)
+        if noise is not None:
+            noise = _lib.require_gpu_tensor(noise, "noise")
+        elif seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+        _, x_noisy, noise = ops.obs_forward_process(x_start, None, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, e_q=noise,
+                                                    seed=seed or 0, want_cond=False)
+        model_output = self.apply_model(x_noisy, t.long(), cond)
+        invmask = (1 - _lib.require_gpu_tensor(mask, "mask")) if vp["masked_loss"] else None
+        out = ops.diffusion_losses(model_output, noise, t, self.logvar, self.lvlb_weights, vp["loss_type"], vp["l_simple_weight"],
+                                   vp["original_elbo_weight"], invmask=invmask)
+        return out[2], {"val/loss_simple": out[0], "val/loss_vlb": out[1], "val/loss": out[2]}
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx, *, seed=None):
+        """ddpm.py:373-379: the losses on the live weights and, under ema_scope, on the EMA weights (keys + "_ema").  The reference logs the
+        two dicts; there is no logger here, so the merged six-key dict is returned (0-dim device tensors).  ``seed``: the draws of the live pass
+        are keyed by it, those of the EMA pass by seed + 1 (the reference draws twice from one generator)."""
+        _, loss_dict = self.shared_step(batch, seed=seed)
+        with self.ema_scope():
+            _, loss_dict_ema = self.shared_step(batch, seed=None if seed is None else seed + 1)
+        merged = dict(loss_dict)
+        merged.update({key + "_ema": v for key, v in loss_dict_ema.items()})
+        return merged
 
     @torch.no_grad()
     def get_cond_for_predict(self, batch: Dict[str, Union[torch.Tensor, str]], bs: Optional[int] = None, force_c_encode: bool = False,

@@ -156,6 +156,98 @@ def validation_losses(model_out, Lr_k, Lr_km1, K, z_out, z_k, z_K, reversed_k, z
     return out
 
 
+# ------------------------------------------------------------------------------------------------ ObsNet's forward process and losses (csrc/obs_forward.hip)
+
+PADDING_MODES = {"zeros": 0, "noise": 1}
+
+
+@torch.no_grad()
+def obs_forward_process(x, mask, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, noisy_observe: float = 0.0, padding_mode: str = "noise", *,
+                        e_observe=None, e_padding=None, e_q=None, seed: int = 0, want_cond: bool = True, want_q: bool = True):
+    """models/obsnet.py:375-398 and ddpm.py:288-294 in one launch (drm_obs_forward_process): x [B, C, H, W] (the transformed LrK), mask
+    [B, 1, H, W], t [B] -> (cond, x_noisy, noise) with cond = mask x + noisy_observe e1 + (1 - mask) e2 (the e1 term only when noisy_observe > 0,
+    the e2 term only for padding_mode "noise"), x_noisy = a[t] x + s[t] e3 and noise = e3.  e_observe / e_padding / e_q inject e1 / e2 / e3; a draw
+    that is not injected comes from the Philox stream of ``seed`` at offsets 0, n and 2 n (n = x.numel()).  ``want_cond=False`` leaves the
+    conditioning out (cond is None; mask may be None), ``want_q=False`` the q_sample (x_noisy and noise are None; t and the tables may be None):
+    the two halves of one seed, run in two calls, are what one call returns."""
+    if padding_mode not in PADDING_MODES:
+        raise NotImplementedError(f"padding_mode {padding_mode!r}")
+    if not (want_cond or want_q):
+        raise ValueError("obs_forward_process: nothing asked for")
+    x = _lib.require_gpu_tensor(x, "x")
+    if x.ndim != 4:
+        raise RuntimeError("obs_forward_process expects x [B, C, H, W]")
+    dev = x.device
+    B, C, H, W = x.shape
+    mh = mw = 0
+    if want_cond:
+        mask = _lib.require_gpu_tensor(mask, "mask")
+        if mask.ndim != 4 or mask.shape[0] != B or mask.shape[1] != 1:
+            raise RuntimeError(f"mask must be [B={B}, 1, H, W], got {tuple(mask.shape)}")
+        mh, mw = int(mask.shape[2]), int(mask.shape[3])
+    else:
+        mask = None
+    sa = s1 = None
+    if want_q:
+        t = _lib.require_gpu_tensor(t.to(torch.int32), "t", torch.int32)
+        if tuple(t.shape) != (B,):
+            raise RuntimeError(f"t must be [B={B}]")
+        sa = _lib.require_gpu_tensor(sqrt_alphas_cumprod, "sqrt_alphas_cumprod")
+        s1 = _lib.require_gpu_tensor(sqrt_one_minus_alphas_cumprod, "sqrt_one_minus_alphas_cumprod")
+        if sa.ndim != 1 or sa.shape != s1.shape:
+            raise RuntimeError("the two schedule tables must be [T]")
+    else:
+        t = None
+    draws = [None if e is None else _lib.require_gpu_tensor(e, n) for e, n in ((e_observe, "e_observe"), (e_padding, "e_padding"), (e_q, "e_q"))]
+    if any(e is not None and e.shape != x.shape for e in draws):
+        raise RuntimeError(f"injected draws must have the shape of x {tuple(x.shape)}")
+    cond = torch.empty_like(x) if want_cond else None
+    x_noisy, noise = (torch.empty_like(x), torch.empty_like(x)) if want_q else (None, None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_obs_forward_process(x.data_ptr(), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(sa), _lib.ptr(s1), 0 if sa is None else sa.numel(),
+                                                      float(noisy_observe), PADDING_MODES[padding_mode], _lib.ptr(draws[0]), _lib.ptr(draws[1]),
+                                                      _lib.ptr(draws[2]), int(seed), _lib.ptr(cond), _lib.ptr(x_noisy), _lib.ptr(noise), B, C, H, W,
+                                                      mh, mw, _lib.stream_ptr(dev)))
+    return cond, x_noisy, noise
+
+
+@torch.no_grad()
+def diffusion_losses(model_out, target, t, logvar, lvlb_weights, loss_type: str = "l2", l_simple_weight: float = 1.0, original_elbo_weight: float = 0.0,
+                     invmask=None, return_rows: bool = False):
+    """models/obsnet.py:469-498 in eval mode (drm_diffusion_losses): model_out, target [B, C, H, W]; t [B]; logvar, lvlb_weights [T];
+    invmask [B, 1, H, W] (1 - mask) for masked_loss or None -> fp32 [3] on the device = (loss_simple, loss_vlb, loss), with ``return_rows`` also
+    the per-row loss_simple [B].  Two launches, no host synchronisation; fp64 sums in a fixed order."""
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError(f"unknown loss type '{loss_type}'")
+    model_out = _lib.require_gpu_tensor(model_out, "model_out")
+    dev = model_out.device
+    target = _lib.require_gpu_tensor(target, "target")
+    if target.shape != model_out.shape or model_out.ndim < 2:
+        raise RuntimeError(f"model_out and target must share one [B, C, ...] shape, got {tuple(model_out.shape)} and {tuple(target.shape)}")
+    B, C = model_out.shape[0], model_out.shape[1]
+    per_row = model_out.numel() // B
+    if invmask is not None:
+        invmask = _lib.require_gpu_tensor(invmask, "invmask")
+        if invmask.numel() != B * (per_row // C) or invmask.shape[0] != B:
+            raise RuntimeError(f"invmask must be [B={B}, 1, ...] with one plane per row, got {tuple(invmask.shape)}")
+    t = _lib.require_gpu_tensor(t.to(torch.int32), "t", torch.int32)
+    if tuple(t.shape) != (B,):
+        raise RuntimeError(f"t must be [B={B}]")
+    logvar = _lib.require_gpu_tensor(logvar, "logvar")
+    lvlb_weights = _lib.require_gpu_tensor(lvlb_weights, "lvlb_weights")
+    if logvar.ndim != 1 or logvar.shape != lvlb_weights.shape:
+        raise RuntimeError("logvar and lvlb_weights must be [T]")
+    ws = torch.empty(_lib.diffusion_loss_workspace_bytes(B) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    rows = torch.empty(B, dtype=torch.float32, device=dev) if return_rows else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_diffusion_losses(model_out.data_ptr(), target.data_ptr(), _lib.ptr(invmask), t.data_ptr(), logvar.data_ptr(),
+                                                   lvlb_weights.data_ptr(), logvar.numel(), LOSS_TYPES[loss_type], float(l_simple_weight),
+                                                   float(original_elbo_weight), B, per_row, C, ws.data_ptr(), ws.numel() * 8, out.data_ptr(),
+                                                   _lib.ptr(rows), _lib.stream_ptr(dev)))
+    return (out, rows) if return_rows else out
+
+
 # ------------------------------------------------------------------------------------------------ boundary maps (csrc/transform.hip)
 
 MAP_CODES = {"log_p1": 0, "log10": 1, "lowerbound": 2, "unit_to_signed": 3, "norm_log": 4, "exp_m1": 5, "exp10": 6, "signed_to_unit": 7,

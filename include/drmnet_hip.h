@@ -398,6 +398,53 @@ int drm_validation_losses(const float* model_out, const float* Lr_k, const float
                           const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double l_refmap_weight,
                           double l_refcode_weight, int B, int64_t per_row, int P, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ObsNetDiffusion's validation pass around its network forward (csrc/obs_forward.hip).
+ * ------------------------------------------------------------------------------------------- */
+/* The forward process of a batch in one elementwise launch: the conditioning of ObsNetDiffusion.get_input for cond_key "masked_LrK"
+ * (models/obsnet.py:375-398: cond = mask * LrK; cond = noisy_observe * randn_like(cond) + cond; cond += (1 - mask) * randn_like(cond)) and
+ * q_sample of p_losses (ldm/models/diffusion/ddpm.py:288-294).
+ *   x [B][C][H][W]: the transformed LrK; mask [B][1][mask_H][mask_W] fp32 with mask_H == H and mask_W == W (any other size is DRM_ERR_INVALID:
+ *   resize it first); t int32[B] (device); sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod fp32[T] (device).
+ *     cond    = mask x + noisy_observe e1 + (1 - mask) e2     the e1 term only when noisy_observe > 0, the e2 term only for DRM_PAD_NOISE;
+ *                                                             a dropped term is not computed (no draw, no add)
+ *     x_noisy = sqrt_alphas_cumprod[t_b] x + sqrt_one_minus_alphas_cumprod[t_b] e3
+ *     noise   = e3                                            the loss target
+ *   e_observe (e1), e_padding (e2), e_q (e3): [B][C][H][W] device tensors (parity runs), each or NULL.  A NULL one is drawn from the library's
+ *   Philox stream of `seed`: with n = B C H W, e1 is elements [0, n), e2 [n, 2 n), e3 [2 n, 3 n) (what drm_randn(seed, offset) returns), the
+ *   reference's draw order (observe, padding, q-noise).
+ *   The reference's in-place "cond +=" also lands in c (IdentityFirstStage.encode returns its argument): cond here is what the network is
+ *   conditioned on, after padding.  A t_b outside [0, T) is not looked up: its row of x_noisy is NaN.  fp32 arithmetic, no contraction.
+ *   Either half may be left out: cond == NULL skips the conditioning (mask and its draws are not read), x_noisy == noise == NULL skips
+ *   q_sample (t and the tables are not read).  The offsets of the three Philox ranges do not depend on which halves run, so two calls with one
+ *   seed, one per half, give what one call gives. */
+#define DRM_PAD_ZEROS 0
+#define DRM_PAD_NOISE 1
+int drm_obs_forward_process(const float* x, const float* mask, const int32_t* t, const float* sqrt_alphas_cumprod,
+                            const float* sqrt_one_minus_alphas_cumprod, int T, float noisy_observe, int padding_mode, const float* e_observe,
+                            const float* e_padding, const float* e_q, uint64_t seed, float* cond, float* x_noisy, float* noise, int B, int C, int H,
+                            int W, int mask_H, int mask_W, void* stream);
+/* ObsNetDiffusion.p_losses after the network, in eval mode (models/obsnet.py:469-498 with get_loss, ddpm.py:296-308): two launches, no host
+ * synchronisation.
+ *   model_out, target [B][per_row] fp32 (per_row = C HW); invmask [B][per_row / C] fp32 (1 - mask, broadcast over the channels) for masked_loss,
+ *   or NULL; t int32[B]; logvar, lvlb_weights fp32[T]; loss_type DRM_LOSS_L1 (|d|) or DRM_LOSS_L2 (d^2), d = model_out - target.
+ *     L_b         = mean of f(d) over row b                                    (invmask == NULL)
+ *                 = sum f(d) invmask / (sum invmask * C)                       (masked; the second sum runs over one channel plane)
+ *     loss_simple = mean_b L_b
+ *     loss_vlb    = mean_b lvlb_weights[t_b] L_b
+ *     loss        = l_simple_weight mean_b (L_b / exp(logvar[t_b]) + logvar[t_b]) + original_elbo_weight loss_vlb
+ *   out fp32[3] on the device = (loss_simple, loss_vlb, loss); loss_simple_rows fp32[B] = L_b, or NULL.
+ *   A masked row whose mask is all ones (invmask all zero) gives L_b = 0 / 0 = NaN, and with it NaN in all three scalars, as the reference does.
+ *   A t_b outside [0, T) is not looked up: loss_vlb and loss are NaN.
+ *   Element arithmetic and sums are fp64, every thread, tree and row in a fixed order without atomics (two calls are bitwise equal, whatever the
+ *   alignment of the pointers); the results are rounded to fp32 once.  workspace: DRM_DIFFUSION_LOSS_WORKSPACE_BYTES(B) of device memory,
+ *   contents irrelevant. */
+#define DRM_DIFFUSION_LOSS_MAX_PARTS 32
+#define DRM_DIFFUSION_LOSS_WORKSPACE_BYTES(B) ((size_t)(B) * DRM_DIFFUSION_LOSS_MAX_PARTS * 2 * sizeof(double))
+int drm_diffusion_losses(const float* model_out, const float* target, const float* invmask, const int32_t* t, const float* logvar,
+                         const float* lvlb_weights, int T, int loss_type, double l_simple_weight, double original_elbo_weight, int B,
+                         int64_t per_row, int C, void* workspace, size_t workspace_bytes, float* out, float* loss_simple_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

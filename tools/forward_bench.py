@@ -8,6 +8,10 @@
     python tools/forward_bench.py step [--batch 20]
         one DRMNet.validation_step at full width (synthetic weights, 128 x 128, 128 x 256 maps) split into forward process (renders +
         transforms), networks and loss by device events.  Run it under `rocprofv3 --kernel-trace --stats -- python ...` for the kernel table.
+    python tools/forward_bench.py obs_step [--batch 20]
+        the same for one pass of ObsNetDiffusion's validation at full width (configs/obsnet/eval_obsnet.yaml's network with the validation
+        keys of the reference's train_obsnet.yaml, synthetic weights, 128 x 128, 128 x 256 maps, random sparse masks): get_input (render,
+        masked transform, conditioning half of drm_obs_forward_process), q_sample half + network, drm_diffusion_losses.
 """
 import argparse
 import ctypes as C
@@ -139,9 +143,61 @@ def bench_step(args):
     print(f"validation step B={B} {args.precision}: wall {wall:.1f} ms per pass of one weight set; losses {out.tolist()}", flush=True)
 
 
+def bench_obs_step(args):
+    from drmnet_amd import ops, synth
+    from drmnet_amd.config import load_config
+    from drmnet_amd.dataset import BaseDataset
+    from drmnet_amd.obsnet import ObsNetDiffusion
+    from drmnet_amd.render import RefMapRenderer
+
+    dev = torch.device("cuda:0")
+    params = dict(load_config(os.path.join(ROOT, "configs/obsnet/eval_obsnet.yaml"))["model"]["params"], ckpt_path=None, use_ema=False,
+                  cond_stage_key="masked_LrK", noisy_observe=0.04, masked_loss=False)
+    m = ObsNetDiffusion(**params)
+    names = ["metallic.value", "base_color.value.R", "base_color.value.G", "base_color.value.B", "roughness.value", "specular"]
+    m.renderer = RefMapRenderer(128, brdf_param_names=names)
+    synth.load_synth(m.model.diffusion_model, synth.SEED_OBSNET)
+    m.ds = BaseDataset(128, "0p1tom1p1_normalizedLogarithmic_lowerbound1e-6")
+    m = m.to(dev).set_precision(args.precision)
+    B = args.batch
+    g = torch.Generator().manual_seed(2)
+    phi = torch.rand((B,), generator=g) * 6.2831853
+    batch = {"zK": torch.rand((B, 6), generator=g), "envmap_name": [f"e{i}" for i in range(B)],
+             "view_from": torch.stack([torch.sin(phi), torch.zeros(B), torch.cos(phi)], dim=-1),
+             "envmap": (torch.rand((B, 128, 256, 3), generator=g) + 0.05).to(dev), "mask": (torch.rand((B, 128, 128), generator=g) > 0.7).double()}
+    t = torch.randint(0, m.num_timesteps, (B,), generator=g).to(dev)
+    parts = {}
+
+    def step():
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        marks[0].record()
+        x, c, mask = m.get_input(batch, "LrK", seed=7)
+        marks[1].record()
+        _, x_noisy, noise = ops.obs_forward_process(x, None, t, m.sqrt_alphas_cumprod, m.sqrt_one_minus_alphas_cumprod, seed=7, want_cond=False)
+        model_out = m.apply_model(x_noisy, t, c)
+        marks[2].record()
+        out = ops.diffusion_losses(model_out, noise, t, m.logvar, m.lvlb_weights, "l2", 1.0, 0.0)
+        marks[3].record()
+        marks[3].synchronize()
+        for name, i in (("get_input (render + masked transform + conditioning)", 0), ("q_sample + network", 1), ("loss", 2)):
+            parts.setdefault(name, []).append(marks[i].elapsed_time(marks[i + 1]))
+        return out
+
+    step()
+    parts.clear()
+    t0 = time.time()
+    for _ in range(args.reps):
+        out = step()
+    wall = (time.time() - t0) / args.reps * 1e3
+    for name, ms in parts.items():
+        ms = sorted(ms)
+        print(f"ObsNet validation step B={B} {args.precision}: {name}: median {ms[len(ms) // 2]:.2f} ms (min {ms[0]:.2f}, max {ms[-1]:.2f}, n={len(ms)})")
+    print(f"ObsNet validation step B={B} {args.precision}: wall {wall:.1f} ms per pass of one weight set; losses {out.tolist()}", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["render", "step"])
+    ap.add_argument("what", choices=["render", "step", "obs_step"])
     ap.add_argument("--libs", nargs="*", default=["-"])
     ap.add_argument("--stack", type=int, default=4)
     ap.add_argument("--batch", type=int, default=20)
@@ -149,4 +205,4 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="f16mx")
     a = ap.parse_args()
-    {"render": bench_render, "step": bench_step}[a.what](a)
+    {"render": bench_render, "step": bench_step, "obs_step": bench_obs_step}[a.what](a)
