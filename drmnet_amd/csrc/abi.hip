@@ -273,6 +273,14 @@ int drm_op_resblock(const float* x0, int C0, int up0, const float* x1, int C1, c
       float* skw = ar.alloc<float>(packed_conv_weight_floats(1, Cout, cin)); float* skb = ar.alloc<float>(Cout);
       float* s1 = ar.alloc<float>(64); float* s2 = ar.alloc<float>(64); float* s3 = ar.alloc<float>(64); float* scratch = ar.alloc<float>(64);
       float* e_out = ar.alloc<float>((size_t)N * Cout);
+      // in_layers over cat(up(x0), x1): the two extra images UNet::load packs for such a block (run_resblock decides whether they run)
+      const bool upw = up0 && upconv_split_packable(C0, C1, Cout);
+      float *c1aw = nullptr, *c1bw = nullptr, *s4 = nullptr, *s5 = nullptr, *wa_raw = nullptr, *wb_raw = nullptr;
+      if (upw) {
+        c1aw = ar.alloc<float>(packed_conv_weight_floats(4, 4 * Cout, C0)); c1bw = ar.alloc<float>(packed_conv_weight_floats(9, Cout, C1));
+        s4 = ar.alloc<float>(64); s5 = ar.alloc<float>(64);
+        wa_raw = ar.alloc<float>((size_t)16 * Cout * C0); wb_raw = ar.alloc<float>((size_t)9 * Cout * C1);
+      }
       Act a0 = new_act(c, C0, H, W);
       a0.up = up0;
       Act a1 = new_act(c, C1 > 0 ? C1 : 4, H, W);
@@ -287,6 +295,12 @@ int drm_op_resblock(const float* x0, int C0, int up0, const float* x1, int C1, c
         };
         DRM_TRY(cp(n1w, params[0], cin)); DRM_TRY(cp(n1b, params[1], cin));
         DRM_TRY(pack_for_ops(op_prec, params[2], c1w, s1, scratch, Cout, cin, 9, Cout, cin, s, true)); DRM_TRY(cp(c1b, params[3], Cout));
+        if (upw) {
+          r.up_c0 = C0; r.c1a_w = off(c1aw); r.c1a_s = off(s4); r.c1b_w = off(c1bw); r.c1b_s = off(s5);
+          DRM_TRY(launch_fold_upconv_weight(params[2], wa_raw, wb_raw, Cout, C0, C1, s));
+          DRM_TRY(pack_for_ops(op_prec, wa_raw, c1aw, s4, scratch, 4 * Cout, C0, 4, 4 * Cout, C0, s, true));
+          DRM_TRY(pack_for_ops(op_prec, wb_raw, c1bw, s5, scratch, Cout, C1, 9, Cout, C1, s, true));
+        }
         DRM_TRY(launch_linear(emb, params[4], params[5], e_out, N, emb_dim, Cout, 1, 0, s));
         DRM_TRY(cp(n2w, params[6], Cout)); DRM_TRY(cp(n2b, params[7], Cout));
         DRM_TRY(pack_for_ops(op_prec, params[8], c2w, s2, scratch, Cout, Cout, 9, Cout, Cout, s, true)); DRM_TRY(cp(c2b, params[9], Cout));
@@ -485,6 +499,14 @@ int drm_set_op_precision(int precision) {
     DRM_REQUIRE(precision_valid(precision),
                 "precision must be 0 (fp32 MFMA), 1 (split fp16 x3), 2 (plain fp16 operands), 3 (split fp16 with fp8 cross terms) or 4 (plain bf16 operands)");
     g_op_precision.store(precision, std::memory_order_relaxed);
+    return DRM_OK;
+  });
+}
+
+int drm_set_upconv_split(int mode) {
+  return guarded([&]() -> int {
+    DRM_REQUIRE(mode >= 0 && mode <= 2, "upconv split mode: 0 = never, 1 = by the measured rule, 2 = wherever the form applies");
+    set_upconv_split(mode);
     return DRM_OK;
   });
 }

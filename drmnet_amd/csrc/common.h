@@ -70,7 +70,9 @@ struct ConvArgs {
   int silu = 0;                     // apply x*sigmoid(x) after the affine
   const float* w = nullptr;         // packed [taps][Cin/4][Cout][4]
   const float* bias = nullptr;      // [Cout]
-  int taps = 9;                     // 9 (3x3, pad 1) or 1 (1x1)
+  int taps = 9;                     // 9 (3x3, pad 1), 1 (1x1) or 4: the 3x3 conv over a nearest-x2 input as four 2x2 convs on the stored map --
+                                    // Cout = 4 x the real count, parity-major (channel p * Cout/4 + co, p = 2 (y & 1) + (x & 1) of the output
+                                    // pixel); out is the [N][2H][2W][Cout/4] tensor (pixel shuffle in the epilogue); no bias / emb / res / stats
   int Cout = 0;                     // padded Cout (multiple of 32)
   const float* emb = nullptr;       // optional per-(sample, cout) add: emb[n*emb_stride + co]
   int emb_stride = 0;
@@ -93,6 +95,7 @@ struct ConvArgs {
   double2* pool_stat = nullptr;        // same epilogue, with its [N][Cout] (sum, sum of squares) (zeroed) -- plan_conv says which launches can
   const float* w_inv_scale = nullptr;  // split-precision path: device scalar 2^-k undoing the weight pre-scaling
   int ld0 = 0;                         // channel stride of src0's pixels when it is a channel slice of a wider tensor (0 = C0)
+  int gn_ld = 0;                       // row stride of gn_scale / gn_shift when they are a channel slice of a wider block's tables (0 = C0 + C1)
   long long w_img_stride_f4 = 0;       // split 1x1 path: every image has its own packed weight set this many float4 apart (attention GEMMs)
   const float* w_inv_img = nullptr;    // ... and its own 2^-k weight factor [N] (replaces w_inv_scale)
   int prof_kind = -1;                  // launch-profiler family override (-1 = by tap count, PROF_KINDS = no scope of its own)
@@ -143,6 +146,10 @@ inline int precision_terms(int p) { return p == PREC_F16 ? 1 : (p == PREC_BF16 ?
 int launch_pack_conv_weight(const float* w, float* packed, int Cout, int Cin, int taps, int CoutP, int CinP, hipStream_t s);
 // attention parameter fold (conv_split.hip): raw qkv [3C][C] / [3C] and proj_out [C][C] / [C] -> w_out [3C][C], b_out [3C] whose v rows hold
 // Wp Wv and Wp bv + bp (fp64 products, rounded once); what every attention block's qkv conv is packed from
+// 3x3 conv over cat(nearest_x2(x0), x1) split by linearity (engine.hip plan_upconv_split): w [Cout][C0 + C1][3][3] -> wa [4 * Cout][C0][2][2], the
+// parity-major 2x2 kernels on the stored x0 (sums of the 3x3 taps that fall on one stored pixel, fp64, rounded once), and wb [Cout][C1][3][3], the
+// x1 slice; both are ordinary conv weights for the packers (taps = 4 / 9)
+int launch_fold_upconv_weight(const float* w, float* wa, float* wb, int Cout, int C0, int C1, hipStream_t s);
 int launch_fold_attn_params(const float* qkv_w, const float* qkv_b, const float* proj_w, const float* proj_b, float* w_out, float* b_out, int C,
                             hipStream_t s);
 size_t packed_conv_weight_floats(int taps, int CoutP, int CinP);

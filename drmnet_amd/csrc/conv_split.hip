@@ -162,4 +162,48 @@ int launch_fold_attn_params(const float* qkv_w, const float* qkv_b, const float*
   return DRM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// 3x3 conv over a nearest-x2 upsampled input: output pixel (2i + a, 2j + b) reads stored pixels (i + a - 1 + dy, j + b - 1 + dx), dy, dx in {0, 1},
+// and the 3x3 taps that land on one stored pixel add up -- rows: a = 0: dy 0 <- ky {0}, dy 1 <- ky {1, 2}; a = 1: dy 0 <- ky {0, 1}, dy 1 <- ky {2};
+// columns likewise.  Zero padding outside the stored map is exactly the full-resolution padding.  wa: [p = 2a + b][Cout][C0][dy][dx], summed in
+// fp64 and rounded once; wb: the input channels [C0, C0 + C1) of w as they are.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fold_upconv_weight_kernel(const float* __restrict__ w, float* __restrict__ wa, float* __restrict__ wb, int Cout,
+                                                                 int C0, int C1) {
+  const int Cin = C0 + C1;
+  const size_t na = (size_t)16 * Cout * C0, nb = (size_t)Cout * C1 * 9;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < na + nb; i += (size_t)gridDim.x * blockDim.x) {
+    if (i < na) {
+      const int dx = i % 2, dy = (i / 2) % 2;
+      size_t t = i / 4;
+      const int ci = t % C0; t /= C0;
+      const int co = t % Cout;
+      const int p = (int)(t / Cout), pa = p >> 1, pb = p & 1;
+      // tap range [lo, hi] of (parity, window position): (0,0) -> 0..0, (0,1) -> 1..2, (1,0) -> 0..1, (1,1) -> 2..2
+      const int ky0 = dy ? 2 - (1 - pa) : 0, ky1 = dy ? 2 : pa;
+      const int kx0 = dx ? 2 - (1 - pb) : 0, kx1 = dx ? 2 : pb;
+      const float* src = w + ((size_t)co * Cin + ci) * 9;
+      double acc = 0.0;
+      for (int ky = ky0; ky <= ky1; ++ky)
+        for (int kx = kx0; kx <= kx1; ++kx) acc += (double)src[ky * 3 + kx];
+      wa[i] = (float)acc;
+    } else {
+      const size_t k = i - na;
+      const int tap = k % 9;
+      size_t t = k / 9;
+      const int ci = t % C1;
+      const int co = (int)(t / C1);
+      wb[k] = w[((size_t)co * Cin + C0 + ci) * 9 + tap];
+    }
+  }
+}
+
+int launch_fold_upconv_weight(const float* w, float* wa, float* wb, int Cout, int C0, int C1, hipStream_t s) {
+  DRM_REQUIRE(w && wa && wb && Cout > 0 && C0 > 0 && C1 > 0, "upsampled-conv weight fold: arguments");
+  const size_t n = (size_t)16 * Cout * C0 + (size_t)Cout * C1 * 9;
+  hipLaunchKernelGGL(fold_upconv_weight_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, w, wa, wb, Cout, C0, C1);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
 }  // namespace drm

@@ -86,14 +86,14 @@ struct S2Cfg {
   static constexpr int BM = WM * MT * 32;
   static constexpr int BN = WN * NT * 32;
   static constexpr int TN = BM / (TH * TW);
-  static constexpr int HALO = (TAPS == 9) ? 1 : 0;
+  static constexpr int HALO = (TAPS == 9 || TAPS == 4) ? 1 : 0;  // (4: the 2x2 windows of the four output parities lie inside the 3x3 halo tile)
   static constexpr int HT = TH + 2 * HALO, WT = TW + 2 * HALO;
   static constexpr int HPI = HT * WT;  // halo pixels per image that are loaded
   // LDS image of the halo tile.  With 16-pixel-wide tiles the 32 rows of an MFMA tile are a 4 x 8 pixel patch and the
   // halo rows are stored 24 pixels apart: the four 16-lane groups of a ds_read_b128 then hit 64 distinct banks for every
   // tap offset (stride = 8 mod 16 pixels; the natural 18-pixel stride with 2 x 16 patches measured 35 % conflict cycles).
   static constexpr bool SUB48 = (TW % 8 == 0) && (TH % 4 == 0);
-  static constexpr int WTP_TRY = (TAPS == 9 && TW == 16) ? 24 : WT;
+  static constexpr int WTP_TRY = (TAPS != 1 && TW == 16) ? 24 : WT;
   static constexpr int RING_ST_F4 = R * TPS * 8 * (WN * NT * 32) + TN * (WN * NT * 32);
   static constexpr int A_COPIES = (TAPS == 1) ? 2 : 1;  // 1x1: a new activation tile every step, double-buffered
   static constexpr bool PAD_FITS = (A_COPIES * 8 * TN * HT * WTP_TRY + RING_ST_F4) * 16 <= 160 * 1024;
@@ -137,6 +137,7 @@ struct S2Cfg {
       px = row % TW;
     }
   }
+  static_assert(TAPS == 9 || TAPS == 4 || TAPS == 1, "3x3, 1x1, or the four parity 2x2 convs of a 3x3 over a nearest-x2 input");
   static_assert(TAPS % TPS == 0, "taps per step must divide the taps");
   static_assert(B_DMA_F4 % 64 == 0 && B_PER >= 1, "whole 1-KiB LDS-DMA instructions; a wave issues B_PER of them or none");
   static_assert(TERMS == 4 || TERMS == 3 || TERMS == 2 || TERMS == 1 || TERMS == 0,
@@ -400,8 +401,9 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
       if (ok) avalid |= 1u << j;
     }
     if (piece == C::A_SLOTS) {  // always 4 loads (a harmless re-read of the input when there is no GroupNorm) so every chunk issues A_CNT loads
-      const float* gs = has_gn ? a.gn_scale + (size_t)l_nc * Ctot + c + 8 * l_o : a.src0;
-      const float* gb = has_gn ? a.gn_shift + (size_t)l_nc * Ctot + c + 8 * l_o : a.src0;
+      const int tab_ld = a.gn_ld ? a.gn_ld : Ctot;  // (tables that are a channel slice of a wider block's)
+      const float* gs = has_gn ? a.gn_scale + (size_t)l_nc * tab_ld + c + 8 * l_o : a.src0;
+      const float* gb = has_gn ? a.gn_shift + (size_t)l_nc * tab_ld + c + 8 * l_o : a.src0;
       gload16x2(sc[0], sc[1], gs);
       gload16x2(sh[0], sh[1], gb);
     }
@@ -659,7 +661,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
   const bool y_first = (C::NW == 8) && (wave >= C::NW / 2);
   // 3x3: static priority for the second-dispatched wave half, which otherwise loses every issue arbitration by age and arrives last at every
   // barrier (A/B on one box: 3x3 family -0.6 %; the HBM-bound 1x1 form gets 5.7 % slower with it, so it stays without)
-  if (TAPS == 9 && C::NW == 8 && wave >= C::NW / 2) __builtin_amdgcn_s_setprio(1);
+  if (TAPS != 1 && C::NW == 8 && wave >= C::NW / 2) __builtin_amdgcn_s_setprio(1);
   constexpr int BASE = C::G_PER * (R - 2);
   int step = 0;  // steps executed so far (== gseq - (R-1))
   while (true) {
@@ -670,6 +672,12 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
     ++stamp_tiles;
     S2_STAMP(1);  // tile start
 #endif
+    // TAPS == 4: the tile's Cout columns belong to ONE output parity (a, b) (Cout % BN == 0); its 2x2 window starts (a, b) pixels into the halo tile
+    [[maybe_unused]] int par_off = 0;
+    if constexpr (TAPS == 4) {
+      const int par = cur.co0 / (a.Cout >> 2);
+      par_off = __builtin_amdgcn_readfirstlane((par >> 1) * C::WTP + (par & 1));
+    }
     // One tap (or 32-channel slab pair) of MFMAs: LDS fragment reads + 3 MFMAs per 32x32x16 product
     auto mma_tap = [&](const float4* Ab, const float4* Bc, int tapoff, auto&& hook) {
       if constexpr (TERMS == 0) {
@@ -866,7 +874,8 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 #pragma unroll
           for (int u = 0; u < TPS; ++u) {
             const int tap = g * TPS + u;
-            mma_tap(Ac, Bg + u * C::B_F4, (tap / 3) * C::WTP + (tap % 3), [&](int s2) {
+            const int tapoff = (TAPS == 4) ? par_off + (tap / 2) * C::WTP + (tap % 2) : (tap / 3) * C::WTP + (tap % 3);
+            mma_tap(Ac, Bg + u * C::B_F4, tapoff, [&](int s2) {
               const int hp = u * 2 + s2;
               if (hp < DMA_HP) {
 #pragma unroll
@@ -960,8 +969,9 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
     // (i, g).  Loads are issued unconditionally on clamped addresses (batched ahead of the math); stores are predicated
     // and fire-and-forget: they drain while the next tile's main loop runs (they are OLDER than every vector-memory operation
     // the next tile counts, so their number does not enter the counted waits).
+    constexpr int MT_EPI = (TAPS == 4) ? 0 : MT;  // (the pixel-shuffle epilogue of the parity form follows this loop)
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
+    for (int i = 0; i < MT_EPI; ++i) {
       size_t pixb[4];
       int nimg[4];
       bool okg[4];
@@ -1283,6 +1293,44 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
         }
       }
     }
+    if constexpr (TAPS == 4) {
+      // Pixel shuffle: GEMM row (n, y, x) on the stored map, column co' = p * Cout + co (p = 2a + b, one parity per tile) is output pixel
+      // (n, 2y + a, 2x + b), channel co of the [N][2H][2W][Cout] tensor.  The lane's four k rows are four consecutive stored pixels: after the
+      // quad transpose lane q of a quad owns pixel x + q, two output pixels further.  Only the weight un-scaling is applied here: bias, emb and
+      // the output statistics belong to the launch that adds the skip tensor's share on top (ConvArgs::res = this output).
+      static_assert(!RAG && !SK && !POOL, "the parity form has no ragged, split-K or pooled instantiation");
+      const int CoutR = a.Cout >> 2;
+      const int par = cur.co0 / CoutR, pa = par >> 1, pb = par & 1;
+      const int cob = cur.co0 - par * CoutR;
+      const size_t H2 = 2 * (size_t)a.H, W2 = 2 * (size_t)a.W;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        size_t pix2[4];
+        bool okg[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int row = (wm * MT + i) * 32 + 8 * g + 4 * h;
+          int img, py, px;
+          C::rowmap(row, img, py, px);
+          const int n = cur.n0 + img;
+          okg[g] = n < a.N;
+          pix2[g] = ((size_t)(okg[g] ? n : a.N - 1) * H2 + (2 * (cur.ty0 + py) + pa)) * W2 + (2 * (cur.tx0 + px) + pb);
+        }
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+          const int cq = cob + (wn * NT + c) * 32 + (r & ~3);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            float v0 = acc[i][c][4 * g] * inv_scale, v1 = acc[i][c][4 * g + 1] * inv_scale, v2 = acc[i][c][4 * g + 2] * inv_scale,
+                  v3 = acc[i][c][4 * g + 3] * inv_scale;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[i][c][4 * g + k] = 0.f;  // ready for the next tile
+            quad_transpose(v0, v1, v2, v3, r);
+            if (okg[g]) *reinterpret_cast<float4*>(&a.out[(pix2[g] + 2 * (r & 3)) * CoutR + cq]) = make_float4(v0, v1, v2, v3);
+          }
+        }
+      }
+    }
     // The LDS statistics keep accumulating while the workgroup's next tile covers the same images and output channels (on the big maps a
     // workgroup visits several tiles of one image in a row): the fold -- two barriers and TN * BN * 2 global fp64 atomics -- runs only
     // when that changes, not once per tile.
@@ -1330,6 +1378,12 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
   DRM_REQUIRE(RAG || (a.H % TH == 0 && a.W % TW == 0), "conv tile does not divide the map");
   DRM_REQUIRE(POOL == (a.pool_out != nullptr), "pooled output: only launches plan_conv pools");
   DRM_REQUIRE(!POOL || (a.pool_stat && a.stat_out && a.ksplit <= 1 && !a.out_nchw), "pooled output: needs both statistics tables, no split-K");
+  if constexpr (TAPS == 4) {
+    static_assert(!RAG && !SK && !POOL, "the parity form has no ragged, split-K or pooled instantiation");
+    DRM_REQUIRE(!a.bias && !a.emb && !a.res && !a.stat_out && !a.out_nchw && a.ksplit <= 1 && !a.gnf.mom0 && !a.in_inv && a.w_img_stride_f4 == 0,
+                "parity (4-tap) conv: weight un-scaling only -- no bias, emb, residual, statistics, split-K or GroupNorm fold");
+    DRM_REQUIRE(a.C1 == 0 && !a.up0 && a.Cout % 4 == 0 && (a.Cout / 4) % C::BN == 0, "parity (4-tap) conv: one stored source, a Cout tile inside one parity");
+  }
   const size_t lds_bytes = (size_t)(C::LDS_F4 + (POOL ? C::ST_F4 : 0)) * sizeof(float4);
   static_assert((C::LDS_F4 + (POOL ? C::ST_F4 : 0)) * 16 <= 160 * 1024, "LDS budget");
   const DeviceInfo* di = device_info();  // fails loudly on anything that is not an MI355X-shaped gfx950 (256 CUs, 160 KiB LDS)
@@ -1369,7 +1423,9 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
       prof_variant(vname.c_str());
     }
     DRM_REQUIRE(a.w_img_stride_f4 == 0 || (C::TN == 1 && ks == 1), "per-image weights need one image per tile (H*W a multiple of the 256-pixel tile)");
-    ProfScope ps(a.prof_kind == PROF_KINDS ? -1 : (a.prof_kind >= 0 ? a.prof_kind : (TAPS == 9 ? PROF_CONV3 : PROF_CONV1)), 2.0 * px * TAPS * cin * cout,
+    // (the parity form reports the algorithmic FLOPs of the conv it replaces: 9 taps at 4 x the pixels on a quarter of its GEMM columns)
+    constexpr int ALG_TAPS = (TAPS == 4) ? 9 : TAPS;
+    ProfScope ps(a.prof_kind == PROF_KINDS ? -1 : (a.prof_kind >= 0 ? a.prof_kind : (TAPS != 1 ? PROF_CONV3 : PROF_CONV1)), 2.0 * px * ALG_TAPS * cin * cout,
                  4.0 * (px_in + px * cout * (a.res ? 2 : 1) + (double)TAPS * cin * cout), s);
 #ifdef DRM_S2_STAMP
     // DRM_S2_STAMP_FILE=<path> [DRM_S2_STAMP_BLOCK=<workgroup>] [DRM_S2_STAMP_TILE0=<first recorded tile>]: appends one record
@@ -1420,9 +1476,26 @@ static int no_form(const ConvPlan& p) {  // (a plan that names a form no unit in
 // multi-image halo tiles leave no room for 96 KB of weights.
 template <int TAPS, int TH, int TW, int TERMS>
 static int launch_s2_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  constexpr int TPS = (TAPS == 9) ? 3 : 1, RG = (TAPS == 9) ? 2 : 4;
+  constexpr int TPS = (TAPS == 9) ? 3 : (TAPS == 4 ? 2 : 1), RG = (TAPS == 1) ? 4 : 2;
   constexpr bool T16 = TH == 16 && TW == 16, ROWS256 = TAPS == 1 || TH >= 8;
-  if (p.ragged) {
+  if constexpr (TAPS == 4) {
+    // the parity form of a 3x3 conv over a nearest-x2 input: one window ROW (2 taps) per step and barrier, ring of 2, on every GEMM tile of the
+    // 3x3 form (two-tap groups fit next to the halo tile where three-tap groups did not: 192-wide and 128x128 tiles); never ragged, split or pooled
+    if (p.ragged || p.pool || p.ksplit > 1) return no_form(p);
+    if (p.tile == TILE_256x192) {
+      if constexpr (T16 && (TERMS == 3 || TERMS == 2)) return launch_s2<TAPS, TH, TW, 4, 2, 2, 3, RG, TPS, TERMS>(a, s);
+    } else if (p.tile == TILE_256x128) {
+      if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS>(a, s);
+    } else if (p.tile == TILE_128x128) {
+      if constexpr (!ROWS256) return launch_s2<TAPS, TH, TW, 2, 2, 2, 2, RG, TPS, TERMS>(a, s);
+    } else if (p.tile == TILE_256x64) {
+      if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 1, RG, TPS, TERMS>(a, s);
+    } else if constexpr (!T16) {
+      if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS>(a, s);
+      if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS>(a, s);
+    }
+    return no_form(p);
+  } else if (p.ragged) {
     if constexpr (TERMS != 0 && !T16 && !(TH == 4 && TW == 8)) {  // (the ragged families; fp32 runs ragged maps on conv_igemm_kernel)
       if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS, true>(a, s);
       if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS, true>(a, s);
@@ -1470,6 +1543,11 @@ extern template int dispatch_s2<9, 4>(const ConvArgs&, const ConvPlan&, hipStrea
 extern template int dispatch_s2<1, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
 extern template int dispatch_s2<9, 2>(const ConvArgs&, const ConvPlan&, hipStream_t);
 extern template int dispatch_s2<9, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<4, 0>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<4, 1>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<4, 2>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<4, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
+extern template int dispatch_s2<4, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
 extern template int dispatch_s2<1, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
 int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s);  // (conv.hip)
 
@@ -1544,7 +1622,7 @@ ConvPlan plan_conv(const ConvArgs& a, int precision, bool want_pool, bool gn_fol
     // its activation staging and its barrier once per 24 MFMAs of a wave; here per 48 (the 64x128-map skip convs: 11-15 % faster).  The
     // 1x1 kernel has the registers for it (176 -> 256 VGPRs, 2 spilled); the 3x3 kernel does not.
     tile(TILE_256x256, true);
-  } else if (t16 && (p.terms == 3 || (a.taps == 9 && p.terms == 2)) && a.Cout % 192 == 0 && wgs(256, 192) >= 512) {
+  } else if (t16 && (p.terms == 3 || (a.taps != 1 && p.terms == 2)) && a.Cout % 192 == 0 && wgs(256, 192) >= 512) {
     // 192 output channels per tile (64 x 96 per wave, one-tap weight ring of 3).  1x1 for Cout = 384 / 1152 / 1536 ...: qkv 512->1536 @16x32 and
     // the 32x64-map skip convs 12-16 % faster.  3x3 (f16x3, f16mx; the three-tap groups would not fit next to the halo tile) for Cout = 384 on
     // big maps: 12 fragment reads per 18 MFMA products instead of 8 per 12 -- 5 % faster there.  Fits since the scalar-base DMA addressing took
@@ -1657,7 +1735,8 @@ static int launch_splitk_reduce(const ConvArgs& a, const float* partial, hipStre
 }
 
 int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  DRM_REQUIRE(a.taps == 9 || a.taps == 1, "conv taps must be 9 or 1");
+  DRM_REQUIRE(a.taps == 9 || a.taps == 1 || a.taps == 4, "conv taps must be 9, 1 or 4 (the parity form of a 3x3 over a nearest-x2 input)");
+  DRM_REQUIRE(a.taps != 4 || (p.kernel == CONV_PIPELINE && p.finish == SPLIT_NONE), "the parity (4-tap) form runs on the pipeline kernel, un-split");
   DRM_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv shape");
   DRM_REQUIRE(!a.up0 || (a.H % 2 == 0 && a.W % 2 == 0), "upsampled source needs even output size");
   DRM_REQUIRE(a.ksplit == p.ksplit && (p.ksplit == 1 || a.split_ws), "split-K launch without its slab workspace");
@@ -1665,8 +1744,16 @@ int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   DRM_REQUIRE(p.kernel == CONV_PIPELINE, "no conv kernel takes this shape (per-image weights: split modes, maps of whole 16x16 tiles, 128-channel multiples)");
   DRM_REQUIRE(a.Cout % 32 == 0 && (a.C0 + a.C1) % 32 == 0 && a.C0 % 32 == 0, "split conv needs channels % 32 == 0");
   DRM_REQUIRE(a.terms == p.terms, "ConvArgs::terms differs from the plan");
-  DRM_REQUIRE(p.terms != 2 || (a.taps == 9 && a.gn_scale && !a.in_inv && a.w_img_stride_f4 == 0), "f16mx: 3x3 convs on a GroupNorm-ed input only");
+  DRM_REQUIRE(p.terms != 2 || (a.taps != 1 && a.gn_scale && !a.in_inv && a.w_img_stride_f4 == 0), "f16mx: 3x3 convs on a GroupNorm-ed input only");
   auto run = [&](const ConvArgs& x) -> int {
+    if (a.taps == 4) switch (p.terms) {
+      case 0: return dispatch_s2<4, 0>(x, p, s);
+      case 1: return dispatch_s2<4, 1>(x, p, s);
+      case 2: return dispatch_s2<4, 2>(x, p, s);
+      case 3: return dispatch_s2<4, 3>(x, p, s);
+      case 4: return dispatch_s2<4, 4>(x, p, s);
+      default: return no_form(p);
+    }
     switch (p.terms) {
       case 0: return a.taps == 9 ? dispatch_s2<9, 0>(x, p, s) : dispatch_s2<1, 0>(x, p, s);  // exact fp32 operands (DRM_PREC_FP32)
       case 1: return a.taps == 9 ? dispatch_s2<9, 1>(x, p, s) : dispatch_s2<1, 1>(x, p, s);  // plain fp16 operands, one MFMA per product (DRM_PREC_F16)

@@ -80,6 +80,10 @@ struct ParamSlot {
   size_t scale_dst = 0;    // PK_CONV: 2 floats (2^k, 2^-k) of the split-precision weight pre-scaling
   bool mx_site = false;    // PK_CONV: a GroupNorm-fed 3x3 conv of a res block (PREC_F16MX packs the f16mx image for it)
   bool attn_fold = false;  // PK_CONV: qkv.weight of an attention block -- packed from the fold of this and the next three tensors (qkv.bias, proj_out.*)
+  // PK_CONV: in_layers conv of a ResBlock whose first up_c0 input channels arrive nearest-x2 upsampled (first block of a finer decoder level):
+  // two more images are packed from it (launch_fold_upconv_weight) -- the parity-major 2x2 kernels on those channels and the skip tensor's slice
+  int up_c0 = 0;
+  size_t upa_dst = 0, upa_scale = 0, upb_dst = 0, upb_scale = 0;
 };
 
 struct ResLayer {
@@ -88,6 +92,10 @@ struct ResLayer {
   size_t c1_s = 0, c2_s = 0, sk_s = 0;  // weight pre-scaling slots (split-precision path)
   int emb_off = 0;  // column offset of this block's emb_layers output in the fused embedding buffer
   bool has_skip = false;
+  // in_layers over cat(up(x0), x1) as two launches (plan_upconv_split): images and pre-scaling slots of the 4-tap conv on x0's up_c0 channels
+  // (c1a) and of the 3x3 conv on x1 (c1b); up_c0 = 0: not packed
+  int up_c0 = 0;
+  size_t c1a_w = 0, c1a_s = 0, c1b_w = 0, c1b_s = 0;
 };
 struct AttnLayer {
   int ch = 0;
@@ -134,7 +142,7 @@ class UNet {
  private:
   size_t add_copy(const std::string& name, std::vector<int64_t> shape, size_t padded_count = 0);
   size_t add_conv(const std::string& name, int cout, int cin, int k, int coutp, int cinp, bool conv1d = false, size_t* scale_off = nullptr, bool mx_site = false);
-  void add_res(Layer& l, const std::string& prefix, int cin, int cout);
+  void add_res(Layer& l, const std::string& prefix, int cin, int cout, int up_c0 = 0);  // up_c0: leading input channels that arrive upsampled
   void add_attn(Layer& l, const std::string& prefix, int ch);
 };
 
@@ -149,6 +157,11 @@ struct Ctx {
   int terms() const { return precision_terms(precision); }
 };
 Act new_act(Ctx& c, int C, int H, int W);
+// in_layers conv over cat(nearest_x2(x0), x1) as a 4-tap conv on the stored x0 + a 3x3 conv on x1 (engine.hip plan_upconv_split):
+// 0 = never, 1 = by the measured per-level rule (default), 2 = wherever the form applies (tests, A/Bs)
+void set_upconv_split(int mode);
+// whether a block with these channel counts gets the two extra weight images at all
+inline bool upconv_split_packable(int c0, int c1, int cout) { return c0 > 0 && c1 > 0 && c0 % 32 == 0 && c1 % 32 == 0 && cout % 32 == 0; }
 int ensure_moments(Ctx& c, Act& a);
 // pool (optional): the Downsample that follows this block -- when the out_layers conv's plan writes the 2x2 average pool of `out` and its statistics
 // from its own epilogue (ConvPlan::pool) it does, and *pooled is set; otherwise the caller runs launch_avgpool2

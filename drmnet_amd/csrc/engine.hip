@@ -98,13 +98,26 @@ size_t UNet::add_conv(const std::string& name, int cout, int cin, int k, int cou
   return p.dst;
 }
 
-void UNet::add_res(Layer& l, const std::string& px, int cin, int cout) {
+void UNet::add_res(Layer& l, const std::string& px, int cin, int cout, int up_c0) {
   l.kind = Layer::RES;
   ResLayer& r = l.res;
   r.cin = cin; r.cout = cout; r.has_skip = (cin != cout);
   r.n1_w = add_copy(px + ".in_layers.0.weight", {cin});
   r.n1_b = add_copy(px + ".in_layers.0.bias", {cin});
   r.c1_w = add_conv(px + ".in_layers.2.weight", cout, cin, 3, cout, cin, false, &r.c1_s, true);
+  if (upconv_split_packable(up_c0, cin - up_c0, cout)) {  // (same tensor, two more images: the parameter table does not change)
+    ParamSlot& p = params.back();
+    auto take = [&](size_t n) {
+      const size_t at = wbuf_floats;
+      wbuf_floats += (n + 63) & ~size_t(63);
+      return at;
+    };
+    p.up_c0 = r.up_c0 = up_c0;
+    p.upa_dst = r.c1a_w = take(packed_conv_weight_floats(4, 4 * cout, up_c0));
+    p.upa_scale = r.c1a_s = take(64);
+    p.upb_dst = r.c1b_w = take(packed_conv_weight_floats(9, cout, cin - up_c0));
+    p.upb_scale = r.c1b_s = take(64);
+  }
   r.c1_b = add_copy(px + ".in_layers.2.bias", {cout});
   r.emb_off = emb_total;
   emb_total += cout;
@@ -202,13 +215,15 @@ int UNet::build(const drm_unet_desc& d) {
   add_res(middle[2], "middle_block.2", ch, ch);
   if (d.kind == 0) {
     int oidx = 0;
+    bool up_in = false;  // the block's input h arrives through an Upsample
     for (int level = d.n_levels - 1; level >= 0; --level) {
       const int m = d.channel_mult[level];
       for (int i = 0; i <= d.num_res_blocks; ++i) {
         const int ich = chans.back();
         chans.pop_back();
         std::vector<Layer> ls(1);
-        add_res(ls[0], "output_blocks." + std::to_string(oidx) + ".0", ch + ich, mc * m);
+        add_res(ls[0], "output_blocks." + std::to_string(oidx) + ".0", ch + ich, mc * m, up_in ? ch : 0);
+        up_in = false;
         ch = mc * m;
         if (has_attn(ds)) {
           ls.emplace_back();
@@ -217,6 +232,7 @@ int UNet::build(const drm_unet_desc& d) {
         if (level && i == d.num_res_blocks) {
           ls.emplace_back();
           ls.back().kind = Layer::UP;
+          up_in = true;
           ds /= 2;
         }
         output_blocks.push_back(ls);
@@ -276,6 +292,18 @@ int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
   for (const ParamSlot& p : params)
     if (p.attn_fold) fold_floats = std::max(fold_floats, (size_t)p.cout * p.cin + (size_t)p.cout);
   if (fold_floats) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fold.p), fold_floats * sizeof(float)));
+  // ... and for the two raw weight tensors an upsampled-input in_layers conv is split into (launch_fold_upconv_weight)
+  Staging upw{nullptr, s};
+  size_t upw_floats = 0;
+  for (const ParamSlot& p : params)
+    if (p.up_c0) upw_floats = std::max(upw_floats, (size_t)16 * p.cout * p.up_c0 + (size_t)9 * p.cout * (p.cin - p.up_c0));
+  if (upw_floats) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&upw.p), upw_floats * sizeof(float)));
+  auto pack = [&](const float* w, size_t dst, size_t scale_dst, int cout, int cin, int taps, int coutp, int cinp, bool mx_site) -> int {
+    if (conv_split_weights(precision, cinp))
+      return launch_pack_conv_weight_split(w, wbuf + dst, wbuf + scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), cout, cin, taps, coutp, cinp,
+                                           s, precision == PREC_F16MX && mx_site, precision == PREC_BF16);
+    return launch_pack_conv_weight(w, wbuf + dst, cout, cin, taps, coutp, cinp, s);
+  };
   for (size_t i = 0; i < params.size(); ++i) {
     const ParamSlot& p = params[i];
     DRM_REQUIRE(ptrs[i] != nullptr, "null parameter pointer for " + p.name);
@@ -290,11 +318,16 @@ int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
     }
     if (p.kind == PK_COPY) {
       DRM_HIP_CHECK(hipMemcpyAsync(wbuf + p.dst, w, p.count * sizeof(float), hipMemcpyDeviceToDevice, s));
-    } else if (conv_split_weights(precision, p.cinp)) {
-      DRM_TRY(launch_pack_conv_weight_split(w, wbuf + p.dst, wbuf + p.scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), p.cout,
-                                            p.cin, p.taps, p.coutp, p.cinp, s, precision == PREC_F16MX && p.mx_site, precision == PREC_BF16));
     } else {
-      DRM_TRY(launch_pack_conv_weight(w, wbuf + p.dst, p.cout, p.cin, p.taps, p.coutp, p.cinp, s));
+      DRM_TRY(pack(w, p.dst, p.scale_dst, p.cout, p.cin, p.taps, p.coutp, p.cinp, p.mx_site));
+      if (p.up_c0) {  // each image with its own pre-scaling: the folded taps are sums of up to four weights
+        const int c0 = p.up_c0, c1 = p.cin - p.up_c0;
+        float* wa = upw.p;
+        float* wb = upw.p + (size_t)16 * p.cout * c0;
+        DRM_TRY(launch_fold_upconv_weight(w, wa, wb, p.cout, c0, c1, s));
+        DRM_TRY(pack(wa, p.upa_dst, p.upa_scale, 4 * p.cout, c0, 4, 4 * p.cout, c0, p.mx_site));
+        DRM_TRY(pack(wb, p.upb_dst, p.upb_scale, p.cout, c1, 9, p.cout, c1, p.mx_site));
+      }
     }
   }
   if (stem_direct_w >= 0) DRM_TRY(launch_pack_stem_weight(ptrs[stem_param], wbuf + stem_direct_w, desc.model_channels, desc.in_channels, precision == PREC_FP32, s));
@@ -411,6 +444,43 @@ static int arena_ok(const Ctx& c) {
   return DRM_ERR_WORKSPACE;
 }
 
+static std::atomic<int> g_upconv_split{1};
+void set_upconv_split(int mode) { g_upconv_split.store(mode); }
+
+// in_layers conv over cat(nearest_x2(x0), x1), by linearity: conv3x3(cat(up(a0), a1)) = PS(conv2x2'(a0)) + conv3x3(a1), a = SiLU(GN(x)) with the
+// block's tables (per element: it commutes with the replication).  Launch A: the four parity 2x2 convs on the STORED x0 (taps = 4, Cout' = 4 Cout),
+// pixel-shuffled straight into h1; launch B: the ordinary 3x3 conv on x1 with bias, emb, res = out = h1 and the fused output statistics.  A runs 4
+// taps where the single launch ran 9 on x0's channels and stages a quarter of the halo pixels.  Takes nothing from the arena or the statistics pool.
+// The form runs only where the single launch and both new ones are whole-tile, un-split pipeline launches with no GroupNorm fold (N > 4); the sizing
+// pass and the real pass both decide here.
+struct UpconvSplit {
+  bool on = false;
+  ConvArgs a4, b9;  // shape fields
+  ConvPlan p4, p9;
+};
+static UpconvSplit plan_upconv_split(const Ctx& c, const ResLayer& r, const ConvArgs& a, const ConvPlan& pa, const Act& x0, const Act* x1) {
+  UpconvSplit u;
+  const int mode = g_upconv_split.load(std::memory_order_relaxed);
+  if (mode == 0 || !r.up_c0 || !x0.up || !x1 || x0.C != r.up_c0 || !upconv_split_packable(x0.C, x1->C, r.cout)) return u;
+  auto plain = [](const ConvPlan& p) { return p.kernel == CONV_PIPELINE && !p.ragged && p.ksplit == 1 && !p.gn_fold && !p.pool; };
+  if (!plain(pa)) return u;
+  u.a4.C0 = x0.C; u.a4.N = a.N; u.a4.H = a.H >> 1; u.a4.W = a.W >> 1; u.a4.taps = 4; u.a4.Cout = 4 * r.cout; u.a4.mx_site = 1;
+  u.b9.C0 = x1->C; u.b9.N = a.N; u.b9.H = a.H; u.b9.W = a.W; u.b9.taps = 9; u.b9.Cout = r.cout; u.b9.mx_site = 1;
+  u.p4 = plan_conv(u.a4, c.precision);
+  u.p9 = plan_conv(u.b9, c.precision);
+  if (!plain(u.p4) || !plain(u.p9)) return u;
+  static const int tile_bn[] = {256, 192, 128, 128, 64, 64, 32};  // (ConvTile order) a Cout tile of A lies inside one parity
+  if (r.cout % tile_bn[u.p4.tile] != 0) return u;
+  // The rule (mode 1).  Measured on the five decoder levels of the batch-32 step, f16mx, single launch -> A + B, two interleaved rounds on one
+  // device (profiles/upconv_split_shapes.txt): 128x256 1.755 -> 1.419 ms, 64x128 1.409 -> 1.105, 32x64 0.700 -> 0.544, 16x32 0.310 -> 0.254,
+  // round-to-round spread of a shape 0.2 .. 3 %: every level where the form applies wins by 18 .. 22 %, all of them on 256-row tiles at least 128
+  // channels wide for A and B alike.  (The 8x16 level is split-K and keeps the single launch.)  Launches on the narrow tiles of sparse grids --
+  // small batches, where a launch is a few microseconds and one more launch and epilogue weigh most -- were not measured: they keep the single launch.
+  if (mode == 1 && (u.p4.tile > TILE_256x128 || u.p9.tile > TILE_256x128)) return u;
+  u.on = true;
+  return u;
+}
+
 int run_resblock(Ctx& c, const float* Wb, const ResLayer& r, Act& x0, Act* x1, const float* emb_all, int emb_stride, Act& out, Act* pool, bool* pooled) {
   DRM_TRY(arena_ok(c));
   const int H = x0.H, W = x0.W;
@@ -436,7 +506,21 @@ int run_resblock(Ctx& c, const float* Wb, const ResLayer& r, Act& x0, Act* x1, c
   }
   DRM_TRY(gn_params(c, x0, x1, Wb + r.n1_w, Wb + r.n1_b, sc1, sh1, pk.split() ? &k : nullptr, pa.gn_fold ? &a : nullptr));
   splitk_workspace(c, a, pa);
-  if (!c.dry()) {
+  UpconvSplit up = plan_upconv_split(c, r, a, pa, x0, x1);
+  if (up.on) {
+    if (!c.dry()) {
+      ConvArgs& a4 = up.a4;  // A: the parity 2x2 convs on the stored x0, pixel-shuffled into h1 (weight un-scaling only)
+      a4.src0 = x0.p; a4.gn_scale = sc1; a4.gn_shift = sh1; a4.gn_ld = r.cin; a4.silu = 1;
+      a4.w = Wb + r.c1a_w; a4.out = h1.p;
+      DRM_TRY(run_conv(c, a4, up.p4, Wb, r.c1a_s, nullptr));
+      ConvArgs& b9 = up.b9;  // B: 3x3 on the skip tensor + bias + emb + A's result (res = out), statistics of the sum
+      b9.src0 = x1->p; b9.gn_scale = sc1 + x0.C; b9.gn_shift = sh1 + x0.C; b9.gn_ld = r.cin; b9.silu = 1;
+      b9.w = Wb + r.c1b_w; b9.bias = Wb + r.c1_b;
+      b9.emb = emb_all ? emb_all + r.emb_off : nullptr; b9.emb_stride = emb_stride;
+      b9.res = h1.p; b9.out = h1.p;
+      DRM_TRY(run_conv(c, b9, up.p9, Wb, r.c1b_s, &h1));
+    }
+  } else if (!c.dry()) {
     a.gn_scale = sc1; a.gn_shift = sh1; a.silu = 1;
     a.w = Wb + r.c1_w; a.bias = Wb + r.c1_b;
     a.emb = emb_all ? emb_all + r.emb_off : nullptr; a.emb_stride = emb_stride;

@@ -26,6 +26,33 @@ def set_graph_replay(on: bool) -> None:
     _lib.check(_lib.lib().drm_set_graph_replay(int(bool(on))))
 
 
+def set_upconv_split(mode: int) -> None:
+    """in_layers conv over cat(nearest_x2(x0), x1) as a 4-tap conv on the stored x0 + a 3x3 conv on x1: 0 = never, 1 = by the measured per-level
+    rule (default), 2 = wherever the form applies; see include/drmnet_hip.h.  For tests and A/B measurements."""
+    _lib.check(_lib.lib().drm_set_upconv_split(int(mode)))
+
+
+# parity of the output row (column) -> window position dy (dx) -> the 3x3 taps ky (kx) that land on that stored pixel of a nearest-x2 input
+UPCONV_TAP_GROUPS = {0: {0: (0,), 1: (1, 2)}, 1: {0: (0, 1), 1: (2,)}}
+
+
+def fold_upconv_weight(w: torch.Tensor, c0: int):
+    """What csrc/conv_split.hip fold_upconv_weight_kernel computes, in torch (any device): w [Cout, C0 + C1, 3, 3] ->
+    (wa [4 * Cout, C0, 2, 2], parity-major p = 2a + b, tap sums in fp64 rounded once; wb [Cout, C1, 3, 3]).  Output pixel (2i + a, 2j + b) of
+    conv3x3(nearest_x2(x)) is sum wa[p][dy, dx] * x[i + a - 1 + dy, j + b - 1 + dx] with zero padding outside the stored map."""
+    cout = w.shape[0]
+    w0 = w[:, :c0].double()
+    wa = torch.zeros((4, cout, c0, 2, 2), dtype=torch.float64, device=w.device)
+    for a in (0, 1):
+        for b in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    for ky in UPCONV_TAP_GROUPS[a][dy]:
+                        for kx in UPCONV_TAP_GROUPS[b][dx]:
+                            wa[2 * a + b, :, :, dy, dx] += w0[:, :, ky, kx]
+    return wa.reshape(4 * cout, c0, 2, 2).to(w.dtype), w[:, c0:].contiguous()
+
+
 def graph_launches() -> int:
     return int(_lib.lib().drm_graph_launches())
 

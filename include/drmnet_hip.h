@@ -259,6 +259,13 @@ size_t drm_sampler_workspace_bytes(const drm_unet* net, int N, int H, int W);
  * it applies to chains of >= 4 steps and steps aside while the launch profiler records (events do not belong in a graph).  With replay the call returns after the chain has
  * finished (the executable graph is destroyed behind its last launch).  drm_graph_launches counts hipGraphLaunch calls so far. */
 int drm_set_graph_replay(int on);
+
+/* The in_layers conv of a ResBlock whose input is cat(nearest_x2(x0), x1) (first block of every finer decoder level) can run as two
+ * launches: the four parity 2x2 convs on the stored x0 (4 taps in place of 9, pixel-shuffled into the output) and the 3x3 conv on x1
+ * that adds bias, embedding and the first launch's result.  mode 0 = never, 1 = where the measured per-level rule says it is faster
+ * (default), 2 = wherever the form applies (whole-tile, un-split launches, batch > 4).  Same function either way (fp32 reassociation of
+ * the nine taps into four); library-level, for tests and A/B measurements. */
+int drm_set_upconv_split(int mode);
 int64_t drm_graph_launches(void);
 
 /* Launch profiler (HIP events on the launch stream around each kernel family; used by bench.py for the roofline
