@@ -17,20 +17,6 @@ struct drm_drmnet {
 
 namespace {
 
-// RAII device scratch for the op-level entry points (tests / per-module drop-ins only).
-struct Scratch {
-  void* p = nullptr;
-  hipStream_t s;
-  explicit Scratch(hipStream_t st) : s(st) {}
-  int reserve(size_t bytes) { DRM_HIP_CHECK(hipMalloc(&p, bytes)); return DRM_OK; }
-  ~Scratch() {
-    if (p) {
-      (void)hipStreamSynchronize(s);
-      (void)hipFree(p);
-    }
-  }
-};
-
 int make_arena(Arena& ar, void* ws, size_t bytes, size_t need) {
   if (need == 0) return DRM_ERR_INVALID;  // error text already set by the dry run
   if (bytes < need || ws == nullptr) {
@@ -55,7 +41,7 @@ int guarded(F&& f) {
   }
 }
 
-// shared driver for the two block-level ops: runs `body` twice (measure, then execute) over a private scratch arena
+// shared driver for the block-level ops (tests / per-module drop-ins only): runs `body` twice (measure, then execute) over a private scratch arena
 template <typename Body>
 int with_scratch(hipStream_t s, Body&& body) {
   Arena dry;
@@ -77,13 +63,13 @@ int with_scratch(hipStream_t s, Body&& body) {
 // effect for calls that start after it.  The network / sampler handles carry their own mode (drm_unet_set_precision).
 std::atomic<int> g_op_precision{PREC_FP32};
 
-// packs one conv weight for the op precision `prec`; `slot` = 64-float scale slot (2^k, 2^-k), `scratch` = 1 uint
-int pack_for_ops(int prec, const float* w, float* dst, float* slot, float* scratch, int cout, int cin, int taps, int coutp, int cinp, hipStream_t s,
-                 bool mx_site = false) {
-  if (conv_split_weights(prec, cinp))
-    return launch_pack_conv_weight_split(w, dst, slot, reinterpret_cast<unsigned*>(scratch), cout, cin, taps, coutp, cinp, s,
-                                         prec == PREC_F16MX && mx_site, prec == PREC_BF16);
-  return launch_pack_conv_weight(w, dst, cout, cin, taps, coutp, cinp, s);
+// the weights of a block-level op: its one-layer table packed from the caller's tensors (they arrive in the table's order) by the code a network's
+// load runs, into *wbuf; buffers from the call's scratch arena in both passes of with_scratch, launches in the real pass only
+int pack_block(const ParamTable& tab, const float* const* params, int count, Arena& ar, int precision, hipStream_t s, float** wbuf) {
+  *wbuf = ar.alloc<float>(tab.wbuf_floats);
+  float* staging = ar.alloc<float>(tab.staging_floats());
+  if (ar.dry) return DRM_OK;
+  return tab.pack(params, count, *wbuf, precision, staging, s);
 }
 
 size_t unet_ws(UNet& net, int N, int H, int W) {
@@ -223,7 +209,7 @@ int drm_op_norm_act_conv(const float* x, const float* gamma, const float* beta, 
         return DRM_OK;
       }
       DRM_TRY(launch_pack_input(x, nullptr, nullptr, xa.p, N, H, W, Cin, 0, cinp, s));
-      DRM_TRY(pack_for_ops(op_prec, w, wp, wb, scratch, Cout, Cin, taps, coutp, cinp, s));
+      DRM_TRY(pack_conv_image(op_prec, w, wp, wb, reinterpret_cast<unsigned*>(scratch), Cout, Cin, taps, coutp, cinp, false, s));
       if (b) DRM_HIP_CHECK(hipMemcpyAsync(bp, b, Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
       if (!gamma) {
         xa.mom_valid = false;
@@ -261,56 +247,24 @@ int drm_op_resblock(const float* x0, int C0, int up0, const float* x1, int C1, c
     return with_scratch(s, [&](Arena& ar) -> int {
       const int op_prec = g_op_precision.load(std::memory_order_relaxed);  // (read once: the whole call runs in this mode)
       Ctx c{&ar, s, N, op_prec};
-      // packed weights laid out like UNet::add_res
-      ResLayer r;
-      r.cin = cin; r.cout = Cout; r.has_skip = has_skip; r.emb_off = 0;
-      float* wb = ar.alloc<float>(1);  // base pointer for offsets
-      auto off = [&](float* p) { return (size_t)(p - wb); };
-      float* n1w = ar.alloc<float>(cin); float* n1b = ar.alloc<float>(cin);
-      float* c1w = ar.alloc<float>(packed_conv_weight_floats(9, Cout, cin)); float* c1b = ar.alloc<float>(Cout);
-      float* n2w = ar.alloc<float>(Cout); float* n2b = ar.alloc<float>(Cout);
-      float* c2w = ar.alloc<float>(packed_conv_weight_floats(9, Cout, Cout)); float* c2b = ar.alloc<float>(Cout);
-      float* skw = ar.alloc<float>(packed_conv_weight_floats(1, Cout, cin)); float* skb = ar.alloc<float>(Cout);
-      float* s1 = ar.alloc<float>(64); float* s2 = ar.alloc<float>(64); float* s3 = ar.alloc<float>(64); float* scratch = ar.alloc<float>(64);
+      ParamTable tab;
+      tab.emb_dim = emb_dim;
+      Layer l;
+      tab.add_res(l, "", cin, Cout, up0 ? C0 : 0);
+      tab.finish();
+      float* wb = nullptr;
+      DRM_TRY(pack_block(tab, params, n_params, ar, op_prec, s, &wb));
       float* e_out = ar.alloc<float>((size_t)N * Cout);
-      // in_layers over cat(up(x0), x1): the two extra images UNet::load packs for such a block (run_resblock decides whether they run)
-      const bool upw = up0 && upconv_split_packable(C0, C1, Cout);
-      float *c1aw = nullptr, *c1bw = nullptr, *s4 = nullptr, *s5 = nullptr, *wa_raw = nullptr, *wb_raw = nullptr;
-      if (upw) {
-        c1aw = ar.alloc<float>(packed_conv_weight_floats(4, 4 * Cout, C0)); c1bw = ar.alloc<float>(packed_conv_weight_floats(9, Cout, C1));
-        s4 = ar.alloc<float>(64); s5 = ar.alloc<float>(64);
-        wa_raw = ar.alloc<float>((size_t)16 * Cout * C0); wb_raw = ar.alloc<float>((size_t)9 * Cout * C1);
-      }
       Act a0 = new_act(c, C0, H, W);
       a0.up = up0;
       Act a1 = new_act(c, C1 > 0 ? C1 : 4, H, W);
       Act o = new_act(c, Cout, H, W);
       if (!ar.dry) {
-        r.n1_w = off(n1w); r.n1_b = off(n1b); r.c1_w = off(c1w); r.c1_b = off(c1b); r.n2_w = off(n2w); r.n2_b = off(n2b);
-        r.c2_w = off(c2w); r.c2_b = off(c2b); r.sk_w = off(skw); r.sk_b = off(skb);
-        r.c1_s = off(s1); r.c2_s = off(s2); r.sk_s = off(s3);
-        auto cp = [&](float* d, const float* sp, size_t n) -> int {
-          DRM_HIP_CHECK(hipMemcpyAsync(d, sp, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-          return DRM_OK;
-        };
-        DRM_TRY(cp(n1w, params[0], cin)); DRM_TRY(cp(n1b, params[1], cin));
-        DRM_TRY(pack_for_ops(op_prec, params[2], c1w, s1, scratch, Cout, cin, 9, Cout, cin, s, true)); DRM_TRY(cp(c1b, params[3], Cout));
-        if (upw) {
-          r.up_c0 = C0; r.c1a_w = off(c1aw); r.c1a_s = off(s4); r.c1b_w = off(c1bw); r.c1b_s = off(s5);
-          DRM_TRY(launch_fold_upconv_weight(params[2], wa_raw, wb_raw, Cout, C0, C1, s));
-          DRM_TRY(pack_for_ops(op_prec, wa_raw, c1aw, s4, scratch, 4 * Cout, C0, 4, 4 * Cout, C0, s, true));
-          DRM_TRY(pack_for_ops(op_prec, wb_raw, c1bw, s5, scratch, Cout, C1, 9, Cout, C1, s, true));
-        }
-        DRM_TRY(launch_linear(emb, params[4], params[5], e_out, N, emb_dim, Cout, 1, 0, s));
-        DRM_TRY(cp(n2w, params[6], Cout)); DRM_TRY(cp(n2b, params[7], Cout));
-        DRM_TRY(pack_for_ops(op_prec, params[8], c2w, s2, scratch, Cout, Cout, 9, Cout, Cout, s, true)); DRM_TRY(cp(c2b, params[9], Cout));
-        if (has_skip) {
-          DRM_TRY(pack_for_ops(op_prec, params[10], skw, s3, scratch, Cout, cin, 1, Cout, cin, s)); DRM_TRY(cp(skb, params[11], Cout));
-        }
+        DRM_TRY(launch_linear(emb, wb + tab.embcat_w, wb + tab.embcat_b, e_out, N, emb_dim, tab.emb_total, 1, 0, s));
         DRM_TRY(launch_nchw_to_nhwc(x0, a0.p, N, H >> up0, W >> up0, C0, s));
         if (C1 > 0) DRM_TRY(launch_nchw_to_nhwc(x1, a1.p, N, H, W, C1, s));
       }
-      DRM_TRY(run_resblock(c, wb, r, a0, C1 > 0 ? &a1 : nullptr, e_out, Cout, o));
+      DRM_TRY(run_resblock(c, wb, l.res, a0, C1 > 0 ? &a1 : nullptr, e_out, tab.emb_total, o));
       if (!ar.dry) DRM_TRY(launch_nhwc_to_nchw(o.p, out, N, H, W, Cout, s));
       return DRM_OK;
     });
@@ -324,25 +278,16 @@ int drm_op_attention_block(const float* x, const float* const* params, float* ou
     return with_scratch(s, [&](Arena& ar) -> int {
       const int op_prec = g_op_precision.load(std::memory_order_relaxed);  // (read once: the whole call runs in this mode)
       Ctx c{&ar, s, N, op_prec};
-      AttnLayer l;
-      l.ch = C;
-      float* wb = ar.alloc<float>(1);
-      auto off = [&](float* p) { return (size_t)(p - wb); };
-      float* nw = ar.alloc<float>(C); float* nb = ar.alloc<float>(C);
-      float* qw = ar.alloc<float>(packed_conv_weight_floats(1, 3 * C, C)); float* qb = ar.alloc<float>(3 * C);
-      float* fw = ar.alloc<float>((size_t)3 * C * C);  // raw [3C][C] qkv weight with proj_out folded into its v rows, as UNet::load forms it
-      float* s1 = ar.alloc<float>(64); float* scratch = ar.alloc<float>(64);
+      ParamTable tab;
+      Layer l;
+      tab.add_attn(l, "", C);
+      tab.finish();
+      float* wb = nullptr;
+      DRM_TRY(pack_block(tab, params, 6, ar, op_prec, s, &wb));
       Act a = new_act(c, C, H, W);
       Act o = new_act(c, C, H, W);
-      if (!ar.dry) {
-        l.n_w = off(nw); l.n_b = off(nb); l.qkv_w = off(qw); l.qkv_b = off(qb); l.qkv_s = off(s1);
-        DRM_HIP_CHECK(hipMemcpyAsync(nw, params[0], C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DRM_HIP_CHECK(hipMemcpyAsync(nb, params[1], C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DRM_TRY(launch_fold_attn_params(params[2], params[3], params[4], params[5], fw, qb, C, s));
-        DRM_TRY(pack_for_ops(op_prec, fw, qw, s1, scratch, 3 * C, C, 1, 3 * C, C, s));
-        DRM_TRY(launch_nchw_to_nhwc(x, a.p, N, H, W, C, s));
-      }
-      DRM_TRY(run_attention(c, wb, l, a, o));
+      if (!ar.dry) DRM_TRY(launch_nchw_to_nhwc(x, a.p, N, H, W, C, s));
+      DRM_TRY(run_attention(c, wb, l.attn, a, o));
       if (!ar.dry) DRM_TRY(launch_nhwc_to_nchw(o.p, out, N, H, W, C, s));
       return DRM_OK;
     });

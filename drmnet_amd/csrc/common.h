@@ -144,6 +144,10 @@ inline bool precision_valid(int p) { return p >= PREC_FP32 && p <= PREC_BF16; }
 inline int precision_terms(int p) { return p == PREC_F16 ? 1 : (p == PREC_BF16 ? 4 : (p == PREC_FP32 ? 0 : 3)); }
 // repack PyTorch conv weight [Cout][Cin][kh][kw] -> [taps][CinP/4][CoutP][4] (zero padded)
 int launch_pack_conv_weight(const float* w, float* packed, int Cout, int Cin, int taps, int CoutP, int CinP, hipStream_t s);
+// one conv weight in the image its consumer reads in `precision` (engine.hip): the pre-split one where conv_split_weights says so -- f16mx for an
+// mx_site in PREC_F16MX, bf16 in PREC_BF16 -- with its pre-scaling (2^k, 2^-k) at `scale`, else plain fp32; `scratch` = 1 uint on the device
+int pack_conv_image(int precision, const float* w, float* packed, float* scale, unsigned* scratch, int Cout, int Cin, int taps, int CoutP, int CinP,
+                    bool mx_site, hipStream_t s);
 // attention parameter fold (conv_split.hip): raw qkv [3C][C] / [3C] and proj_out [C][C] / [C] -> w_out [3C][C], b_out [3C] whose v rows hold
 // Wp Wv and Wp bv + bp (fp64 products, rounded once); what every attention block's qkv conv is packed from
 // 3x3 conv over cat(nearest_x2(x0), x1) split by linearity (engine.hip plan_upconv_split): w [Cout][C0 + C1][3][3] -> wa [4 * Cout][C0][2][2], the

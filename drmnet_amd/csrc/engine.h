@@ -64,9 +64,27 @@ struct Act {  // NHWC activation (+ cached per-channel moments for GroupNorm)
   bool mom_valid = false;
   bool mom_sums = false;    // table holds raw sums over the stored pixels (fused conv-epilogue statistics) instead of means
   bool mom_zeroed = false;  // table comes from the pass's pre-zeroed statistics pool
+  // what turns the table into means, whichever it holds: a finalise kernel multiplies by mom_inv(); mom_cnt() = the pixel count of a table of means, 0 for sums
+  double mom_pixels() const { return (double)(H >> up) * (W >> up); }
+  double mom_inv() const { return mom_sums ? 1.0 / mom_pixels() : 1.0; }
+  double mom_cnt() const { return mom_sums ? 0.0 : mom_pixels(); }
 };
 
-// PK_FOLDED: a tensor of an attention block that the fold launched at the block's qkv.weight slot consumes (qkv.bias, proj_out.*): load() copies
+// RAII device buffer: freed once the work queued on `s` has run
+struct Scratch {
+  void* p = nullptr;
+  hipStream_t s;
+  explicit Scratch(hipStream_t st) : s(st) {}
+  int reserve(size_t bytes) { DRM_HIP_CHECK(hipMalloc(&p, bytes)); return DRM_OK; }
+  ~Scratch() {
+    if (p) {
+      (void)hipStreamSynchronize(s);
+      (void)hipFree(p);
+    }
+  }
+};
+
+// PK_FOLDED: a tensor of an attention block that the fold launched at the block's qkv.weight slot consumes (qkv.bias, proj_out.*): pack() copies
 // nothing for it on its own; proj_out.* have no storage in the packed buffer at all
 enum ParamKind { PK_COPY, PK_CONV, PK_FOLDED };
 
@@ -107,20 +125,38 @@ struct Layer {
   AttnLayer attn;
 };
 
-class UNet {
+// Parameter table: the tensors in reference state_dict() order, where each lands in the packed weight buffer, and the packing itself.  A network
+// is one table (UNet); the block-level drm_op_* entry points build a one-layer table per call, so both run the same layout and packing code.
+struct ParamTable {
+  std::vector<ParamSlot> params;  // reference state_dict() order
+  int emb_dim = 0, emb_total = 0;
+  size_t wbuf_floats = 0;
+  size_t embcat_w = 0, embcat_b = 0, scratch_off = 0;  // (finish()) the fused [emb_total][emb_dim] emb_layers matrix and bias; the packers' scratch slot
+
+  size_t reserve(size_t floats);  // a 64-float-aligned region of the packed buffer
+  size_t add_copy(const std::string& name, std::vector<int64_t> shape, size_t padded_count = 0);
+  size_t add_conv(const std::string& name, int cout, int cin, int k, int coutp, int cinp, bool conv1d = false, size_t* scale_off = nullptr, bool mx_site = false);
+  void add_res(Layer& l, const std::string& prefix, int cin, int cout, int up_c0 = 0);  // up_c0: leading input channels that arrive upsampled
+  void add_attn(Layer& l, const std::string& prefix, int ch);
+  void finish();  // after the last add_*: places what depends on the whole table
+  // Fills `wbuf` (wbuf_floats) from the `count` tensors of `ptrs` (device, table order): copies, the attention fold, every conv in the image its
+  // consumer reads in `precision`.  `staging`: staging_floats() device floats for the folds, reused slot after slot in stream order.
+  size_t staging_floats() const;
+  int pack(const float* const* ptrs, int count, float* wbuf, int precision, float* staging, hipStream_t s) const;
+};
+
+class UNet : public ParamTable {
  public:
   drm_unet_desc desc{};
-  std::vector<ParamSlot> params;  // reference state_dict() order
   std::vector<std::vector<Layer>> input_blocks, output_blocks;  // input_blocks[0] is the stem (empty list)
   std::vector<Layer> middle;
-  int final_ch = 0, emb_dim = 0, emb_total = 0, in_cp = 0, out_cp = 0;
+  int final_ch = 0, in_cp = 0, out_cp = 0;
   size_t stem_s = 0;
   // packed-buffer offsets
-  size_t te0_w = 0, te0_b = 0, te2_w = 0, te2_b = 0, stem_w = 0, stem_b = 0, embcat_w = 0, embcat_b = 0, on_w = 0, on_b = 0, oc_w = 0, oc_b = 0, oc_s = 0, scratch_off = 0;
+  size_t te0_w = 0, te0_b = 0, te2_w = 0, te2_b = 0, stem_w = 0, stem_b = 0, on_w = 0, on_b = 0, oc_w = 0, oc_b = 0, oc_s = 0;
   // direct stem kernel (stemhead.hip): its own weight image, packed next to the generic one; -1 = the generic conv path
   long long stem_direct_w = -1;
   int stem_param = -1;  // index of the source tensor in `params`
-  size_t wbuf_floats = 0;
   // Packed weight images.  A network keeps up to DRM_WEIGHT_SETS of them side by side (set 0 = the live parameters, set 1 = the
   // EMA shadow the reference swaps in for sampling, ema.py:46-76): each is packed / pre-split ONCE and selected per forward, so
   // entering and leaving ema_scope costs no re-upload.
@@ -138,12 +174,6 @@ class UNet {
               float* out, int N, int H, int W, Arena& ar, hipStream_t s);
   int dry_forward(int N, int H, int W, Arena& probe);  // the sizing walk: makes `probe` a dry arena and runs forward over it with no tensors
   ~UNet();
-
- private:
-  size_t add_copy(const std::string& name, std::vector<int64_t> shape, size_t padded_count = 0);
-  size_t add_conv(const std::string& name, int cout, int cin, int k, int coutp, int cinp, bool conv1d = false, size_t* scale_off = nullptr, bool mx_site = false);
-  void add_res(Layer& l, const std::string& prefix, int cin, int cout, int up_c0 = 0);  // up_c0: leading input channels that arrive upsampled
-  void add_attn(Layer& l, const std::string& prefix, int ch);
 };
 
 // building blocks shared with the op-level ABI entry points
@@ -163,6 +193,8 @@ void set_upconv_split(int mode);
 // whether a block with these channel counts gets the two extra weight images at all
 inline bool upconv_split_packable(int c0, int c1, int cout) { return c0 > 0 && c1 > 0 && c0 % 32 == 0 && c1 % 32 == 0 && cout % 32 == 0; }
 int ensure_moments(Ctx& c, Act& a);
+// `a`'s producer accumulates raw sums into its statistics table: marks the table so and, in a real pass, zeroes it unless it comes from the pre-zeroed pool
+int expect_raw_sums(Ctx& c, Act& a);
 // pool (optional): the Downsample that follows this block -- when the out_layers conv's plan writes the 2x2 average pool of `out` and its statistics
 // from its own epilogue (ConvPlan::pool) it does, and *pooled is set; otherwise the caller runs launch_avgpool2
 int run_resblock(Ctx& c, const float* wbuf, const ResLayer& r, Act& x0, Act* x1, const float* emb_all, int emb_stride, Act& out, Act* pool = nullptr,

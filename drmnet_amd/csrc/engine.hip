@@ -67,7 +67,13 @@ UNet::~UNet() {
     if (w) (void)hipFree(w);
 }
 
-size_t UNet::add_copy(const std::string& name, std::vector<int64_t> shape, size_t padded_count) {
+size_t ParamTable::reserve(size_t floats) {
+  const size_t at = wbuf_floats;
+  wbuf_floats += (floats + 63) & ~size_t(63);
+  return at;
+}
+
+size_t ParamTable::add_copy(const std::string& name, std::vector<int64_t> shape, size_t padded_count) {
   ParamSlot p;
   p.name = name;
   p.shape = shape;
@@ -75,13 +81,12 @@ size_t UNet::add_copy(const std::string& name, std::vector<int64_t> shape, size_
   size_t cnt = 1;
   for (auto v : shape) cnt *= (size_t)v;
   p.count = cnt;
-  p.dst = wbuf_floats;
-  wbuf_floats += (std::max(cnt, padded_count) + 63) & ~size_t(63);
+  p.dst = reserve(std::max(cnt, padded_count));
   params.push_back(p);
   return p.dst;
 }
 
-size_t UNet::add_conv(const std::string& name, int cout, int cin, int k, int coutp, int cinp, bool conv1d, size_t* scale_off, bool mx_site) {
+size_t ParamTable::add_conv(const std::string& name, int cout, int cin, int k, int coutp, int cinp, bool conv1d, size_t* scale_off, bool mx_site) {
   ParamSlot p;
   p.name = name;
   if (conv1d) p.shape = {cout, cin, k};
@@ -89,16 +94,14 @@ size_t UNet::add_conv(const std::string& name, int cout, int cin, int k, int cou
   p.kind = PK_CONV;
   p.cout = cout; p.cin = cin; p.taps = conv1d ? k : k * k; p.coutp = coutp; p.cinp = cinp;
   p.mx_site = mx_site;
-  p.dst = wbuf_floats;
-  wbuf_floats += (packed_conv_weight_floats(p.taps, coutp, cinp) + 63) & ~size_t(63);
-  p.scale_dst = wbuf_floats;
-  wbuf_floats += 64;
+  p.dst = reserve(packed_conv_weight_floats(p.taps, coutp, cinp));
+  p.scale_dst = reserve(64);
   if (scale_off) *scale_off = p.scale_dst;
   params.push_back(p);
   return p.dst;
 }
 
-void UNet::add_res(Layer& l, const std::string& px, int cin, int cout, int up_c0) {
+void ParamTable::add_res(Layer& l, const std::string& px, int cin, int cout, int up_c0) {
   l.kind = Layer::RES;
   ResLayer& r = l.res;
   r.cin = cin; r.cout = cout; r.has_skip = (cin != cout);
@@ -107,21 +110,16 @@ void UNet::add_res(Layer& l, const std::string& px, int cin, int cout, int up_c0
   r.c1_w = add_conv(px + ".in_layers.2.weight", cout, cin, 3, cout, cin, false, &r.c1_s, true);
   if (upconv_split_packable(up_c0, cin - up_c0, cout)) {  // (same tensor, two more images: the parameter table does not change)
     ParamSlot& p = params.back();
-    auto take = [&](size_t n) {
-      const size_t at = wbuf_floats;
-      wbuf_floats += (n + 63) & ~size_t(63);
-      return at;
-    };
     p.up_c0 = r.up_c0 = up_c0;
-    p.upa_dst = r.c1a_w = take(packed_conv_weight_floats(4, 4 * cout, up_c0));
-    p.upa_scale = r.c1a_s = take(64);
-    p.upb_dst = r.c1b_w = take(packed_conv_weight_floats(9, cout, cin - up_c0));
-    p.upb_scale = r.c1b_s = take(64);
+    p.upa_dst = r.c1a_w = reserve(packed_conv_weight_floats(4, 4 * cout, up_c0));
+    p.upa_scale = r.c1a_s = reserve(64);
+    p.upb_dst = r.c1b_w = reserve(packed_conv_weight_floats(9, cout, cin - up_c0));
+    p.upb_scale = r.c1b_s = reserve(64);
   }
   r.c1_b = add_copy(px + ".in_layers.2.bias", {cout});
   r.emb_off = emb_total;
   emb_total += cout;
-  // emb_layers.1.{weight,bias}: destinations are fixed up once emb_total is known (fused [sum Cout][emb_dim] matrix)
+  // emb_layers.1.{weight,bias}: destinations are fixed up by finish(), once emb_total is known (fused [sum Cout][emb_dim] matrix)
   ParamSlot ew; ew.name = px + ".emb_layers.1.weight"; ew.shape = {cout, emb_dim}; ew.kind = PK_COPY; ew.count = (size_t)cout * emb_dim; ew.dst = (size_t)-1; ew.cout = r.emb_off;
   params.push_back(ew);
   ParamSlot eb; eb.name = px + ".emb_layers.1.bias"; eb.shape = {cout}; eb.kind = PK_COPY; eb.count = (size_t)cout; eb.dst = (size_t)-2; eb.cout = r.emb_off;
@@ -136,13 +134,13 @@ void UNet::add_res(Layer& l, const std::string& px, int cin, int cout, int up_c0
   }
 }
 
-void UNet::add_attn(Layer& l, const std::string& px, int ch) {
+void ParamTable::add_attn(Layer& l, const std::string& px, int ch) {
   l.kind = Layer::ATTN;
   AttnLayer& a = l.attn;
   a.ch = ch;
   a.n_w = add_copy(px + ".norm.weight", {ch});
   a.n_b = add_copy(px + ".norm.bias", {ch});
-  // proj_out is folded into the v rows of qkv when a parameter set is loaded (load(): launch_fold_attn_params over these four tensors); the
+  // proj_out is folded into the v rows of qkv when a parameter set is packed (pack(): launch_fold_attn_params over these four tensors); the
   // manifest keeps all of them, the packed buffer only the folded qkv
   a.qkv_w = add_conv(px + ".qkv.weight", 3 * ch, ch, 1, 3 * ch, ch, true, &a.qkv_s);
   params.back().attn_fold = true;
@@ -251,58 +249,47 @@ int UNet::build(const drm_unet_desc& d) {
     oc_w = add_copy("out.3.weight", {d.out_channels, ch, 1, 1});
     oc_b = add_copy("out.3.bias", {d.out_channels});
   }
-  scratch_off = wbuf_floats;
-  wbuf_floats += 64;
-  if (stem_direct_applicable(d.in_channels, mc)) {
-    stem_direct_w = (long long)wbuf_floats;
-    wbuf_floats += (stem_weight_floats() + 63) & ~size_t(63);
-  }
+  if (stem_direct_applicable(d.in_channels, mc)) stem_direct_w = (long long)reserve(stem_weight_floats());
+  finish();
+  return DRM_OK;
+}
+
+void ParamTable::finish() {
+  scratch_off = reserve(64);
   // fused embedding projection
-  embcat_w = wbuf_floats;
-  wbuf_floats += ((size_t)emb_total * emb_dim + 63) & ~size_t(63);
-  embcat_b = wbuf_floats;
-  wbuf_floats += ((size_t)emb_total + 63) & ~size_t(63);
+  embcat_w = reserve((size_t)emb_total * emb_dim);
+  embcat_b = reserve((size_t)emb_total);
   for (auto& p : params) {
     if (p.dst == (size_t)-1) p.dst = embcat_w + (size_t)p.cout * emb_dim;
     else if (p.dst == (size_t)-2) p.dst = embcat_b + (size_t)p.cout;
   }
-  return DRM_OK;
 }
 
-int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
-  DRM_REQUIRE(set >= 0 && set < NSETS, "weight set index");
+int pack_conv_image(int precision, const float* w, float* packed, float* scale, unsigned* scratch, int Cout, int Cin, int taps, int CoutP, int CinP,
+                    bool mx_site, hipStream_t s) {
+  if (conv_split_weights(precision, CinP))
+    return launch_pack_conv_weight_split(w, packed, scale, scratch, Cout, Cin, taps, CoutP, CinP, s, precision == PREC_F16MX && mx_site,
+                                         precision == PREC_BF16);
+  return launch_pack_conv_weight(w, packed, Cout, Cin, taps, CoutP, CinP, s);
+}
+
+// the widest of: the folded attention parameters ([3C][C] weight + [3C] bias), the two raw weight tensors an upsampled-input in_layers conv is
+// split into (launch_fold_upconv_weight)
+size_t ParamTable::staging_floats() const {
+  size_t n = 0;
+  for (const ParamSlot& p : params) {
+    if (p.attn_fold) n = std::max(n, (size_t)p.cout * p.cin + (size_t)p.cout);
+    if (p.up_c0) n = std::max(n, (size_t)16 * p.cout * p.up_c0 + (size_t)9 * p.cout * (p.cin - p.up_c0));
+  }
+  return n;
+}
+
+int ParamTable::pack(const float* const* ptrs, int count, float* wbuf, int precision, float* staging, hipStream_t s) const {
   DRM_REQUIRE(count == (int)params.size(), "parameter count mismatch: got " + std::to_string(count) + ", expected " + std::to_string(params.size()));
-  if (!wsets[set]) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&wsets[set]), wbuf_floats * sizeof(float)));
-  float* wbuf = wsets[set];
-  loaded[set] = false;
   DRM_HIP_CHECK(hipMemsetAsync(wbuf, 0, wbuf_floats * sizeof(float), s));
-  // staging for the folded attention parameters ([3C][C] weight + [3C] bias of the widest block): reused block after block in stream order,
-  // freed when the last pack has run
-  struct Staging {
-    float* p = nullptr;
-    hipStream_t s;
-    ~Staging() {
-      if (p) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(p);
-      }
-    }
-  } fold{nullptr, s};
-  size_t fold_floats = 0;
-  for (const ParamSlot& p : params)
-    if (p.attn_fold) fold_floats = std::max(fold_floats, (size_t)p.cout * p.cin + (size_t)p.cout);
-  if (fold_floats) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fold.p), fold_floats * sizeof(float)));
-  // ... and for the two raw weight tensors an upsampled-input in_layers conv is split into (launch_fold_upconv_weight)
-  Staging upw{nullptr, s};
-  size_t upw_floats = 0;
-  for (const ParamSlot& p : params)
-    if (p.up_c0) upw_floats = std::max(upw_floats, (size_t)16 * p.cout * p.up_c0 + (size_t)9 * p.cout * (p.cin - p.up_c0));
-  if (upw_floats) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&upw.p), upw_floats * sizeof(float)));
-  auto pack = [&](const float* w, size_t dst, size_t scale_dst, int cout, int cin, int taps, int coutp, int cinp, bool mx_site) -> int {
-    if (conv_split_weights(precision, cinp))
-      return launch_pack_conv_weight_split(w, wbuf + dst, wbuf + scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), cout, cin, taps, coutp, cinp,
-                                           s, precision == PREC_F16MX && mx_site, precision == PREC_BF16);
-    return launch_pack_conv_weight(w, wbuf + dst, cout, cin, taps, coutp, cinp, s);
+  auto conv = [&](const float* w, size_t dst, size_t scale_dst, int cout, int cin, int taps, int coutp, int cinp, bool mx_site) -> int {
+    return pack_conv_image(precision, w, wbuf + dst, wbuf + scale_dst, reinterpret_cast<unsigned*>(wbuf + scratch_off), cout, cin, taps, coutp, cinp,
+                           mx_site, s);
   };
   for (size_t i = 0; i < params.size(); ++i) {
     const ParamSlot& p = params[i];
@@ -311,25 +298,36 @@ int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
     const float* w = ptrs[i];
     if (p.attn_fold) {
       DRM_REQUIRE(i + 3 < params.size() && ptrs[i + 1] && ptrs[i + 2] && ptrs[i + 3], "attention block parameters of " + p.name);
-      float* fb = fold.p + (size_t)p.cout * p.cin;
-      DRM_TRY(launch_fold_attn_params(ptrs[i], ptrs[i + 1], ptrs[i + 2], ptrs[i + 3], fold.p, fb, p.cin, s));
+      float* fb = staging + (size_t)p.cout * p.cin;
+      DRM_TRY(launch_fold_attn_params(ptrs[i], ptrs[i + 1], ptrs[i + 2], ptrs[i + 3], staging, fb, p.cin, s));
       DRM_HIP_CHECK(hipMemcpyAsync(wbuf + params[i + 1].dst, fb, (size_t)p.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-      w = fold.p;
+      w = staging;
     }
     if (p.kind == PK_COPY) {
       DRM_HIP_CHECK(hipMemcpyAsync(wbuf + p.dst, w, p.count * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else {
-      DRM_TRY(pack(w, p.dst, p.scale_dst, p.cout, p.cin, p.taps, p.coutp, p.cinp, p.mx_site));
+      DRM_TRY(conv(w, p.dst, p.scale_dst, p.cout, p.cin, p.taps, p.coutp, p.cinp, p.mx_site));
       if (p.up_c0) {  // each image with its own pre-scaling: the folded taps are sums of up to four weights
         const int c0 = p.up_c0, c1 = p.cin - p.up_c0;
-        float* wa = upw.p;
-        float* wb = upw.p + (size_t)16 * p.cout * c0;
+        float* wa = staging;
+        float* wb = staging + (size_t)16 * p.cout * c0;
         DRM_TRY(launch_fold_upconv_weight(w, wa, wb, p.cout, c0, c1, s));
-        DRM_TRY(pack(wa, p.upa_dst, p.upa_scale, 4 * p.cout, c0, 4, 4 * p.cout, c0, p.mx_site));
-        DRM_TRY(pack(wb, p.upb_dst, p.upb_scale, p.cout, c1, 9, p.cout, c1, p.mx_site));
+        DRM_TRY(conv(wa, p.upa_dst, p.upa_scale, 4 * p.cout, c0, 4, 4 * p.cout, c0, p.mx_site));
+        DRM_TRY(conv(wb, p.upb_dst, p.upb_scale, p.cout, c1, 9, p.cout, c1, p.mx_site));
       }
     }
   }
+  return DRM_OK;
+}
+
+int UNet::load(const float* const* ptrs, int count, hipStream_t s, int set) {
+  DRM_REQUIRE(set >= 0 && set < NSETS, "weight set index");
+  if (!wsets[set]) DRM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&wsets[set]), wbuf_floats * sizeof(float)));
+  float* wbuf = wsets[set];
+  loaded[set] = false;
+  Scratch staging(s);  // (freed when the last pack has run)
+  if (staging_floats()) DRM_TRY(staging.reserve(staging_floats() * sizeof(float)));
+  DRM_TRY(pack(ptrs, count, wbuf, precision, static_cast<float*>(staging.p), s));
   if (stem_direct_w >= 0) DRM_TRY(launch_pack_stem_weight(ptrs[stem_param], wbuf + stem_direct_w, desc.model_channels, desc.in_channels, precision == PREC_FP32, s));
   loaded[set] = true;
   loaded_precision[set] = precision;
@@ -358,6 +356,13 @@ int ensure_moments(Ctx& c, Act& a) {
   return DRM_OK;
 }
 
+int expect_raw_sums(Ctx& c, Act& a) {
+  if (!c.dry() && !a.mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(a.mom, 0, (size_t)c.N * a.C * sizeof(double2), c.s));
+  a.mom_valid = true;
+  a.mom_sums = true;
+  return DRM_OK;
+}
+
 // a.ksplit of the plan and, for a split-K plan, its workspace (allocated in sizing and real passes alike): a.split_stride, the slabs at
 // a.split_ws and, for the in-launch finish, the zeroed arrival counters at a.tile_ticket -- from the pass's statistics pool, else zeroed here
 static void splitk_workspace(Ctx& c, ConvArgs& a, const ConvPlan& p) {
@@ -377,10 +382,8 @@ int run_conv(Ctx& c, ConvArgs& a, const ConvPlan& p, const float* Wb, size_t sca
     a.w_inv_scale = c.split() ? Wb + scale_off + 1 : nullptr;  // (fp32 weights are packed unscaled)
     a.terms = p.terms;
     if (stats_for && !a.out_nchw) {  // (the pipeline accumulates the output's statistics in its epilogue)
-      if (!stats_for->mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(stats_for->mom, 0, (size_t)c.N * stats_for->C * sizeof(double2), c.s));
+      DRM_TRY(expect_raw_sums(c, *stats_for));
       a.stat_out = stats_for->mom;
-      stats_for->mom_valid = true;
-      stats_for->mom_sums = true;
     }
   }
   return launch_conv(a, p, c.s);
@@ -398,9 +401,8 @@ int raw_input_guard(Ctx& c, ConvArgs& a, const ConvPlan& p, Act* x0, int lo0, in
   if (x0) DRM_TRY(ensure_moments(c, *x0));
   if (x1) DRM_TRY(ensure_moments(c, *x1));
   if (c.dry()) return DRM_OK;
-  auto cnt = [](const Act& t) { return t.mom_sums ? 0.0 : (double)(t.H >> t.up) * (t.W >> t.up); };
-  DRM_TRY(launch_act_pow2_scale(x0 ? x0->mom : nullptr, x0 ? x0->C : 0, lo0, hi0, x0 ? cnt(*x0) : 0.0, x1 ? x1->mom : nullptr, x1 ? x1->C : 0,
-                                x1 ? cnt(*x1) : 0.0, absmax_bits, Ctab, c.N, sc, sh, inv, c.s, absmax_parts));
+  DRM_TRY(launch_act_pow2_scale(x0 ? x0->mom : nullptr, x0 ? x0->C : 0, lo0, hi0, x0 ? x0->mom_cnt() : 0.0, x1 ? x1->mom : nullptr, x1 ? x1->C : 0,
+                                x1 ? x1->mom_cnt() : 0.0, absmax_bits, Ctab, c.N, sc, sh, inv, c.s, absmax_parts));
   a.gn_scale = sc;
   a.gn_shift = sh;
   a.in_inv = inv;
@@ -423,18 +425,16 @@ int gn_params(Ctx& c, Act& x0, Act* x1, const float* gamma, const float* beta, f
     guard_for->in_inv = gi;
   }
   if (c.dry()) return DRM_OK;
-  auto inv = [](const Act& a) { return a.mom_sums ? 1.0 / ((double)(a.H >> a.up) * (a.W >> a.up)) : 1.0; };
-  auto cnt = [](const Act& t) { return t.mom_sums ? 0.0 : (double)(t.H >> t.up) * (t.W >> t.up); };
   if (fold_into) {
     GnFold& f = fold_into->gnf;
-    f.mom0 = x0.mom; f.C0 = x0.C; f.inv0 = inv(x0); f.cnt0 = cnt(x0);
-    f.mom1 = x1 ? x1->mom : nullptr; f.C1 = x1 ? x1->C : 0; f.inv1 = x1 ? inv(*x1) : 1.0; f.cnt1 = x1 ? cnt(*x1) : 0.0;
+    f.mom0 = x0.mom; f.C0 = x0.C; f.inv0 = x0.mom_inv(); f.cnt0 = x0.mom_cnt();
+    f.mom1 = x1 ? x1->mom : nullptr; f.C1 = x1 ? x1->C : 0; f.inv1 = x1 ? x1->mom_inv() : 1.0; f.cnt1 = x1 ? x1->mom_cnt() : 0.0;
     f.gamma = gamma; f.beta = beta; f.scale = scale; f.shift = shift;
     f.guard_scale = gs; f.guard_shift = gh; f.guard_inv = gi;
     return DRM_OK;
   }
-  return launch_gn_finalize(x0.mom, x0.C, inv(x0), x1 ? x1->mom : nullptr, x1 ? x1->C : 0, x1 ? inv(*x1) : 1.0, gamma, beta, c.N, scale, shift, c.s,
-                            cnt(x0), x1 ? cnt(*x1) : 0.0, gs, gh, gi);
+  return launch_gn_finalize(x0.mom, x0.C, x0.mom_inv(), x1 ? x1->mom : nullptr, x1 ? x1->C : 0, x1 ? x1->mom_inv() : 1.0, gamma, beta, c.N, scale,
+                            shift, c.s, x0.mom_cnt(), x1 ? x1->mom_cnt() : 0.0, gs, gh, gi);
 }
 
 // a real pass whose arena ran out hands out null tables: stop before any kernel is launched on them
@@ -533,10 +533,7 @@ int run_resblock(Ctx& c, const float* Wb, const ResLayer& r, Act& x0, Act* x1, c
   DRM_TRY(gn_params(c, h1, nullptr, Wb + r.n2_w, Wb + r.n2_b, sc2, sh2, nullptr, pb.gn_fold ? &b : nullptr));
   splitk_workspace(c, b, pb);
   if (pooled) *pooled = pb.pool;
-  if (pb.pool) {
-    pool->mom_valid = true;
-    pool->mom_sums = true;
-  }
+  if (pb.pool) DRM_TRY(expect_raw_sums(c, *pool));
   if (r.has_skip) splitk_workspace(c, k, pk);
   if (!c.dry()) {
     const float* res = x0.p;
@@ -551,7 +548,6 @@ int run_resblock(Ctx& c, const float* Wb, const ResLayer& r, Act& x0, Act* x1, c
     b.w = Wb + r.c2_w; b.bias = Wb + r.c2_b;
     b.res = res; b.out = out.p;
     if (pb.pool) {
-      if (!pool->mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(pool->mom, 0, (size_t)c.N * pool->C * sizeof(double2), c.s));
       b.pool_out = pool->p;
       b.pool_stat = pool->mom;
     }
@@ -602,12 +598,13 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
       (void)c.ar->alloc<float>((size_t)c.N * T * C * pp.ksplit);
     }
   }
+  // (the attention core's last kernel accumulates them; zeroed ahead of the qkv conv: `out` is never `x`, and nothing before that kernel touches out.mom)
+  if (!flash) DRM_TRY(expect_raw_sums(c, out));
   if (!c.dry()) {
     a.src0 = x.p;
     a.gn_scale = sc; a.gn_shift = sh; a.silu = 0;
     a.w = Wb + l.qkv_w; a.bias = Wb + l.qkv_b; a.out = qkv;
     DRM_TRY(run_conv(c, a, pa, Wb, l.qkv_s, &qkv_act));
-    if (!flash && !out.mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(out.mom, 0, (size_t)c.N * C * sizeof(double2), c.s));
     if (flash) DRM_TRY(launch_attention_flash(qkv, qkv_act.mom, x.p, out.p, aws, c.N, T, C, c.terms(), c.s));
     else if (on_conv) DRM_TRY(launch_attention_conv(qkv, qkv_act.mom, x.p, scores, out.p, out.mom, aws, c.N, H, W, C, c.precision, c.s));
     else DRM_TRY(launch_attention(qkv, x.p, scores, out.p, out.mom, c.N, T, C, c.s, c.split() ? c.terms() : 0, small_guard ? qkv_act.mom : nullptr, aws));
@@ -617,9 +614,6 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
                 //  place of the block's temporaries, which are dead in stream order)
     out.mom_valid = false;
     DRM_TRY(ensure_moments(c, out));
-  } else {
-    out.mom_valid = true;
-    out.mom_sums = true;
   }
   return DRM_OK;
 }
@@ -709,12 +703,8 @@ int UNet::forward(const float* x, int Cx, const float* cond, int Cc, const int32
   Act* h = make(mc, H, W);
   if (stem_direct) {
     // stem conv on the NCHW boundary tensors (cat, row gather, exact fp32 products and the output's GroupNorm sums in one launch: stemhead.hip)
-    if (!c.dry()) {
-      if (!h->mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(h->mom, 0, (size_t)N * mc * sizeof(double2), s));
-      DRM_TRY(launch_stem_conv(x, Cx, cond, Cc, rows, Wb + stem_direct_w, Wb + stem_b, h->p, h->mom, N, H, W, mc, precision == PREC_FP32, s));
-    }
-    h->mom_valid = true;
-    h->mom_sums = true;
+    DRM_TRY(expect_raw_sums(c, *h));
+    if (!c.dry()) DRM_TRY(launch_stem_conv(x, Cx, cond, Cc, rows, Wb + stem_direct_w, Wb + stem_b, h->p, h->mom, N, H, W, mc, precision == PREC_FP32, s));
   } else {
     ConvArgs a;  // stem conv: raw network input
     a.C0 = in_cp; a.N = N; a.H = H; a.W = W; a.taps = 9; a.Cout = mc;
@@ -757,10 +747,8 @@ int UNet::forward(const float* x, int Cx, const float* cond, int Cc, const int32
           continue;
         }
         if (!c.dry()) {
-          if (!o->mom_zeroed) DRM_HIP_CHECK(hipMemsetAsync(o->mom, 0, (size_t)N * o->C * sizeof(double2), s));
+          DRM_TRY(expect_raw_sums(c, *o));
           DRM_TRY(launch_avgpool2(h->p, o->p, N, h->H, h->W, h->C, s, o->mom));  // pooled tensor + its GroupNorm sums in one pass
-          o->mom_valid = true;
-          o->mom_sums = true;
         }
         h = o;
       } else {  // UP: nearest x2, folded into the consumer (moments are unchanged by replication)
