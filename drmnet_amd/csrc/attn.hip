@@ -681,16 +681,10 @@ static int launch_softmax_rows(float* S, long long rows, int T, hipStream_t s) {
 #ifndef DRM_ATTN_GROUP_MIB
 #define DRM_ATTN_GROUP_MIB 1024
 #endif
-int attention_group(int N, int T) {
+static int attention_group(int N, int T) {
   const size_t per_image = (size_t)T * T * sizeof(float);
   const size_t g = ((size_t)DRM_ATTN_GROUP_MIB << 20) / (per_image ? per_image : 1);
   return (int)std::max<size_t>(1, std::min<size_t>(g, (size_t)N));
-}
-size_t attention_scores_floats(int N, int T) { return (size_t)attention_group(N, T) * T * T; }
-
-size_t attention_conv_workspace_floats(int N, int T, int C) {
-  const size_t Z = (size_t)(C > T ? C : T);
-  return 2 * (size_t)N * T * C + (size_t)N * (C + T + Z) + 6 * (size_t)N + 64;
 }
 // S = alpha q k^T (cin = C, cout = T) and O = P v (cin = T, cout = C) of nb images: 1x1 convs with per-image weights (k, v^T)
 static ConvArgs attention_gemm(int nb, int H, int W, int cin, int cout) {
@@ -699,142 +693,159 @@ static ConvArgs attention_gemm(int nb, int H, int W, int cin, int cout) {
   a.w_img_stride_f4 = (long long)cin * cout / 4; a.prof_kind = PROF_KINDS;  // (inside the core's profiler scope)
   return a;
 }
-bool attention_conv_planned(int H, int W, int C, int precision) {
-  return plan_conv(attention_gemm(1, H, W, C, H * W), precision).kernel == CONV_PIPELINE &&
-         plan_conv(attention_gemm(1, H, W, H * W, C), precision).kernel == CONV_PIPELINE;
+
+// The one walk over a core's workspace: the pointers for `ws`, and in *end the floats it spans -- plan_attention sizes the workspace by the same walk
+// (null ws), so a size and its carve cannot disagree.
+static AttnTables attention_tables(const AttnPlan& p, float* ws, size_t* end = nullptr) {
+  AttnTables t;
+  const size_t N = (size_t)p.N, T = (size_t)p.H * p.W, C = (size_t)p.C, Z = C > T ? C : T;
+  const bool flash = p.form == ATTN_FLASH, conv = p.form == ATTN_CONV;
+  size_t at = 0;
+  auto take = [&](bool have, size_t n) { float* r = have && ws ? ws + at : nullptr; at += have ? n : 0; return r; };
+  if (flash || conv || p.guard) {
+    t.wq = take(flash, N * T * C);
+    t.wk = take(flash || conv, N * T * C);
+    t.wv = take(flash || conv, N * T * C);
+    t.q_tab = take(true, N * C);
+    t.p_tab = take(true, N * T);
+    t.zero_tab = take(true, N * Z);
+    t.qk_inv = take(true, N); t.k_scale = take(true, N); t.k_inv = take(true, N);
+    t.pv_inv = take(true, N); t.v_scale = take(true, N); t.v_inv = take(true, N);
+    t.q_scale = take(!conv, N);  // (the conv pipeline reads q's factor from q_tab)
+    at += 64;
+  }
+  if (end) *end = at;
+  return t;
 }
 
-// (for attn_flash.hip: the per-image factor tables and the row-major pre-split image of q / k)
-void launch_attn_scales(const double2* mom, int N, int C, int T, float alpha, float* q_tab, float* p_tab, float* zero_tab, float* qk_inv, float* k_scale,
-                        float* k_inv, float* pv_inv, float* v_scale, float* v_inv, float* q_scale, hipStream_t s) {
-  hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, mom, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale, v_inv,
-                     q_scale);
+AttnPlan plan_attention(int N, int H, int W, int C, int precision) {
+  AttnPlan p;
+  const int T = H * W;
+  p.N = N; p.H = H; p.W = W; p.C = C;
+  p.terms = precision_terms(precision);
+  p.group = attention_group(N, T);
+  if (attention_flash_applicable(T, C, p.terms)) {
+    p.form = ATTN_FLASH;
+    p.out_stats = false;
+  } else {
+    // the T >= 256 levels: both GEMMs on the conv pipeline (which kernel takes them does not depend on the image count) -- except on sparse launches
+    // (the 16x16 level of a batch-1 step: six launches, 51 us, where the short-sequence form -- qk_small, softmax, P v -- takes three and ~25 us)
+    const ConvPlan qk = plan_conv(attention_gemm(p.group, H, W, C, T), precision), pv = plan_conv(attention_gemm(p.group, H, W, T, C), precision);
+    if (qk.kernel == CONV_PIPELINE && pv.kernel == CONV_PIPELINE && (long long)N * T > 1024) {
+      p.form = ATTN_CONV;
+      p.qk[0] = qk; p.pv[0] = pv;
+      if (N % p.group) {  // (the tile of a launch depends on its image count)
+        p.qk[1] = plan_conv(attention_gemm(N % p.group, H, W, C, T), precision);
+        p.pv[1] = plan_conv(attention_gemm(N % p.group, H, W, T, C), precision);
+      }
+    } else {
+      // S = q k^T needs whole 32-chunks of C only (rows beyond T are masked); P v needs them of T: the 4x4 level (T = 16) of a 128x128 input keeps
+      // the exact-fp32 form for P v and takes the split form for S like every other level
+      p.split_qk = p.guard = p.terms != 0 && C % 32 == 0;
+      p.split_pv = p.split_qk && T % 32 == 0;
+    }
+    p.scores_floats = (size_t)p.group * T * T;
+  }
+  attention_tables(p, nullptr, &p.ws_floats);
+  return p;
 }
-int launch_pack_attn_rows(const float* src, long long img_stride, int ld, const float* scale, float* dst, int rows, int cin, int N, hipStream_t s, bool bf16) {
-  const unsigned pb = (unsigned)std::min<size_t>(((size_t)rows * cin / 8 + 255) / 256, 4096);
-  hipLaunchKernelGGL(pack_attn_weight_kernel<true>, dim3(pb, N), dim3(256), 0, s, src, img_stride, ld, scale, reinterpret_cast<float4*>(dst), rows, cin, bf16 ? 1 : 0);
+
+// q or k (ROWS: [T][C] as they lie in qkv) or v^T of every image, times its power of two -> the pre-split weight image of the conv pipeline
+template <bool ROWS>
+static int pack_attn_weight(const AttnPlan& p, const float* src, const float* scale, float* dst, hipStream_t s) {
+  const int T = p.H * p.W, C = p.C;
+  const unsigned pb = (unsigned)std::min<size_t>(((size_t)T * C / 8 + 255) / 256, 4096);
+  hipLaunchKernelGGL(pack_attn_weight_kernel<ROWS>, dim3(pb, p.N), dim3(256), 0, s, src, (long long)T * 3 * C, 3 * C, scale, reinterpret_cast<float4*>(dst),
+                     ROWS ? T : C, ROWS ? C : T, p.terms == 4 ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
 
-// qkv [N][T][3C] (+ its fused per-channel statistics), x [N][T][C], scores workspace [N][T][T], out = x + P v [N][T][C], out_stat [N][C] (zeroed),
-// ws: attention_conv_workspace_floats.  The residual add and the output statistics are the P v launch's own epilogue (ConvArgs::res / stat_out).
-int launch_attention_conv(const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat, float* ws, int N, int H,
-                          int W, int C, int precision, hipStream_t s) {
-  const int T = H * W;
-  DRM_REQUIRE(attention_conv_planned(H, W, C, precision) && qkv_mom && x && out_stat, "attention on the conv pipeline: shape");
+// Conv-pipeline form.  The residual add and the output statistics are the P v launch's own epilogue (ConvArgs::res / stat_out).
+static int attention_conv(const AttnPlan& p, const AttnTables& t, const float* qkv, const float* x, float* scores, float* out, double2* out_stat,
+                          hipStream_t s) {
+  const int N = p.N, H = p.H, W = p.W, T = H * W, C = p.C;
   const size_t Z = (size_t)(C > T ? C : T);
-  float* wk = ws;                           // [N] packed k:   Cout = T, Cin = C
-  float* wv = wk + (size_t)N * T * C;       // [N] packed v^T: Cout = C, Cin = T
-  float* q_tab = wv + (size_t)N * T * C;    // [N][C]
-  float* p_tab = q_tab + (size_t)N * C;     // [N][T]
-  float* zero_tab = p_tab + (size_t)N * T;  // [N][max(C, T)]
-  float* vec = zero_tab + (size_t)N * Z;    // 6 x [N]
-  float *qk_inv = vec, *k_scale = vec + N, *k_inv = vec + 2 * N, *pv_inv = vec + 3 * N, *v_scale = vec + 4 * N, *v_inv = vec + 5 * N;
-  const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
-  prof_tag(N, T, 1, C, C);
-  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C + 4.0 * T * T), s);  // one scope for the whole core (q, k, v, x in, out)
-  hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, qkv_mom, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv,
-                     v_scale, v_inv, nullptr);
-  DRM_HIP_CHECK(hipGetLastError());
-  const unsigned pb = (unsigned)std::min<size_t>(((size_t)T * C / 8 + 255) / 256, 4096);
-  hipLaunchKernelGGL(pack_attn_weight_kernel<true>, dim3(pb, N), dim3(256), 0, s, qkv + C, (long long)T * 3 * C, 3 * C, k_scale,
-                     reinterpret_cast<float4*>(wk), T, C, precision == PREC_BF16 ? 1 : 0);
-  DRM_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(pack_attn_weight_kernel<false>, dim3(pb, N), dim3(256), 0, s, qkv + 2 * C, (long long)T * 3 * C, 3 * C, v_scale,
-                     reinterpret_cast<float4*>(wv), C, T, precision == PREC_BF16 ? 1 : 0);
-  DRM_HIP_CHECK(hipGetLastError());
-  const int NB = attention_group(N, T);
-  for (int n0 = 0; n0 < N; n0 += NB) {  // one pass per image group (scores = the group's [nb, T, T] buffer)
-    const int nb = std::min(NB, N - n0);
+  DRM_TRY(pack_attn_weight<false>(p, qkv + 2 * C, t.v_scale, t.wv, s));  // v^T: Cout = C, Cin = T
+  for (int n0 = 0; n0 < N; n0 += p.group) {  // one pass per image group (scores = the group's [nb, T, T] buffer)
+    const int nb = std::min(p.group, N - n0), g = nb != p.group;
     ConvArgs a = attention_gemm(nb, H, W, C, T);  // S = alpha q k^T
     a.src0 = qkv + (size_t)n0 * T * 3 * C; a.ld0 = 3 * C;
-    a.gn_scale = q_tab + (size_t)n0 * C; a.gn_shift = zero_tab + (size_t)n0 * Z;
-    a.w = wk + (size_t)n0 * T * C; a.w_inv_img = k_inv + n0; a.in_inv = qk_inv + n0; a.out = scores;
-    const ConvPlan qk_plan = plan_conv(a, precision);
-    a.terms = qk_plan.terms;
-    DRM_TRY(launch_conv(a, qk_plan, s));
+    a.gn_scale = t.q_tab + (size_t)n0 * C; a.gn_shift = t.zero_tab + (size_t)n0 * Z;
+    a.w = t.wk + (size_t)n0 * T * C; a.w_inv_img = t.k_inv + n0; a.in_inv = t.qk_inv + n0; a.out = scores;
+    a.terms = p.qk[g].terms;
+    DRM_TRY(launch_conv(a, p.qk[g], s));
     DRM_TRY(launch_softmax_rows(scores, (long long)nb * T, T, s));
     ConvArgs b = attention_gemm(nb, H, W, T, C);  // out = x + P v, and its statistics
     b.res = x + (size_t)n0 * T * C; b.stat_out = out_stat + (size_t)n0 * C;
     b.src0 = scores;
-    b.gn_scale = p_tab + (size_t)n0 * T; b.gn_shift = zero_tab + (size_t)n0 * Z;
-    b.w = wv + (size_t)n0 * T * C; b.w_inv_img = v_inv + n0; b.in_inv = pv_inv + n0; b.out = out + (size_t)n0 * T * C;
-    const ConvPlan pv_plan = plan_conv(b, precision);
-    b.terms = pv_plan.terms;
-    DRM_TRY(launch_conv(b, pv_plan, s));
+    b.gn_scale = t.p_tab + (size_t)n0 * T; b.gn_shift = t.zero_tab + (size_t)n0 * Z;
+    b.w = t.wv + (size_t)n0 * T * C; b.w_inv_img = t.v_inv + n0; b.in_inv = t.pv_inv + n0; b.out = out + (size_t)n0 * T * C;
+    b.terms = p.pv[g].terms;
+    DRM_TRY(launch_conv(b, p.pv[g], s));
   }
   return DRM_OK;
 }
 
-size_t attention_small_workspace_floats(int N, int T, int C) {
-  const size_t Z = (size_t)(C > T ? C : T);
-  return (size_t)N * (C + T + Z) + 7 * (size_t)N + 64;
-}
+static auto qk_small_for(int terms) { return terms == 4 ? qk_small_kernel<4> : terms == 1 ? qk_small_kernel<1> : qk_small_kernel<3>; }
+static auto pv_small_for(int terms) { return terms == 4 ? pv_small_kernel<4> : terms == 1 ? pv_small_kernel<1> : pv_small_kernel<3>; }
 
 // Short-sequence form (T <= 256 off the conv pipeline, and every level of a sparse launch): S by qk_small_kernel, row softmax, P v by the 64x64-tile
-// GEMM.  qkv_mom + ws (attention_small_workspace_floats): the split modes stage q, k and v through their per-image powers of two (attn_scales_kernel --
-// the same range guard as the conv-pipeline form: |v| or |q| beyond fp16's range is exact).  The P v kernel of either form adds x and accumulates
-// out_stat (zeroed by the caller).
-int launch_attention(const float* qkv, const float* x, float* scores, float* out, double2* out_stat, int N, int T, int C, hipStream_t s, int terms,
-                     const double2* qkv_mom, float* ws) {
-  bool split = terms != 0;
-  DRM_REQUIRE(C % 4 == 0 && T > 0 && N > 0 && x && out_stat, "attention shape");
-  const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
-  const int tb = (T + 63) / 64;
-  prof_tag(N, T, 1, C, C);
-  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C + 4.0 * T * T), s);
-  // S = q k^T needs whole 32-chunks of C only (rows beyond T are masked); P v needs them of T: the 4x4 level (T = 16) of a 128x128 input keeps
-  // the exact-fp32 form for P v and takes the split form for S like every other level
-  const bool split_qk = split && (C % 32 == 0);
-  split = split_qk && (T % 32 == 0);
-  const bool guard = split_qk && qkv_mom && ws;
-  float *q_scale = nullptr, *k_scale = nullptr, *qk_inv = nullptr, *k_inv = nullptr, *v_scale = nullptr, *v_inv = nullptr;
-  if (guard) {
-    const size_t Z = (size_t)(C > T ? C : T);
-    float* q_tab = ws;                        // [N][C]
-    float* p_tab = q_tab + (size_t)N * C;     // [N][T]
-    float* zero_tab = p_tab + (size_t)N * T;  // [N][max(C, T)]
-    float* vec = zero_tab + (size_t)N * Z;    // 7 x [N]
-    qk_inv = vec; k_scale = vec + N; k_inv = vec + 2 * N; float* pv_inv = vec + 3 * N; v_scale = vec + 4 * N; v_inv = vec + 5 * N; q_scale = vec + 6 * N;
-    hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, qkv_mom, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale,
-                       v_inv, q_scale);
-    DRM_HIP_CHECK(hipGetLastError());
-  }
-  const int NB = attention_group(N, T), t32 = (T + 31) / 32;
+// GEMM.  Guarded (the split modes): q, k and v are staged through their per-image powers of two -- the same range guard as the conv-pipeline form:
+// |v| or |q| beyond fp16's range is exact.  The P v kernel of either form adds x and accumulates out_stat.
+static int attention_small(const AttnPlan& p, const AttnTables& t, const float* qkv, const float* x, float* scores, float* out, double2* out_stat,
+                           float alpha, hipStream_t s) {
+  const int N = p.N, T = p.H * p.W, C = p.C;
+  const int tb = (T + 63) / 64, t32 = (T + 31) / 32;
   const long long sq = (long long)T * 3 * C;  // image stride of qkv
-  auto at = [&](float* p, int n0) { return p ? p + n0 : nullptr; };
-  for (int n0 = 0; n0 < N; n0 += NB) {
-    const int nb = std::min(NB, N - n0);
+  const float pscale = p.terms == 4 ? 1.0f : 4096.0f;  // fp16: probabilities are scaled by 2^12 before the conversion (largest 4096, smallest normal 2^-26)
+  auto at = [&](float* q, int n0) { return q ? q + n0 : nullptr; };
+  for (int n0 = 0; n0 < N; n0 += p.group) {
+    const int nb = std::min(p.group, N - n0);
     const float* qg = qkv + (size_t)n0 * sq;
     float* og = out + (size_t)n0 * T * C;
     const float* xg = x + (size_t)n0 * T * C;
     double2* sg = out_stat + (size_t)n0 * C;
-    if (split_qk && terms == 4)
-      hipLaunchKernelGGL(qk_small_kernel<4>, dim3(t32, t32, nb), dim3(256), 0, s, qg, qg + C, scores, T, C, 3 * C, sq, (long long)T * T, alpha, at(q_scale, n0), at(k_scale, n0), at(qk_inv, n0), at(k_inv, n0));
-    else if (split_qk && terms == 1)
-      hipLaunchKernelGGL(qk_small_kernel<1>, dim3(t32, t32, nb), dim3(256), 0, s, qg, qg + C, scores, T, C, 3 * C, sq, (long long)T * T, alpha, at(q_scale, n0), at(k_scale, n0), at(qk_inv, n0), at(k_inv, n0));
-    else if (split_qk)
-      hipLaunchKernelGGL(qk_small_kernel<3>, dim3(t32, t32, nb), dim3(256), 0, s, qg, qg + C, scores, T, C, 3 * C, sq, (long long)T * T, alpha, at(q_scale, n0), at(k_scale, n0), at(qk_inv, n0), at(k_inv, n0));
+    if (p.split_qk)
+      hipLaunchKernelGGL(qk_small_for(p.terms), dim3(t32, t32, nb), dim3(256), 0, s, qg, qg + C, scores, T, C, 3 * C, sq, (long long)T * T, alpha,
+                         at(t.q_scale, n0), at(t.k_scale, n0), at(t.qk_inv, n0), at(t.k_inv, n0));
     else
       hipLaunchKernelGGL(bgemm64_kernel<true>, dim3(tb, tb, nb), dim3(256), 0, s, qg, qg + C, scores, T, T, C, 3 * C, 3 * C, T, sq, sq, (long long)T * T, alpha);
     DRM_HIP_CHECK(hipGetLastError());
-    if (!split) DRM_TRY(launch_softmax_rows(scores, (long long)nb * T, T, s));  // (the split P v applies the row softmax while it stages the scores)
-    if (split && terms == 4)
-      hipLaunchKernelGGL(pv_small_kernel<4>, dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
-                         (long long)T * C, 1.0f, 1.0f, at(v_scale, n0), at(v_inv, n0), xg, sg);
-    else if (split && terms == 1)  // probabilities are scaled by 2^12 before the fp16 conversion (largest 4096, smallest normal 2^-26)
-      hipLaunchKernelGGL(pv_small_kernel<1>, dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
-                         (long long)T * C, 1.0f / 4096.0f, 4096.0f, at(v_scale, n0), at(v_inv, n0), xg, sg);
-    else if (split)
-      hipLaunchKernelGGL(pv_small_kernel<3>, dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
-                         (long long)T * C, 1.0f / 4096.0f, 4096.0f, at(v_scale, n0), at(v_inv, n0), xg, sg);
+    if (!p.split_pv) DRM_TRY(launch_softmax_rows(scores, (long long)nb * T, T, s));  // (the split P v applies the row softmax while it stages the scores)
+    if (p.split_pv)
+      hipLaunchKernelGGL(pv_small_for(p.terms), dim3((C + 31) / 32, t32, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, 3 * C, (long long)T * T, sq,
+                         (long long)T * C, 1.0f / pscale, pscale, at(t.v_scale, n0), at(t.v_inv, n0), xg, sg);
     else
       hipLaunchKernelGGL(bgemm64_kernel<false>, dim3((C + 63) / 64, tb, nb), dim3(256), 0, s, scores, qg + 2 * C, og, T, C, T, T, 3 * C, C,
                          (long long)T * T, sq, (long long)T * C, 1.0f, xg, sg);
     DRM_HIP_CHECK(hipGetLastError());
   }
   return DRM_OK;
+}
+
+int launch_attention_core(const AttnPlan& p, const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat,
+                          float* ws, hipStream_t s) {
+  const int N = p.N, T = p.H * p.W, C = p.C;
+  DRM_REQUIRE(C % 4 == 0 && T > 0 && N > 0 && qkv && x && out, "attention shape");
+  DRM_REQUIRE((!p.scores_floats || scores) && (!p.out_stats || out_stat) && (!p.ws_floats || (ws && qkv_mom)), "attention workspace");
+  const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
+  prof_tag(N, T, 1, C, C);
+  // one scope for the whole core; algorithmic bytes: q, k, v, x in, out, and the scores written and read twice where they leave the chip
+  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C + (p.scores_floats ? 4.0 * T * T : 0.0)), s);
+  const AttnTables t = attention_tables(p, ws);
+  if (p.ws_floats) {
+    hipLaunchKernelGGL(attn_scales_kernel, dim3(N), dim3(256), 0, s, qkv_mom, C, T, alpha, t.q_tab, t.p_tab, t.zero_tab, t.qk_inv, t.k_scale, t.k_inv,
+                       t.pv_inv, t.v_scale, t.v_inv, t.q_scale);
+    DRM_HIP_CHECK(hipGetLastError());
+  }
+  if (t.wq) DRM_TRY(pack_attn_weight<true>(p, qkv, t.q_scale, t.wq, s));
+  if (t.wk) DRM_TRY(pack_attn_weight<true>(p, qkv + C, t.k_scale, t.wk, s));  // k: Cout = T, Cin = C; v^T is packed in the order its form reads
+  switch (p.form) {
+    case ATTN_FLASH: return launch_attention_flash(p, t, qkv, x, out, s);
+    case ATTN_CONV: return attention_conv(p, t, qkv, x, scores, out, out_stat, s);
+    default: return attention_small(p, t, qkv, x, scores, out, out_stat, alpha, s);
+  }
 }
 
 }  // namespace drm

@@ -27,7 +27,6 @@
 #include <utility>
 
 #include "common.h"
-#include "profiler.h"
 
 namespace drm {
 
@@ -421,40 +420,16 @@ __global__ __launch_bounds__(256) void pack_attn_v_perm_kernel(const float* __re
 #endif
 bool attention_flash_applicable(int T, int C, int terms) { return (terms == 3 || terms == 1 || terms == 4) && C == 384 && T % FA_KT == 0 && T >= FA_MIN_T; }
 
-size_t attention_flash_workspace_floats(int N, int T, int C) {
-  const size_t Z = (size_t)(C > T ? C : T);
-  return 3 * (size_t)N * T * C + (size_t)N * (C + T + Z) + 7 * (size_t)N + 64;
-}
-
-// (attn.hip)
-void launch_attn_scales(const double2* mom, int N, int C, int T, float alpha, float* q_tab, float* p_tab, float* zero_tab, float* qk_inv, float* k_scale,
-                        float* k_inv, float* pv_inv, float* v_scale, float* v_inv, float* q_scale, hipStream_t s);
-int launch_pack_attn_rows(const float* src, long long img_stride, int ld, const float* scale, float* dst, int rows, int cin, int N, hipStream_t s, bool bf16);
-
-// qkv [N][T][3C] (+ its fused per-channel statistics), x [N][T][C], out = x + P v [N][T][C], ws: attention_flash_workspace_floats.
+// The tail of the single-kernel form (launch_attention_core, attn.hip, has written the factor tables and the row-major images of q and k): v^T in
+// the kernel's key order, then the kernel.  qkv [N][T][3C], x [N][T][C], out = x + P v [N][T][C].
 // The statistics of `out` are NOT accumulated here (the kernel runs one wave per SIMD on the whole register file, its epilogue has no LDS left
 // to reduce in): the caller takes them with the stand-alone moments launch.
-int launch_attention_flash(const float* qkv, const double2* qkv_mom, const float* x, float* out, float* ws, int N, int T, int C, int terms, hipStream_t s) {
-  DRM_REQUIRE(attention_flash_applicable(T, C, terms) && qkv_mom && x, "single-kernel attention: shape");
-  const size_t Z = (size_t)(C > T ? C : T);
-  float* wq = ws;                           // three pre-split images, T * C * 4 bytes per image each
-  float* wk = wq + (size_t)N * T * C;
-  float* wv = wk + (size_t)N * T * C;
-  float* q_tab = wv + (size_t)N * T * C;    // [N][C]   (tables of the conv-pipeline form, written by the shared scales kernel; only the [N] factors are read here)
-  float* p_tab = q_tab + (size_t)N * C;     // [N][T]
-  float* zero_tab = p_tab + (size_t)N * T;  // [N][max(C, T)]
-  float* vec = zero_tab + (size_t)N * Z;    // 7 x [N]
-  float *qk_inv = vec, *k_scale = vec + N, *k_inv = vec + 2 * N, *pv_inv = vec + 3 * N, *v_scale = vec + 4 * N, *v_inv = vec + 5 * N, *q_scale = vec + 6 * N;
-  const float alpha = 1.0f / sqrtf((float)C);  // (C^-1/4)^2, applied once to the dot product
-  prof_tag(N, T, 1, C, C);
-  ProfScope ps(PROF_ATTN, 4.0 * N * (double)T * T * C, 4.0 * N * ((double)T * 5 * C), s);  // algorithmic bytes: q, k, v, x in, out
-  launch_attn_scales(qkv_mom, N, C, T, alpha, q_tab, p_tab, zero_tab, qk_inv, k_scale, k_inv, pv_inv, v_scale, v_inv, q_scale, s);
-  DRM_HIP_CHECK(hipGetLastError());
-  const long long sq = (long long)T * 3 * C;
-  DRM_TRY(launch_pack_attn_rows(qkv, sq, 3 * C, q_scale, wq, T, C, N, s, terms == 4));
-  DRM_TRY(launch_pack_attn_rows(qkv + C, sq, 3 * C, k_scale, wk, T, C, N, s, terms == 4));
+int launch_attention_flash(const AttnPlan& p, const AttnTables& t, const float* qkv, const float* x, float* out, hipStream_t s) {
+  DRM_REQUIRE(p.form == ATTN_FLASH && t.wq && t.wk && t.wv, "single-kernel attention: plan");
+  const int N = p.N, T = p.H * p.W, C = p.C, terms = p.terms;
   const unsigned pb = (unsigned)std::min<size_t>(((size_t)T * C / 8 + 255) / 256, 4096);
-  hipLaunchKernelGGL(pack_attn_v_perm_kernel, dim3(pb, N), dim3(256), 0, s, qkv + 2 * C, sq, 3 * C, v_scale, reinterpret_cast<float4*>(wv), C, T, terms == 4 ? 1 : 0);
+  hipLaunchKernelGGL(pack_attn_v_perm_kernel, dim3(pb, N), dim3(256), 0, s, qkv + 2 * C, (long long)T * 3 * C, 3 * C, t.v_scale,
+                     reinterpret_cast<float4*>(t.wv), C, T, terms == 4 ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   const size_t lds_bytes = (size_t)FA_SLOTS * FA_SLOT_F4 * sizeof(float4);
   const DeviceInfo* di = device_info();
@@ -465,8 +440,8 @@ int launch_attention_flash(const float* qkv, const double2* qkv_mom, const float
       DRM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
       attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(N * (T / FA_QT))), dim3(256), lds_bytes, s, reinterpret_cast<const float4*>(wq), reinterpret_cast<const float4*>(wk),
-                       reinterpret_cast<const float4*>(wv), x, out, qk_inv, k_inv, v_inv, N, T);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(N * (T / FA_QT))), dim3(256), lds_bytes, s, reinterpret_cast<const float4*>(t.wq), reinterpret_cast<const float4*>(t.wk),
+                       reinterpret_cast<const float4*>(t.wv), x, out, t.qk_inv, t.k_inv, t.v_inv, N, T);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;
   };

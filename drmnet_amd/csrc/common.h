@@ -172,31 +172,47 @@ int launch_gn_finalize(const double2* mom0, int C0, double inv0, const double2* 
                        const float* beta, int N, float* scale, float* shift, hipStream_t s, double cnt0 = 0.0, double cnt1 = 0.0,
                        float* guard_scale = nullptr, float* guard_shift = nullptr, float* guard_inv = nullptr);
 
-// attention (attn.hip): qkv [N][T][3C] (v thirds = proj_out folded into v: launch_fold_attn_params), x [N][T][C] the block's input
-// -> out = x + softmax(q k^T) v [N][T][C] and out_stat [N][C] += per-channel (sum, sum of squares) of out (zeroed by the caller);
-// scores workspace [N][T][T]
 size_t refmap_workspace_bytes(long long n, int res, float thr);
 int launch_refmap_mask_make(const float* colors, const float* normals, long long n, int C, int res, float thr, int min_points, float* refmap,
                             unsigned char* refmask, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_erode_mask(const unsigned char* mask, int H, int W, int k, unsigned char* out, hipStream_t s);
-// terms: 0 = fp32 MFMA, 3 = fp16 hi/lo split, 1 = plain fp16 operands
-// qkv_mom + ws (attention_small_workspace_floats floats): per-image range guard of q, k, v in the split modes
-int launch_attention(const float* qkv, const float* x, float* scores, float* out, double2* out_stat, int N, int T, int C, hipStream_t s, int terms = 0,
-                     const double2* qkv_mom = nullptr, float* ws = nullptr);
-size_t attention_small_workspace_floats(int N, int T, int C);
-// split-precision attention core on the fused 1x1 conv pipeline (per-image weights = k, v^T): whether plan_conv takes both GEMMs
-bool attention_conv_planned(int H, int W, int C, int precision);
-// single-kernel form (attn_flash.hip): the long-sequence level (T >= 1024, C = 384), no score matrix in HBM; adds x, leaves out's statistics
-// to the caller (one wave per SIMD on the whole register file: no room for the reduction)
+// attention (attn.hip): qkv [N][T][3C] (v thirds = proj_out folded into v: launch_fold_attn_params), x [N][T][C] the block's input
+// -> out = x + softmax(q k^T) v [N][T][C] and out_stat [N][C] += per-channel (sum, sum of squares) of out (zeroed by the caller);
+// scores workspace [group][T][T].
+// One decision per attention core, like ConvPlan per conv: plan_attention (pure host code) picks the form and all that follows from it,
+// launch_attention_core carries it out.
+enum AttnForm : unsigned char {
+  ATTN_SMALL,  // short-sequence form (qk_small / softmax / P v), and every exact-fp32 core
+  ATTN_CONV,   // both GEMMs on the fused 1x1 conv pipeline (per-image weights = k, v^T): where plan_conv takes them and N * T > 1024
+  ATTN_FLASH   // single-kernel form (attn_flash.hip): the long-sequence level (T >= 1024, C = 384) in the split modes, no score matrix in HBM
+};
+struct AttnPlan {
+  AttnForm form = ATTN_SMALL;
+  int N = 0, H = 0, W = 0, C = 0;
+  int terms = 0;  // precision_terms: 0 = fp32 MFMA, 3 = fp16 hi/lo split, 1 = plain fp16 operands, 4 = plain bf16 operands
+  // ATTN_SMALL: S on the split kernel (whole 32-chunks of C), P v too (... and of T), per-image range guard of q, k, v (attn_scales_kernel)
+  bool split_qk = false, split_pv = false, guard = false;
+  int group = 1;             // images per pass: the [group, T, T] scores of one pass live in `scores` (independent of the batch beyond one group)
+  size_t scores_floats = 0;  // 0: ATTN_FLASH
+  size_t ws_floats = 0;      // AttnTables (0: the unguarded ATTN_SMALL takes no workspace)
+  bool out_stats = true;     // the last kernel accumulates out_stat (not ATTN_FLASH: one wave per SIMD on the whole register file, no room for it)
+  ConvPlan qk[2], pv[2];     // ATTN_CONV: the two GEMMs of a pass of `group` images [0] and of the short last pass [1] (N % group images)
+};
+AttnPlan plan_attention(int N, int H, int W, int C, int precision);
+// the workspace of a core (between attn.hip and attn_flash.hip only): 0, 2 or 3 packed operand images ([N] x T * C floats: fp16 hi + lo planes) ahead of the per-image factor tables
+struct AttnTables {
+  float *wq = nullptr, *wk = nullptr, *wv = nullptr;                 // ATTN_FLASH: q, k, v^T; ATTN_CONV: k, v^T
+  float *q_tab = nullptr, *p_tab = nullptr, *zero_tab = nullptr;     // [N][C], [N][T], [N][max(C, T)]
+  float *qk_inv = nullptr, *k_scale = nullptr, *k_inv = nullptr, *pv_inv = nullptr, *v_scale = nullptr, *v_inv = nullptr;  // [N] each
+  float* q_scale = nullptr;                                          // [N], not ATTN_CONV
+};
+// scores: plan.scores_floats, ws: plan.ws_floats floats; out_stat (zeroed by the caller) where plan.out_stats
+int launch_attention_core(const AttnPlan& p, const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat,
+                          float* ws, hipStream_t s);
+// attn_flash.hip, for launch_attention_core alone (no other caller): the rule of ATTN_FLASH, and its tail once the tables and the row-major images of
+// q and k are written (v^T pack + the kernel)
 bool attention_flash_applicable(int T, int C, int terms);
-size_t attention_flash_workspace_floats(int N, int T, int C);
-int launch_attention_flash(const float* qkv, const double2* qkv_mom, const float* x, float* out, float* ws, int N, int T, int C, int terms, hipStream_t s);
-// images per attention pass and the score workspace that takes ([group, T, T] floats: independent of the batch beyond one group)
-int attention_group(int N, int T);
-size_t attention_scores_floats(int N, int T);
-size_t attention_conv_workspace_floats(int N, int T, int C);
-int launch_attention_conv(const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat, float* ws, int N, int H,
-                          int W, int C, int precision, hipStream_t s);
+int launch_attention_flash(const AttnPlan& p, const AttnTables& t, const float* qkv, const float* x, float* out, hipStream_t s);
 
 // boundary maps and the envmap warp (transform.hip)
 int launch_map_chain(const float* x, float* out, long long per_image, int B, const int32_t* ops, const float* args, int n_ops, const float* lo,

@@ -571,22 +571,15 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
   DRM_TRY(gn_params(c, x, nullptr, Wb + l.n_w, Wb + l.n_b, sc, sh, nullptr, pa.gn_fold ? &a : nullptr));
   Act qkv_act = new_act(c, 3 * C, H, W);  // its per-channel sums (fused into the qkv conv's epilogue) bound |q|, |k|, |v| for the split cores
   float* qkv = qkv_act.p;
-  const bool flash = c.split() && attention_flash_applicable(T, C, c.terms());  // the long-sequence level: one kernel, no score matrix (attn_flash.hip)
-  float* scores = flash ? nullptr : c.ar->alloc<float>(attention_scores_floats(c.N, T));  // one image group at a time (attn.hip attention_group)
+  const AttnPlan ap = plan_attention(c.N, H, W, C, c.precision);  // which form of the core, and its buffers (attn.hip)
+  float* scores = ap.scores_floats ? c.ar->alloc<float>(ap.scores_floats) : nullptr;  // one image group at a time
   // Sizing contract: what drm_*_workspace_bytes answers per network, shape and mode is a recorded table (tests/golden/workspace_bytes.json) that
   // callers size long-lived buffers by.  The fold removed the proj_out stage -- its input tensor, its [N][C] guard table, its split-K slabs and
   // tickets -- and the block still reserves their share of the arena and of the statistics pool, untouched, in the order they were taken, so
   // every recorded answer stands.  (Dropping the reservation means re-recording that table; nothing here reads these bytes.)
   (void)c.ar->alloc<float>((size_t)c.N * T * C);
   const size_t proj_tab = (size_t)c.N * C;
-  // the T >= 256 levels: both GEMMs on the conv pipeline -- except on sparse launches (the 16x16 level of a batch-1 step: six launches, 51 us, where
-  // the short-sequence form -- qk_small, softmax, P v -- takes three and ~25 us)
-  const bool on_conv = flash || (attention_conv_planned(H, W, C, c.precision) && (long long)c.N * T > 1024);
-  // (the short-sequence form in the split modes: per-image guard factors from one attn_scales launch)
-  const bool small_guard = !on_conv && c.split() && C % 32 == 0;
-  float* aws = flash ? c.ar->alloc<float>(attention_flash_workspace_floats(c.N, T, C) + proj_tab)
-               : on_conv ? c.ar->alloc<float>(attention_conv_workspace_floats(c.N, T, C) + proj_tab)
-               : small_guard ? c.ar->alloc<float>(attention_small_workspace_floats(c.N, T, C) + proj_tab) : nullptr;
+  float* aws = ap.ws_floats ? c.ar->alloc<float>(ap.ws_floats + proj_tab) : nullptr;
   splitk_workspace(c, a, pa);
   {  // (the sizing contract above: the split-K share of a C -> C 1x1 conv on this map)
     ConvArgs p;
@@ -599,18 +592,16 @@ int run_attention(Ctx& c, const float* Wb, const AttnLayer& l, Act& x, Act& out)
     }
   }
   // (the attention core's last kernel accumulates them; zeroed ahead of the qkv conv: `out` is never `x`, and nothing before that kernel touches out.mom)
-  if (!flash) DRM_TRY(expect_raw_sums(c, out));
+  if (ap.out_stats) DRM_TRY(expect_raw_sums(c, out));
   if (!c.dry()) {
     a.src0 = x.p;
     a.gn_scale = sc; a.gn_shift = sh; a.silu = 0;
     a.w = Wb + l.qkv_w; a.bias = Wb + l.qkv_b; a.out = qkv;
     DRM_TRY(run_conv(c, a, pa, Wb, l.qkv_s, &qkv_act));
-    if (flash) DRM_TRY(launch_attention_flash(qkv, qkv_act.mom, x.p, out.p, aws, c.N, T, C, c.terms(), c.s));
-    else if (on_conv) DRM_TRY(launch_attention_conv(qkv, qkv_act.mom, x.p, scores, out.p, out.mom, aws, c.N, H, W, C, c.precision, c.s));
-    else DRM_TRY(launch_attention(qkv, x.p, scores, out.p, out.mom, c.N, T, C, c.s, c.split() ? c.terms() : 0, small_guard ? qkv_act.mom : nullptr, aws));
+    DRM_TRY(launch_attention_core(ap, qkv, qkv_act.mom, x.p, scores, out.p, out.mom, aws, c.s));
   }
   c.ar->release(mark);
-  if (flash) {  // (the single-kernel form leaves the statistics of its output to the stand-alone moments launch; its partial table takes the
+  if (!ap.out_stats) {  // (the single-kernel form leaves the statistics of its output to the stand-alone moments launch; its partial table takes the
                 //  place of the block's temporaries, which are dead in stream order)
     out.mom_valid = false;
     DRM_TRY(ensure_moments(c, out));

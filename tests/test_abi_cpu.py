@@ -131,3 +131,27 @@ def sampler_workspace_table():
 def test_sampler_workspace_bytes_match_the_recorded_sizing():
     with open(os.path.join(GOLD, "sampler_workspace_bytes.json")) as f:
         assert sampler_workspace_table() == json.load(f)
+
+
+# every branch of the attention plan (attn.hip plan_attention: single-kernel, conv-pipeline and short-sequence forms, guarded or not) at the
+# smallest shape that reaches it, sized through a two-level U-Net whose only attention blocks run at C channels on the H x W map; the recorded
+# answers (tests/golden/attn_workspace_bytes.json) are those of the code before the plan existed
+ATTN_WS_CASES = [(384, 32, 32, (1, 3), ["f16x3", "f16mx", "f16", "bf16"]), (384, 32, 32, (2,), ["fp32"]), (512, 16, 16, (5,), ["f16x3", "bf16", "fp32"]),
+                 (512, 16, 16, (2,), ["f16x3", "f16", "bf16"]), (64, 4, 4, (3,), ["f16x3"]), (32, 8, 4, (1,), ["fp32"]), (640, 8, 8, (2,), ["fp32"]),
+                 (768, 4, 8, (2,), ["f16x3", "f16mx"])]
+
+
+def test_attention_workspace_bytes_match_the_recorded_sizing():
+    from drmnet_amd.unet import UNetModel
+
+    nets, out = {}, {}
+    for c, h, w, ns, modes in ATTN_WS_CASES:
+        if c not in nets:
+            nets[c] = UNetModel(image_size=16, in_channels=6, model_channels=min(c, 128), out_channels=3, num_res_blocks=1, attention_resolutions=[2],
+                                channel_mult=[1, max(1, c // 128)], num_heads=1, resblock_updown=False, conv_resample=False)
+        for mode in modes:
+            nets[c].set_precision(mode)
+            for n in ns:
+                out[f"{c} {mode} {n}x{h}x{w}"] = nets[c].workspace_bytes(n, 2 * h, 2 * w)
+    with open(os.path.join(GOLD, "attn_workspace_bytes.json")) as f:
+        assert out == json.load(f)
