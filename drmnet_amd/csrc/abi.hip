@@ -544,6 +544,16 @@ int drm_render_refmap_views(const float* z, int L, const float* envmap, const fl
   });
 }
 
+size_t drm_render_light_workspace_bytes(int B, int EH, int EW, int light_samples) { return render_light_workspace_bytes(B, EH, EW, light_samples); }
+
+int drm_render_refmap_lit(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
+                          int flip, int light_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_refmap_lit(z, L, envmap, view, out, B, R, EH, EW, quad, subpixel, flip, light_samples, workspace, workspace_bytes,
+                                    static_cast<hipStream_t>(stream));
+  });
+}
+
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream) {
   return guarded([&]() -> int { return launch_brdf_eval(z, z_rows, n, v, l, out, (long long)N, static_cast<hipStream_t>(stream)); });
 }

@@ -230,6 +230,10 @@ int launch_render_refmap(const float* z, const float* env, float* out, int B, in
 // rotations, or null: +z)
 int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
                                int subpixel, int flip, hipStream_t s);
+// the light-sampled form (see drm_render_refmap_lit); light_samples == 0 or env == null is launch_render_refmap_views
+size_t render_light_workspace_bytes(int B, int EH, int EW, int light_samples);
+int launch_render_refmap_lit(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
+                             int flip, int light_samples, void* workspace, size_t workspace_bytes, hipStream_t s);
 // validation losses (losses.hip): see drm_validation_losses
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,

@@ -13,6 +13,11 @@
 // cosine-weighted directions for the diffuse one, at S x S sub-pixel normals.  One wave
 // owns one pixel: its lanes split the Q^2 grid, keep their partial sums in a fixed order and meet in a fixed butterfly, so a render is
 // bitwise reproducible (no atomics).
+//
+// Light sampling (opt-in, light_samples = M > 0): the quadrature never consults the map when it places samples, so a light a few texels
+// wide can fall between the strata of a rough lobe.  drm_render_refmap_lit adds a third technique, M directions drawn from the map's own
+// light density, and combines the three with lobe-separated multiple importance sampling (power heuristic, beta = 2): see "light density"
+// below.  The plain instantiations (LIGHT = false) are the kernels they always were.
 #include "common.h"
 
 namespace drm {
@@ -167,14 +172,88 @@ __host__ __device__ __forceinline__ V3 to_world(const ViewRot& r, V3 l) {
   return v3(r.m[0] * l.x + r.m[1] * l.y + r.m[2] * l.z, r.m[3] * l.x + r.m[4] * l.y + r.m[5] * l.z, r.m[6] * l.x + r.m[7] * l.y + r.m[8] * l.z);
 }
 
+// Rot^T w: a world direction (a light sample) in the row's frame
+template <bool VIEW>
+__host__ __device__ __forceinline__ V3 from_world(const ViewRot& r, V3 w) {
+  if (!VIEW || !r.on) return w;
+  return v3(r.m[0] * w.x + r.m[3] * w.y + r.m[6] * w.z, r.m[1] * w.x + r.m[4] * w.y + r.m[7] * w.z, r.m[2] * w.x + r.m[5] * w.y + r.m[8] * w.z);
+}
+
+// ------------------------------------------------------------------------------------------------ light density
+// The density lives on the dual grid of the bilinear lookup, where env_lookup is exactly bilinear.  Cell (c, j), c = 0 .. EH, j = 0 .. EW - 1,
+// spans theta in [lo_c, hi_c] = [(c - 1/2), (c + 1/2)] pi / EH clipped to [0, pi] (the polar rows are half cells) and psi in
+// [(j + 1/2), (j + 3/2)] dpsi, dpsi = 2 pi / EW (wrapping); its corners are the texels (clamp(c - 1), clamp(c)) x (j, j + 1 mod EW), each
+// valued at its Rec. 709 luminance clamped at 0.  With respect to (theta, psi) the density inside a cell is val sc_c / (tot dpsi): val the
+// bilinear interpolant of the corner luminances, sc_c = sin((lo_c + hi_c) / 2), tot = sum over cells of mean4(corners) sc_c (hi_c - lo_c).
+// The solid-angle pdf is p_L(w) = density / max(sin theta, 1e-6): any direction's pdf follows from the four texels its lookup loads and
+// norm = 1 / (tot dpsi); there is no pdf image.
+//
+// Workspace of one map (light_ws_stride bytes): fp64 cdf[EH + 2] (cdf[0] = 0, cdf[EH + 1] = tot), rowsum[EH + 1] (sum over j of mean4),
+// mass[EH + 1] (rowsum sc (hi - lo)); fp32 norm (0: the map has no light: black, or all non-positive) and a pad; the sample table, seven
+// planes of M floats (direction x y z, radiance r g b, p_L: 28 bytes a sample, laid out so a wave's loads are contiguous).
+struct LightTable {
+  const float* tab;
+  int M;
+  float norm;
+};
+__host__ __device__ __forceinline__ size_t light_ws_doubles(int EH) { return 3 * (size_t)EH + 4; }
+__host__ __device__ __forceinline__ size_t light_ws_stride(int EH, int M) { return light_ws_doubles(EH) * 8 + 8 + 28 * (size_t)M; }
+__host__ __device__ __forceinline__ LightTable light_table(const char* ws, int b, int EH, int M) {
+  const char* base = ws + (size_t)b * light_ws_stride(EH, M) + light_ws_doubles(EH) * 8;
+  LightTable lt;
+  lt.norm = *reinterpret_cast<const float*>(base);
+  lt.tab = reinterpret_cast<const float*>(base + 8);
+  lt.M = M;
+  return lt;
+}
+
+// a^2 / (a^2 + b^2) for a > 0 (the lobe pdfs are positive wherever a lobe sample is kept)
+__host__ __device__ __forceinline__ float power_weight(float a, float b) { return (a * a) / (a * a + b * b); }
+__host__ __device__ __forceinline__ float luma(const float* t) { return fmaxf(0.2126f * t[0] + 0.7152f * t[1] + 0.0722f * t[2], 0.0f); }
+
+// env_lookup (the same expressions: the same bits in L) that also returns p_L(w) from the four texels it loads.  sc_pole = sin(pi / (4 EH)).
+__host__ __device__ __forceinline__ float env_lookup_pdf(const float* __restrict__ env, int EH, int EW, V3 w, float norm, float sc_pole, float L[3]) {
+  const float u = atan2f(w.x, -w.z) * (0.5f / kPi);
+  const float t = acosf(fminf(fmaxf(w.y, -1.0f), 1.0f)) * (1.0f / kPi);
+  const float x = u * (float)EW - 0.5f;
+  const float yu = t * (float)EH - 0.5f;
+  const float y = fminf(fmaxf(yu, 0.0f), (float)(EH - 1));
+  const float xf = floorf(x), yf = floorf(y);
+  const float fx = x - xf, fy = y - yf;
+  int j0 = (int)xf % EW;
+  if (j0 < 0) j0 += EW;
+  const int j1 = j0 + 1 == EW ? 0 : j0 + 1;
+  const int i0 = (int)yf, i1 = i0 + 1 < EH ? i0 + 1 : EH - 1;
+  const float* r0 = env + (size_t)i0 * EW * 3;
+  const float* r1 = env + (size_t)i1 * EW * 3;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float top = (1.0f - fx) * r0[j0 * 3 + ch] + fx * r0[j1 * 3 + ch];
+    const float bot = (1.0f - fx) * r1[j0 * 3 + ch] + fx * r1[j1 * 3 + ch];
+    L[ch] = (1.0f - fy) * top + fy * bot;
+  }
+  // cell row: c = floor(yu) + 1 clamped to [0, EH]; in the half cells y is clamped, fy = 0 and the value is the polar texel row's
+  const bool pole = yu < 0.0f || yu >= (float)(EH - 1);
+  const float sc = pole ? sc_pole : sinf((float)(i0 + 1) * (kPi / (float)EH));
+  const float top = (1.0f - fx) * luma(r0 + j0 * 3) + fx * luma(r0 + j1 * 3);
+  const float bot = (1.0f - fx) * luma(r1 + j0 * 3) + fx * luma(r1 + j1 * 3);
+  const float val = (1.0f - fy) * top + fy * bot;
+  return val * sc * norm / fmaxf(sqrtf(w.x * w.x + w.z * w.z), 1e-6f);
+}
+
 // one lane's share of pixel (i, j): every sub-pixel, the grid points q = lane, lane + lanes, ... of both lobes, summed in that order
 // into acc (unnormalised).  env == nullptr: white environment (L = 1).
-template <bool VIEW>
+// LIGHT: lt.norm > 0 adds the light technique: every lobe sample is weighted by the power heuristic against the n_L = lt.M light samples,
+// and the lanes stride the light table as they stride the grid, summing into accL (normalised by 1 / S^2 only: the weights hold 1 / n).
+template <bool VIEW, bool LIGHT>
 __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
-                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3]) {
+                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3], const LightTable& lt,
+                                                        float accL[3]) {
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
+  const bool lit = LIGHT && lt.norm > 0.0f;
+  const float nlobe = (float)(Q * Q), nlight = (float)lt.M, sc_pole = LIGHT ? sinf(0.25f * kPi / (float)EH) : 0.0f;
   for (int sy = 0; sy < S; ++sy) {
     for (int sx = 0; sx < S; ++sx) {
       const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
@@ -191,6 +270,8 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
       const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
       const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
       const float vs = 0.5f * (1.0f + Vz);
+      // G1(v): v = +z is above the surface on the whole film and v.h > 0 wherever it is used
+      const float g1v = LIGHT ? ggx_g1(p.a2, cv, n.x * n.x + n.y * n.y, 1.0f) : 0.0f;
       for (int q = lane; q < Q * Q; q += lanes) {
         const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
         const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
@@ -211,9 +292,18 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
           if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
             const float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh);
             const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-            if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+            if constexpr (LIGHT) {
+              // p_s(l) = G1(v) D(h) / (4 n.v): the density of l under the visible-normal sampling above
+              const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
+              const float ps = g1v * ggx_d(p.a2, nh, s2h) / (4.0f * cv);
+              const float wm = w * (lit ? power_weight(nlobe * ps, nlight * pl) : 1.0f);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
+              for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * wm * L[c];
+            } else {
+              if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+#pragma unroll
+              for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
+            }
           }
         }
         // diffuse lobe: cosine-weighted l; weight pi diff / (n.l) = (1 - m) c shape
@@ -223,9 +313,43 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
           V3 h = v3(l.x, l.y, l.z + 1.0f);
           const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
           const float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd);
-          if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+          if constexpr (LIGHT) {
+            const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
+            const float wm = w * (lit ? power_weight(nlobe * cl * (1.0f / kPi), nlight * pl) : 1.0f);  // p_d(l) = n.l / pi
 #pragma unroll
-          for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
+            for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * wm * L[c];
+          } else {
+            if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
+          }
+        }
+      }
+      if constexpr (LIGHT) {
+        if (lit) {
+          // the light technique: table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame
+          for (int k = lane; k < lt.M; k += lanes) {
+            const V3 wd = v3(lt.tab[k], lt.tab[lt.M + k], lt.tab[2 * lt.M + k]);
+            const float pl = lt.tab[6 * lt.M + k];
+            const V3 l = from_world<VIEW>(rot, wd);
+            const float cl = dot3(n, l);
+            if (cl > 0.0f && pl > 0.0f) {
+              V3 h = v3(l.x, l.y, l.z + 1.0f);
+              const float hinv = 1.0f / sqrtf(dot3(h, h));
+              h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
+              const float vh = h.z, nh = dot3(n, h);
+              const float D = ggx_d(p.a2, nh, cross_sq(n, h));
+              const float ps = g1v * D / (4.0f * cv);
+              const float ks = ps * ggx_g1(p.a2, cl, cross_sq(n, l), dot3(l, h));  // D G / (4 n.v)
+              const float kd = diffuse ? (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, vh) * (1.0f / kPi) : 0.0f;
+              const float a = nlight * pl, as = nlobe * ps, ad = diffuse ? nlobe * cl * (1.0f / kPi) : 0.0f;
+              const float ws = ks * (a / (as * as + a * a)), wd2 = kd * (a / (ad * ad + a * a));
+              const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
+#pragma unroll
+              for (int c = 0; c < 3; ++c)
+                accL[c] += lt.tab[(3 + c) * lt.M + k] * ((fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * ws + p.c[c] * wd2);
+            }
+          }
         }
       }
     }
@@ -234,9 +358,14 @@ __host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, con
 
 // grid: ceil(L B R^2 / 4) workgroups of 4 waves; wave = pixel (row, i, j), row = l B + b lit by env[b] and seen through view[b];
 // z [L][B][6], out [L][B][3][R][R].  Every row runs the same per-lane order whatever L is, so a stacked render equals its rows rendered alone.
-template <bool VIEW>
+// LIGHT: lws is the light workspace of the B maps (M samples each).  The table of map b is read from memory by every pixel of its L rows, a
+// wave's loads contiguous: it is not staged in LDS.  (Staging would tie the four waves of a workgroup, which may belong to different maps
+// and may have left at the bounds check, to barriers, and a table of M = 65536 samples, 1.8 MB, does not fit; the 28 KB of M = 1024 stay
+// cache-resident across the map's pixels.)
+template <bool VIEW, bool LIGHT>
 __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
-                                                            float* __restrict__ out, int rows, int B, int R, int EH, int EW, int Q, int S, int flip) {
+                                                            float* __restrict__ out, int rows, int B, int R, int EH, int EW, int Q, int S, int flip,
+                                                            const char* __restrict__ lws, int M) {
   const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (pix >= (long long)rows * R * R) return;  // (wave-uniform)
@@ -247,17 +376,166 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
   const Principled p = principled(z + 6 * (size_t)row);
   const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
   const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  pixel_lane_sum<VIEW>(p, e, rot, EH, EW, R, i, j, Q, S, flip, lane, 64, acc);
+  float acc[3] = {0.0f, 0.0f, 0.0f}, accL[3] = {0.0f, 0.0f, 0.0f};
+  LightTable lt{nullptr, 0, 0.0f};
+  if constexpr (LIGHT) lt = light_table(lws, b, EH, M);
+  pixel_lane_sum<VIEW, LIGHT>(p, e, rot, EH, EW, R, i, j, Q, S, flip, lane, 64, acc, lt, accL);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], o);
+    if constexpr (LIGHT) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) accL[c] += __shfl_xor(accL[c], o);
+    }
   }
   if (lane == 0) {
     const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale;
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (LIGHT)
+        out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale + accL[c] * (1.0f / (float)(S * S));
+      else
+        out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale;
+    }
+  }
+}
+
+// ---- building the light workspace: three launches per render, fp64 sums in a fixed order, no atomics
+constexpr double kPiD = 3.14159265358979323846;
+__device__ __forceinline__ double luma64(const float* t) { return fmax(0.2126 * (double)t[0] + 0.7152 * (double)t[1] + 0.0722 * (double)t[2], 0.0); }
+struct LightCell {
+  double v00, v01, v10, v11;  // corner luminances, v{theta}{psi}
+};
+__device__ __forceinline__ LightCell light_cell(const float* __restrict__ env, int EH, int EW, int c, int j) {
+  const int i0 = c > 0 ? c - 1 : 0, i1 = c < EH ? c : EH - 1, j1 = j + 1 == EW ? 0 : j + 1;
+  const float* r0 = env + (size_t)i0 * EW * 3;
+  const float* r1 = env + (size_t)i1 * EW * 3;
+  return LightCell{luma64(r0 + 3 * j), luma64(r0 + 3 * j1), luma64(r1 + 3 * j), luma64(r1 + 3 * j1)};
+}
+__device__ __forceinline__ double mean4(const LightCell& v) { return 0.25 * (v.v00 + v.v01 + v.v10 + v.v11); }
+__device__ __forceinline__ double cell_lo(int c, int EH) { return c > 0 ? ((double)c - 0.5) * kPiD / (double)EH : 0.0; }
+__device__ __forceinline__ double cell_hi(int c, int EH) { return c < EH ? ((double)c + 0.5) * kPiD / (double)EH : kPiD; }
+// inclusive prefix sum over the 64 lanes, in a fixed order
+__device__ __forceinline__ double wave_scan(double x, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double t = __shfl_up(x, o);
+    if (lane >= o) x += t;
+  }
+  return x;
+}
+// x in [0, 1] whose cdf is u under the density proportional to (1 - x) a + x b; x = u where a + b = 0
+__device__ __forceinline__ double linear_inverse(double u, double a, double b) {
+  const double d = a + sqrt((1.0 - u) * a * a + u * b * b);
+  return (a + b > 0.0 && d > 0.0) ? u * (a + b) / d : u;
+}
+
+// grid (EH + 1, B), 256 threads: rowsum[c] and mass[c] of cell row c of map b
+__global__ __launch_bounds__(256) void light_rows_kernel(const float* __restrict__ env, char* __restrict__ ws, int EH, int EW, int M) {
+  __shared__ double sh[256];
+  const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const float* e = env + (size_t)b * EH * EW * 3;
+  double s = 0.0;
+  for (int j = tid; j < EW; j += 256) s += mean4(light_cell(e, EH, EW, c, j));
+  sh[tid] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double* d = reinterpret_cast<double*>(ws + (size_t)b * light_ws_stride(EH, M));
+    const double lo = cell_lo(c, EH), hi = cell_hi(c, EH);
+    d[(EH + 2) + c] = sh[0];
+    d[(EH + 2) + (EH + 1) + c] = sh[0] * sin(0.5 * (lo + hi)) * (hi - lo);
+  }
+}
+
+// grid B, one wave: the marginal CDF over the EH + 1 rows, tot and norm = 1 / (tot dpsi) (0 for a map without light)
+__global__ __launch_bounds__(64) void light_cdf_kernel(char* __restrict__ ws, int EH, int EW, int M) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double* d = reinterpret_cast<double*>(ws + (size_t)b * light_ws_stride(EH, M));
+  const double* mass = d + (EH + 2) + (EH + 1);
+  double run = 0.0;
+  if (lane == 0) d[0] = 0.0;
+  for (int base = 0; base <= EH; base += 64) {
+    const int c = base + lane;
+    const double incl = wave_scan(c <= EH ? mass[c] : 0.0, lane);
+    if (c <= EH) d[c + 1] = run + incl;
+    run += __shfl(incl, 63);
+  }
+  if (lane == 0) {
+    const bool ok = run > 0.0 && run < 1e300;  // (an infinite total gives a map no light technique either; a NaN texel has luminance 0)
+    *reinterpret_cast<float*>(d + light_ws_doubles(EH)) = ok ? (float)(1.0 / (run * (2.0 * kPiD / (double)EW))) : 0.0f;
+  }
+}
+
+// grid (M / 4, B), 4 waves: one wave per sample k, the Hammersley point U1 = (k + 1/2) / M, U2 = bitreverse32(k) 2^-32 + 1 / (2 M).  U1 picks
+// the cell row through the marginal CDF; U2 picks the column through the row's conditional CDF, which is not stored: the wave scans the row
+// in 64-wide chunks in a fixed order.  The remapped pair is the position inside the cell, found by inverting the bilinear density: theta from
+// the linear marginal (v00 + v01, v10 + v11), then psi from the linear conditional.  The radiance is the bilinear interpolant of the cell's
+// corners at that position (what env_lookup reads there) and p_L the cell's own density, both evaluated in fp64.
+__global__ __launch_bounds__(256) void light_table_kernel(const float* __restrict__ env, char* __restrict__ ws, int EH, int EW, int M) {
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y, lane = threadIdx.x & 63;
+  char* base_ws = ws + (size_t)b * light_ws_stride(EH, M);
+  const double* cdf = reinterpret_cast<const double*>(base_ws);
+  const double* rowsum = cdf + (EH + 2);
+  const double* mass = rowsum + (EH + 1);
+  const float norm = *reinterpret_cast<const float*>(base_ws + light_ws_doubles(EH) * 8);
+  if (k >= M || !(norm > 0.0f)) return;  // (wave-uniform)
+  float* tab = reinterpret_cast<float*>(base_ws + light_ws_doubles(EH) * 8 + 8);
+  const float* e = env + (size_t)b * EH * EW * 3;
+  const double tot = cdf[EH + 1];
+  const double U1 = ((double)k + 0.5) / (double)M;
+  const double U2 = (double)__brev((unsigned)k) * (1.0 / 4294967296.0) + 0.5 / (double)M;
+  // the last row whose cdf is <= U1 tot
+  const double t1 = U1 * tot;
+  int c = 0, hi = EH + 1;
+  while (hi - c > 1) {
+    const int mid = (c + hi) >> 1;
+    if (cdf[mid] <= t1) c = mid; else hi = mid;
+  }
+  const double u1 = mass[c] > 0.0 ? fmin(fmax((t1 - cdf[c]) / mass[c], 0.0), 1.0) : 0.5;
+  // the first column whose running sum exceeds U2 rowsum
+  const double t2 = U2 * rowsum[c];
+  double run = 0.0, before = 0.0;
+  int j = -1;
+  for (int base = 0; base < EW && j < 0; base += 64) {
+    const int jj = base + lane;
+    const double x = jj < EW ? mean4(light_cell(e, EH, EW, c, jj)) : 0.0;
+    const double incl = wave_scan(x, lane);
+    const unsigned long long hit = __ballot(jj < EW && run + incl > t2);
+    if (hit) {
+      const int f = __ffsll((long long)hit) - 1;
+      j = base + f;
+      const double prev = __shfl(incl, f > 0 ? f - 1 : 0);
+      before = f > 0 ? run + prev : run;
+    }
+    run += __shfl(incl, 63);
+  }
+  const bool found = j >= 0;
+  if (!found) j = EW - 1;  // (U2 rowsum at or past the scanned total: rounding only)
+  const LightCell v = light_cell(e, EH, EW, c, j);
+  const double m4 = mean4(v);
+  const double u2 = !found ? 1.0 : m4 > 0.0 ? fmin(fmax((t2 - before) / m4, 0.0), 1.0) : 0.5;
+  const double s = linear_inverse(u1, v.v00 + v.v01, v.v10 + v.v11);
+  const double t = linear_inverse(u2, (1.0 - s) * v.v00 + s * v.v10, (1.0 - s) * v.v01 + s * v.v11);
+  const double lo = cell_lo(c, EH), hic = cell_hi(c, EH), dpsi = 2.0 * kPiD / (double)EW;
+  const double theta = lo + s * (hic - lo), psi = ((double)j + 0.5 + t) * dpsi;
+  const double st = sin(theta), val = (1.0 - s) * ((1.0 - t) * v.v00 + t * v.v01) + s * ((1.0 - t) * v.v10 + t * v.v11);
+  const double pdf = val * sin(0.5 * (lo + hic)) / (tot * dpsi) / fmax(st, 1e-6);
+  if (lane == 0) {
+    tab[k] = (float)(st * sin(psi));
+    tab[M + k] = (float)cos(theta);
+    tab[2 * M + k] = (float)(-st * cos(psi));
+    const int i0 = c > 0 ? c - 1 : 0, i1 = c < EH ? c : EH - 1, j1 = j + 1 == EW ? 0 : j + 1;
+    const float* r0 = e + (size_t)i0 * EW * 3;
+    const float* r1 = e + (size_t)i1 * EW * 3;
+    for (int ch = 0; ch < 3; ++ch)
+      tab[(3 + ch) * M + k] = (float)((1.0 - s) * ((1.0 - t) * (double)r0[3 * j + ch] + t * (double)r0[3 * j1 + ch]) +
+                                      s * ((1.0 - t) * (double)r1[3 * j + ch] + t * (double)r1[3 * j1 + ch]));
+    tab[6 * M + k] = (float)pdf;
   }
 }
 
@@ -287,8 +565,42 @@ int launch_render_refmap_views(const float* z, int L, const float* env, const fl
   DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: L B R^2 too large for one launch");
   // (a view only turns the environment: under a white one it changes nothing and is not read)
   const bool with_view = env && view;
-  hipLaunchKernelGGL(with_view ? refmap_render_kernel<true> : refmap_render_kernel<false>, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env,
-                     with_view ? view : nullptr, out, L * B, B, R, env ? EH : 1, env ? EW : 1, quad, subpixel, flip ? 1 : 0);
+  hipLaunchKernelGGL((with_view ? refmap_render_kernel<true, false> : refmap_render_kernel<false, false>), dim3((unsigned)blocks), dim3(64 * kRenderWaves),
+                     0, s, z, env, with_view ? view : nullptr, out, L * B, B, R, env ? EH : 1, env ? EW : 1, quad, subpixel, flip ? 1 : 0, nullptr, 0);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+static bool light_samples_ok(int M) { return M >= 64 && M <= 65536 && (M & (M - 1)) == 0; }
+
+size_t render_light_workspace_bytes(int B, int EH, int EW, int light_samples) {
+  if (B < 1 || EH < 1 || EW < 1 || (long long)EH * EW > (1LL << 28) || !light_samples_ok(light_samples)) return 0;
+  return (size_t)B * light_ws_stride(EH, light_samples);
+}
+
+int launch_render_refmap_lit(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
+                             int flip, int light_samples, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  DRM_REQUIRE(light_samples >= 0, "render_refmap_lit: light_samples >= 0");
+  if (light_samples == 0 || !env) return launch_render_refmap_views(z, L, env, view, out, B, R, EH, EW, quad, subpixel, flip, s);
+  DRM_REQUIRE(z && out, "render_refmap: null pointer");
+  DRM_REQUIRE(L > 0 && B > 0 && B <= 65535 && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
+              "render_refmap_lit: L >= 1 stacks of 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192");
+  DRM_REQUIRE(quad >= 1 && quad <= 1024 && subpixel >= 1 && subpixel <= 16, "render_refmap: quad in [1, 1024], subpixel in [1, 16]");
+  DRM_REQUIRE(EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28), "render_refmap: envmap must be EH x EW with EH, EW >= 1");
+  DRM_REQUIRE(light_samples_ok(light_samples), "render_refmap_lit: light_samples must be 0 or a power of two in [64, 65536]");
+  const size_t need = render_light_workspace_bytes(B, EH, EW, light_samples);
+  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
+    set_error("render_refmap_lit: workspace must be 8-byte aligned and hold drm_render_light_workspace_bytes = " + std::to_string(need) + " bytes");
+    return DRM_ERR_WORKSPACE;
+  }
+  const long long blocks = ((long long)L * B * R * R + kRenderWaves - 1) / kRenderWaves;
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: L B R^2 too large for one launch");
+  char* ws = static_cast<char*>(workspace);
+  hipLaunchKernelGGL(light_rows_kernel, dim3((unsigned)(EH + 1), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
+  hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)B), dim3(64), 0, s, ws, EH, EW, light_samples);
+  hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(light_samples / 4), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
+  hipLaunchKernelGGL((view ? refmap_render_kernel<true, true> : refmap_render_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
+                     env, view, out, L * B, B, R, EH, EW, quad, subpixel, flip ? 1 : 0, ws, light_samples);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -75,9 +75,12 @@ def view_rotation(view_from) -> torch.Tensor:
 
 @torch.no_grad()
 def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD,
-           subpixel: int = SUBPIXEL, flip: bool = False, view_from=None) -> torch.Tensor:
+           subpixel: int = SUBPIXEL, flip: bool = False, view_from=None, light_samples: int = 0) -> torch.Tensor:
     """One launch of drm_render_refmap_views: z [B, P] or [L, B, P], envmaps [B, H, W, 3] (or None: white), view_from [B, 3] (or None: +z)
-    -> reflectance maps [B, 3, res, res] or [L, B, 3, res, res].  The L rows of a batch item read the same map: nothing is expanded."""
+    -> reflectance maps [B, 3, res, res] or [L, B, 3, res, res].  The L rows of a batch item read the same map: nothing is expanded.
+    ``light_samples`` = M > 0 (a power of two in [64, 65536]) renders through drm_render_refmap_lit: M directions drawn from each map's own
+    light density join the two lobe quadratures by multiple importance sampling, which is what a map with a sun or a lamp a few texels wide
+    needs (the plain quadrature can be 10 % off there).  0, or no envmaps, is the plain render bit for bit."""
     dev = _device(z, envmaps)
     z = torch.as_tensor(z).to(dev)
     if z.dim() not in (2, 3):
@@ -99,6 +102,19 @@ def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] =
             raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
         view = view.to(dev)
     out = torch.empty((L * B, 3, res, res), dtype=torch.float32, device=dev)
+    light_samples = int(light_samples)
+    if light_samples < 0:
+        raise ValueError(f"light_samples must be >= 0, got {light_samples}")
+    if light_samples and env is not None:
+        lib = _lib.lib()
+        nbytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
+        if nbytes == 0:
+            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.drm_render_refmap_lit(rows.data_ptr(), L, env.data_ptr(), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad),
+                                                 int(subpixel), int(bool(flip)), light_samples, ws.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+        return out.reshape(L, B, 3, res, res) if stacked else out
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().drm_render_refmap_views(rows.data_ptr(), L, _lib.ptr(env), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad),
                                                       int(subpixel), int(bool(flip)), _lib.stream_ptr(dev)))
@@ -109,12 +125,13 @@ class RefMapRenderer:
     """MitsubaRefMapRenderer (utils/mitsuba3_utils.py:324-430) on drm_render_refmap: the sphere seen from +z under the scene's
     environment map, ``direct`` integration, box-filtered pixels.  The integral is a deterministic quadrature (``quad`` x ``quad``
     points per lobe at ``subpixel`` x ``subpixel`` normals per pixel), so ``spp`` and ``denoise`` are accepted and ignored: there is
-    no Monte-Carlo noise to average or denoise.  A per-call ``view_from`` turns the environment (render.view_rotation); a scene whose own
+    no Monte-Carlo noise to average or denoise.  ``light_samples`` = M > 0 adds M light samples per map (see ``render``; reachable from a YAML
+    ``renderer_config``); the default 0 is the plain quadrature.  A per-call ``view_from`` turns the environment (render.view_rotation); a scene whose own
     sensor is off the +z axis (``init_view_from``) and the normal / depth outputs are not implemented.  Construction does not touch the GPU."""
 
     def __init__(self, refmap_res: int, spp: int = 1024, envmap_size=(1000, 2000), denoise: Optional[str] = None, return_normal: bool = False,
                  return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
-                 subpixel: int = SUBPIXEL):
+                 subpixel: int = SUBPIXEL, light_samples: int = 0):
         if return_normal or return_depth:
             raise NotImplementedError("normal / depth outputs of the reflectance-map renderer")
         view = [float(t) for t in init_view_from]
@@ -127,6 +144,9 @@ class RefMapRenderer:
         self.return_normal, self.return_depth = return_normal, return_depth
         self.brdf_param_names = brdf_param_names
         self.quad, self.subpixel = int(quad), int(subpixel)
+        self.light_samples = int(light_samples)
+        if self.light_samples and (self.light_samples < 64 or self.light_samples > 65536 or self.light_samples & (self.light_samples - 1)):
+            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
         self.flip = False
         self._envmap: Optional[torch.Tensor] = None  # the scene's map; None = the initial all-zero bitmap of envmap_size
         self._view_from: Optional[torch.Tensor] = None  # the scene's view; None = the sensor's own (+z)
@@ -135,7 +155,7 @@ class RefMapRenderer:
         """Batched form: z [B, P] or [L, B, P], envmaps [B, H, W, 3] or None (white), view_from [B, 3] or None (+z) -> [(L,) B, 3, R, R] in
         one launch."""
         return render(z, brdf_param_names or self.brdf_param_names, envmaps, res=res or self.refmap_res, quad=self.quad, subpixel=self.subpixel,
-                      flip=self.flip if flip is None else flip, view_from=view_from)
+                      flip=self.flip if flip is None else flip, view_from=view_from, light_samples=self.light_samples)
 
     def rendering(self, z, brdf_param_names, envmap: Optional[torch.Tensor] = None, view_from=None, flip: Optional[bool] = None, sensor=0,
                   spp: int = 0, new_scene: bool = False, channel_first: bool = False) -> torch.Tensor:

@@ -34,6 +34,22 @@ QUADRATURE_NOTE = ("the reflectance maps are rendered with a fixed 32 x 32 quadr
                    "environment map: it is unvalidated for small, very bright lights in 1000 x 2000 maps")
 
 
+def light_note(light_samples: int) -> str:
+    """The caveat's replacement once the renders are light-sampled"""
+    return (f"the reflectance maps are rendered with a 32 x 32 quadrature per lobe combined by multiple importance sampling with M = {light_samples} "
+            "light samples drawn from each environment map (drm_render_refmap_lit)")
+
+
+def set_light_samples(model, light_samples: int) -> None:
+    """--light_samples on the model's reflectance-map renderer (a DRMNet without a renderer_config gets its default renderer first)"""
+    from .render import RefMapRenderer
+
+    renderer = model._renderer() if hasattr(model, "_renderer") else getattr(model, "renderer", None)
+    if not isinstance(renderer, RefMapRenderer):
+        raise SystemExit("validate: --light_samples needs a model whose renderer is drmnet_amd.render.RefMapRenderer")
+    renderer.light_samples = RefMapRenderer(1, light_samples=light_samples).light_samples  # (validated as the constructor validates it)
+
+
 def collate(items):
     """torch's default_collate (main.py:366-371 without the mesh entry this dataset never has)."""
     from torch.utils.data import default_collate
@@ -93,8 +109,9 @@ def build_dataset(config: dict, args):
     return ParametricRefmapDataset(**kw)
 
 
-def make_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m drmnet_amd.validate", description="Validation losses of a DRMNet or ObsNetDiffusion checkpoint on the GPU. Note: " + QUADRATURE_NOTE + ".")
+def make_parser(light_samples: int = 0) -> argparse.ArgumentParser:
+    note = light_note(light_samples) if light_samples > 0 else QUADRATURE_NOTE
+    p = argparse.ArgumentParser(prog="python -m drmnet_amd.validate", description="Validation losses of a DRMNet or ObsNetDiffusion checkpoint on the GPU. Note: " + note + ".")
     p.add_argument("--base", type=Path, required=True, help="the model config (the reference's eval or training YAML)")
     p.add_argument("--data_root", type=Path, default=None, help="directory of the <name>.exr environment maps (overrides the YAML's validation node)")
     p.add_argument("--split", choices=["train", "val", "test"], default="val")
@@ -107,18 +124,25 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", default="auto", help="conv arithmetic of the networks (DRMNet.set_precision / ObsNetDiffusion.set_precision)")
     p.add_argument("--seed", type=int, default=0, help="keys the forward noise (ObsNet: the steps t as well)")
     p.add_argument("--ckpt", type=Path, default=None, help="checkpoint to load instead of the YAML's ckpt_path")
+    p.add_argument("--light_samples", type=int, default=0,
+                   help="M > 0 (a power of two in [64, 65536]): render with M light samples per environment map, for maps with suns and lamps "
+                        "(sets light_samples on the model's RefMapRenderer); 0 keeps the plain quadrature")
     return p
 
 
 def main(argv=None) -> dict:
     from .config import instantiate_from_config, load_config
 
-    args = make_parser().parse_args(argv)
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--light_samples", type=int, default=0)
+    args = make_parser(pre.parse_known_args(argv)[0].light_samples).parse_args(argv)
     config = load_config(args.base)
     model_cfg = {"target": config["model"]["target"], "params": dict(config["model"].get("params") or {})}
     if args.ckpt is not None:
         model_cfg["params"]["ckpt_path"] = str(args.ckpt)
     model = instantiate_from_config(model_cfg).cuda()
+    if args.light_samples:
+        set_light_samples(model, args.light_samples)
     dataset = build_dataset(config, args)
     result = validate(model, dataset, args.batch_size, limit=args.limit, precision=args.precision, seed=args.seed)
     result.pop("per_batch")

@@ -378,6 +378,27 @@ int drm_render_refmap(const float* z, const float* envmap, float* out, int B, in
  *   Every row is summed in the per-lane order of drm_render_refmap whatever L is: a stacked render equals its rows rendered one by one. */
 int drm_render_refmap_views(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
                             int subpixel, int flip, void* stream);
+/* drm_render_refmap_views with light sampling, for maps with small bright lights (a sun, a lamp) that fall between the strata of a rough
+ * lobe's quadrature.  light_samples = M directions are drawn from each map's own light density and combined with the two lobe quadratures by
+ * lobe-separated multiple importance sampling, power heuristic (beta = 2).  Additive: the ABI version is unchanged.
+ *   Light density.  On the dual grid of the bilinear lookup: cell (c, j), c = 0 .. EH, j = 0 .. EW - 1, spans theta in
+ *   [(c - 1/2), (c + 1/2)] pi / EH clipped to [0, pi] and psi in [(j + 1/2), (j + 3/2)] 2 pi / EW; its corners are the texels
+ *   (clamp(c - 1), clamp(c)) x (j, j + 1 mod EW), valued at their Rec. 709 luminance clamped at 0.  Density with respect to (theta, psi):
+ *   val sc_c / (tot dpsi), val the bilinear interpolant of the corners, sc_c the sine of the row's mid colatitude, tot the sum over cells of
+ *   mean4(corners) sc_c (hi_c - lo_c); p_L(w) = density / max(sin theta, 1e-6).
+ *   Samples.  Sample k is the Hammersley point ((k + 1/2) / M, bitreverse32(k) 2^-32 + 1 / (2 M)) taken through the marginal CDF over rows, the
+ *   row's conditional CDF over columns and the inverse of the bilinear density inside the cell.  fp64, fixed order, no atomics.
+ *   Estimator.  With n_s = n_d = quad^2 (n_d = 0 for a metal) and n_L = M: each lobe sample is weighted by (n p)^2 / ((n p)^2 + (n_L p_L)^2),
+ *   p = G1(v) D(h) / (4 n.v) for the specular lobe and n.l / pi for the diffuse one; light sample k with n.l_k > 0 adds
+ *   L_k [f_s cos n_L p_L / ((n_s p_s)^2 + (n_L p_L)^2) + f_d cos n_L p_L / ((n_d p_d)^2 + (n_L p_L)^2)] / subpixel^2.
+ *   light_samples: 0, or a power of two in [64, 65536].  0, or envmap == NULL, is drm_render_refmap_views exactly (workspace not read).
+ *   workspace: at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device memory, 8-byte aligned; it is rebuilt by
+ *   every call (three small launches before the render) and holds nothing the caller needs.  A map whose tot is 0 (black, or all
+ *   non-positive) has no light technique: its rows are the plain quadrature.  Bitwise reproducible; a stacked render equals its rows alone.
+ *   DRM_ERR_INVALID for a bad light_samples, DRM_ERR_WORKSPACE for a missing, misaligned or short workspace: nothing is launched. */
+size_t drm_render_light_workspace_bytes(int B, int EH, int EW, int light_samples); /* 0 for arguments drm_render_refmap_lit rejects */
+int drm_render_refmap_lit(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
+                          int subpixel, int flip, int light_samples, void* workspace, size_t workspace_bytes, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */

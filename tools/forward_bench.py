@@ -5,6 +5,8 @@
         L x B stacked rows at R = 128 through drm_render_refmap_views (maps indexed per row) against the same L B rows through
         drm_render_refmap with the maps expanded L times, per library, alternating ("-" = the product library; a library without the
         stacked entry point, e.g. the parent commit's built with tools/build_variant.sh, runs the expanded form only).
+        --light_samples M also times the same stacked rows through drm_render_refmap_lit (the density and table launches included; under
+        `rocprofv3 --kernel-trace --stats` the three light kernels and the render show on their own).
     python tools/forward_bench.py step [--batch 20]
         one DRMNet.validation_step at full width (synthetic weights, 128 x 128, 128 x 256 maps) split into forward process (renders +
         transforms), networks and loss by device events.  Run it under `rocprofv3 --kernel-trace --stats -- python ...` for the kernel table.
@@ -65,6 +67,16 @@ def bench_render(args):
                 def stacked():
                     assert lib.drm_render_refmap_views(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0, stream) == 0
 
+                def lit():
+                    assert lib.drm_render_refmap_lit(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0,
+                                                     args.light_samples, vp(ws.data_ptr()), C.c_size_t(ws.numel() * 8), stream) == 0
+
+                if args.light_samples and hasattr(lib, "drm_render_refmap_lit"):
+                    lib.drm_render_light_workspace_bytes.restype = C.c_size_t
+                    nbytes = lib.drm_render_light_workspace_bytes(B, EH, EW, args.light_samples)
+                    assert nbytes > 0, "--light_samples: a power of two in [64, 65536]"
+                    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+                    results.setdefault((name, f"drm_render_refmap_lit M={args.light_samples}"), []).extend(timed(lit, args.reps))
                 results.setdefault((name, "expanded + drm_render_refmap"), []).extend(timed(expanded, args.reps))
                 if has_views:
                     results.setdefault((name, "drm_render_refmap_views"), []).extend(timed(stacked, args.reps))
@@ -204,5 +216,6 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="f16mx")
+    ap.add_argument("--light_samples", type=int, default=0, help="render: also time drm_render_refmap_lit with this many light samples per map")
     a = ap.parse_args()
     {"render": bench_render, "step": bench_step, "obs_step": bench_obs_step}[a.what](a)
