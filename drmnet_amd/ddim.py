@@ -130,11 +130,7 @@ class DDIMSampler(object):
         c = cond[0] if isinstance(cond, (list, tuple)) else cond
         c = _lib.require_gpu_tensor(c, "conditioning")
         noise = None if noise is None else _lib.require_gpu_tensor(noise, "noise")
-        unet = self.model.model.diffusion_model
-        h = unet.engine_handle()
-        if getattr(self.model, "_auto_chain", None) is not None:  # auto mode: the model's chain probe may move the network to f16x3 for these weights
-            self.model._auto_chain_probe(c)  # (on rows of the caller's conditioning, once per weight signature)
-            h = unet.engine_handle()
+        h = self.model._engine(c)  # (auto mode: behind the chain probe, on rows of this conditioning)
         L = _lib.lib()
         n, _, hh, ww = shape
         ws = self._ws.get(int(L.drm_sampler_workspace_bytes(h, n, hh, ww)), dev)

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .autoprec import ChainProbe, tensor_sig
 from .config import instantiate_from_config
 from .wrappers import DiffusionWrapper, IdentityFirstStage, LitEma, ZEmbDiffusionWrapper, ema_weights, load_checkpoint
 
@@ -286,109 +287,51 @@ class DRMNet(nn.Module):
         weights agrees with f16x3 to 5e-5, else f16x3: unet.set_precision_auto), "f16" / "bf16" (reduced precision)."""
         self.illnet_model.diffusion_model.set_precision(precision)
         self.refnet_model.diffusion_model.set_precision(precision)
-        # "auto": besides the per-network probes (unet.py), the CHAIN is measured before f16mx is kept -- see _auto_chain_probe
+        # "auto": besides the per-network probes (unet.py), the CHAIN is measured before f16mx is kept (autoprec.ChainProbe over _run_probe_chain)
         # ``probe`` [n,3,H,W]: refmaps of the CALLER to measure the chain on (the first and the middle row are used) instead of the seeded synthetic
         # pair; without it the first batch p_sample_loop sees is handed to the probe (once per weight signature)
-        self._auto_chain = {"tolerance": self.AUTO_CHAIN_TOLERANCE, "steps": self.AUTO_CHAIN_STEPS, "done": {}, "busy": False, "report": None,
-                            "probe": None if probe is None else _lib.require_gpu_tensor(probe, "probe").detach()} if precision == "auto" else None
+        self._auto_chain = ChainProbe(self.AUTO_CHAIN_TOLERANCE, self.AUTO_CHAIN_STEPS, None if probe is None else _lib.require_gpu_tensor(probe, "probe").detach(),
+                                      step_name="DRMNet steps", probe_text="{dims} {rows}, {steps} reverse steps, worst row") if precision == "auto" else None
         return self
 
     AUTO_CHAIN_TOLERANCE = 5e-5  # half the 1e-4 contract, like the per-network probe
     AUTO_CHAIN_STEPS = 8
+    _auto_chain: Optional[ChainProbe] = None  # None outside auto mode (assigning None switches the chain probe off, the networks' modes stay)
 
     @property
     def auto_chain_report(self) -> Optional[dict]:
         """{"kept", "rel_l2_chain_vs_f16x3" (worst row), "steps", "tolerance", "modes"} of the last chain probe; None outside auto mode / before it ran"""
-        ac = getattr(self, "_auto_chain", None)
-        return None if ac is None else ac["report"]
+        return None if self._auto_chain is None else self._auto_chain.report
 
     def calibrate_precision(self, probe: Optional[torch.Tensor] = None) -> Optional[dict]:
         """Auto mode: runs the per-network probes and the chain probe now (weights on a GPU) and returns the chain report.  ``probe``: refmaps of the
         caller to run the chain on (re-measured for these rows even if a probe of these weights is on record)."""
-        ac = getattr(self, "_auto_chain", None)
-        if ac is not None and probe is not None:
-            ac["probe"] = _lib.require_gpu_tensor(probe, "probe").detach()
-            ac["done"] = {k: v for k, v in ac["done"].items() if k[-1] != "data"}
+        if self._auto_chain is not None and probe is not None:
+            self._auto_chain.set_probe(_lib.require_gpu_tensor(probe, "probe").detach())
         self._engine()
         return self.auto_chain_report
 
-    @torch.no_grad()
-    def _auto_chain_probe(self, which: str, data: Optional[torch.Tensor] = None) -> None:
-        """A per-network probe compares ONE forward; the sampler applies ~100 of them to its own output.  So where the networks settled on f16mx, eight
-        reverse steps (RefNet -> schedule -> z-MLP -> IllNet -> update, Philox noise from a fixed key, every row active: drm_drmnet_step) are run in
-        the chosen modes and in f16x3; f16mx is kept only if every row of the final state agrees to `tolerance`, otherwise BOTH networks run in f16x3
-        for these weights.  The rows: the CALLER's refmaps when there are any -- ``data`` (the batch p_sample_loop was called with, or the ``probe`` of
-        set_precision / calibrate_precision; first and middle row, at their own size), once per weight signature -- else two seeded synthetic refmaps at
-        128x128 (calibrate_precision() before any data exists)."""
-        from . import synth
-
-        ac = self._auto_chain
-        ill, ref = self.illnet_model.diffusion_model, self.refnet_model.diffusion_model
-        if ill.auto_report is None or ref.auto_report is None:
-            return
-        if data is None:
-            data = ac.get("probe")
-        sigs = (which, ill.__dict__["_auto"]["sig"], ref.__dict__["_auto"]["sig"])
-        key = sigs + ("data" if data is not None else "synth",)
-        if data is None and sigs + ("data",) in ac["done"]:
-            key = sigs + ("data",)  # (measured on the caller's rows before: that record stands)
-        if key in ac["done"]:
-            ac["report"] = ac["done"][key]
-            return
-        if "f16mx" not in (ill.precision, ref.precision):
-            return
-        ac["busy"] = True
-        try:
-            dev = next(ill.parameters()).device
-            if data is not None:
-                x = data[[0, data.shape[0] // 2]] if data.shape[0] > 1 else data[:1]
-                x = x.detach().to(dev, torch.float32).contiguous()
-                B, H, W = x.shape[0], x.shape[2], x.shape[3]
-            else:
-                B, H, W = 2, 128, 128
-                x = synth.synth_refmaps(B, H, W, 4321).to(dev)
-            L = _lib.lib()
-            chosen = (ill.precision, ref.precision)
-
-            def chain():
-                h = self._engine_raw()
-                ws = self._ws.get(int(L.drm_drmnet_workspace_bytes(h, B, H, W)), dev)
-                Lr_k = x.clone()
-                with torch.cuda.device(dev):
-                    for i in range(ac["steps"]):
-                        _lib.check(L.drm_drmnet_step(h, Lr_k.data_ptr(), x.data_ptr(), None, B, i, None, 20261004, None, None, None, B, H, W, ws.data_ptr(),
-                                                     ws.numel(), _lib.stream_ptr(dev)))
-                return Lr_k.double().flatten(1)
-
-            a = chain()
-            ill._set_mode("f16x3")
-            ref._set_mode("f16x3")
-            b = chain()
-            rows = ((a - b).norm(dim=1) / b.norm(dim=1).clamp_min(1e-300)).tolist()
-            err = max(rows)
-            kept = err <= ac["tolerance"] and bool(torch.isfinite(a).all())
-            if kept:
-                ill._set_mode(chosen[0])
-                ref._set_mode(chosen[1])
-            else:
-                why = f"chain probe: {ac['steps']} DRMNet steps differ from f16x3 by {err:.2e} > {ac['tolerance']:.0e}"
-                ill.auto_override("f16x3", why)
-                ref.auto_override("f16x3", why)
-            ac["report"] = {"kept": kept, "rel_l2_chain_vs_f16x3": err, "rows": [float(f"{r:.3e}") for r in rows], "steps": ac["steps"], "tolerance": ac["tolerance"],
-                            "modes": {"illnet": chosen[0], "refnet": chosen[1]}, "probe_source": "caller" if data is not None else "synthetic",
-                            "probe": f"{B}x3x{H}x{W} {'rows of the caller' if data is not None else 'seeded refmaps'}, {ac['steps']} reverse steps, worst row"}
-            ac["done"][key] = ac["report"]
-        finally:
-            ac["busy"] = False
+    def _run_probe_chain(self, x: torch.Tensor) -> torch.Tensor:
+        """The chain of autoprec.ChainProbe: eight reverse steps (RefNet -> schedule -> z-MLP -> IllNet -> update, Philox noise from a fixed key, every
+        row active: drm_drmnet_step) from the refmaps ``x``, on the handle of the modes the networks are in when it runs."""
+        (B, _, H, W), dev, L = x.shape, x.device, _lib.lib()
+        h = self._engine_raw()
+        ws = self._ws.get(int(L.drm_drmnet_workspace_bytes(h, B, H, W)), dev)
+        Lr_k = x.clone()
+        with torch.cuda.device(dev):
+            for i in range(self._auto_chain.steps):
+                _lib.check(L.drm_drmnet_step(h, Lr_k.data_ptr(), x.data_ptr(), None, B, i, None, 20261004, None, None, None, B, H, W, ws.data_ptr(),
+                                             ws.numel(), _lib.stream_ptr(dev)))
+        return Lr_k
 
     # ------------------------------------------------------------------ the device sampler
     def _engine(self, data: Optional[torch.Tensor] = None):
         """_engine_raw() behind the auto mode's chain probe (which may move both networks to f16x3 for the current weights); ``data``: the refmaps
         the caller is about to sample from -- the chain probe runs on rows of them (once per weight signature)."""
         h = self._engine_raw()
-        ac = getattr(self, "_auto_chain", None)
-        if ac is not None and not ac["busy"]:
-            self._auto_chain_probe(getattr(self, "_weight_set", "live"), data)
+        if self._auto_chain is not None and not self._auto_chain.busy:
+            ill, ref = self.illnet_model.diffusion_model, self.refnet_model.diffusion_model
+            self._auto_chain.measure({"illnet": ill, "refnet": ref}, getattr(self, "_weight_set", "live"), self._run_probe_chain, data, next(ill.parameters()).device)
             h = self._engine_raw()
         return h
 
@@ -404,7 +347,7 @@ class DRMNet(nn.Module):
             zp = [p.detach() for p in self.illnet_model.z_emb_params()]
         for p in zp:
             _lib.require_gpu_tensor(p, "z_emb_layer parameter")
-        sig = (hi.value, hr.value, ill.precision, ref.precision, tuple((p.data_ptr(), p._version) for p in zp), float(self.gamma), float(self.epsilon),
+        sig = (hi.value, hr.value, ill.precision, ref.precision, tensor_sig(zp), float(self.gamma), float(self.epsilon),
                float(self.delta), int(self.max_timesteps), tuple(self._z0.tolist()))
         cached = self._samplers.get(which)
         if cached is not None and cached[1] == sig:

@@ -25,7 +25,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .autoprec import ChainProbe
 from .config import instantiate_from_config
+from .ddim import DDIMSampler
 from .wrappers import DiffusionWrapper, IdentityFirstStage, LitEma, ema_weights, load_checkpoint
 
 
@@ -205,87 +207,55 @@ class LatentDiffusion(DDPM):
         """Conv arithmetic of the U-Net: "fp32" (exact fp32 MFMA), "f16x3" (split fp16, fp32-accurate, ~2.5x faster), "f16mx" (f16x3 with
         fp8 cross terms on the 3x3 convs: ~4e-5 per forward, ~3x faster) or "f16" (reduced precision)."""
         self.model.diffusion_model.set_precision(precision)
-        # "auto": the per-network probe (unet.py) + a chain probe before f16mx is kept (_auto_chain_probe)
+        # "auto": the per-network probe (unet.py) + a chain probe before f16mx is kept (autoprec.ChainProbe over _auto_chain_probe)
         # ``probe`` [n,3,H,W]: conditioning refmaps of the CALLER for the chain probe; without it the first batch a sampler sees is handed to it
-        self._auto_chain = {"tolerance": 5e-5, "steps": 8, "done": {}, "busy": False, "report": None,
-                            "probe": None if probe is None else _lib.require_gpu_tensor(probe, "probe").detach()} if precision == "auto" else None
+        self._auto_chain = ChainProbe(self.AUTO_CHAIN_TOLERANCE, self.AUTO_CHAIN_STEPS, None if probe is None else _lib.require_gpu_tensor(probe, "probe").detach(),
+                                      step_name="DDIM steps", probe_text="{dims} {rows}: first {steps} steps of the DDIM-50 chain (eta 1), worst row",
+                                      caller_rows="conditioning rows of the caller") if precision == "auto" else None
         return self
+
+    AUTO_CHAIN_TOLERANCE = 5e-5  # half the 1e-4 contract, like the per-network probe
+    AUTO_CHAIN_STEPS = 8
+    _auto_chain: Optional[ChainProbe] = None  # None outside auto mode (assigning None switches the chain probe off, the network's mode stays)
 
     @property
     def auto_chain_report(self):
-        ac = getattr(self, "_auto_chain", None)
-        return None if ac is None else ac["report"]
+        return None if self._auto_chain is None else self._auto_chain.report
 
     def calibrate_precision(self, probe=None):
         """Auto mode: runs the network's probe and the chain probe now (weights on a GPU); returns the chain report.  ``probe``: conditioning refmaps
         of the caller to run the chain on (re-measured for these rows)."""
-        ac = getattr(self, "_auto_chain", None)
-        if ac is not None and probe is not None:
-            ac["probe"] = _lib.require_gpu_tensor(probe, "probe").detach()
-            ac["done"] = {k: v for k, v in ac["done"].items() if k[-1] != "data"}
+        if self._auto_chain is not None and probe is not None:
+            self._auto_chain.set_probe(_lib.require_gpu_tensor(probe, "probe").detach())
         self.model.diffusion_model.calibrate_precision()
         self._auto_chain_probe()
         return self.auto_chain_report
 
-    @torch.no_grad()
     def _auto_chain_probe(self, data=None) -> None:
-        """Where the U-Net's own probe settled on f16mx: the first eight steps of the DDIM-50 chain (eta = 1, Philox noise from a fixed key: the steps with the
-        largest 1 / sqrt(alpha_bar) amplification) from a seeded x_T, in f16mx and in f16x3; f16mx is kept only if every row of the state agrees to
-        `tolerance` (5e-5, half the contract), otherwise the network runs in f16x3 for these weights.  The conditioning rows: the CALLER's (``data`` = the
-        conditioning a sampler was called with, or the ``probe`` of set_precision / calibrate_precision; first and middle row at their own size), once
-        per weight signature -- else two seeded synthetic refmaps at 128x128."""
-        ac = getattr(self, "_auto_chain", None)
-        unet = self.model.diffusion_model
-        if ac is None or ac["busy"] or unet.auto_report is None:
+        """The chain of autoprec.ChainProbe: the first eight steps of the DDIM-50 chain (eta = 1, Philox noise from a fixed key: the steps with the
+        largest 1 / sqrt(alpha_bar) amplification) from a seeded x_T, conditioned on rows of ``data``.  (ddim_sampling comes back here through _engine: the
+        probe is busy then and returns at once.)"""
+        ac, unet = self._auto_chain, self.model.diffusion_model
+        if ac is None:
             return
-        if data is None:
-            data = ac.get("probe")
-        sigs = (unet._active_set, unet.__dict__["_auto"]["sig"])
-        key = sigs + ("data" if data is not None else "synth",)
-        if data is None and sigs + ("data",) in ac["done"]:
-            key = sigs + ("data",)  # (measured on the caller's rows before: that record stands)
-        if key in ac["done"]:
-            ac["report"] = ac["done"][key]
-            return
-        if unet.precision != "f16mx":
-            return
-        ac["busy"] = True
-        try:
-            from . import synth
-            from .ddim import DDIMSampler
 
-            dev = next(unet.parameters()).device
-            if data is not None:
-                cond = data[[0, data.shape[0] // 2]] if data.shape[0] > 1 else data[:1]
-                cond = cond.detach().to(dev, torch.float32).contiguous()
-                B, H, W = cond.shape[0], cond.shape[2], cond.shape[3]
-            else:
-                B, H, W = 2, 128, 128
-                cond = synth.synth_refmaps(B, H, W, 4321).to(dev)
-            x_T = torch.randn((B, 3, H, W), generator=torch.Generator().manual_seed(20261004)).to(dev)
+        def run_chain(cond):
+            x_T = torch.randn((cond.shape[0], 3, *cond.shape[2:]), generator=torch.Generator().manual_seed(20261004)).to(cond.device)
             smp = DDIMSampler(self)
             smp.make_schedule(50, ddim_eta=1.0, verbose=False)
+            return smp.ddim_sampling(cond, tuple(x_T.shape), x_T=x_T, seed=20261004, num_steps=ac.steps, log_every_t=0, verbose=False)[0]
 
-            def chain():
-                x, _ = smp.ddim_sampling(cond, (B, 3, H, W), x_T=x_T, seed=20261004, num_steps=ac["steps"], log_every_t=0, verbose=False)
-                return x.double().flatten(1)
+        ac.measure({"unet": unet}, unet._active_set, run_chain, data, next(unet.parameters()).device)
 
-            a = chain()
-            unet._set_mode("f16x3")
-            b = chain()
-            rows = ((a - b).norm(dim=1) / b.norm(dim=1).clamp_min(1e-300)).tolist()
-            err = max(rows)
-            kept = err <= ac["tolerance"] and bool(torch.isfinite(a).all())
-            if kept:
-                unet._set_mode("f16mx")
-            else:
-                unet.auto_override("f16x3", f"chain probe: {ac['steps']} DDIM steps differ from f16x3 by {err:.2e} > {ac['tolerance']:.0e}")
-            ac["report"] = {"kept": kept, "rel_l2_chain_vs_f16x3": err, "rows": [float(f"{r:.3e}") for r in rows], "steps": ac["steps"], "tolerance": ac["tolerance"],
-                            "probe_source": "caller" if data is not None else "synthetic",
-                            "probe": f"{B}x3x{H}x{W} {'conditioning rows of the caller' if data is not None else 'seeded refmaps'}: first {ac['steps']} steps of the DDIM-50 chain (eta 1), worst row"}
-            ac["done"][key] = ac["report"]
-        finally:
-            ac["busy"] = False
+    def _engine(self, cond=None):
+        """The U-Net's engine handle behind the auto mode's chain probe (which may move the network to f16x3 for these weights); ``cond``: the
+        conditioning the caller is about to sample with -- the chain probe runs on rows of it (once per weight signature)."""
+        unet = self.model.diffusion_model
+        h = unet.engine_handle()
+        if self._auto_chain is not None:
+            self._auto_chain_probe(cond)
+            h = unet.engine_handle()
+        return h
 
     def get_learned_conditioning(self, c):
         if self.cond_stage_forward is None:
@@ -363,11 +333,7 @@ class LatentDiffusion(DDPM):
         if start_T is not None:
             T = min(T, start_T)
         noise = None if noise is None else _lib.require_gpu_tensor(noise, "noise")
-        unet = self.model.diffusion_model
-        h = unet.engine_handle()
-        if getattr(self, "_auto_chain", None) is not None:  # auto mode: the chain probe may move the network to f16x3 for these weights
-            self._auto_chain_probe(c)  # (on rows of the caller's conditioning, once per weight signature)
-            h = unet.engine_handle()
+        h = self._engine(c)
         L = _lib.lib()
         n, _, hh, ww = shape
         ws = self._ws.get(int(L.drm_sampler_workspace_bytes(h, n, hh, ww)), dev)
@@ -457,8 +423,6 @@ class ObsNetDiffusion(LatentDiffusion):
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
         """models/obsnet.py:566-583."""
         if ddim:
-            from .ddim import DDIMSampler
-
             ddim_sampler = DDIMSampler(self)
             shape = (self.channels, self.image_size, self.image_size)
             samples, intermediates = ddim_sampler.sample(

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .autoprec import ProbeState, tensor_sig, worst_row_rel_l2
 
 _ZERO_INIT_SUFFIXES = (".out_layers.3.weight", ".out_layers.3.bias", ".proj_out.weight", ".proj_out.bias")
 
@@ -105,6 +106,7 @@ class _HipUNetBase(nn.Module):
         self._active_set = "live"
         self._ema_source: Optional[List[torch.Tensor]] = None
         self.precision = "fp32"
+        self._auto: Optional[ProbeState] = None  # set in auto mode (autoprec.py)
         # parameter table straight from the engine == reference state_dict() order
         n = L.drm_unet_param_count(h)
         self._keys: List[str] = []
@@ -151,7 +153,7 @@ class _HipUNetBase(nn.Module):
             return self.set_precision_auto()
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {list(self.PRECISIONS) + ['auto']}")
-        self.__dict__["_auto"] = None
+        self._auto = None
         return self._set_mode(precision)
 
     def _set_mode(self, precision: str) -> "._HipUNetBase":
@@ -162,19 +164,19 @@ class _HipUNetBase(nn.Module):
 
     # "auto": f16mx only where it demonstrably holds.  f16mx carries about twenty times the rounding noise of exact fp32 (its cross terms keep four
     # significant bits); on the shipped architectures with O(1) GroupNorm gains that is 2e-5 .. 4e-5 per network, but a network that amplifies rounding
-    # noise -- GroupNorm gains x 10 take RefNet from 3e-6 to 9e-4 (tests/test_gpu_round4.py) -- leaves the 1e-4 contract in f16mx while f16x3 stays at
+    # noise -- GroupNorm gains x 10 take RefNet from 3e-6 to 9e-4 (tests/test_gpu_auto_precision.py) -- leaves the 1e-4 contract in f16mx while f16x3 stays at
     # 1e-5.  So the choice is MEASURED on the weights actually loaded: a seeded probe batch in f16x3 and in f16mx -- two refmap-like inputs x three
     # timesteps / embeddings spread over the schedule, six rows at 128x128, a batch that runs the kernels of production batches (GroupNorm tables from
     # their own launch, the conv-pipeline attention) rather than the sparse-launch forms of a single image; f16mx is kept only if EVERY row agrees with
     # f16x3 to `tolerance` (default 5e-5, half the contract), otherwise the network runs in f16x3.  Re-measured when the weights change; the reports are
     # kept per (weight set, weight signature), so entering / leaving ema_scope does not repeat a measurement.  The model classes add a chain probe on
-    # top (DRMNet: eight reverse steps, drmnet.py calibrate_precision; ObsNet: eight DDIM steps).
+    # top (DRMNet: eight reverse steps; ObsNet: eight DDIM steps).  The protocol of both layers (state, signature, worst-row figure, the chain probe's
+    # records and override) is autoprec.py; _auto_resolve below keeps what is this network's own: its probe batch and its forward.
     AUTO_TOLERANCE = 5e-5
     AUTO_PROBE_HW = (128, 128)
 
     def set_precision_auto(self, tolerance: Optional[float] = None, probe_hw: Optional[Tuple[int, int]] = None) -> "._HipUNetBase":
-        self.__dict__["_auto"] = {"tolerance": float(self.AUTO_TOLERANCE if tolerance is None else tolerance),
-                                  "probe_hw": tuple(self.AUTO_PROBE_HW if probe_hw is None else probe_hw), "sig": None, "report": None, "busy": False, "cache": {}}
+        self._auto = ProbeState(self.AUTO_TOLERANCE if tolerance is None else tolerance, self.AUTO_PROBE_HW if probe_hw is None else probe_hw)
         if self.precision not in ("f16x3", "f16mx"):
             self._set_mode("f16x3")  # (until the first forward has weights on a GPU to measure with)
         return self
@@ -182,8 +184,11 @@ class _HipUNetBase(nn.Module):
     @property
     def auto_report(self) -> Optional[dict]:
         """{"chosen", "rel_l2_f16mx_vs_f16x3" (worst row), "rows", "tolerance", "probe"} of the last calibration, or None (not in auto mode / not yet measured)"""
-        a = self.__dict__.get("_auto")
-        return None if a is None else a["report"]
+        return None if self._auto is None else self._auto.report
+
+    @property
+    def auto_sig(self) -> Optional[tuple]:  # signature of the weights ``auto_report`` was measured on: a model's chain probe keys its records by it
+        return None if self._auto is None else self._auto.sig
 
     def calibrate_precision(self) -> Optional[dict]:
         """Runs the auto-mode measurement now (weights must be on a GPU) and returns its report; None outside auto mode."""
@@ -192,37 +197,37 @@ class _HipUNetBase(nn.Module):
 
     def auto_override(self, mode: str, why: str) -> None:
         """A model-level chain probe (DRMNet / ObsNet calibrate_precision) overrules the per-network choice for the current weights."""
-        a = self.__dict__.get("_auto")
-        if a is None or a["report"] is None:
+        a = self._auto
+        if a is None or a.report is None:
             return
-        a["report"] = dict(a["report"], chosen=mode, overridden_by=why)
-        a["cache"][(self._active_set, a["sig"])] = a["report"]
+        a.report = dict(a.report, chosen=mode, overridden_by=why)
+        a.cache[(self._active_set, a.sig)] = a.report
         if self.precision != mode:
             self._set_mode(mode)
 
     @torch.no_grad()
     def _auto_resolve(self) -> None:
-        a = self.__dict__.get("_auto")
-        if a is None or a["busy"]:
+        a = self._auto
+        if a is None or a.busy:
             return
         ps = self.param_tensors() if self._active_set == "live" else self._ema_source
         if not ps or not ps[0].is_cuda:
             return
-        sig = tuple((p.data_ptr(), p._version) for p in ps)
-        if sig == a["sig"]:
+        sig = tensor_sig(ps)
+        if sig == a.sig:
             return
-        known = a["cache"].get((self._active_set, sig))
+        known = a.cache.get((self._active_set, sig))
         if known is not None:  # measured before on exactly these tensors (live <-> EMA toggling)
-            a["sig"], a["report"] = sig, known
+            a.sig, a.report = sig, known
             if self.precision != known["chosen"]:
                 self._set_mode(known["chosen"])
             return
-        a["busy"] = True
+        a.busy = True
         try:
             from . import synth
 
             dev = ps[0].device
-            h, w = a["probe_hw"]
+            h, w = a.probe_hw
             down = 2 ** (len(self.channel_mult) - 1)
             h, w = max(down, h // down * down), max(down, w // down * down)
             gen = torch.Generator().manual_seed(20261003)
@@ -243,16 +248,15 @@ class _HipUNetBase(nn.Module):
             for mode in ("f16x3", "f16mx"):
                 self._set_mode(mode)
                 outs[mode] = self._run(x, None, t_emb, ts).double().flatten(1)
-            rows = ((outs["f16mx"] - outs["f16x3"]).norm(dim=1) / outs["f16x3"].norm(dim=1).clamp_min(1e-300)).tolist()
-            err = max(rows)
-            chosen = "f16mx" if err <= a["tolerance"] and bool(torch.isfinite(outs["f16mx"]).all()) else "f16x3"
+            err, rows = worst_row_rel_l2(outs["f16mx"], outs["f16x3"])
+            chosen = "f16mx" if err <= a.tolerance and bool(torch.isfinite(outs["f16mx"]).all()) else "f16x3"
             self._set_mode(chosen)
-            a["sig"] = sig
-            a["report"] = {"chosen": chosen, "rel_l2_f16mx_vs_f16x3": err, "rows": [float(f"{r:.3e}") for r in rows], "tolerance": a["tolerance"],
+            a.sig = sig
+            a.report = {"chosen": chosen, "rel_l2_f16mx_vs_f16x3": err, "rows": [float(f"{r:.3e}") for r in rows], "tolerance": a.tolerance,
                            "probe": f"{n_in * n_t}x{self.in_channels}x{h}x{w}: {n_in} seeded refmap-like inputs x {n_t} timesteps / embeddings, worst row"}
-            a["cache"][(self._active_set, sig)] = a["report"]
+            a.cache[(self._active_set, sig)] = a.report
         finally:
-            a["busy"] = False
+            a.busy = False
 
     # ------------------------------------------------------------------ weights
     def param_tensors(self) -> List[torch.Tensor]:
@@ -289,7 +293,7 @@ class _HipUNetBase(nn.Module):
         self._auto_resolve()
         which = self._active_set
         ps = self.param_tensors() if which == "live" else self._ema_source
-        sig = (self.precision,) + tuple((p.data_ptr(), p._version) for p in ps)
+        sig = (self.precision,) + tensor_sig(ps)
         L = _lib.lib()
         if force or sig != self._set_sig[which]:
             dev = ps[0].device
