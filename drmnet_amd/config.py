@@ -18,9 +18,9 @@ TARGET_REMAP: Dict[str, str] = {
     "ldm.models.autoencoder.IdentityFirstStage": "drmnet_amd.wrappers.IdentityFirstStage",
     "dataset.basedataset.BaseDataset": "drmnet_amd.dataset.BaseDataset",
     "dataset.parametricrefmap.ParametricRefmapDataset": "drmnet_amd.dataset.ParametricRefmapDataset",
-    # the reflectance-map renderer is csrc/render.hip; the mesh path tracer of the training data stays out of scope (Mitsuba 3 / OptiX)
+    # the reflectance-map renderer is csrc/render.hip; the mesh renderer is csrc/mesh.hip + render.hip: direct light, no shadow rays
     "utils.mitsuba3_utils.MitsubaRefMapRenderer": "drmnet_amd.render.RefMapRenderer",
-    "utils.mitsuba3_utils.MitsubaOrthoRenderer": "drmnet_amd.wrappers.NullRenderer",
+    "utils.mitsuba3_utils.MitsubaOrthoRenderer": "drmnet_amd.mesh.MeshRenderer",
 }
 
 

@@ -234,6 +234,21 @@ int launch_render_refmap_views(const float* z, int L, const float* env, const fl
 size_t render_light_workspace_bytes(int B, int EH, int EW, int light_samples);
 int launch_render_refmap_lit(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
                              int flip, int light_samples, void* workspace, size_t workspace_bytes, hipStream_t s);
+// object images of a triangle mesh (see drm_render_mesh): visibility in mesh.hip, shading in render.hip next to the lobe code it shares.
+// The workspace holds [B][F] face records of kMeshRecordWords 32-bit words, then [B][H S][W S] hits of kMeshHitWords words.
+//   record: words 0-5 the view-space (x, y) of the three vertices, 6-8 their view-space z, 9 the signed 1 / (twice the screen area),
+//   10-13 the screen box (xmin, xmax, ymin, ymax; an empty box (+inf, -inf) on a skipped face), 14-16 the vertex indices (int32),
+//   17 the valid flag (int32), 18-19 padding
+//   hit: (face id as int32 or -1, u, v, view-space z): the point is (1 - u - v) p0 + u p1 + v p2
+constexpr int kMeshRecordWords = 20, kMeshHitWords = 4;
+constexpr int kMeshRecIndex = 14, kMeshRecValid = 17;
+size_t render_mesh_workspace_bytes(long long F, int B, int H, int W, int subpixel);
+// the two visibility launches: records of every (row, face), then the nearest covering face of every film sample.  view [B][9] or null.
+int launch_mesh_visibility(const float* positions, const int32_t* faces, long long V, long long F, const float* view, int B, int H, int W, int subpixel,
+                           float* records, float* hits, hipStream_t s);
+int launch_render_mesh(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
+                       const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
+                       int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s);
 // validation losses (losses.hip): see drm_validation_losses
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,

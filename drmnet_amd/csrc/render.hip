@@ -18,6 +18,10 @@
 // wide can fall between the strata of a rough lobe.  drm_render_refmap_lit adds a third technique, M directions drawn from the map's own
 // light density, and combines the three with lobe-separated multiple importance sampling (power heuristic, beta = 2): see "light density"
 // below.  The plain instantiations (LIGHT = false) are the kernels they always were.
+//
+// Object images of meshes (drm_render_mesh): mesh.hip finds which face every film sample sees; mesh_shade_kernel here shades the hit with
+// normal_lane_sum, the per-normal body of the sphere's sum, so a mesh point is shaded exactly as the sphere point with the same normal
+// (direct light, no self-shadowing, no interreflection).
 #include "common.h"
 
 namespace drm {
@@ -241,117 +245,125 @@ __host__ __device__ __forceinline__ float env_lookup_pdf(const float* __restrict
   return val * sc * norm / fmaxf(sqrtf(w.x * w.x + w.z * w.z), 1e-6f);
 }
 
-// one lane's share of pixel (i, j): every sub-pixel, the grid points q = lane, lane + lanes, ... of both lobes, summed in that order
-// into acc (unnormalised).  env == nullptr: white environment (L = 1).
+// one lane's share of the radiance a surface point with unit normal n (n.z > -1; the callers pass n.z > 0) reflects toward the viewer at +z:
+// the grid points q = lane, lane + lanes, ... of both lobes, summed in that order into acc (unnormalised).  env == nullptr: white
+// environment (L = 1).  The sphere (pixel_lane_sum) and the mesh (mesh_shade_kernel) share this body.
 // LIGHT: lt.norm > 0 adds the light technique: every lobe sample is weighted by the power heuristic against the n_L = lt.M light samples,
 // and the lanes stride the light table as they stride the grid, summing into accL (normalised by 1 / S^2 only: the weights hold 1 / n).
 template <bool VIEW, bool LIGHT>
-__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
-                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3], const LightTable& lt,
-                                                        float accL[3]) {
+__host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n,
+                                                         int Q, int lane, int lanes, float acc[3], const LightTable& lt, float accL[3]) {
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
   const bool lit = LIGHT && lt.norm > 0.0f;
   const float nlobe = (float)(Q * Q), nlight = (float)lt.M, sc_pole = LIGHT ? sinf(0.25f * kPi / (float)EH) : 0.0f;
+  const float cv = n.z;  // n.v for v = +z
+  // orthonormal frame (t, bt, n) (Duff et al. 2017; n.z > 0 on the whole film); v = (-n.x, -n.y, n.z) in it
+  const float ka = -1.0f / (1.0f + n.z), kb = n.x * n.y * ka;
+  const V3 t = v3(1.0f + n.x * n.x * ka, kb, -n.x), bt = v3(kb, 1.0f + n.y * n.y * ka, -n.y);
+  // visible-normal sampling frame: V = normalize(alpha v_t, alpha v_b, v_n), T1 = normalize(z x V) (x if V = z), T2 = V x T1
+  float Vx = -p.alpha * n.x, Vy = -p.alpha * n.y, Vz = cv;
+  const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
+  Vx *= vinv; Vy *= vinv; Vz *= vinv;
+  const float lensq = Vx * Vx + Vy * Vy;
+  const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
+  const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
+  const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
+  const float vs = 0.5f * (1.0f + Vz);
+  // G1(v): v = +z is above the surface on the whole film and v.h > 0 wherever it is used
+  const float g1v = LIGHT ? ggx_g1(p.a2, cv, n.x * n.x + n.y * n.y, 1.0f) : 0.0f;
+  for (int q = lane; q < Q * Q; q += lanes) {
+    const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
+    const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
+    float L[3] = {1.0f, 1.0f, 1.0f};
+    // specular lobe: h from the GGX distribution of visible normals (Heitz 2018) seen from v, l = reflect(v, h); weight F G1(l)
+    {
+      const float rs = sqrtf(u1), t1 = rs * cp;
+      const float t2 = (1.0f - vs) * sqrtf(1.0f - t1 * t1) + vs * rs * sp;
+      const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
+      const float hx = p.alpha * (t1 * T1x + t2 * T2x + tz * Vx), hy = p.alpha * (t1 * T1y + t2 * T2y + tz * Vy);
+      const float hz = fmaxf(t2 * T2z + tz * Vz, 0.0f);
+      const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
+      const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
+      const V3 h = axpy(nh, n, axpy(hy * hinv, bt, v3(hx * hinv * t.x, hx * hinv * t.y, hx * hinv * t.z)));
+      const float vh = dot3(v, h);
+      const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
+      const float cl = dot3(n, l);
+      if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
+        const float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh);
+        const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
+        if constexpr (LIGHT) {
+          // p_s(l) = G1(v) D(h) / (4 n.v): the density of l under the visible-normal sampling above
+          const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
+          const float ps = g1v * ggx_d(p.a2, nh, s2h) / (4.0f * cv);
+          const float wm = w * (lit ? power_weight(nlobe * ps, nlight * pl) : 1.0f);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * wm * L[c];
+        } else {
+          if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
+        }
+      }
+    }
+    // diffuse lobe: cosine-weighted l; weight pi diff / (n.l) = (1 - m) c shape
+    if (diffuse) {
+      const float rs = sqrtf(u1), cl = sqrtf(1.0f - u1);
+      const V3 l = axpy(cl, n, axpy(rs * sp, bt, v3(rs * cp * t.x, rs * cp * t.y, rs * cp * t.z)));
+      V3 h = v3(l.x, l.y, l.z + 1.0f);
+      const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
+      const float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd);
+      if constexpr (LIGHT) {
+        const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
+        const float wm = w * (lit ? power_weight(nlobe * cl * (1.0f / kPi), nlight * pl) : 1.0f);  // p_d(l) = n.l / pi
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * wm * L[c];
+      } else {
+        if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
+      }
+    }
+  }
+  if constexpr (LIGHT) {
+    if (lit) {
+      // the light technique: table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame
+      for (int k = lane; k < lt.M; k += lanes) {
+        const V3 wd = v3(lt.tab[k], lt.tab[lt.M + k], lt.tab[2 * lt.M + k]);
+        const float pl = lt.tab[6 * lt.M + k];
+        const V3 l = from_world<VIEW>(rot, wd);
+        const float cl = dot3(n, l);
+        if (cl > 0.0f && pl > 0.0f) {
+          V3 h = v3(l.x, l.y, l.z + 1.0f);
+          const float hinv = 1.0f / sqrtf(dot3(h, h));
+          h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
+          const float vh = h.z, nh = dot3(n, h);
+          const float D = ggx_d(p.a2, nh, cross_sq(n, h));
+          const float ps = g1v * D / (4.0f * cv);
+          const float ks = ps * ggx_g1(p.a2, cl, cross_sq(n, l), dot3(l, h));  // D G / (4 n.v)
+          const float kd = diffuse ? (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, vh) * (1.0f / kPi) : 0.0f;
+          const float a = nlight * pl, as = nlobe * ps, ad = diffuse ? nlobe * cl * (1.0f / kPi) : 0.0f;
+          const float ws = ks * (a / (as * as + a * a)), wd2 = kd * (a / (ad * ad + a * a));
+          const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            accL[c] += lt.tab[(3 + c) * lt.M + k] * ((fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * ws + p.c[c] * wd2);
+        }
+      }
+    }
+  }
+}
+
+// one lane's share of pixel (i, j) of the sphere: normal_lane_sum at every sub-pixel normal, in sub-pixel order
+template <bool VIEW, bool LIGHT>
+__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
+                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3], const LightTable& lt,
+                                                        float accL[3]) {
   for (int sy = 0; sy < S; ++sy) {
     for (int sx = 0; sx < S; ++sx) {
       const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
-      const float cv = n.z;  // n.v for v = +z
-      // orthonormal frame (t, bt, n) (Duff et al. 2017; n.z > 0 on the whole film); v = (-n.x, -n.y, n.z) in it
-      const float ka = -1.0f / (1.0f + n.z), kb = n.x * n.y * ka;
-      const V3 t = v3(1.0f + n.x * n.x * ka, kb, -n.x), bt = v3(kb, 1.0f + n.y * n.y * ka, -n.y);
-      // visible-normal sampling frame: V = normalize(alpha v_t, alpha v_b, v_n), T1 = normalize(z x V) (x if V = z), T2 = V x T1
-      float Vx = -p.alpha * n.x, Vy = -p.alpha * n.y, Vz = cv;
-      const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
-      Vx *= vinv; Vy *= vinv; Vz *= vinv;
-      const float lensq = Vx * Vx + Vy * Vy;
-      const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
-      const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
-      const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
-      const float vs = 0.5f * (1.0f + Vz);
-      // G1(v): v = +z is above the surface on the whole film and v.h > 0 wherever it is used
-      const float g1v = LIGHT ? ggx_g1(p.a2, cv, n.x * n.x + n.y * n.y, 1.0f) : 0.0f;
-      for (int q = lane; q < Q * Q; q += lanes) {
-        const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
-        const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
-        float L[3] = {1.0f, 1.0f, 1.0f};
-        // specular lobe: h from the GGX distribution of visible normals (Heitz 2018) seen from v, l = reflect(v, h); weight F G1(l)
-        {
-          const float rs = sqrtf(u1), t1 = rs * cp;
-          const float t2 = (1.0f - vs) * sqrtf(1.0f - t1 * t1) + vs * rs * sp;
-          const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
-          const float hx = p.alpha * (t1 * T1x + t2 * T2x + tz * Vx), hy = p.alpha * (t1 * T1y + t2 * T2y + tz * Vy);
-          const float hz = fmaxf(t2 * T2z + tz * Vz, 0.0f);
-          const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
-          const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
-          const V3 h = axpy(nh, n, axpy(hy * hinv, bt, v3(hx * hinv * t.x, hx * hinv * t.y, hx * hinv * t.z)));
-          const float vh = dot3(v, h);
-          const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
-          const float cl = dot3(n, l);
-          if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
-            const float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh);
-            const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-            if constexpr (LIGHT) {
-              // p_s(l) = G1(v) D(h) / (4 n.v): the density of l under the visible-normal sampling above
-              const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
-              const float ps = g1v * ggx_d(p.a2, nh, s2h) / (4.0f * cv);
-              const float wm = w * (lit ? power_weight(nlobe * ps, nlight * pl) : 1.0f);
-#pragma unroll
-              for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * wm * L[c];
-            } else {
-              if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
-#pragma unroll
-              for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
-            }
-          }
-        }
-        // diffuse lobe: cosine-weighted l; weight pi diff / (n.l) = (1 - m) c shape
-        if (diffuse) {
-          const float rs = sqrtf(u1), cl = sqrtf(1.0f - u1);
-          const V3 l = axpy(cl, n, axpy(rs * sp, bt, v3(rs * cp * t.x, rs * cp * t.y, rs * cp * t.z)));
-          V3 h = v3(l.x, l.y, l.z + 1.0f);
-          const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
-          const float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd);
-          if constexpr (LIGHT) {
-            const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
-            const float wm = w * (lit ? power_weight(nlobe * cl * (1.0f / kPi), nlight * pl) : 1.0f);  // p_d(l) = n.l / pi
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * wm * L[c];
-          } else {
-            if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
-          }
-        }
-      }
-      if constexpr (LIGHT) {
-        if (lit) {
-          // the light technique: table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame
-          for (int k = lane; k < lt.M; k += lanes) {
-            const V3 wd = v3(lt.tab[k], lt.tab[lt.M + k], lt.tab[2 * lt.M + k]);
-            const float pl = lt.tab[6 * lt.M + k];
-            const V3 l = from_world<VIEW>(rot, wd);
-            const float cl = dot3(n, l);
-            if (cl > 0.0f && pl > 0.0f) {
-              V3 h = v3(l.x, l.y, l.z + 1.0f);
-              const float hinv = 1.0f / sqrtf(dot3(h, h));
-              h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
-              const float vh = h.z, nh = dot3(n, h);
-              const float D = ggx_d(p.a2, nh, cross_sq(n, h));
-              const float ps = g1v * D / (4.0f * cv);
-              const float ks = ps * ggx_g1(p.a2, cl, cross_sq(n, l), dot3(l, h));  // D G / (4 n.v)
-              const float kd = diffuse ? (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, vh) * (1.0f / kPi) : 0.0f;
-              const float a = nlight * pl, as = nlobe * ps, ad = diffuse ? nlobe * cl * (1.0f / kPi) : 0.0f;
-              const float ws = ks * (a / (as * as + a * a)), wd2 = kd * (a / (ad * ad + a * a));
-              const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-#pragma unroll
-              for (int c = 0; c < 3; ++c)
-                accL[c] += lt.tab[(3 + c) * lt.M + k] * ((fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * ws + p.c[c] * wd2);
-            }
-          }
-        }
-      }
+      normal_lane_sum<VIEW, LIGHT>(p, env, rot, EH, EW, n, Q, lane, lanes, acc, lt, accL);
     }
   }
 }
@@ -398,6 +410,73 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
       else
         out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale;
     }
+  }
+}
+
+// Shading of the hits of mesh.hip's visibility pass.  grid: ceil(B H W / 4) workgroups of 4 waves; wave = pixel (row b, i, j) of the object image,
+// lit by env[b] and seen through view[b].  For each of the pixel's S x S samples, in sample order, the wave fetches the hit (one address: a
+// broadcast), forms the shading normal -- the barycentric mix of the face's vertex normals, taken into the view frame (Rot^T n) and normalised;
+// a zero mix stays zero -- and, where n.z > 0, runs the sphere's normal_lane_sum: the same Q x Q grids, per-lane order and butterfly, so a
+// mesh point is shaded exactly as the sphere point with that normal.  Lane 0 also writes the means of the normals, of 1.1 - z over the
+// hits, and the hit fraction.  rec / hits: the workspace halves of launch_mesh_visibility.
+template <bool VIEW>
+__global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
+                                                         const float* __restrict__ vnormal, const float* __restrict__ rec, const float* __restrict__ hits,
+                                                         float* __restrict__ image, float* __restrict__ normal, float* __restrict__ depth,
+                                                         float* __restrict__ alpha, int B, long long F, int H, int W, int EH, int EW, int Q, int S) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
+  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
+  const int rem = (int)(pix - (long long)b * H * W);
+  const int i = rem / W, j = rem - (rem / W) * W;
+  const Principled p = principled(z + 6 * (size_t)b);
+  const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+  const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+  const float4* hit = reinterpret_cast<const float4*>(hits) + (size_t)b * H * S * W * S;
+  const float* records = rec + (size_t)b * F * kMeshRecordWords;
+  const LightTable lt{nullptr, 0, 0.0f};
+  float acc[3] = {0.0f, 0.0f, 0.0f}, unused[3] = {0.0f, 0.0f, 0.0f};
+  float nsum[3] = {0.0f, 0.0f, 0.0f}, dsum = 0.0f;
+  int count = 0;
+  for (int sy = 0; sy < S; ++sy) {
+    for (int sx = 0; sx < S; ++sx) {
+      const float4 h = hit[((size_t)i * S + sy) * W * S + (size_t)j * S + sx];
+      const int f = __float_as_int(h.x);
+      if (f < 0) continue;  // (wave-uniform: every lane read the same hit)
+      const float* r = records + (size_t)f * kMeshRecordWords;
+      const float* n0 = vnormal + 3 * (size_t)__float_as_int(r[kMeshRecIndex]);
+      const float* n1 = vnormal + 3 * (size_t)__float_as_int(r[kMeshRecIndex + 1]);
+      const float* n2 = vnormal + 3 * (size_t)__float_as_int(r[kMeshRecIndex + 2]);
+      const float w0 = 1.0f - h.y - h.z;
+      V3 n = from_world<VIEW>(rot, v3(w0 * n0[0] + h.y * n1[0] + h.z * n2[0], w0 * n0[1] + h.y * n1[1] + h.z * n2[1],
+                                      w0 * n0[2] + h.y * n1[2] + h.z * n2[2]));
+      const float len2 = dot3(n, n);
+      const float ninv = len2 > 0.0f ? 1.0f / sqrtf(len2) : 0.0f;  // (a NaN mix fails the comparison: zero as well)
+      n = len2 > 0.0f ? v3(n.x * ninv, n.y * ninv, n.z * ninv) : v3(0.0f, 0.0f, 0.0f);
+      nsum[0] += n.x;
+      nsum[1] += n.y;
+      nsum[2] += n.z;
+      dsum += 1.1f - h.w;
+      ++count;
+      if (n.z > 0.0f) normal_lane_sum<VIEW, false>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lt, unused);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], o);
+  }
+  if (lane == 0) {
+    const float inv_s2 = 1.0f / (float)(S * S), scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
+    const size_t at = (size_t)i * W + j, plane = (size_t)H * W;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      image[((size_t)b * 3 + c) * plane + at] = acc[c] * scale;
+      if (normal) normal[((size_t)b * 3 + c) * plane + at] = nsum[c] * inv_s2;
+    }
+    if (depth) depth[(size_t)b * plane + at] = count > 0 ? dsum / (float)count : 0.0f;
+    if (alpha) alpha[(size_t)b * plane + at] = (float)count * inv_s2;
   }
 }
 
@@ -601,6 +680,30 @@ int launch_render_refmap_lit(const float* z, int L, const float* env, const floa
   hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(light_samples / 4), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
   hipLaunchKernelGGL((view ? refmap_render_kernel<true, true> : refmap_render_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
                      env, view, out, L * B, B, R, EH, EW, quad, subpixel, flip ? 1 : 0, ws, light_samples);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+int launch_render_mesh(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
+                       const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
+                       int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  DRM_REQUIRE(positions && normals && faces && z && image, "render_mesh: null pointer");
+  DRM_REQUIRE(quad >= 1 && quad <= 1024, "render_mesh: quad in [1, 1024]");
+  DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), "render_mesh: envmap must be EH x EW with EH, EW >= 1");
+  const size_t need = render_mesh_workspace_bytes(F, B, H, W, subpixel);
+  DRM_REQUIRE(need != 0 && V >= 1 && V <= 0x7fffffffLL,
+              "render_mesh: 1 <= F < 2^24 faces, V >= 1 vertices, 1 <= B <= 65535 rows, H and W in [1, 4096], subpixel in [1, 4]");
+  const long long blocks = ((long long)B * H * W + kRenderWaves - 1) / kRenderWaves;
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_mesh: B H W too large for one launch");
+  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
+    set_error("render_mesh: workspace must be 16-byte aligned and hold drm_render_mesh_workspace_bytes = " + std::to_string(need) + " bytes");
+    return DRM_ERR_WORKSPACE;
+  }
+  float* records = static_cast<float*>(workspace);
+  float* hits = records + (size_t)B * F * kMeshRecordWords;
+  DRM_TRY(launch_mesh_visibility(positions, faces, V, F, view, B, H, W, subpixel, records, hits, s));
+  hipLaunchKernelGGL((view ? mesh_shade_kernel<true> : mesh_shade_kernel<false>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, view,
+                     normals, records, hits, image, normal, depth, alpha, B, F, H, W, env ? EH : 1, env ? EW : 1, quad, subpixel);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -1,0 +1,233 @@
+"""Object images of triangle meshes -- the input side of the chain -- on csrc/mesh.hip (visibility) and csrc/render.hip (shading).
+
+Operator surface of the reference's mesh helpers (utils/mitsuba3_utils.py): ``MeshRenderer`` stands in for ``MitsubaOrthoRenderer``
+(:433-564), ``load_mesh`` keeps its name and its result (:690-699: a dict of ``vertex_positions`` [V, 3] float32, ``vertex_normals``
+[V, 3] float32 and ``faces`` [F, 3] int32, here torch tensors on the host), ``normalize_mesh`` is the scaling of
+scripts/preprocess_shape.py:40.  Every visible point is shaded as the reflectance-map renderer shades the sphere point with the same
+normal: direct light from the environment map, no self-shadowing, no interreflection, black background.  Loading a mesh
+and constructing a renderer do not touch the GPU; rendering runs there (no CPU path).
+"""
+from __future__ import annotations
+
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .render import QUAD, SUBPIXEL, _device, canonical_rows, view_rotation
+
+Mesh = Dict[str, torch.Tensor]
+_KEYS = ("vertex_positions", "vertex_normals", "faces")
+
+
+def _as_mesh(positions, normals, faces) -> Mesh:
+    return {"vertex_positions": torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)),
+            "vertex_normals": torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)),
+            "faces": torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3))}
+
+
+def area_weighted_normals(positions: np.ndarray, faces: np.ndarray) -> np.ndarray:
+    """Unit vertex normals [V, 3]: the sum over a vertex's faces of the face's cross product (e1 x e2: its normal times twice its area),
+    normalised; a vertex no face uses gets (0, 0, 0).  float64 on the host."""
+    p = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    fn = np.cross(p[f[:, 1]] - p[f[:, 0]], p[f[:, 2]] - p[f[:, 0]])
+    n = np.zeros_like(p)
+    for k in range(3):
+        np.add.at(n, f[:, k], fn)
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.divide(n, length, out=np.zeros_like(n), where=length > 0)
+
+
+def load_obj(path: Union[str, Path]) -> Mesh:
+    """A Wavefront OBJ as the reference's mesh dict.  Reads ``v``, ``vn`` and ``f`` (corners written ``a``, ``a/b``, ``a//c`` or ``a/b/c``;
+    negative indices count back from the last element read so far; polygons are fan-triangulated around their first corner); everything
+    else (``vt``, groups, materials) is ignored.  A vertex is emitted per distinct (v, vn) pair, in order of first use, so a position used
+    with two normals is split.  A file without ``vn`` gets area-weighted vertex normals computed here on the host
+    (``area_weighted_normals``); a file that gives normals to only some corners is a ValueError."""
+    v: List[List[float]] = []
+    vn: List[List[float]] = []
+    corners: Dict[Tuple[int, int], int] = {}
+    faces: List[List[int]] = []
+    with_normal = 0
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                v.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "vn":
+                vn.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "f":
+                ids = []
+                for c in tok[1:]:
+                    part = c.split("/")
+                    a = int(part[0])
+                    a = a - 1 if a > 0 else len(v) + a
+                    b = -1
+                    if len(part) == 3 and part[2]:
+                        b = int(part[2])
+                        b = b - 1 if b > 0 else len(vn) + b
+                        with_normal += 1
+                        if not 0 <= b < len(vn):
+                            raise ValueError(f"{path}: normal index {part[2]} out of range")
+                    if not 0 <= a < len(v):
+                        raise ValueError(f"{path}: vertex index {part[0]} out of range")
+                    ids.append(corners.setdefault((a, b), len(corners)))
+                if len(ids) < 3:
+                    raise ValueError(f"{path}: a face needs at least three corners")
+                faces += [[ids[0], ids[k], ids[k + 1]] for k in range(1, len(ids) - 1)]
+    if not faces:
+        raise ValueError(f"{path}: no faces")
+    if len({b < 0 for _, b in corners}) > 1:
+        raise ValueError(f"{path}: some face corners carry a normal index and some do not")
+    pairs = sorted(corners, key=corners.get)
+    positions = np.array([v[a] for a, _ in pairs], dtype=np.float64)
+    f = np.array(faces, dtype=np.int32)
+    normals = np.array([vn[b] for _, b in pairs], dtype=np.float64) if with_normal else area_weighted_normals(positions, f)
+    return _as_mesh(positions, normals, f)
+
+
+def normalize_mesh(obj: Mesh) -> Mesh:
+    """scripts/preprocess_shape.py:40: the positions scaled by 0.9 / max |v|, so the mesh fits the film (x in [-1, 1]) from every view.
+    Returns a new dict; normals and faces are shared."""
+    p = obj["vertex_positions"].to(torch.float32)
+    return {"vertex_positions": p * (0.9 / torch.linalg.vector_norm(p, dim=-1).max()), "vertex_normals": obj["vertex_normals"], "faces": obj["faces"]}
+
+
+def load_mesh(path: Union[str, Path]) -> Mesh:
+    """utils/mitsuba3_utils.py:690-699: ``.obj`` through ``load_obj``, or a ``.pt`` dict as scripts/preprocess_shape.py:48 writes it."""
+    path = Path(path)
+    if path.suffix == ".obj":
+        return load_obj(path)
+    if path.suffix == ".pt":
+        blob = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(blob, dict) or any(k not in blob for k in _KEYS):
+            raise ValueError(f"{path}: expected a dict with {_KEYS}")
+        return _as_mesh(*(torch.as_tensor(blob[k]).detach().cpu().numpy() for k in _KEYS))
+    raise ValueError(f"{path}: a mesh is an .obj file or a .pt dict (got {path.suffix!r})")
+
+
+def _mesh_on(obj: Mesh, dev: torch.device):
+    if not obj or any(k not in obj for k in _KEYS):
+        raise ValueError(f"a mesh is a dict with {_KEYS}")
+    pos = torch.as_tensor(obj["vertex_positions"]).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    nrm = torch.as_tensor(obj["vertex_normals"]).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    faces = torch.as_tensor(obj["faces"]).to(dev, torch.int32).reshape(-1, 3).contiguous()
+    if nrm.shape[0] != pos.shape[0]:
+        raise ValueError(f"vertex_normals has {nrm.shape[0]} rows, vertex_positions {pos.shape[0]}")
+    return pos, nrm, faces
+
+
+@torch.no_grad()
+def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, image_size, view_from=None,
+                quad: int = QUAD, subpixel: int = SUBPIXEL):
+    """One call of drm_render_mesh: one mesh, lit and seen B ways.  z [B, P], envmaps [B, EH, EW, 3] (or None: white), view_from [B, 3] (or
+    None: +z), image_size H or (H, W) -> (image [B, 3, H, W], normal [B, 3, H, W] in the view frame, depth [B, 1, H, W], alpha [B, H, W]).
+    GPU only: a ``z`` or ``envmaps`` tensor on the CPU, or a machine without a GPU, is a RuntimeError (the mesh itself and ``view_from`` are
+    host data and are brought over)."""
+    for name, t in (("z", z), ("envmaps", envmaps)):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise RuntimeError(f"render_mesh runs on the GPU only (drmnet_amd has no CPU path): {name} is on {t.device}")
+    dev = _device(z, envmaps)
+    z = torch.as_tensor(z).to(dev)
+    if z.dim() != 2:
+        raise ValueError(f"z must be [B, P], got {tuple(z.shape)}")
+    B = int(z.shape[0])
+    H, W = (int(image_size), int(image_size)) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
+    rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
+    pos, nrm, faces = _mesh_on(obj, dev)
+    env, EH, EW = None, 0, 0
+    if envmaps is not None:
+        env = envmaps.to(dev, torch.float32)
+        if env.dim() != 4 or env.shape[0] != B or env.shape[3] != 3:
+            raise ValueError(f"envmaps must be [B={B}, H, W, 3], got {tuple(env.shape)}")
+        env = env.contiguous()
+        EH, EW = int(env.shape[1]), int(env.shape[2])
+    view = None
+    if view_from is not None:
+        view = view_rotation(view_from)
+        if view.shape[0] != B:
+            raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
+        view = view.to(dev)
+    lib = _lib.lib()
+    V, F = int(pos.shape[0]), int(faces.shape[0])
+    nbytes = int(lib.drm_render_mesh_workspace_bytes(F, B, H, W, int(subpixel)))
+    if nbytes == 0 or V < 1:
+        raise ValueError(f"render_mesh: F = {F} faces in [1, 2^24), V = {V} >= 1, B = {B} in [1, 65535], image_size {(H, W)} in [1, 4096], "
+                         f"subpixel = {subpixel} in [1, 4]")
+    image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    normal = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.drm_render_mesh(pos.data_ptr(), nrm.data_ptr(), faces.data_ptr(), V, F, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view),
+                                       image.data_ptr(), normal.data_ptr(), depth.data_ptr(), alpha.data_ptr(), B, H, W, EH, EW, int(quad),
+                                       int(subpixel), ws.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    return image, normal, depth, alpha
+
+
+class MeshRenderer:
+    """MitsubaOrthoRenderer (utils/mitsuba3_utils.py:433-564) on drm_render_mesh: an orthographic view of a smooth-shaded triangle mesh under
+    the scene's environment map.  Differences from Mitsuba's ``path`` integrator, all by design: direct light only, no
+    self-shadowing, no interreflection, and a black background.  The integral is the deterministic quadrature of the reflectance-map
+    renderer, so ``spp`` and ``denoise`` are accepted and ignored.  ``init_view_from`` may be any position off the +-y axis.  The scene
+    state -- environment map, view and mesh -- is kept across ``rendering`` calls as the reference's scene keeps it.  Construction does not
+    touch the GPU."""
+
+    def __init__(self, image_size, spp: int = 1024, envmap_size=(1000, 2000), denoise: Optional[str] = None, return_normal: bool = False,
+                 return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
+                 subpixel: int = SUBPIXEL):
+        self.image_size = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(s) for s in image_size)
+        self.envmap_size = tuple(int(s) for s in envmap_size)
+        self.spp, self.denoise = spp, denoise
+        self.return_normal, self.return_depth = bool(return_normal), bool(return_depth)
+        self.brdf_param_names = brdf_param_names
+        self.quad, self.subpixel = int(quad), int(subpixel)
+        self._view_from = torch.as_tensor(init_view_from).detach().to("cpu", torch.float32).reshape(3)
+        view_rotation(self._view_from)  # (a view along +-y is a ValueError here, not at the first render)
+        self._envmap: Optional[torch.Tensor] = None  # the scene's map; None = the initial all-zero bitmap of envmap_size
+        self._obj: Optional[Mesh] = None  # the scene's mesh; None = none given yet
+
+    def rendering(self, z, brdf_param_names, envmap: Optional[torch.Tensor] = None, view_from=None, obj: Mesh = {}, sensor=0, spp: int = 0,
+                  new_scene: bool = False, channel_first: bool = False):
+        """utils/mitsuba3_utils.py:543-564: the object image [H, W, 3] ([3, H, W] with channel_first), or the list [image, normal [H, W, 3],
+        depth [H, W, 1]] restricted to what ``return_normal`` / ``return_depth`` ask for.  ``envmap`` [EH, EW, 3], ``view_from`` [3] and
+        ``obj`` (a mesh dict; {} = none) replace the scene's and stay with it for later calls; with ``new_scene`` they hold for this call
+        only (and an envmap is required).  No mesh given and none kept is a ValueError."""
+        if not (isinstance(sensor, int) and sensor == 0):
+            raise NotImplementedError("only the scene's own sensor (sensor=0) is modelled")
+        if envmap is not None:
+            assert isinstance(envmap, torch.Tensor) and envmap.dim() == 3 and not torch.isnan(envmap[0, 0, 0]), f"envmap [{envmap.shape}]"
+        mesh = obj if obj else self._obj
+        if not mesh:
+            raise ValueError("no mesh: pass obj = {vertex_positions, vertex_normals, faces} (the scene keeps it for later calls)")
+        dev = _device(z, envmap)
+        if new_scene:
+            if envmap is None:
+                raise ValueError("new_scene needs an envmap")
+            env = envmap.to(dev)
+            view = self._view_from if view_from is None else view_from
+        else:
+            if obj:
+                self._obj = dict(zip(_KEYS, _mesh_on(obj, dev)))
+                mesh = self._obj
+            if envmap is not None:
+                self._envmap = envmap.to(dev)
+            if self._envmap is None:
+                self._envmap = torch.zeros(*self.envmap_size, 3, device=dev)
+            env = self._envmap
+            if view_from is not None:
+                self._view_from = torch.as_tensor(view_from).detach().to("cpu", torch.float32).reshape(3)
+            view = self._view_from
+        z = torch.as_tensor(z).reshape(1, -1).to(dev)
+        image, normal, depth, _ = render_mesh(mesh, z, brdf_param_names or self.brdf_param_names, env[None], image_size=self.image_size,
+                                              view_from=torch.as_tensor(view).reshape(1, 3), quad=self.quad, subpixel=self.subpixel)
+        outs = [image[0]] + ([normal[0]] if self.return_normal else []) + ([depth[0]] if self.return_depth else [])
+        if not channel_first:
+            outs = [o.permute(1, 2, 0) for o in outs]
+        return outs[0] if len(outs) == 1 else outs

@@ -1,0 +1,66 @@
+"""Make the input of ``python -m drmnet_amd.estimate`` from a mesh, a BRDF and an environment map -- the forward model, run forward.
+
+    python -m drmnet_amd.synthesize --mesh M.obj --envmap E.exr --z m R G B r s --view_from x y z --image_size 128 --output_dir D
+
+writes into D the three files ``estimate`` reads,
+
+    image.exr    H x W x 3 radiance of the object (drmnet_amd.mesh.render_mesh: direct light, black background)
+    normal.npy   H x W x 3 float32 shading normals in the view frame (right, up, back)
+    mask.png     |normal| > 0.5: the pixels more than half covered
+
+and ``refmap.exr``: the reflectance map RefMapRenderer renders for the same (z, envmap, view), the ground truth the estimate should approach.
+``--z`` is the canonical row (metallic, base colour R G B, roughness, specular).  The mesh (.obj, or a .pt dict) is scaled to radius 0.9
+so that it fits the film from every view; without ``--envmap`` the environment is white.
+"""
+from __future__ import annotations
+
+import argparse
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from .render import QUAD
+
+# --z in the order of the canonical row, under names canonical_rows reads
+NAMES = ("metallic", "base_color.value.R", "base_color.value.G", "base_color.value.B", "roughness", "specular")
+
+
+def main(argv=None):
+    from . import file_io
+    from .mesh import load_mesh, normalize_mesh, render_mesh
+    from .render import render
+
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--mesh", type=Path, required=True, help="triangle mesh (.obj, or a .pt dict of vertex_positions / vertex_normals / faces)")
+    parser.add_argument("--envmap", type=Path, default=None, help="lat-long environment map (.exr); default: white")
+    parser.add_argument("--z", type=float, nargs=6, required=True, metavar=("m", "R", "G", "B", "r", "s"),
+                        help="metallic, base colour R G B, roughness, specular")
+    parser.add_argument("--view_from", type=float, nargs=3, default=[0.0, 0.0, 1.1], metavar=("x", "y", "z"), help="viewer position (off the +-y axis)")
+    parser.add_argument("--image_size", type=int, default=128)
+    parser.add_argument("--refmap_res", type=int, default=128, help="resolution of refmap.exr")
+    parser.add_argument("--quad", type=int, default=QUAD)
+    parser.add_argument("--output_dir", type=Path, default=Path("./outputs/"))
+    args = parser.parse_args(argv)
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("synthesize renders on the GPU (drmnet_amd has no CPU path) and no GPU is visible")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    obj = normalize_mesh(load_mesh(args.mesh))
+    z = torch.tensor([args.z], dtype=torch.float32, device=dev)
+    env = None if args.envmap is None else file_io.load_exr(args.envmap, as_torch=True).to(dev)[None]
+    view = torch.tensor([args.view_from], dtype=torch.float32)
+    image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad)
+    refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view)
+    normal = normal[0].permute(1, 2, 0).cpu().numpy()
+    mask = np.linalg.norm(normal, axis=-1) > 0.5
+    args.output_dir.mkdir(parents=True, exist_ok=True)
+    file_io.save_exr(args.output_dir / "image.exr", image[0].permute(1, 2, 0))
+    np.save(args.output_dir / "normal.npy", normal)
+    file_io.save_png(args.output_dir / "mask.png", np.repeat(mask[:, :, None].astype(np.float32), 3, axis=-1))
+    file_io.save_exr(args.output_dir / "refmap.exr", refmap[0].permute(1, 2, 0))
+    print(f"wrote image.exr, normal.npy, mask.png ({int(mask.sum())} of {mask.size} pixels) and refmap.exr to {args.output_dir}")
+
+
+if __name__ == "__main__":
+    main()

@@ -40,8 +40,8 @@ class IdentityFirstStage(nn.Module):
 
 
 class NullRenderer:
-    """Stand-in for the Mitsuba mesh renderer of the training data (MitsubaOrthoRenderer; out of scope).  The reflectance-map
-    renderer is drmnet_amd.render.RefMapRenderer."""
+    """A renderer that cannot render, for a config whose renderer is never used.  The reflectance-map renderer is
+    drmnet_amd.render.RefMapRenderer and the mesh renderer (MitsubaOrthoRenderer in the configs) is drmnet_amd.mesh.MeshRenderer."""
 
     def __init__(self, refmap_res: int = 128, **kwargs):
         self.image_size = (refmap_res, refmap_res)

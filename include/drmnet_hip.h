@@ -399,6 +399,36 @@ int drm_render_refmap_views(const float* z, int L, const float* envmap, const fl
 size_t drm_render_light_workspace_bytes(int B, int EH, int EW, int light_samples); /* 0 for arguments drm_render_refmap_lit rejects */
 int drm_render_refmap_lit(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
                           int subpixel, int flip, int light_samples, void* workspace, size_t workspace_bytes, void* stream);
+/* Object images of a triangle mesh: the input side of the chain (csrc/mesh.hip for visibility, csrc/render.hip for shading).  Replaces
+ * MitsubaOrthoRenderer.rendering (utils/mitsuba3_utils.py:433-564: an orthographic camera on a smooth-shaded mesh with image, shading-normal
+ * and depth AOVs).  Every visible point is shaded exactly as drm_render_refmap_views shades the sphere point with the same normal: direct
+ * light from the environment map, NO self-shadowing, NO interreflection (Mitsuba's path integrator has both), and the background is black,
+ * not the environment.  It is the model the reflectance map itself assumes.  Additive: the ABI version is unchanged.
+ *   One mesh per call, lit and seen B ways: vertex_positions, vertex_normals [V][3], faces [F][3] int32 (smooth shading, no back-face
+ *   culling), z [B][6], envmap [B][EH][EW][3] or NULL (white), view [B][9] or NULL (+z).
+ *   View frame.  right, up, back are the columns of the row-major Rot = view[b] (the rotation drm_render_refmap_views takes).  Mesh points
+ *   and normals enter the view frame as Rot^T p and Rot^T n; the environment is looked up at Rot l.  NULL or an exact identity multiplies
+ *   nothing.
+ *   Film samples.  H x W pixels, S x S = subpixel^2 samples per pixel, box filter.  Sample (i, sy, j, sx) is at
+ *   x = (2 (j S + sx) + 1) / (W S) - 1, y = (H / W) (1 - (2 (i S + sy) + 1) / (H S)); the ray runs along -z, and of the faces covering a
+ *   sample the one with the largest view-space z is seen.  The film spans x in [-1, 1] (a mesh normalised to radius 0.9 fits).
+ *   Coverage.  All three edge functions, oriented by the sign of the face's screen area, are >= 0 (edges inclusive).  Ties: larger z, then
+ *   the lower face index, so the result does not depend on the order faces are visited in.  Faces of zero screen area are skipped, and so is
+ *   a face with a vertex index outside [0, V), whose index is never dereferenced.
+ *   Shading normal.  The barycentric mix of the three vertex normals, in the view frame, normalised (a zero mix stays zero).  A sample with
+ *   no hit, or with n.z <= 0, contributes zero radiance.
+ *   Outputs per row b: image [3][H][W] the mean over the S^2 samples of the radiance; normal [3][H][W] the mean of the samples' unit shading
+ *   normals, zero for a miss (|normal| > 0.5 is "more than half covered", the mask the reference derives); depth [1][H][W] the mean of
+ *   1.1 - z_view over the hit samples, 0 where there are none; alpha [H][W] the hit fraction.  normal, depth and alpha may each be NULL.
+ *   Limits: quad in [1, 1024], subpixel in [1, 4], H, W in [1, 4096], 1 <= F < 2^24, V >= 1, 1 <= B <= 65535.  light_samples is not offered.
+ *   workspace: at least drm_render_mesh_workspace_bytes = 80 B F + 16 B (H S) (W S) bytes of device memory, 16-byte aligned: one record per
+ *   (row, face) and one hit per film sample, rebuilt by every call.  Three launches (mesh_setup_kernel, mesh_visibility_kernel,
+ *   mesh_shade_kernel), no atomics: bitwise reproducible, and a call of B rows equals its rows rendered one by one.
+ *   DRM_ERR_INVALID for an argument outside the limits, DRM_ERR_WORKSPACE for a missing, misaligned or short workspace: nothing is launched. */
+size_t drm_render_mesh_workspace_bytes(int64_t F, int B, int H, int W, int subpixel); /* 0 for arguments drm_render_mesh rejects */
+int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                    const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
+                    int quad, int subpixel, void* workspace, size_t workspace_bytes, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
