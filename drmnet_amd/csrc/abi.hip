@@ -3,6 +3,7 @@
 #include <cstring>
 #include <memory>
 
+#include "bvh.h"
 #include "profiler.h"
 #include "samplers.h"
 
@@ -564,6 +565,29 @@ int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, 
   return guarded([&]() -> int {
     return launch_render_mesh(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B, H, W,
                               EH, EW, quad, subpixel, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  });
+}
+
+size_t drm_mesh_bvh_bytes(int64_t F) { return mesh_bvh_bytes((long long)F); }
+
+int drm_mesh_bvh_build(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, void* bvh, size_t bytes) {
+  return guarded([&]() -> int { return mesh_bvh_build(vertex_positions, faces, (long long)V, (long long)F, bvh, bytes); });
+}
+
+int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins, const float* dirs,
+                      const int32_t* exclude, int32_t* out, int64_t N, void* stream) {
+  return guarded([&]() -> int {
+    return launch_mesh_occluded(vertex_positions, faces, (long long)V, (long long)F, bvh, origins, dirs, exclude, out, (long long)N,
+                                static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                             const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                             int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_mesh_shadowed(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B,
+                                       H, W, EH, EW, quad, subpixel, workspace, workspace_bytes, bvh, bvh_bytes, static_cast<hipStream_t>(stream));
   });
 }
 

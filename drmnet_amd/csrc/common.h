@@ -242,6 +242,10 @@ int launch_render_refmap_lit(const float* z, int L, const float* env, const floa
 //   hit: (face id as int32 or -1, u, v, view-space z): the point is (1 - u - v) p0 + u p1 + v p2
 constexpr int kMeshRecordWords = 20, kMeshHitWords = 4;
 constexpr int kMeshRecIndex = 14, kMeshRecValid = 17;
+// film position of sample column c of W S and of sample row r of H S (aspect = H / W): one definition for the visibility pass and for the
+// shadow-ray origins of the shading pass
+__host__ __device__ __forceinline__ float mesh_sample_x(int c, int WS) { return (float)(2 * c + 1) / (float)WS - 1.0f; }
+__host__ __device__ __forceinline__ float mesh_sample_y(int r, int HS, float aspect) { return aspect * (1.0f - (float)(2 * r + 1) / (float)HS); }
 size_t render_mesh_workspace_bytes(long long F, int B, int H, int W, int subpixel);
 // the two visibility launches: records of every (row, face), then the nearest covering face of every film sample.  view [B][9] or null.
 int launch_mesh_visibility(const float* positions, const int32_t* faces, long long V, long long F, const float* view, int B, int H, int W, int subpixel,
@@ -249,6 +253,10 @@ int launch_mesh_visibility(const float* positions, const int32_t* faces, long lo
 int launch_render_mesh(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
                        const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
                        int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s);
+// the same with shadow rays through the blob of drm_mesh_bvh_build (bvh.h): bvh a device pointer to bvh_bytes bytes
+int launch_render_mesh_shadowed(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
+                                const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                                int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, hipStream_t s);
 // validation losses (losses.hip): see drm_validation_losses
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,

@@ -28,8 +28,8 @@ constexpr int kTile = 16;                 // film samples per tile side
 constexpr int kChunk = kTile * kTile;     // threads of a workgroup = records per chunk
 constexpr int kListWords = 16;            // LDS words per surviving record: record words 0-13, the face id, one pad
 
-__device__ __forceinline__ float sample_x(int c, int WS) { return (float)(2 * c + 1) / (float)WS - 1.0f; }
-__device__ __forceinline__ float sample_y(int r, int HS, float aspect) { return aspect * (1.0f - (float)(2 * r + 1) / (float)HS); }
+__device__ __forceinline__ float sample_x(int c, int WS) { return mesh_sample_x(c, WS); }
+__device__ __forceinline__ float sample_y(int r, int HS, float aspect) { return mesh_sample_y(r, HS, aspect); }
 
 // grid (ceil(F / 256), B): thread = (row b, face f)
 __global__ __launch_bounds__(256) void mesh_setup_kernel(const float* __restrict__ pos, const int32_t* __restrict__ faces, const float* __restrict__ view,

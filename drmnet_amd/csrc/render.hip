@@ -21,7 +21,11 @@
 //
 // Object images of meshes (drm_render_mesh): mesh.hip finds which face every film sample sees; mesh_shade_kernel here shades the hit with
 // normal_lane_sum, the per-normal body of the sphere's sum, so a mesh point is shaded exactly as the sphere point with the same normal
-// (direct light, no self-shadowing, no interreflection).
+// (direct light, no interreflection).  drm_render_mesh_shadowed runs mesh_shade_kernel<VIEW, true>, which traces every quadrature direction
+// from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones; the plain instantiations hold no trace of it.
+#include <type_traits>
+
+#include "bvh.h"
 #include "common.h"
 
 namespace drm {
@@ -245,14 +249,36 @@ __host__ __device__ __forceinline__ float env_lookup_pdf(const float* __restrict
   return val * sc * norm / fmaxf(sqrtf(w.x * w.x + w.z * w.z), 1e-6f);
 }
 
+// Is a quadrature direction (in world space, any length) cut off before it reaches the environment?  The sphere and the unshadowed mesh ask
+// nothing (kActive = false: no call is compiled); the shadowed mesh asks the BVH from the sample's hit point.
+struct NoOcclusion {
+  static constexpr bool kActive = false;
+  __host__ __device__ __forceinline__ bool operator()(V3) const { return false; }
+};
+struct MeshOcclusion {
+  static constexpr bool kActive = true;
+  MeshRef mesh;
+  BvhView tree;
+  float o[3];       // the hit point in object space
+  int32_t exclude;  // the hit face
+  __host__ __device__ __forceinline__ bool operator()(V3 w) const {
+    const Ray r{{o[0], o[1], o[2]}, {w.x, w.y, w.z}};
+    return bvh_occluded(mesh, tree, r, exclude);
+  }
+};
+
 // one lane's share of the radiance a surface point with unit normal n (n.z > -1; the callers pass n.z > 0) reflects toward the viewer at +z:
 // the grid points q = lane, lane + lanes, ... of both lobes, summed in that order into acc (unnormalised).  env == nullptr: white
 // environment (L = 1).  The sphere (pixel_lane_sum) and the mesh (mesh_shade_kernel) share this body.
 // LIGHT: lt.norm > 0 adds the light technique: every lobe sample is weighted by the power heuristic against the n_L = lt.M light samples,
 // and the lanes stride the light table as they stride the grid, summing into accL (normalised by 1 / S^2 only: the weights hold 1 / n).
-template <bool VIEW, bool LIGHT>
+// OCC: a lobe direction with a non-zero weight is traced along to_world(rot, l), the vector the environment lookup forms; an occluded one
+// contributes nothing, an open one what it always did (not combined with LIGHT).
+template <bool VIEW, bool LIGHT, typename OCC = NoOcclusion>
 __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n,
-                                                         int Q, int lane, int lanes, float acc[3], const LightTable& lt, float accL[3]) {
+                                                         int Q, int lane, int lanes, float acc[3], const LightTable& lt, float accL[3],
+                                                         const OCC& occ = OCC()) {
+  static_assert(!(LIGHT && OCC::kActive), "the light technique is not traced");
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
@@ -300,6 +326,13 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
           const float wm = w * (lit ? power_weight(nlobe * ps, nlight * pl) : 1.0f);
 #pragma unroll
           for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * wm * L[c];
+        } else if constexpr (OCC::kActive) {
+          const V3 wl = to_world<VIEW>(rot, l);
+          if (!occ(wl)) {
+            if (env) env_lookup(env, EH, EW, wl, L);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
+          }
         } else {
           if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
 #pragma unroll
@@ -319,6 +352,13 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
         const float wm = w * (lit ? power_weight(nlobe * cl * (1.0f / kPi), nlight * pl) : 1.0f);  // p_d(l) = n.l / pi
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * wm * L[c];
+      } else if constexpr (OCC::kActive) {
+        const V3 wl = to_world<VIEW>(rot, l);
+        if (!occ(wl)) {
+          if (env) env_lookup(env, EH, EW, wl, L);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
+        }
       } else {
         if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
 #pragma unroll
@@ -419,11 +459,21 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
 // a zero mix stays zero -- and, where n.z > 0, runs the sphere's normal_lane_sum: the same Q x Q grids, per-lane order and butterfly, so a
 // mesh point is shaded exactly as the sphere point with that normal.  Lane 0 also writes the means of the normals, of 1.1 - z over the
 // hits, and the hit fraction.  rec / hits: the workspace halves of launch_mesh_visibility.
-template <bool VIEW>
+// SHADOW: every lobe direction of a hit sample is traced from the hit point -- the view-space (x_sample, y_sample, z_hit) taken to object
+// space with Rot -- through the BVH in sh, the hit face excluded.  Without it sh is an empty struct and the kernel is the one it always was.
+struct NoShadowArgs {};
+struct ShadowArgs {
+  const float* positions;
+  const int32_t* faces;
+  long long V;
+  const void* bvh;
+};
+template <bool VIEW, bool SHADOW>
 __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
                                                          const float* __restrict__ vnormal, const float* __restrict__ rec, const float* __restrict__ hits,
                                                          float* __restrict__ image, float* __restrict__ normal, float* __restrict__ depth,
-                                                         float* __restrict__ alpha, int B, long long F, int H, int W, int EH, int EW, int Q, int S) {
+                                                         float* __restrict__ alpha, int B, long long F, int H, int W, int EH, int EW, int Q, int S,
+                                                         std::conditional_t<SHADOW, ShadowArgs, NoShadowArgs> sh) {
   const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (pix >= (long long)B * H * W) return;  // (wave-uniform)
@@ -459,7 +509,15 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
       nsum[2] += n.z;
       dsum += 1.1f - h.w;
       ++count;
-      if (n.z > 0.0f) normal_lane_sum<VIEW, false>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lt, unused);
+      if constexpr (SHADOW) {
+        if (n.z > 0.0f) {
+          const V3 o = to_world<VIEW>(rot, v3(mesh_sample_x(j * S + sx, W * S), mesh_sample_y(i * S + sy, H * S, (float)H / (float)W), h.w));
+          const MeshOcclusion occ{MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
+          normal_lane_sum<VIEW, false, MeshOcclusion>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lt, unused, occ);
+        }
+      } else {
+        if (n.z > 0.0f) normal_lane_sum<VIEW, false>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lt, unused);
+      }
     }
   }
 #pragma unroll
@@ -684,9 +742,10 @@ int launch_render_refmap_lit(const float* z, int L, const float* env, const floa
   return DRM_OK;
 }
 
-int launch_render_mesh(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
-                       const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
-                       int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s) {
+// the two mesh renders: the same checks and visibility launches; `shadowed` verifies the blob (nothing is launched before that) and shades with it
+static int render_mesh_impl(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
+                            const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
+                            int subpixel, void* workspace, size_t workspace_bytes, bool shadowed, const void* bvh, size_t bvh_bytes, hipStream_t s) {
   DRM_REQUIRE(positions && normals && faces && z && image, "render_mesh: null pointer");
   DRM_REQUIRE(quad >= 1 && quad <= 1024, "render_mesh: quad in [1, 1024]");
   DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), "render_mesh: envmap must be EH x EW with EH, EW >= 1");
@@ -699,13 +758,34 @@ int launch_render_mesh(const float* positions, const float* normals, const int32
     set_error("render_mesh: workspace must be 16-byte aligned and hold drm_render_mesh_workspace_bytes = " + std::to_string(need) + " bytes");
     return DRM_ERR_WORKSPACE;
   }
+  if (shadowed) DRM_TRY(check_device_bvh(bvh, bvh_bytes, true, F, s, "render_mesh_shadowed"));
   float* records = static_cast<float*>(workspace);
   float* hits = records + (size_t)B * F * kMeshRecordWords;
   DRM_TRY(launch_mesh_visibility(positions, faces, V, F, view, B, H, W, subpixel, records, hits, s));
-  hipLaunchKernelGGL((view ? mesh_shade_kernel<true> : mesh_shade_kernel<false>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, view,
-                     normals, records, hits, image, normal, depth, alpha, B, F, H, W, env ? EH : 1, env ? EW : 1, quad, subpixel);
+  if (shadowed)
+    hipLaunchKernelGGL((view ? mesh_shade_kernel<true, true> : mesh_shade_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
+                       env, view, normals, records, hits, image, normal, depth, alpha, B, F, H, W, env ? EH : 1, env ? EW : 1, quad, subpixel,
+                       ShadowArgs{positions, faces, V, bvh});
+  else
+    hipLaunchKernelGGL((view ? mesh_shade_kernel<true, false> : mesh_shade_kernel<false, false>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
+                       env, view, normals, records, hits, image, normal, depth, alpha, B, F, H, W, env ? EH : 1, env ? EW : 1, quad, subpixel,
+                       NoShadowArgs{});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
+}
+
+int launch_render_mesh(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
+                       const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
+                       int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
+                          workspace_bytes, false, nullptr, 0, s);
+}
+
+int launch_render_mesh_shadowed(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
+                                const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                                int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, hipStream_t s) {
+  return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
+                          workspace_bytes, true, bvh, bvh_bytes, s);
 }
 
 int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {

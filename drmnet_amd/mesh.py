@@ -4,8 +4,10 @@ Operator surface of the reference's mesh helpers (utils/mitsuba3_utils.py): ``Me
 (:433-564), ``load_mesh`` keeps its name and its result (:690-699: a dict of ``vertex_positions`` [V, 3] float32, ``vertex_normals``
 [V, 3] float32 and ``faces`` [F, 3] int32, here torch tensors on the host), ``normalize_mesh`` is the scaling of
 scripts/preprocess_shape.py:40.  Every visible point is shaded as the reflectance-map renderer shades the sphere point with the same
-normal: direct light from the environment map, no self-shadowing, no interreflection, black background.  Loading a mesh
-and constructing a renderer do not touch the GPU; rendering runs there (no CPU path).
+normal: direct light from the environment map, no interreflection, black background.  Self-shadowing is opt-in
+(``shadows=True``): shadow rays through a bounding-volume hierarchy built on the host (``build_bvh``; csrc/bvh.hip), also offered on their
+own as ``occluded``.  Loading a mesh, building its BVH and constructing a renderer do not touch the GPU; rendering and ray queries run
+there (no CPU path).
 """
 from __future__ import annotations
 
@@ -122,10 +124,83 @@ def _mesh_on(obj: Mesh, dev: torch.device):
     return pos, nrm, faces
 
 
+def build_bvh(obj: Mesh) -> torch.Tensor:
+    """drm_mesh_bvh_build: the BVH of a mesh over its object-space positions, as a uint8 host tensor holding exactly the blob (header, nodes,
+    face order; layout in include/drmnet_hip.h).  Host code only: needs no GPU.  The same mesh gives the same bytes."""
+    pos = torch.as_tensor(obj["vertex_positions"]).detach().to("cpu", torch.float32).reshape(-1, 3).contiguous()
+    faces = torch.as_tensor(obj["faces"]).detach().to("cpu", torch.int32).reshape(-1, 3).contiguous()
+    lib = _lib.lib()
+    V, F = int(pos.shape[0]), int(faces.shape[0])
+    nbytes = int(lib.drm_mesh_bvh_bytes(F))
+    if nbytes == 0 or V < 1:
+        raise ValueError(f"build_bvh: F = {F} faces in [1, 2^24), V = {V} >= 1")
+    buf = torch.zeros(nbytes, dtype=torch.uint8)
+    _lib.check(lib.drm_mesh_bvh_build(pos.data_ptr(), faces.data_ptr(), V, F, buf.data_ptr(), nbytes))
+    head = buf[:16].numpy().view(np.uint32)
+    return buf[:BVH_HEADER_BYTES + BVH_NODE_BYTES * int(head[2]) + 4 * int(head[3])].clone()
+
+
+BVH_MAGIC, BVH_HEADER_BYTES, BVH_NODE_BYTES = 0x31485642, 32, 32
+
+
+def decode_bvh(blob) -> Dict[str, np.ndarray]:
+    """A blob of ``build_bvh`` as numpy arrays, for tests and debugging: ``faces`` (the F it was built for), ``box_min`` / ``box_max``
+    [nodes, 3] float32, ``skip`` [nodes] (the node to go to on a box miss or after a leaf), ``first`` / ``count`` [nodes] (count 0 = inner
+    node, whose first child is the next node; a leaf holds ``order[first : first + count]``) and ``order`` (face indices).  Needs no GPU."""
+    raw = np.ascontiguousarray(torch.as_tensor(blob).detach().cpu().numpy()).view(np.uint8).reshape(-1)
+    if raw.size < BVH_HEADER_BYTES:
+        raise ValueError("decode_bvh: shorter than the header")
+    magic, F, nodes, norder = (int(v) for v in raw[:16].view(np.uint32))
+    if magic != BVH_MAGIC or raw.size < BVH_HEADER_BYTES + BVH_NODE_BYTES * nodes + 4 * norder:
+        raise ValueError("decode_bvh: not a build_bvh blob, or a truncated one")
+    words = raw[BVH_HEADER_BYTES:BVH_HEADER_BYTES + BVH_NODE_BYTES * nodes].view(np.uint32).reshape(nodes, 8)
+    order = raw[BVH_HEADER_BYTES + BVH_NODE_BYTES * nodes:][:4 * norder].view(np.int32).copy()
+    return {"faces": F, "box_min": words[:, 0:3].copy().view(np.float32), "box_max": words[:, 3:6].copy().view(np.float32),
+            "skip": words[:, 6].astype(np.int64), "first": (words[:, 7] >> 3).astype(np.int64), "count": (words[:, 7] & 7).astype(np.int64),
+            "order": order}
+
+
+def _bvh_on(blob, dev: torch.device) -> torch.Tensor:
+    t = torch.as_tensor(blob)
+    if t.dtype != torch.uint8 or t.dim() != 1:
+        raise ValueError("a BVH is the uint8 tensor build_bvh returns")
+    return t.to(dev).contiguous()
+
+
+@torch.no_grad()
+def occluded(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto") -> torch.Tensor:
+    """drm_mesh_occluded: for each of N rays (origins, dirs [N, 3] in object space; dirs of any length) whether some face other than
+    ``exclude`` [N] (int32 face indices; None, or -1, for no exclusion) cuts it off -> bool [N] on the GPU.  The intersection rule is stated
+    in include/drmnet_hip.h.  ``bvh``: "auto" builds the mesh's BVH, a ``build_bvh`` blob is used as it is, None tests every face for every
+    ray (the same answers, slowly).  GPU only: an ``origins`` or ``dirs`` tensor on the CPU is a RuntimeError."""
+    for name, t in (("origins", origins), ("dirs", dirs)):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise RuntimeError(f"occluded runs on the GPU only (drmnet_amd has no CPU path): {name} is on {t.device}")
+    dev = _device(origins, dirs)
+    o = torch.as_tensor(origins).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    d = torch.as_tensor(dirs).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    if o.shape != d.shape:
+        raise ValueError(f"origins {tuple(o.shape)} and dirs {tuple(d.shape)} must both be [N, 3]")
+    N = int(o.shape[0])
+    ex = None
+    if exclude is not None:
+        ex = torch.as_tensor(exclude).to(dev, torch.int32).reshape(-1).contiguous()
+        if ex.shape[0] != N:
+            raise ValueError(f"exclude must be [N={N}], got {tuple(ex.shape)}")
+    pos, _, faces = _mesh_on(obj, dev)
+    blob = None if bvh is None else _bvh_on(build_bvh(obj) if isinstance(bvh, str) and bvh == "auto" else bvh, dev)
+    out = torch.zeros(N, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_mesh_occluded(pos.data_ptr(), faces.data_ptr(), int(pos.shape[0]), int(faces.shape[0]), _lib.ptr(blob), o.data_ptr(),
+                                                d.data_ptr(), _lib.ptr(ex), out.data_ptr(), N, _lib.stream_ptr(dev)))
+    return out != 0
+
+
 @torch.no_grad()
 def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, image_size, view_from=None,
-                quad: int = QUAD, subpixel: int = SUBPIXEL):
-    """One call of drm_render_mesh: one mesh, lit and seen B ways.  z [B, P], envmaps [B, EH, EW, 3] (or None: white), view_from [B, 3] (or
+                quad: int = QUAD, subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None):
+    """One call of drm_render_mesh (``shadows=True``: of drm_render_mesh_shadowed, where parts of the mesh cut light off from other parts;
+    ``bvh`` is then the mesh's ``build_bvh`` blob, built here when None): one mesh, lit and seen B ways.  z [B, P], envmaps [B, EH, EW, 3] (or None: white), view_from [B, 3] (or
     None: +z), image_size H or (H, W) -> (image [B, 3, H, W], normal [B, 3, H, W] in the view frame, depth [B, 1, H, W], alpha [B, H, W]).
     GPU only: a ``z`` or ``envmaps`` tensor on the CPU, or a machine without a GPU, is a RuntimeError (the mesh itself and ``view_from`` are
     host data and are brought over)."""
@@ -164,24 +239,30 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
+    args = (pos.data_ptr(), nrm.data_ptr(), faces.data_ptr(), V, F, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(), normal.data_ptr(),
+            depth.data_ptr(), alpha.data_ptr(), B, H, W, EH, EW, int(quad), int(subpixel), ws.data_ptr(), nbytes)
     with torch.cuda.device(dev):
-        _lib.check(lib.drm_render_mesh(pos.data_ptr(), nrm.data_ptr(), faces.data_ptr(), V, F, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view),
-                                       image.data_ptr(), normal.data_ptr(), depth.data_ptr(), alpha.data_ptr(), B, H, W, EH, EW, int(quad),
-                                       int(subpixel), ws.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+        if shadows:
+            blob = _bvh_on(build_bvh(obj) if bvh is None else bvh, dev)
+            _lib.check(lib.drm_render_mesh_shadowed(*args, blob.data_ptr(), int(blob.numel()), _lib.stream_ptr(dev)))
+        else:
+            _lib.check(lib.drm_render_mesh(*args, _lib.stream_ptr(dev)))
     return image, normal, depth, alpha
 
 
 class MeshRenderer:
     """MitsubaOrthoRenderer (utils/mitsuba3_utils.py:433-564) on drm_render_mesh: an orthographic view of a smooth-shaded triangle mesh under
     the scene's environment map.  Differences from Mitsuba's ``path`` integrator, all by design: direct light only, no
-    self-shadowing, no interreflection, and a black background.  The integral is the deterministic quadrature of the reflectance-map
+    interreflection, a black background, and self-shadowing only with ``shadows=True`` (the BVH is built once when a mesh becomes the
+    scene's and kept with it; a ``new_scene`` mesh gets one for that call).  The integral is the deterministic quadrature of the reflectance-map
     renderer, so ``spp`` and ``denoise`` are accepted and ignored.  ``init_view_from`` may be any position off the +-y axis.  The scene
     state -- environment map, view and mesh -- is kept across ``rendering`` calls as the reference's scene keeps it.  Construction does not
     touch the GPU."""
 
     def __init__(self, image_size, spp: int = 1024, envmap_size=(1000, 2000), denoise: Optional[str] = None, return_normal: bool = False,
                  return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
-                 subpixel: int = SUBPIXEL):
+                 subpixel: int = SUBPIXEL, shadows: bool = False):
+        self.shadows = bool(shadows)
         self.image_size = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(s) for s in image_size)
         self.envmap_size = tuple(int(s) for s in envmap_size)
         self.spp, self.denoise = spp, denoise
@@ -192,6 +273,7 @@ class MeshRenderer:
         view_rotation(self._view_from)  # (a view along +-y is a ValueError here, not at the first render)
         self._envmap: Optional[torch.Tensor] = None  # the scene's map; None = the initial all-zero bitmap of envmap_size
         self._obj: Optional[Mesh] = None  # the scene's mesh; None = none given yet
+        self._bvh: Optional[torch.Tensor] = None  # shadows: the BVH of the scene's mesh, on its device
 
     def rendering(self, z, brdf_param_names, envmap: Optional[torch.Tensor] = None, view_from=None, obj: Mesh = {}, sensor=0, spp: int = 0,
                   new_scene: bool = False, channel_first: bool = False):
@@ -207,15 +289,20 @@ class MeshRenderer:
         if not mesh:
             raise ValueError("no mesh: pass obj = {vertex_positions, vertex_normals, faces} (the scene keeps it for later calls)")
         dev = _device(z, envmap)
+        bvh = None  # (a new_scene mesh: render_mesh builds one for this call)
         if new_scene:
             if envmap is None:
                 raise ValueError("new_scene needs an envmap")
             env = envmap.to(dev)
             view = self._view_from if view_from is None else view_from
+            if not obj:
+                bvh = self._bvh
         else:
             if obj:
                 self._obj = dict(zip(_KEYS, _mesh_on(obj, dev)))
                 mesh = self._obj
+                self._bvh = _bvh_on(build_bvh(obj), dev) if self.shadows else None
+            bvh = self._bvh
             if envmap is not None:
                 self._envmap = envmap.to(dev)
             if self._envmap is None:
@@ -226,7 +313,8 @@ class MeshRenderer:
             view = self._view_from
         z = torch.as_tensor(z).reshape(1, -1).to(dev)
         image, normal, depth, _ = render_mesh(mesh, z, brdf_param_names or self.brdf_param_names, env[None], image_size=self.image_size,
-                                              view_from=torch.as_tensor(view).reshape(1, 3), quad=self.quad, subpixel=self.subpixel)
+                                              view_from=torch.as_tensor(view).reshape(1, 3), quad=self.quad, subpixel=self.subpixel,
+                                              shadows=self.shadows, bvh=bvh)
         outs = [image[0]] + ([normal[0]] if self.return_normal else []) + ([depth[0]] if self.return_depth else [])
         if not channel_first:
             outs = [o.permute(1, 2, 0) for o in outs]

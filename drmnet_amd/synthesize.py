@@ -4,7 +4,8 @@
 
 writes into D the three files ``estimate`` reads,
 
-    image.exr    H x W x 3 radiance of the object (drmnet_amd.mesh.render_mesh: direct light, black background)
+    image.exr    H x W x 3 radiance of the object (drmnet_amd.mesh.render_mesh: direct light, black background; with ``--shadows`` the
+                 object shadows itself)
     normal.npy   H x W x 3 float32 shading normals in the view frame (right, up, back)
     mask.png     |normal| > 0.5: the pixels more than half covered
 
@@ -40,6 +41,7 @@ def main(argv=None):
     parser.add_argument("--image_size", type=int, default=128)
     parser.add_argument("--refmap_res", type=int, default=128, help="resolution of refmap.exr")
     parser.add_argument("--quad", type=int, default=QUAD)
+    parser.add_argument("--shadows", action="store_true", help="trace shadow rays: parts of the mesh cut light off from other parts (default: off)")
     parser.add_argument("--output_dir", type=Path, default=Path("./outputs/"))
     args = parser.parse_args(argv)
 
@@ -50,7 +52,7 @@ def main(argv=None):
     z = torch.tensor([args.z], dtype=torch.float32, device=dev)
     env = None if args.envmap is None else file_io.load_exr(args.envmap, as_torch=True).to(dev)[None]
     view = torch.tensor([args.view_from], dtype=torch.float32)
-    image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad)
+    image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows)
     refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view)
     normal = normal[0].permute(1, 2, 0).cpu().numpy()
     mask = np.linalg.norm(normal, axis=-1) > 0.5

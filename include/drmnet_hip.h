@@ -402,8 +402,9 @@ int drm_render_refmap_lit(const float* z, int L, const float* envmap, const floa
 /* Object images of a triangle mesh: the input side of the chain (csrc/mesh.hip for visibility, csrc/render.hip for shading).  Replaces
  * MitsubaOrthoRenderer.rendering (utils/mitsuba3_utils.py:433-564: an orthographic camera on a smooth-shaded mesh with image, shading-normal
  * and depth AOVs).  Every visible point is shaded exactly as drm_render_refmap_views shades the sphere point with the same normal: direct
- * light from the environment map, NO self-shadowing, NO interreflection (Mitsuba's path integrator has both), and the background is black,
- * not the environment.  It is the model the reflectance map itself assumes.  Additive: the ABI version is unchanged.
+ * light from the environment map, NO interreflection (Mitsuba's path integrator has it), and the background is black, not the environment.
+ * drm_render_mesh has NO self-shadowing either: it is the model the reflectance map itself assumes.  drm_render_mesh_shadowed (below) adds
+ * shadow rays.  Additive: the ABI version is unchanged.
  *   One mesh per call, lit and seen B ways: vertex_positions, vertex_normals [V][3], faces [F][3] int32 (smooth shading, no back-face
  *   culling), z [B][6], envmap [B][EH][EW][3] or NULL (white), view [B][9] or NULL (+z).
  *   View frame.  right, up, back are the columns of the row-major Rot = view[b] (the rotation drm_render_refmap_views takes).  Mesh points
@@ -429,6 +430,47 @@ size_t drm_render_mesh_workspace_bytes(int64_t F, int B, int H, int W, int subpi
 int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
                     const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
                     int quad, int subpixel, void* workspace, size_t workspace_bytes, void* stream);
+/* Self-shadowing for the object images: any-hit ray queries against the mesh through a bounding-volume hierarchy (csrc/bvh.h, csrc/bvh.hip).
+ * Additive: the ABI version is unchanged.
+ *   The intersection rule.  A ray (o, d) is given in OBJECT space; d need not be unit length.  It is occluded iff some face g satisfies all of:
+ *   g != exclude; its three vertex indices are in [0, V); and with e1 = p1 - p0, e2 = p2 - p0, pv = d x e2, det = e1.pv, tv = o - p0,
+ *   qv = tv x e1, U = tv.pv, V = d.qv, T = e2.qv and s = sign(det):  det != 0 and det is finite;  s U >= 0;  s V >= 0;  s (U + V) <= |det|;
+ *   s T > 0.  The rule is division-free (integer-valued inputs give exact decisions), edges and vertices are inclusive, a ray lying in a face's
+ *   plane misses that face (det = 0), an origin on a face does not hit that face (T = 0), and the query is any-hit: the answer does not depend
+ *   on the order faces are visited in.  fp32, no contraction.  A face whose fp32 cross product e1 x e2 is exactly (0, 0, 0) occludes nothing:
+ *   in exact arithmetic its det is 0 for every ray, in fp32 it would be rounding noise, and the builder leaves it out by the same arithmetic.
+ *   The BVH never changes an answer: with it the result equals testing every face with the same triangle routine, for every ray.  Its boxes
+ *   are padded at build time (2^-16 of the largest |coordinate|) and per query (2^-16 of the largest |o| component), the slab test's far bound
+ *   has 2^-20 of slack, a direction component that is exactly 0 compares the origin with the slab instead of dividing, and a NaN slab distance
+ *   constrains nothing.
+ *   drm_mesh_bvh_build: pure host code (no HIP call, usable without a GPU), host pointers, over object-space positions: one blob per mesh serves
+ *   all B views of a call.  Deterministic (the same input gives the same bytes), O(F log F): median split of the face centroids along the
+ *   longest axis, leaves of at most 4 faces.  Faces with an index outside [0, V), a non-finite vertex or a zero cross product are left out.
+ *   The buffer must hold drm_mesh_bvh_bytes(F) = 32 + 36 F bytes (0 for F outside [1, 2^24)); the bytes past the blob's own length are zeroed.
+ *   Blob layout (little-endian, 16-byte aligned):  header of 32 bytes = uint32 magic "BVH1" (0x31485642), F, node_count, order_count, 16 bytes of
+ *   zeros;  node_count nodes of 32 bytes in depth-first order = float box_min[3], box_max[3], int32 skip, uint32 first << 3 | count;
+ *   order_count int32 face indices.  count = 0 marks an inner node, whose first child is the next node; a leaf holds the faces
+ *   order[first .. first + count).  skip is the node to go to on a box miss or after a leaf.  Traversal is stackless: on a box hit an inner node
+ *   goes to i + 1, everything else to skip; it ends at node_count.  The blob's length is 32 + 32 node_count + 4 order_count.
+ *   Every consumer reads the header back from the device (a 32-byte copy and a synchronise of `stream`: the one wait these calls make) and
+ *   returns DRM_ERR_INVALID when the magic, F or the counts do not fit; nothing is launched then.
+ *   drm_mesh_occluded: one thread per ray.  All pointers are device pointers: origins, dirs [N][3], exclude [N] int32 (a face index, or any
+ *   value outside [0, F) for none) or NULL, out [N] int32 0 / 1.  bvh == NULL tests all F faces per ray with the same triangle routine (the
+ *   diagnostic path that shows the BVH changes nothing).  The caller vouches for the blob's length as for every other array's.
+ *   drm_render_mesh_shadowed: drm_render_mesh (same arguments, same workspace, same setup and visibility launches) with shadow rays; bvh is a
+ *   device copy of the blob, 16-byte aligned, required, bvh_bytes its length (a length shorter than the header implies is DRM_ERR_INVALID).
+ *   For every hit sample the ray origin is the view-space hit point (x_sample, y_sample, z_hit) taken to object space with Rot (no view:
+ *   nothing is multiplied), exclude is the hit face, and every quadrature direction l with a non-zero weight is traced along Rot l, the vector
+ *   the environment lookup forms: the specular direction inside its (v.h > 0, n.l > 0, D > 0) branch, the diffuse direction always.  An
+ *   occluded direction contributes nothing, an open one exactly what it contributes in drm_render_mesh, so a shadowed image is <= the plain
+ *   one in every pixel and channel under a non-negative map.  Interreflection stays out.  Bitwise reproducible; rows are independent. */
+size_t drm_mesh_bvh_bytes(int64_t F);
+int drm_mesh_bvh_build(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, void* bvh, size_t bytes);
+int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins, const float* dirs,
+                      const int32_t* exclude, int32_t* out, int64_t N, void* stream);
+int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                             const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                             int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
