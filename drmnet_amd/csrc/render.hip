@@ -17,12 +17,17 @@
 // Light sampling (opt-in, light_samples = M > 0): the quadrature never consults the map when it places samples, so a light a few texels
 // wide can fall between the strata of a rough lobe.  drm_render_refmap_lit adds a third technique, M directions drawn from the map's own
 // light density, and combines the three with lobe-separated multiple importance sampling (power heuristic, beta = 2): see "light density"
-// below.  The plain instantiations (LIGHT = false) are the kernels they always were.
+// below.
 //
 // Object images of meshes (drm_render_mesh): mesh.hip finds which face every film sample sees; mesh_shade_kernel here shades the hit with
 // normal_lane_sum, the per-normal body of the sphere's sum, so a mesh point is shaded exactly as the sphere point with the same normal
 // (direct light, no interreflection).  drm_render_mesh_shadowed runs mesh_shade_kernel<VIEW, true>, which traces every quadrature direction
-// from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones; the plain instantiations hold no trace of it.
+// from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones.
+//
+// One statement of the quadrature: normal_lane_sum builds both lobes once and accumulates each in one place; what differs between the
+// renders is its technique parameter (Plain, LightSampled, Occluded: see "techniques"), which decides per lobe sample whether it counts,
+// what radiance it reads and what scales its weight.  Every texel fetch is env_taps + bilerp.  Plain holds nothing: the instantiations
+// without light samples and without shadows carry no code and no registers of the other two.
 #include <type_traits>
 
 #include "bvh.h"
@@ -127,25 +132,39 @@ __host__ __device__ __forceinline__ void principled_eval(const Principled& p, co
 
 // radiance toward w: bilinear in the texel grid of an EH x EW map whose texel (i, j) looks along theta = (i + 1/2) pi / EH,
 // psi = (j + 1/2) 2 pi / EW, w = (sin theta sin psi, cos theta, -sin theta cos psi); wraps in psi, clamps in theta.  env [EH][EW][3].
-__host__ __device__ __forceinline__ void env_lookup(const float* __restrict__ env, int EH, int EW, V3 w, float L[3]) {
+// EnvTaps: the four texels (rows r0 / r1 = texel rows i0 / i0 + 1 clamped, columns j0 / j1) and the fractions of that lookup; pole: w lies
+// in a polar half row, where theta is clamped and fy = 0.
+struct EnvTaps {
+  const float *r0, *r1;
+  int j0, j1, i0;
+  float fx, fy;
+  bool pole;
+};
+__host__ __device__ __forceinline__ EnvTaps env_taps(const float* __restrict__ env, int EH, int EW, V3 w) {
   const float u = atan2f(w.x, -w.z) * (0.5f / kPi);
   const float t = acosf(fminf(fmaxf(w.y, -1.0f), 1.0f)) * (1.0f / kPi);
   const float x = u * (float)EW - 0.5f;
-  const float y = fminf(fmaxf(t * (float)EH - 0.5f, 0.0f), (float)(EH - 1));
+  const float yu = t * (float)EH - 0.5f;
+  const float y = fminf(fmaxf(yu, 0.0f), (float)(EH - 1));
   const float xf = floorf(x), yf = floorf(y);
-  const float fx = x - xf, fy = y - yf;
   int j0 = (int)xf % EW;
   if (j0 < 0) j0 += EW;
   const int j1 = j0 + 1 == EW ? 0 : j0 + 1;
   const int i0 = (int)yf, i1 = i0 + 1 < EH ? i0 + 1 : EH - 1;
-  const float* r0 = env + (size_t)i0 * EW * 3;
-  const float* r1 = env + (size_t)i1 * EW * 3;
+  return EnvTaps{env + (size_t)i0 * EW * 3, env + (size_t)i1 * EW * 3, j0, j1, i0, x - xf, y - yf, yu < 0.0f || yu >= (float)(EH - 1)};
+}
+// the bilinear form over the taps' four corner values v{row}{column}
+__host__ __device__ __forceinline__ float bilerp(const EnvTaps& e, float v00, float v01, float v10, float v11) {
+  const float top = (1.0f - e.fx) * v00 + e.fx * v01;
+  const float bot = (1.0f - e.fx) * v10 + e.fx * v11;
+  return (1.0f - e.fy) * top + e.fy * bot;
+}
+__host__ __device__ __forceinline__ void bilerp(const EnvTaps& e, float L[3]) {
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float top = (1.0f - fx) * r0[j0 * 3 + ch] + fx * r0[j1 * 3 + ch];
-    const float bot = (1.0f - fx) * r1[j0 * 3 + ch] + fx * r1[j1 * 3 + ch];
-    L[ch] = (1.0f - fy) * top + fy * bot;
-  }
+  for (int ch = 0; ch < 3; ++ch) L[ch] = bilerp(e, e.r0[e.j0 * 3 + ch], e.r0[e.j1 * 3 + ch], e.r1[e.j0 * 3 + ch], e.r1[e.j1 * 3 + ch]);
+}
+__host__ __device__ __forceinline__ void env_lookup(const float* __restrict__ env, int EH, int EW, V3 w, float L[3]) {
+  bilerp(env_taps(env, EH, EW, w), L);
 }
 
 // RefMapSensor: the normal seen at film position (px, py) in [0, 1]^2 (from the left / from the top); flip mirrors x
@@ -219,71 +238,104 @@ __host__ __device__ __forceinline__ LightTable light_table(const char* ws, int b
 __host__ __device__ __forceinline__ float power_weight(float a, float b) { return (a * a) / (a * a + b * b); }
 __host__ __device__ __forceinline__ float luma(const float* t) { return fmaxf(0.2126f * t[0] + 0.7152f * t[1] + 0.0722f * t[2], 0.0f); }
 
-// env_lookup (the same expressions: the same bits in L) that also returns p_L(w) from the four texels it loads.  sc_pole = sin(pi / (4 EH)).
+// env_lookup that also returns p_L(w) from the four texels it loads.  sc_pole = sin(pi / (4 EH)).
 __host__ __device__ __forceinline__ float env_lookup_pdf(const float* __restrict__ env, int EH, int EW, V3 w, float norm, float sc_pole, float L[3]) {
-  const float u = atan2f(w.x, -w.z) * (0.5f / kPi);
-  const float t = acosf(fminf(fmaxf(w.y, -1.0f), 1.0f)) * (1.0f / kPi);
-  const float x = u * (float)EW - 0.5f;
-  const float yu = t * (float)EH - 0.5f;
-  const float y = fminf(fmaxf(yu, 0.0f), (float)(EH - 1));
-  const float xf = floorf(x), yf = floorf(y);
-  const float fx = x - xf, fy = y - yf;
-  int j0 = (int)xf % EW;
-  if (j0 < 0) j0 += EW;
-  const int j1 = j0 + 1 == EW ? 0 : j0 + 1;
-  const int i0 = (int)yf, i1 = i0 + 1 < EH ? i0 + 1 : EH - 1;
-  const float* r0 = env + (size_t)i0 * EW * 3;
-  const float* r1 = env + (size_t)i1 * EW * 3;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float top = (1.0f - fx) * r0[j0 * 3 + ch] + fx * r0[j1 * 3 + ch];
-    const float bot = (1.0f - fx) * r1[j0 * 3 + ch] + fx * r1[j1 * 3 + ch];
-    L[ch] = (1.0f - fy) * top + fy * bot;
-  }
+  const EnvTaps e = env_taps(env, EH, EW, w);
+  bilerp(e, L);
   // cell row: c = floor(yu) + 1 clamped to [0, EH]; in the half cells y is clamped, fy = 0 and the value is the polar texel row's
-  const bool pole = yu < 0.0f || yu >= (float)(EH - 1);
-  const float sc = pole ? sc_pole : sinf((float)(i0 + 1) * (kPi / (float)EH));
-  const float top = (1.0f - fx) * luma(r0 + j0 * 3) + fx * luma(r0 + j1 * 3);
-  const float bot = (1.0f - fx) * luma(r1 + j0 * 3) + fx * luma(r1 + j1 * 3);
-  const float val = (1.0f - fy) * top + fy * bot;
+  const float sc = e.pole ? sc_pole : sinf((float)(e.i0 + 1) * (kPi / (float)EH));
+  const float val = bilerp(e, luma(e.r0 + e.j0 * 3), luma(e.r0 + e.j1 * 3), luma(e.r1 + e.j0 * 3), luma(e.r1 + e.j1 * 3));
   return val * sc * norm / fmaxf(sqrtf(w.x * w.x + w.z * w.z), 1e-6f);
 }
 
-// Is a quadrature direction (in world space, any length) cut off before it reaches the environment?  The sphere and the unshadowed mesh ask
-// nothing (kActive = false: no call is compiled); the shadowed mesh asks the BVH from the sample's hit point.
-struct NoOcclusion {
-  static constexpr bool kActive = false;
-  __host__ __device__ __forceinline__ bool operator()(V3) const { return false; }
+// ------------------------------------------------------------------------------------------------ techniques
+// What normal_lane_sum does with one lobe sample is the technique's: take() gets the sample's world direction wl (any length) and np, the
+// lobe's sample count times its density at wl (formed only for kNeedsDensity), and returns whether the sample counts at all; if so it has
+// read the radiance into L (left as it is under a white environment) and scaled the weight w.  begin() opens a normal, finish() closes it.
+struct Plain {
+  static constexpr bool kNeedsDensity = false, kTraces = false;
+  __host__ __device__ __forceinline__ void begin(const Principled&, V3) {}
+  __host__ __device__ __forceinline__ bool take(const float* __restrict__ env, int EH, int EW, V3 wl, float, float&, float L[3]) const {
+    if (env) env_lookup(env, EH, EW, wl, L);
+    return true;
+  }
+  template <bool VIEW>
+  __host__ __device__ __forceinline__ void finish(const Principled&, const ViewRot&, V3, int, int) {}
 };
-struct MeshOcclusion {
-  static constexpr bool kActive = true;
+
+// The shadowed mesh: a direction the BVH finds cut off between the sample's hit point and the environment is dropped before any lookup.
+struct Occluded : Plain {
+  static constexpr bool kTraces = true;
   MeshRef mesh;
   BvhView tree;
   float o[3];       // the hit point in object space
   int32_t exclude;  // the hit face
-  __host__ __device__ __forceinline__ bool operator()(V3 w) const {
-    const Ray r{{o[0], o[1], o[2]}, {w.x, w.y, w.z}};
-    return bvh_occluded(mesh, tree, r, exclude);
+  __host__ __device__ __forceinline__ bool take(const float* __restrict__ env, int EH, int EW, V3 wl, float np, float& w, float L[3]) const {
+    const Ray r{{o[0], o[1], o[2]}, {wl.x, wl.y, wl.z}};
+    return !bvh_occluded(mesh, tree, r, exclude) && Plain::take(env, EH, EW, wl, np, w, L);
   }
 };
 
+// The light technique (not traced): where the map has light (lt.norm > 0) every lobe sample is weighted by the power heuristic against the
+// n_L = lt.M light samples, and finish() lets the lanes stride the light table as they strode the grid, summing into accL (to be
+// normalised by 1 / S^2 only: the weights hold 1 / n).  Needs a map: env is never null here.
+struct LightSampled {
+  static constexpr bool kNeedsDensity = true, kTraces = false;
+  LightTable lt;
+  float accL[3];
+  float nlobe, nlight, sc_pole, g1v;
+  bool lit;
+  // G1(v): v = +z is above the surface on the whole film and v.h > 0 wherever it is used
+  __host__ __device__ __forceinline__ void begin(const Principled& p, V3 n) { g1v = ggx_g1(p.a2, n.z, n.x * n.x + n.y * n.y, 1.0f); }
+  __host__ __device__ __forceinline__ bool take(const float* __restrict__ env, int EH, int EW, V3 wl, float np, float& w, float L[3]) const {
+    const float pl = env_lookup_pdf(env, EH, EW, wl, lt.norm, sc_pole, L);
+    w = w * (lit ? power_weight(np, nlight * pl) : 1.0f);
+    return true;
+  }
+  // table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame
+  template <bool VIEW>
+  __host__ __device__ __forceinline__ void finish(const Principled& p, const ViewRot& rot, V3 n, int lane, int lanes) {
+    if (!lit) return;
+    const bool diffuse = p.m < 1.0f;
+    const float cv = n.z;
+    for (int k = lane; k < lt.M; k += lanes) {
+      const V3 wd = v3(lt.tab[k], lt.tab[lt.M + k], lt.tab[2 * lt.M + k]);
+      const float pl = lt.tab[6 * lt.M + k];
+      const V3 l = from_world<VIEW>(rot, wd);
+      const float cl = dot3(n, l);
+      if (cl > 0.0f && pl > 0.0f) {
+        V3 h = v3(l.x, l.y, l.z + 1.0f);
+        const float hinv = 1.0f / sqrtf(dot3(h, h));
+        h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
+        const float vh = h.z, nh = dot3(n, h);
+        const float D = ggx_d(p.a2, nh, cross_sq(n, h));
+        const float ps = g1v * D / (4.0f * cv);
+        const float ks = ps * ggx_g1(p.a2, cl, cross_sq(n, l), dot3(l, h));  // D G / (4 n.v)
+        const float kd = diffuse ? (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, vh) * (1.0f / kPi) : 0.0f;
+        const float a = nlight * pl, as = nlobe * ps, ad = diffuse ? nlobe * cl * (1.0f / kPi) : 0.0f;
+        const float ws = ks * (a / (as * as + a * a)), wd2 = kd * (a / (ad * ad + a * a));
+        const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) accL[c] += lt.tab[(3 + c) * lt.M + k] * ((fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * ws + p.c[c] * wd2);
+      }
+    }
+  }
+};
+__host__ __device__ __forceinline__ LightSampled light_sampled(const LightTable& lt, int EH, int Q) {
+  return LightSampled{lt, {0.0f, 0.0f, 0.0f}, (float)(Q * Q), (float)lt.M, sinf(0.25f * kPi / (float)EH), 0.0f, lt.norm > 0.0f};
+}
+
 // one lane's share of the radiance a surface point with unit normal n (n.z > -1; the callers pass n.z > 0) reflects toward the viewer at +z:
 // the grid points q = lane, lane + lanes, ... of both lobes, summed in that order into acc (unnormalised).  env == nullptr: white
-// environment (L = 1).  The sphere (pixel_lane_sum) and the mesh (mesh_shade_kernel) share this body.
-// LIGHT: lt.norm > 0 adds the light technique: every lobe sample is weighted by the power heuristic against the n_L = lt.M light samples,
-// and the lanes stride the light table as they stride the grid, summing into accL (normalised by 1 / S^2 only: the weights hold 1 / n).
-// OCC: a lobe direction with a non-zero weight is traced along to_world(rot, l), the vector the environment lookup forms; an occluded one
-// contributes nothing, an open one what it always did (not combined with LIGHT).
-template <bool VIEW, bool LIGHT, typename OCC = NoOcclusion>
+// environment (L = 1).  The sphere (pixel_lane_sum) and the mesh (mesh_shade_kernel) share this body; TECH (above) is asked about every
+// lobe sample with a non-zero weight, along to_world(rot, l), the vector the environment lookup forms.
+template <bool VIEW, typename TECH>
 __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n,
-                                                         int Q, int lane, int lanes, float acc[3], const LightTable& lt, float accL[3],
-                                                         const OCC& occ = OCC()) {
-  static_assert(!(LIGHT && OCC::kActive), "the light technique is not traced");
+                                                         int Q, int lane, int lanes, float acc[3], TECH& tech) {
+  static_assert(!(TECH::kNeedsDensity && TECH::kTraces), "the light technique is not traced");
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
-  const bool lit = LIGHT && lt.norm > 0.0f;
-  const float nlobe = (float)(Q * Q), nlight = (float)lt.M, sc_pole = LIGHT ? sinf(0.25f * kPi / (float)EH) : 0.0f;
   const float cv = n.z;  // n.v for v = +z
   // orthonormal frame (t, bt, n) (Duff et al. 2017; n.z > 0 on the whole film); v = (-n.x, -n.y, n.z) in it
   const float ka = -1.0f / (1.0f + n.z), kb = n.x * n.y * ka;
@@ -297,8 +349,7 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
   const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
   const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
   const float vs = 0.5f * (1.0f + Vz);
-  // G1(v): v = +z is above the surface on the whole film and v.h > 0 wherever it is used
-  const float g1v = LIGHT ? ggx_g1(p.a2, cv, n.x * n.x + n.y * n.y, 1.0f) : 0.0f;
+  tech.begin(p, n);
   for (int q = lane; q < Q * Q; q += lanes) {
     const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
     const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
@@ -317,24 +368,11 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
       const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
       const float cl = dot3(n, l);
       if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
-        const float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh);
+        float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh), np = 0.0f;
         const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-        if constexpr (LIGHT) {
-          // p_s(l) = G1(v) D(h) / (4 n.v): the density of l under the visible-normal sampling above
-          const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
-          const float ps = g1v * ggx_d(p.a2, nh, s2h) / (4.0f * cv);
-          const float wm = w * (lit ? power_weight(nlobe * ps, nlight * pl) : 1.0f);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * wm * L[c];
-        } else if constexpr (OCC::kActive) {
-          const V3 wl = to_world<VIEW>(rot, l);
-          if (!occ(wl)) {
-            if (env) env_lookup(env, EH, EW, wl, L);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
-          }
-        } else {
-          if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+        // p_s(l) = G1(v) D(h) / (4 n.v): the density of l under the visible-normal sampling above
+        if constexpr (TECH::kNeedsDensity) np = tech.nlobe * (tech.g1v * ggx_d(p.a2, nh, s2h) / (4.0f * cv));
+        if (tech.take(env, EH, EW, to_world<VIEW>(rot, l), np, w, L)) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
         }
@@ -346,65 +384,35 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
       const V3 l = axpy(cl, n, axpy(rs * sp, bt, v3(rs * cp * t.x, rs * cp * t.y, rs * cp * t.z)));
       V3 h = v3(l.x, l.y, l.z + 1.0f);
       const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
-      const float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd);
-      if constexpr (LIGHT) {
-        const float pl = env_lookup_pdf(env, EH, EW, to_world<VIEW>(rot, l), lt.norm, sc_pole, L);
-        const float wm = w * (lit ? power_weight(nlobe * cl * (1.0f / kPi), nlight * pl) : 1.0f);  // p_d(l) = n.l / pi
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * wm * L[c];
-      } else if constexpr (OCC::kActive) {
-        const V3 wl = to_world<VIEW>(rot, l);
-        if (!occ(wl)) {
-          if (env) env_lookup(env, EH, EW, wl, L);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
-        }
-      } else {
-        if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+      float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd), np = 0.0f;
+      if constexpr (TECH::kNeedsDensity) np = tech.nlobe * cl * (1.0f / kPi);  // p_d(l) = n.l / pi
+      if (tech.take(env, EH, EW, to_world<VIEW>(rot, l), np, w, L)) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] += p.c[c] * w * L[c];
       }
     }
   }
-  if constexpr (LIGHT) {
-    if (lit) {
-      // the light technique: table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame
-      for (int k = lane; k < lt.M; k += lanes) {
-        const V3 wd = v3(lt.tab[k], lt.tab[lt.M + k], lt.tab[2 * lt.M + k]);
-        const float pl = lt.tab[6 * lt.M + k];
-        const V3 l = from_world<VIEW>(rot, wd);
-        const float cl = dot3(n, l);
-        if (cl > 0.0f && pl > 0.0f) {
-          V3 h = v3(l.x, l.y, l.z + 1.0f);
-          const float hinv = 1.0f / sqrtf(dot3(h, h));
-          h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
-          const float vh = h.z, nh = dot3(n, h);
-          const float D = ggx_d(p.a2, nh, cross_sq(n, h));
-          const float ps = g1v * D / (4.0f * cv);
-          const float ks = ps * ggx_g1(p.a2, cl, cross_sq(n, l), dot3(l, h));  // D G / (4 n.v)
-          const float kd = diffuse ? (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, vh) * (1.0f / kPi) : 0.0f;
-          const float a = nlight * pl, as = nlobe * ps, ad = diffuse ? nlobe * cl * (1.0f / kPi) : 0.0f;
-          const float ws = ks * (a / (as * as + a * a)), wd2 = kd * (a / (ad * ad + a * a));
-          const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            accL[c] += lt.tab[(3 + c) * lt.M + k] * ((fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * ws + p.c[c] * wd2);
-        }
-      }
+  tech.template finish<VIEW>(p, rot, n, lane, lanes);
+}
+
+// one lane's share of pixel (i, j) of the sphere: normal_lane_sum at every sub-pixel normal, in sub-pixel order
+template <bool VIEW, typename TECH>
+__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
+                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3], TECH& tech) {
+  for (int sy = 0; sy < S; ++sy) {
+    for (int sx = 0; sx < S; ++sx) {
+      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
+      normal_lane_sum<VIEW>(p, env, rot, EH, EW, n, Q, lane, lanes, acc, tech);
     }
   }
 }
 
-// one lane's share of pixel (i, j) of the sphere: normal_lane_sum at every sub-pixel normal, in sub-pixel order
-template <bool VIEW, bool LIGHT>
-__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
-                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3], const LightTable& lt,
-                                                        float accL[3]) {
-  for (int sy = 0; sy < S; ++sy) {
-    for (int sx = 0; sx < S; ++sx) {
-      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
-      normal_lane_sum<VIEW, LIGHT>(p, env, rot, EH, EW, n, Q, lane, lanes, acc, lt, accL);
-    }
+// the fixed butterfly in which the 64 lanes' partial sums meet: every lane ends with the wave's sum
+__device__ __forceinline__ void wave_sum3(float a[3]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] += __shfl_xor(a[c], o);
   }
 }
 
@@ -428,27 +436,19 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
   const Principled p = principled(z + 6 * (size_t)row);
   const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
   const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
-  float acc[3] = {0.0f, 0.0f, 0.0f}, accL[3] = {0.0f, 0.0f, 0.0f};
-  LightTable lt{nullptr, 0, 0.0f};
-  if constexpr (LIGHT) lt = light_table(lws, b, EH, M);
-  pixel_lane_sum<VIEW, LIGHT>(p, e, rot, EH, EW, R, i, j, Q, S, flip, lane, 64, acc, lt, accL);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], o);
-    if constexpr (LIGHT) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) accL[c] += __shfl_xor(accL[c], o);
-    }
-  }
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  std::conditional_t<LIGHT, LightSampled, Plain> tech;
+  if constexpr (LIGHT) tech = light_sampled(light_table(lws, b, EH, M), EH, Q);
+  pixel_lane_sum<VIEW>(p, e, rot, EH, EW, R, i, j, Q, S, flip, lane, 64, acc, tech);
+  wave_sum3(acc);
+  if constexpr (LIGHT) wave_sum3(tech.accL);
   if (lane == 0) {
     const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      if constexpr (LIGHT)
-        out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale + accL[c] * (1.0f / (float)(S * S));
-      else
-        out[(((size_t)row * 3 + c) * R + i) * R + j] = acc[c] * scale;
+      float px = acc[c] * scale;
+      if constexpr (LIGHT) px = px + tech.accL[c] * (1.0f / (float)(S * S));
+      out[(((size_t)row * 3 + c) * R + i) * R + j] = px;
     }
   }
 }
@@ -485,8 +485,7 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
   const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
   const float4* hit = reinterpret_cast<const float4*>(hits) + (size_t)b * H * S * W * S;
   const float* records = rec + (size_t)b * F * kMeshRecordWords;
-  const LightTable lt{nullptr, 0, 0.0f};
-  float acc[3] = {0.0f, 0.0f, 0.0f}, unused[3] = {0.0f, 0.0f, 0.0f};
+  float acc[3] = {0.0f, 0.0f, 0.0f};
   float nsum[3] = {0.0f, 0.0f, 0.0f}, dsum = 0.0f;
   int count = 0;
   for (int sy = 0; sy < S; ++sy) {
@@ -509,22 +508,17 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
       nsum[2] += n.z;
       dsum += 1.1f - h.w;
       ++count;
-      if constexpr (SHADOW) {
-        if (n.z > 0.0f) {
+      if (n.z > 0.0f) {
+        std::conditional_t<SHADOW, Occluded, Plain> tech;
+        if constexpr (SHADOW) {
           const V3 o = to_world<VIEW>(rot, v3(mesh_sample_x(j * S + sx, W * S), mesh_sample_y(i * S + sy, H * S, (float)H / (float)W), h.w));
-          const MeshOcclusion occ{MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
-          normal_lane_sum<VIEW, false, MeshOcclusion>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lt, unused, occ);
+          tech = Occluded{{}, MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
         }
-      } else {
-        if (n.z > 0.0f) normal_lane_sum<VIEW, false>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lt, unused);
+        normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], o);
-  }
+  wave_sum3(acc);
   if (lane == 0) {
     const float inv_s2 = 1.0f / (float)(S * S), scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
     const size_t at = (size_t)i * W + j, plane = (size_t)H * W;
@@ -691,22 +685,15 @@ __global__ __launch_bounds__(256) void brdf_eval_kernel(const float* __restrict_
 
 }  // namespace
 
-int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
-                               int subpixel, int flip, hipStream_t s) {
-  DRM_REQUIRE(z && out, "render_refmap: null pointer");
-  DRM_REQUIRE(L > 0 && B > 0 && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
-              "render_refmap: L >= 1 stacks of B >= 1 rows of R x R pixels, 1 <= R <= 8192");
-  DRM_REQUIRE(quad >= 1 && quad <= 1024 && subpixel >= 1 && subpixel <= 16, "render_refmap: quad in [1, 1024], subpixel in [1, 16]");
-  DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), "render_refmap: envmap must be EH x EW with EH, EW >= 1");
-  const long long blocks = ((long long)L * B * R * R + kRenderWaves - 1) / kRenderWaves;
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: L B R^2 too large for one launch");
-  // (a view only turns the environment: under a white one it changes nothing and is not read)
-  const bool with_view = env && view;
-  hipLaunchKernelGGL((with_view ? refmap_render_kernel<true, false> : refmap_render_kernel<false, false>), dim3((unsigned)blocks), dim3(64 * kRenderWaves),
-                     0, s, z, env, with_view ? view : nullptr, out, L * B, B, R, env ? EH : 1, env ? EW : 1, quad, subpixel, flip ? 1 : 0, nullptr, 0);
-  DRM_HIP_CHECK(hipGetLastError());
+// What every launch of a pixel kernel checks of its quadrature and environment (`who` names the entry in the message; subpixel_max = 0: the
+// caller bounds subpixel itself), and its grid: one wave per pixel, kRenderWaves to a workgroup.
+static int check_quadrature(const std::string& who, int quad, int subpixel, int subpixel_max, const float* env, int EH, int EW) {
+  DRM_REQUIRE(quad >= 1 && quad <= 1024 && (!subpixel_max || (subpixel >= 1 && subpixel <= subpixel_max)),
+              who + ": quad in [1, 1024]" + (subpixel_max ? ", subpixel in [1, " + std::to_string(subpixel_max) + "]" : ""));
+  DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), who + ": envmap must be EH x EW with EH, EW >= 1");
   return DRM_OK;
 }
+static long long pixel_blocks(long long pixels) { return (pixels + kRenderWaves - 1) / kRenderWaves; }
 
 static bool light_samples_ok(int M) { return M >= 64 && M <= 65536 && (M & (M - 1)) == 0; }
 
@@ -715,31 +702,45 @@ size_t render_light_workspace_bytes(int B, int EH, int EW, int light_samples) {
   return (size_t)B * light_ws_stride(EH, light_samples);
 }
 
+// every sphere render: light_samples = 0, or a white environment, is the plain one (no workspace, no light kernels)
 int launch_render_refmap_lit(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
                              int flip, int light_samples, void* workspace, size_t workspace_bytes, hipStream_t s) {
   DRM_REQUIRE(light_samples >= 0, "render_refmap_lit: light_samples >= 0");
-  if (light_samples == 0 || !env) return launch_render_refmap_views(z, L, env, view, out, B, R, EH, EW, quad, subpixel, flip, s);
+  const bool lit = light_samples > 0 && env;
   DRM_REQUIRE(z && out, "render_refmap: null pointer");
-  DRM_REQUIRE(L > 0 && B > 0 && B <= 65535 && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
-              "render_refmap_lit: L >= 1 stacks of 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192");
-  DRM_REQUIRE(quad >= 1 && quad <= 1024 && subpixel >= 1 && subpixel <= 16, "render_refmap: quad in [1, 1024], subpixel in [1, 16]");
-  DRM_REQUIRE(EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28), "render_refmap: envmap must be EH x EW with EH, EW >= 1");
-  DRM_REQUIRE(light_samples_ok(light_samples), "render_refmap_lit: light_samples must be 0 or a power of two in [64, 65536]");
-  const size_t need = render_light_workspace_bytes(B, EH, EW, light_samples);
-  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
-    set_error("render_refmap_lit: workspace must be 8-byte aligned and hold drm_render_light_workspace_bytes = " + std::to_string(need) + " bytes");
-    return DRM_ERR_WORKSPACE;
+  DRM_REQUIRE(L > 0 && B > 0 && (!lit || B <= 65535) && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
+              lit ? "render_refmap_lit: L >= 1 stacks of 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192"
+                  : "render_refmap: L >= 1 stacks of B >= 1 rows of R x R pixels, 1 <= R <= 8192");
+  DRM_TRY(check_quadrature("render_refmap", quad, subpixel, 16, env, EH, EW));
+  char* ws = lit ? static_cast<char*>(workspace) : nullptr;
+  if (lit) {
+    DRM_REQUIRE(light_samples_ok(light_samples), "render_refmap_lit: light_samples must be 0 or a power of two in [64, 65536]");
+    const size_t need = render_light_workspace_bytes(B, EH, EW, light_samples);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
+      set_error("render_refmap_lit: workspace must be 8-byte aligned and hold drm_render_light_workspace_bytes = " + std::to_string(need) + " bytes");
+      return DRM_ERR_WORKSPACE;
+    }
   }
-  const long long blocks = ((long long)L * B * R * R + kRenderWaves - 1) / kRenderWaves;
+  const long long blocks = pixel_blocks((long long)L * B * R * R);
   DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: L B R^2 too large for one launch");
-  char* ws = static_cast<char*>(workspace);
-  hipLaunchKernelGGL(light_rows_kernel, dim3((unsigned)(EH + 1), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
-  hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)B), dim3(64), 0, s, ws, EH, EW, light_samples);
-  hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(light_samples / 4), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
-  hipLaunchKernelGGL((view ? refmap_render_kernel<true, true> : refmap_render_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
-                     env, view, out, L * B, B, R, EH, EW, quad, subpixel, flip ? 1 : 0, ws, light_samples);
+  if (lit) {
+    hipLaunchKernelGGL(light_rows_kernel, dim3((unsigned)(EH + 1), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
+    hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)B), dim3(64), 0, s, ws, EH, EW, light_samples);
+    hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(light_samples / 4), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, light_samples);
+  }
+  // (a view only turns the environment: under a white one it changes nothing and is not read)
+  const bool with_view = env && view;
+  const auto kernel = lit ? (with_view ? refmap_render_kernel<true, true> : refmap_render_kernel<false, true>)
+                          : (with_view ? refmap_render_kernel<true, false> : refmap_render_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, with_view ? view : nullptr, out, L * B, B, R, env ? EH : 1,
+                     env ? EW : 1, quad, subpixel, flip ? 1 : 0, ws, lit ? light_samples : 0);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
+}
+
+int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
+                               int subpixel, int flip, hipStream_t s) {
+  return launch_render_refmap_lit(z, L, env, view, out, B, R, EH, EW, quad, subpixel, flip, 0, nullptr, 0, s);
 }
 
 // the two mesh renders: the same checks and visibility launches; `shadowed` verifies the blob (nothing is launched before that) and shades with it
@@ -747,12 +748,11 @@ static int render_mesh_impl(const float* positions, const float* normals, const 
                             const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
                             int subpixel, void* workspace, size_t workspace_bytes, bool shadowed, const void* bvh, size_t bvh_bytes, hipStream_t s) {
   DRM_REQUIRE(positions && normals && faces && z && image, "render_mesh: null pointer");
-  DRM_REQUIRE(quad >= 1 && quad <= 1024, "render_mesh: quad in [1, 1024]");
-  DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), "render_mesh: envmap must be EH x EW with EH, EW >= 1");
+  DRM_TRY(check_quadrature("render_mesh", quad, subpixel, 0, env, EH, EW));
   const size_t need = render_mesh_workspace_bytes(F, B, H, W, subpixel);
   DRM_REQUIRE(need != 0 && V >= 1 && V <= 0x7fffffffLL,
               "render_mesh: 1 <= F < 2^24 faces, V >= 1 vertices, 1 <= B <= 65535 rows, H and W in [1, 4096], subpixel in [1, 4]");
-  const long long blocks = ((long long)B * H * W + kRenderWaves - 1) / kRenderWaves;
+  const long long blocks = pixel_blocks((long long)B * H * W);
   DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_mesh: B H W too large for one launch");
   if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
     set_error("render_mesh: workspace must be 16-byte aligned and hold drm_render_mesh_workspace_bytes = " + std::to_string(need) + " bytes");
@@ -762,14 +762,12 @@ static int render_mesh_impl(const float* positions, const float* normals, const 
   float* records = static_cast<float*>(workspace);
   float* hits = records + (size_t)B * F * kMeshRecordWords;
   DRM_TRY(launch_mesh_visibility(positions, faces, V, F, view, B, H, W, subpixel, records, hits, s));
-  if (shadowed)
-    hipLaunchKernelGGL((view ? mesh_shade_kernel<true, true> : mesh_shade_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
-                       env, view, normals, records, hits, image, normal, depth, alpha, B, F, H, W, env ? EH : 1, env ? EW : 1, quad, subpixel,
-                       ShadowArgs{positions, faces, V, bvh});
-  else
-    hipLaunchKernelGGL((view ? mesh_shade_kernel<true, false> : mesh_shade_kernel<false, false>), dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z,
-                       env, view, normals, records, hits, image, normal, depth, alpha, B, F, H, W, env ? EH : 1, env ? EW : 1, quad, subpixel,
-                       NoShadowArgs{});
+  const auto shade = [&](auto kernel, auto sh) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, view, normals, records, hits, image, normal, depth, alpha, B, F,
+                       H, W, env ? EH : 1, env ? EW : 1, quad, subpixel, sh);
+  };
+  if (shadowed) shade(view ? mesh_shade_kernel<true, true> : mesh_shade_kernel<false, true>, ShadowArgs{positions, faces, V, bvh});
+  else shade(view ? mesh_shade_kernel<true, false> : mesh_shade_kernel<false, false>, NoShadowArgs{});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

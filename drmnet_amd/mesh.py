@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .render import QUAD, SUBPIXEL, _device, canonical_rows, view_rotation
+from .render import QUAD, SUBPIXEL, _device, _env_and_view, canonical_rows, view_rotation
 
 Mesh = Dict[str, torch.Tensor]
 _KEYS = ("vertex_positions", "vertex_normals", "faces")
@@ -215,19 +215,7 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     H, W = (int(image_size), int(image_size)) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
     rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
     pos, nrm, faces = _mesh_on(obj, dev)
-    env, EH, EW = None, 0, 0
-    if envmaps is not None:
-        env = envmaps.to(dev, torch.float32)
-        if env.dim() != 4 or env.shape[0] != B or env.shape[3] != 3:
-            raise ValueError(f"envmaps must be [B={B}, H, W, 3], got {tuple(env.shape)}")
-        env = env.contiguous()
-        EH, EW = int(env.shape[1]), int(env.shape[2])
-    view = None
-    if view_from is not None:
-        view = view_rotation(view_from)
-        if view.shape[0] != B:
-            raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
-        view = view.to(dev)
+    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
     lib = _lib.lib()
     V, F = int(pos.shape[0]), int(faces.shape[0])
     nbytes = int(lib.drm_render_mesh_workspace_bytes(F, B, H, W, int(subpixel)))

@@ -73,6 +73,24 @@ def view_rotation(view_from) -> torch.Tensor:
     return torch.stack([right, up, back], dim=-1).contiguous()
 
 
+def _env_and_view(envmaps, view_from, B: int, dev: torch.device):
+    """envmaps [B, H, W, 3] (or None: white) and view_from [B, 3] (or None: +z), checked against B and brought to ``dev`` ->
+    (env, EH, EW, view [B, 3, 3]); None, 0, 0 and None for what is not given."""
+    env, EH, EW, view = None, 0, 0, None
+    if envmaps is not None:
+        env = envmaps.to(dev, torch.float32)
+        if env.dim() != 4 or env.shape[0] != B or env.shape[3] != 3:
+            raise ValueError(f"envmaps must be [B={B}, H, W, 3], got {tuple(env.shape)}")
+        env = env.contiguous()
+        EH, EW = int(env.shape[1]), int(env.shape[2])
+    if view_from is not None:
+        view = view_rotation(view_from)
+        if view.shape[0] != B:
+            raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
+        view = view.to(dev)
+    return env, EH, EW, view
+
+
 @torch.no_grad()
 def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD,
            subpixel: int = SUBPIXEL, flip: bool = False, view_from=None, light_samples: int = 0) -> torch.Tensor:
@@ -88,36 +106,22 @@ def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] =
     stacked = z.dim() == 3
     L, B = (z.shape[0], z.shape[1]) if stacked else (1, z.shape[0])
     rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
-    env, EH, EW = None, 0, 0
-    if envmaps is not None:
-        env = envmaps.to(dev, torch.float32)
-        if env.dim() != 4 or env.shape[0] != B or env.shape[3] != 3:
-            raise ValueError(f"envmaps must be [B={B}, H, W, 3], got {tuple(env.shape)}")
-        env = env.contiguous()
-        EH, EW = int(env.shape[1]), int(env.shape[2])
-    view = None
-    if view_from is not None:
-        view = view_rotation(view_from)
-        if view.shape[0] != B:
-            raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
-        view = view.to(dev)
+    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
     out = torch.empty((L * B, 3, res, res), dtype=torch.float32, device=dev)
     light_samples = int(light_samples)
     if light_samples < 0:
         raise ValueError(f"light_samples must be >= 0, got {light_samples}")
+    lib = _lib.lib()
+    entry, light_args = lib.drm_render_refmap_views, ()
     if light_samples and env is not None:
-        lib = _lib.lib()
         nbytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
         if nbytes == 0:
             raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
         ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.drm_render_refmap_lit(rows.data_ptr(), L, env.data_ptr(), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad),
-                                                 int(subpixel), int(bool(flip)), light_samples, ws.data_ptr(), nbytes, _lib.stream_ptr(dev)))
-        return out.reshape(L, B, 3, res, res) if stacked else out
+        entry, light_args = lib.drm_render_refmap_lit, (light_samples, ws.data_ptr(), nbytes)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().drm_render_refmap_views(rows.data_ptr(), L, _lib.ptr(env), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad),
-                                                      int(subpixel), int(bool(flip)), _lib.stream_ptr(dev)))
+        _lib.check(entry(rows.data_ptr(), L, _lib.ptr(env), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad), int(subpixel),
+                         int(bool(flip)), *light_args, _lib.stream_ptr(dev)))
     return out.reshape(L, B, 3, res, res) if stacked else out
 
 

@@ -143,53 +143,20 @@ def render_mis(z, env, R, Q=32, S=2, M=1024, flip=False, rot=None, rows=None):
 def _mis_rows(z, den, n, Q, M, rot, table):
     m, c, r, alpha, eta = rr.params(z)
     S2 = n.shape[2]
+    ns = nd = float(Q * Q)
+    # the lobes of render_ref, each sample weighted by the power heuristic against the light technique
+    acc = 0.0
+    for lobe in rr.lobes(z, n, Q):
+        if lobe is None:
+            continue
+        w = lobe.w
+        if M:
+            w = w * np.where(lobe.ok, _power(ns * lobe.pdf, M * light_pdf(den, lobe.l @ rot.T)), 0.0)[..., None]
+        acc = acc + (w * rr.env_lookup(den.env, lobe.l, rot)).sum(axis=(2, 3))
+    acc = acc / (S2 * Q * Q)
     n = n[..., None, :]  # [rows, R, S2, 1, 3]
     v = np.array([0.0, 0.0, 1.0])
     cv = n[..., 2]
-    t, bt = rr._frame(n)
-    g = (np.arange(Q) + 0.5) / Q
-    U1, U2 = (a.reshape(-1) for a in np.meshgrid(g, g, indexing="ij"))
-    cp, sp = np.cos(2 * PI * U2)[:, None], np.sin(2 * PI * U2)[:, None]
-    ns = nd = float(Q * Q)
-    # specular lobe (render_ref._quadrature), each sample weighted by the power heuristic against the light technique
-    V = np.stack([-alpha * n[..., 0], -alpha * n[..., 1], cv], axis=-1)
-    V = V / np.linalg.norm(V, axis=-1, keepdims=True)
-    lensq = V[..., 0] ** 2 + V[..., 1] ** 2
-    with np.errstate(divide="ignore", invalid="ignore"):
-        T1 = np.where((lensq > 0)[..., None], np.stack([-V[..., 1], V[..., 0], np.zeros_like(lensq)], axis=-1) / np.sqrt(lensq)[..., None],
-                      np.array([1.0, 0.0, 0.0]))
-    T2 = np.cross(V, T1)
-    rs = np.sqrt(U1)
-    t1 = rs * cp[:, 0]
-    vs = 0.5 * (1 + V[..., 2])
-    t2 = (1 - vs) * np.sqrt(1 - t1 * t1) + vs * rs * sp[:, 0]
-    tz = np.sqrt(np.maximum(1 - t1 * t1 - t2 * t2, 0))
-    Nh = t1[:, None] * T1 + t2[..., None] * T2 + tz[..., None] * V
-    Ne = np.stack([alpha * Nh[..., 0], alpha * Nh[..., 1], np.maximum(Nh[..., 2], 0)], axis=-1)
-    Ne = Ne / np.linalg.norm(Ne, axis=-1, keepdims=True)
-    h = Ne[..., 0:1] * t + Ne[..., 1:2] * bt + Ne[..., 2:3] * n
-    vh = h[..., 2]
-    l = 2 * vh[..., None] * h - v
-    cl = rr._dot(n, l)
-    D = rr.ggx_d(alpha, Ne[..., 2])
-    ok = (vh > 0) & (cl > 0) & (D > 0)
-    w = np.where(ok, rr.ggx_g1(alpha, cl, vh), 0.0)
-    if M:
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ps = rr.ggx_g1(alpha, cv, vh) * D / (4 * cv)
-        w = w * np.where(ok, _power(ns * ps, M * light_pdf(den, l @ rot.T)), 0.0)
-    F = (1 - m) * rr.fresnel_dielectric(vh, eta)[..., None] + m * (c + (1 - c) * rr.schlick(vh)[..., None])
-    acc = (F * w[..., None] * rr.env_lookup(den.env, l @ rot.T)).sum(axis=(2, 3))
-    # diffuse lobe
-    if m < 1:
-        rs, cl = np.sqrt(U1)[:, None], np.sqrt(1 - U1)
-        l = cl[:, None] * n + rs * cp * t + rs * sp * bt
-        cd = rr._normalize(l + v)[..., 2]
-        w = (1 - m) * rr.diffuse_shape(r, cl, cv, cd)
-        if M:
-            w = w * _power(nd * cl / PI, M * light_pdf(den, l @ rot.T))
-        acc = acc + (c * w[..., None] * rr.env_lookup(den.env, l @ rot.T)).sum(axis=(2, 3))
-    acc = acc / (S2 * Q * Q)
     if M:
         d, L, pl = table
         keep = pl > 0

@@ -120,19 +120,6 @@ def shading_normals(vis, normals, faces, Rot):
     return np.where(hit[..., None], unit, 0.0)
 
 
-def _quadrature_view(z, env, n, Q, Rot):
-    """render_ref._quadrature with the environment looked up at Rot l"""
-    if env is None or Rot is None:
-        return rr._quadrature(z, env, n, Q)
-    R = np.asarray(Rot, dtype=np.float64)
-    plain = rr.env_lookup
-    rr.env_lookup = lambda e, w: plain(e, w @ R.T)
-    try:
-        return rr._quadrature(z, env, n, Q)
-    finally:
-        rr.env_lookup = plain
-
-
 def sample_radiance(z, env, n, Q, Rot=None, chunk=2048):
     """[..., 3] radiance toward +z of surface points with unit normals n [..., 3]; zero where n.z <= 0"""
     n = np.asarray(n, dtype=np.float64)
@@ -141,7 +128,7 @@ def sample_radiance(z, env, n, Q, Rot=None, chunk=2048):
     lit = np.nonzero(flat[:, 2] > 0)[0]
     for k in range(0, len(lit), chunk):
         sel = lit[k:k + chunk]
-        out[sel] = _quadrature_view(z, env, flat[sel].reshape(-1, 1, 1, 3), Q, Rot)[:, :, 0].T
+        out[sel] = rr._quadrature(z, env, flat[sel].reshape(-1, 1, 1, 3), Q, Rot)[:, :, 0].T
     return out.reshape(n.shape)
 
 

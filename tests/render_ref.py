@@ -3,6 +3,8 @@ Mitsuba 3's principled BSDF restricted to (metallic, base colour, roughness, spe
 envmap lookup.  Used by tests/test_render_cpu.py and tests/test_gpu_render.py; nothing here touches a GPU.
 
 A canonical BSDF row is z = (metallic m, base colour c_R, c_G, c_B, roughness r, specular s).  Vectors are [..., 3] arrays."""
+from collections import namedtuple
+
 import numpy as np
 
 PI = np.pi
@@ -86,9 +88,11 @@ def env_dirs(EH, EW):
     return d, np.sin(T) * (PI / EH) * (2 * PI / EW)
 
 
-def env_lookup(env, w):
-    """bilinear radiance of env [EH, EW, 3] toward unit directions w [..., 3]: wraps in psi, clamps in theta"""
+def env_lookup(env, w, rot=None):
+    """bilinear radiance of env [EH, EW, 3] toward unit directions w [..., 3] (rot [3, 3]: toward rot w): wraps in psi, clamps in theta"""
     EH, EW = env.shape[:2]
+    if rot is not None:
+        w = w @ np.asarray(rot, dtype=np.float64).T
     u = np.arctan2(w[..., 0], -w[..., 2]) / (2 * PI)
     t = np.arccos(np.clip(w[..., 1], -1, 1)) / PI
     x = u * EW - 0.5
@@ -118,12 +122,57 @@ def sensor_normals(R, S, flip=False):
     return n.reshape(R, S, R, S, 3).transpose(0, 2, 1, 3, 4).reshape(R, R, S * S, 3)
 
 
-def _frame(n):
-    ka = -1.0 / (1.0 + n[..., 2])
+Lobe = namedtuple("Lobe", "l w ok pdf")
+
+
+def lobes(z, n, Q):
+    """The lobe construction, stated once: for unit normals n [..., 3] with n.z > 0 and every point q = q1 Q + q2 of the Q x Q midpoint grid,
+    (specular, diffuse) as Lobe(l [..., Q^2, 3] direction, w [..., Q^2, 3] RGB weight, ok [..., Q^2] validity, pdf [..., Q^2] sampling
+    density); diffuse is None when m == 1.  The radiance toward +z is (sum w_s L(l_s) + sum w_d L(l_d)) / Q^2.
+    Specular: h from the visible normals of GGX seen from v (Heitz 2018), l = reflect(v, h), w = F G1(l) (0 where not ok),
+    pdf = G1(v) D / (4 n.v).  Diffuse: cosine-weighted l, w = c (1 - m) shape, pdf = n.l / pi, ok everywhere."""
+    m, c, r, alpha, eta = params(z)
+    n = np.asarray(n, dtype=np.float64)[..., None, :]
+    v = np.array([0.0, 0.0, 1.0])
+    cv = n[..., 2]
+    ka = -1.0 / (1.0 + n[..., 2])  # the frame (t, bt, n) of Duff et al. 2017
     kb = n[..., 0] * n[..., 1] * ka
     t = np.stack([1 + n[..., 0] ** 2 * ka, kb, -n[..., 0]], axis=-1)
     bt = np.stack([kb, 1 + n[..., 1] ** 2 * ka, -n[..., 1]], axis=-1)
-    return t, bt
+    g = (np.arange(Q) + 0.5) / Q
+    U1, U2 = (a.reshape(-1) for a in np.meshgrid(g, g, indexing="ij"))
+    cp, sp = np.cos(2 * PI * U2), np.sin(2 * PI * U2)
+    V = np.stack([-alpha * n[..., 0], -alpha * n[..., 1], cv], axis=-1)  # v in the (t, bt, n) frame, stretched
+    V = V / np.linalg.norm(V, axis=-1, keepdims=True)
+    lensq = V[..., 0] ** 2 + V[..., 1] ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        T1 = np.where((lensq > 0)[..., None], np.stack([-V[..., 1], V[..., 0], np.zeros_like(lensq)], axis=-1) / np.sqrt(lensq)[..., None],
+                      np.array([1.0, 0.0, 0.0]))
+    T2 = np.cross(V, T1)
+    rs = np.sqrt(U1)
+    t1 = rs * cp
+    vs = 0.5 * (1 + V[..., 2])
+    t2 = (1 - vs) * np.sqrt(1 - t1 * t1) + vs * rs * sp
+    tz = np.sqrt(np.maximum(1 - t1 * t1 - t2 * t2, 0))
+    Nh = t1[:, None] * T1 + t2[..., None] * T2 + tz[..., None] * V
+    Ne = np.stack([alpha * Nh[..., 0], alpha * Nh[..., 1], np.maximum(Nh[..., 2], 0)], axis=-1)
+    Ne = Ne / np.linalg.norm(Ne, axis=-1, keepdims=True)
+    h = Ne[..., 0:1] * t + Ne[..., 1:2] * bt + Ne[..., 2:3] * n
+    vh = h[..., 2]
+    l = 2 * vh[..., None] * h - v
+    cl = _dot(n, l)
+    D = ggx_d(alpha, Ne[..., 2])
+    ok = (vh > 0) & (cl > 0) & (D > 0)
+    F = (1 - m) * fresnel_dielectric(vh, eta)[..., None] + m * (c + (1 - c) * schlick(vh)[..., None])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        spec = Lobe(l, F * np.where(ok, ggx_g1(alpha, cl, vh), 0.0)[..., None], ok, ggx_g1(alpha, cv, vh) * D / (4 * cv))
+    if not m < 1:
+        return spec, None
+    cl = np.sqrt(1 - U1)
+    l = cl[:, None] * n + (rs * cp)[:, None] * t + (rs * sp)[:, None] * bt
+    cd = _normalize(l + v)[..., 2]
+    w = c * ((1 - m) * diffuse_shape(r, cl, cv, cd))[..., None]
+    return spec, Lobe(l, w, np.ones(ok.shape, dtype=bool), np.broadcast_to(cl / PI, ok.shape))
 
 
 def render_quadrature(z, env, R, Q=32, S=2, flip=False):
@@ -133,49 +182,13 @@ def render_quadrature(z, env, R, Q=32, S=2, flip=False):
     return np.concatenate([_quadrature(z, env, n[i:i + rows], Q) for i in range(0, R, rows)], axis=1)
 
 
-def _quadrature(z, env, n, Q):
-    m, c, r, alpha, eta = params(z)
-    S2 = n.shape[2]
-    n = n[..., None, :]  # [rows, R, S2, 1, 3]
-    v = np.array([0.0, 0.0, 1.0])
-    cv = n[..., 2]
-    t, bt = _frame(n)
-    g = (np.arange(Q) + 0.5) / Q
-    U1, U2 = (a.reshape(-1) for a in np.meshgrid(g, g, indexing="ij"))  # q = q1 * Q + q2
-    cp, sp = np.cos(2 * PI * U2)[:, None], np.sin(2 * PI * U2)[:, None]
-    look = (lambda w: np.ones(w.shape[:-1] + (3,))) if env is None else (lambda w: env_lookup(env, w))
-    # specular lobe: visible normals of GGX seen from v (Heitz 2018), l = reflect(v, h), weight F G1(l)
-    V = np.stack([-alpha * n[..., 0], -alpha * n[..., 1], cv], axis=-1)  # v in the (t, bt, n) frame, stretched
-    V = V / np.linalg.norm(V, axis=-1, keepdims=True)
-    lensq = V[..., 0] ** 2 + V[..., 1] ** 2
-    with np.errstate(divide="ignore", invalid="ignore"):
-        T1 = np.where((lensq > 0)[..., None], np.stack([-V[..., 1], V[..., 0], np.zeros_like(lensq)], axis=-1) / np.sqrt(lensq)[..., None],
-                      np.array([1.0, 0.0, 0.0]))
-    T2 = np.cross(V, T1)
-    rs = np.sqrt(U1)
-    t1 = rs * cp[:, 0]
-    vs = 0.5 * (1 + V[..., 2])
-    t2 = (1 - vs) * np.sqrt(1 - t1 * t1) + vs * rs * sp[:, 0]
-    tz = np.sqrt(np.maximum(1 - t1 * t1 - t2 * t2, 0))
-    Nh = t1[:, None] * T1 + t2[..., None] * T2 + tz[..., None] * V
-    Ne = np.stack([alpha * Nh[..., 0], alpha * Nh[..., 1], np.maximum(Nh[..., 2], 0)], axis=-1)
-    Ne = Ne / np.linalg.norm(Ne, axis=-1, keepdims=True)
-    h = Ne[..., 0:1] * t + Ne[..., 1:2] * bt + Ne[..., 2:3] * n
-    vh = h[..., 2]
-    l = 2 * vh[..., None] * h - v
-    cl = _dot(n, l)
-    ok = (vh > 0) & (cl > 0) & (ggx_d(alpha, Ne[..., 2]) > 0)
-    w = np.where(ok, ggx_g1(alpha, cl, vh), 0.0)[..., None]
-    F = (1 - m) * fresnel_dielectric(vh, eta)[..., None] + m * (c + (1 - c) * schlick(vh)[..., None])
-    acc = (F * w * look(l)).sum(axis=(2, 3))
-    # diffuse lobe
-    if m < 1:
-        rs, cl = np.sqrt(U1)[:, None], np.sqrt(1 - U1)
-        l = cl[:, None] * n + rs * cp * t + rs * sp * bt
-        cd = _normalize(l + v)[..., 2]
-        w = ((1 - m) * diffuse_shape(r, cl, cv, cd))[..., None]
-        acc = acc + (c * w * look(l)).sum(axis=(2, 3))
-    return (acc / (S2 * Q * Q)).transpose(2, 0, 1)
+def _quadrature(z, env, n, Q, rot=None):
+    """the plain sum over both lobes and the S2 normals of every pixel: n [rows, R, S2, 3] -> [3, rows, R]; the environment is read at rot l"""
+    acc = 0.0
+    for lobe in lobes(z, n, Q):
+        if lobe is not None:
+            acc = acc + (lobe.w if env is None else lobe.w * env_lookup(env, lobe.l, rot)).sum(axis=(2, 3))
+    return (acc / (n.shape[2] * Q * Q)).transpose(2, 0, 1)
 
 
 def render_texel_sum(z, env, R, S=2, supersample=4, flip=False, rows=None):

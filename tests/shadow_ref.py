@@ -92,50 +92,6 @@ def occluded(positions, faces, origins, dirs, exclude=None, chunk=None, marginal
     return (hit, marg) if marginal else hit
 
 
-def lobes(z, n, Q):
-    """The directions and weights of render_ref._quadrature, kept per direction, for unit normals n [M, 3] with n.z > 0.  Returns
-    (l_spec [M, Q^2, 3], w_spec [M, Q^2, 3], traced_spec [M, Q^2], l_diff [M, Q^2, 3] or None, w_diff [M, Q^2, 3] or None): the radiance is
-    (sum w_spec L(l_spec) + sum w_diff L(l_diff)) / Q^2; traced_spec marks the specular directions with a non-zero weight."""
-    m, c, r, alpha, eta = rr.params(z)
-    n = np.asarray(n, dtype=np.float64)[:, None, :]
-    v = np.array([0.0, 0.0, 1.0])
-    cv = n[..., 2]
-    t, bt = rr._frame(n)
-    g = (np.arange(Q) + 0.5) / Q
-    U1, U2 = (a.reshape(-1) for a in np.meshgrid(g, g, indexing="ij"))
-    cp, sp = np.cos(2 * rr.PI * U2), np.sin(2 * rr.PI * U2)
-    Vv = np.stack([-alpha * n[..., 0], -alpha * n[..., 1], cv], axis=-1)
-    Vv = Vv / np.linalg.norm(Vv, axis=-1, keepdims=True)
-    lensq = Vv[..., 0] ** 2 + Vv[..., 1] ** 2
-    with np.errstate(divide="ignore", invalid="ignore"):
-        T1 = np.where((lensq > 0)[..., None], np.stack([-Vv[..., 1], Vv[..., 0], np.zeros_like(lensq)], axis=-1) / np.sqrt(lensq)[..., None],
-                      np.array([1.0, 0.0, 0.0]))
-    T2 = np.cross(Vv, T1)
-    rs = np.sqrt(U1)
-    t1 = rs * cp
-    vs = 0.5 * (1 + Vv[..., 2])
-    t2 = (1 - vs) * np.sqrt(1 - t1 * t1) + vs * rs * sp
-    tz = np.sqrt(np.maximum(1 - t1 * t1 - t2 * t2, 0))
-    Nh = t1[:, None] * T1 + t2[..., None] * T2 + tz[..., None] * Vv
-    Ne = np.stack([alpha * Nh[..., 0], alpha * Nh[..., 1], np.maximum(Nh[..., 2], 0)], axis=-1)
-    Ne = Ne / np.linalg.norm(Ne, axis=-1, keepdims=True)
-    h = Ne[..., 0:1] * t + Ne[..., 1:2] * bt + Ne[..., 2:3] * n
-    vh = h[..., 2]
-    l_spec = 2 * vh[..., None] * h - v
-    cl = rr._dot(n, l_spec)
-    ok = (vh > 0) & (cl > 0) & (rr.ggx_d(alpha, Ne[..., 2]) > 0)
-    w = np.where(ok, rr.ggx_g1(alpha, cl, vh), 0.0)[..., None]
-    Fr = (1 - m) * rr.fresnel_dielectric(vh, eta)[..., None] + m * (c + (1 - c) * rr.schlick(vh)[..., None])
-    w_spec = Fr * w
-    if not m < 1:
-        return l_spec, w_spec, ok, None, None
-    rs, cl = np.sqrt(U1)[:, None], np.sqrt(1 - U1)
-    l_diff = cl[:, None] * n + rs * cp[:, None] * t + rs * sp[:, None] * bt
-    cd = rr._normalize(l_diff + v)[..., 2]
-    w_diff = c * ((1 - m) * rr.diffuse_shape(r, cl, cv, cd))[..., None]
-    return l_spec, w_spec, ok, l_diff, w_diff
-
-
 def trace(positions, normals, faces, z, Rot, H, W, S, Q, shadows=True, guard=GUARD):
     """Everything of one row that does not depend on the environment: mesh_ref's visibility and shading normals, and for the M lit samples
     (a hit with n.z > 0) the lobe directions with their weights, visibility (`open_*`: 1 where the ray is not occluded) and marginal masks.
@@ -149,25 +105,24 @@ def trace(positions, normals, faces, z, Rot, H, W, S, Q, shadows=True, guard=GUA
     R = np.eye(3) if Rot is None else np.asarray(Rot, dtype=np.float64)
     origin = np.stack([X[lit], Y[lit], vis["z"][lit]], axis=-1) @ R.T
     face = vis["face"][lit]
-    l_spec, w_spec, traced_spec, l_diff, w_diff = lobes(z, n[lit], Q)
-    M, QQ = traced_spec.shape
-    out = dict(vis=vis, normal=n, lit=lit, origin=origin, face=face, Rot=Rot, shape=(H, W, S, Q), l_spec=l_spec, w_spec=w_spec,
-               traced_spec=traced_spec, l_diff=l_diff, w_diff=w_diff)
-    for name, l in (("spec", l_spec), ("diff", l_diff)):
-        if l is None:
+    spec, diff = rr.lobes(z, n[lit], Q)
+    M, QQ = spec.ok.shape
+    out = dict(vis=vis, normal=n, lit=lit, origin=origin, face=face, Rot=Rot, shape=(H, W, S, Q), traced_spec=spec.ok, traced=0, marginal=0,
+               occluded=0)
+    for name, lobe in (("spec", spec), ("diff", diff)):
+        out["l_" + name], out["w_" + name] = (None, None) if lobe is None else (lobe.l, lobe.w)
+        if lobe is None:
             continue
         if shadows:
-            hit, marg = occluded(positions, faces, np.repeat(origin, QQ, axis=0), (l @ R.T).reshape(-1, 3), np.repeat(face, QQ), marginal=True)
+            hit, marg = occluded(positions, faces, np.repeat(origin, QQ, axis=0), (lobe.l @ R.T).reshape(-1, 3), np.repeat(face, QQ), marginal=True)
             hit, marg = hit.reshape(M, QQ), marg.reshape(M, QQ)
         else:
             hit, marg = np.zeros((M, QQ), dtype=bool), np.zeros((M, QQ), dtype=bool)
-        if name == "spec":  # (only directions with a non-zero weight are traced)
-            hit, marg = hit & traced_spec, marg & traced_spec
+        hit, marg = hit & lobe.ok, marg & lobe.ok  # (only directions with a non-zero weight are traced: every diffuse one)
         out["open_" + name], out["marginal_" + name] = ~hit, marg
-    traced = int(traced_spec.sum()) + (0 if l_diff is None else M * QQ)
-    out["traced"] = traced
-    out["marginal"] = int(out["marginal_spec"].sum()) + (0 if l_diff is None else int(out["marginal_diff"].sum()))
-    out["occluded"] = int((~out["open_spec"]).sum()) + (0 if l_diff is None else int((~out["open_diff"]).sum()))
+        out["traced"] += int(lobe.ok.sum())
+        out["marginal"] += int(marg.sum())
+        out["occluded"] += int(hit.sum())
     return out
 
 
@@ -175,8 +130,7 @@ def shade(tr, env):
     """The row's pixels under env [EH, EW, 3] (None: white) -> dict of image [3, H, W], slack [3, H, W] (the sum of the absolute contributions
     of the pixel's marginal rays) and unsafe_pixel [H, W] (mesh_ref's: some sample of the pixel is within the guard of an edge or a depth tie)."""
     H, W, S, Q = tr["shape"]
-    R = np.eye(3) if tr["Rot"] is None else np.asarray(tr["Rot"], dtype=np.float64)
-    look = (lambda l: np.ones(l.shape)) if env is None else (lambda l: rr.env_lookup(env, l @ R.T))
+    look = (lambda l: np.ones(l.shape)) if env is None else (lambda l: rr.env_lookup(env, l, tr["Rot"]))
     M = len(tr["face"])
     rad, slack = np.zeros((M, 3)), np.zeros((M, 3))
     for name in ("spec", "diff"):
