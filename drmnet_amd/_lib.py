@@ -41,7 +41,7 @@ SYMBOLS = [
     "drm_render_refmap", "drm_brdf_eval", "drm_render_refmap_views", "drm_validation_losses",
     "drm_render_refmap_lit", "drm_render_light_workspace_bytes",
     "drm_render_mesh_workspace_bytes", "drm_render_mesh",
-    "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed",
+    "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed", "drm_render_mesh_lit",
     "drm_obs_forward_process", "drm_diffusion_losses",
 ]
 
@@ -209,6 +209,8 @@ def lib() -> C.CDLL:
     L.drm_mesh_occluded.argtypes = [fp, vp, C.c_int64, C.c_int64, vp, fp, fp, vp, vp, C.c_int64, vp]
     L.drm_render_mesh_shadowed.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t,
                                            vp, C.c_size_t, vp]
+    L.drm_render_mesh_lit.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t,
+                                      vp, C.c_size_t, i32, vp, C.c_size_t, vp]
     L.drm_validation_losses.argtypes = [fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]
     L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]

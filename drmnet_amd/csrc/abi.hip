@@ -591,6 +591,17 @@ int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_
   });
 }
 
+int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                        const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
+                        int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
+                        void* light_workspace, size_t light_workspace_bytes, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_mesh_lit(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B, H, W,
+                                  EH, EW, quad, subpixel, workspace, workspace_bytes, bvh, bvh_bytes, light_samples, light_workspace,
+                                  light_workspace_bytes, static_cast<hipStream_t>(stream));
+  });
+}
+
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream) {
   return guarded([&]() -> int { return launch_brdf_eval(z, z_rows, n, v, l, out, (long long)N, static_cast<hipStream_t>(stream)); });
 }

@@ -1,5 +1,5 @@
 // Any-hit ray queries against a triangle mesh: the blob layout of drm_mesh_bvh_build, the triangle rule and the stackless traversal.  Shared by
-// bvh.hip (the host builder, drm_mesh_occluded) and render.hip (mesh_shade_kernel<VIEW, true>).  Everything here is plain C++ compiled for host
+// bvh.hip (the host builder, drm_mesh_occluded) and render.hip (mesh_shade_kernel<VIEW, true, LIGHT>).  Everything here is plain C++ compiled for host
 // and device with -ffp-contract=off: the builder's box arithmetic and the kernels' triangle arithmetic round identically on both sides.
 //
 // The rule (the same text as include/drmnet_hip.h).  A ray (o, d) in object space, d of any length, is occluded iff some face g != exclude with

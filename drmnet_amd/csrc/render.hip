@@ -21,13 +21,15 @@
 //
 // Object images of meshes (drm_render_mesh): mesh.hip finds which face every film sample sees; mesh_shade_kernel here shades the hit with
 // normal_lane_sum, the per-normal body of the sphere's sum, so a mesh point is shaded exactly as the sphere point with the same normal
-// (direct light, no interreflection).  drm_render_mesh_shadowed runs mesh_shade_kernel<VIEW, true>, which traces every quadrature direction
-// from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones.
+// (direct light, no interreflection).  drm_render_mesh_shadowed runs mesh_shade_kernel<VIEW, true, false>, which traces every quadrature
+// direction from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones.  drm_render_mesh_lit runs
+// mesh_shade_kernel<VIEW, SHADOW, true>: the light samples of the sphere's lit render on the mesh, each traced like a lobe direction where
+// there is a BVH.
 //
 // One statement of the quadrature: normal_lane_sum builds both lobes once and accumulates each in one place; what differs between the
-// renders is its technique parameter (Plain, LightSampled, Occluded: see "techniques"), which decides per lobe sample whether it counts,
-// what radiance it reads and what scales its weight.  Every texel fetch is env_taps + bilerp.  Plain holds nothing: the instantiations
-// without light samples and without shadows carry no code and no registers of the other two.
+// renders is its technique parameter (Plain, LightSampled, Occluded, LitOccluded: see "techniques"), which decides per lobe sample whether
+// it counts, what radiance it reads and what scales its weight.  Every texel fetch is env_taps + bilerp.  Plain holds nothing: the
+// instantiations without light samples and without shadows carry no code and no registers of the others.
 #include <type_traits>
 
 #include "bvh.h"
@@ -253,7 +255,7 @@ __host__ __device__ __forceinline__ float env_lookup_pdf(const float* __restrict
 // lobe's sample count times its density at wl (formed only for kNeedsDensity), and returns whether the sample counts at all; if so it has
 // read the radiance into L (left as it is under a white environment) and scaled the weight w.  begin() opens a normal, finish() closes it.
 struct Plain {
-  static constexpr bool kNeedsDensity = false, kTraces = false;
+  static constexpr bool kNeedsDensity = false;
   __host__ __device__ __forceinline__ void begin(const Principled&, V3) {}
   __host__ __device__ __forceinline__ bool take(const float* __restrict__ env, int EH, int EW, V3 wl, float, float&, float L[3]) const {
     if (env) env_lookup(env, EH, EW, wl, L);
@@ -265,7 +267,6 @@ struct Plain {
 
 // The shadowed mesh: a direction the BVH finds cut off between the sample's hit point and the environment is dropped before any lookup.
 struct Occluded : Plain {
-  static constexpr bool kTraces = true;
   MeshRef mesh;
   BvhView tree;
   float o[3];       // the hit point in object space
@@ -276,11 +277,13 @@ struct Occluded : Plain {
   }
 };
 
-// The light technique (not traced): where the map has light (lt.norm > 0) every lobe sample is weighted by the power heuristic against the
+// The light technique: where the map has light (lt.norm > 0) every lobe sample is weighted by the power heuristic against the
 // n_L = lt.M light samples, and finish() lets the lanes stride the light table as they strode the grid, summing into accL (to be
-// normalised by 1 / S^2 only: the weights hold 1 / n).  Needs a map: env is never null here.
+// normalised by 1 / S^2 only: the weights hold 1 / n).  Needs a map: env is never null here.  The table loop is table_sum, written once for
+// this technique and for LitOccluded: it asks open() about a table direction after the cheap rejections (n.l > 0, p_L > 0); here
+// every direction is open and the question compiles to nothing.
 struct LightSampled {
-  static constexpr bool kNeedsDensity = true, kTraces = false;
+  static constexpr bool kNeedsDensity = true;
   LightTable lt;
   float accL[3];
   float nlobe, nlight, sc_pole, g1v;
@@ -292,10 +295,15 @@ struct LightSampled {
     w = w * (lit ? power_weight(np, nlight * pl) : 1.0f);
     return true;
   }
-  // table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame
-  template <bool VIEW>
-  __host__ __device__ __forceinline__ void finish(const Principled& p, const ViewRot& rot, V3 n, int lane, int lanes) {
-    if (!lit) return;
+  __host__ __device__ __forceinline__ bool open(V3) const { return true; }
+  // table entry k = (direction, radiance, p_L), SoA planes of M floats; l_k = Rot^T w_k in the row's frame.  t: the technique itself
+  // (accL, the table) with its own open().
+  template <bool VIEW, typename T>
+  __host__ __device__ static __forceinline__ void table_sum(T& t, const Principled& p, const ViewRot& rot, V3 n, int lane, int lanes) {
+    if (!t.lit) return;
+    const LightTable& lt = t.lt;
+    const float nlight = t.nlight, nlobe = t.nlobe, g1v = t.g1v;
+    float* accL = t.accL;
     const bool diffuse = p.m < 1.0f;
     const float cv = n.z;
     for (int k = lane; k < lt.M; k += lanes) {
@@ -303,7 +311,7 @@ struct LightSampled {
       const float pl = lt.tab[6 * lt.M + k];
       const V3 l = from_world<VIEW>(rot, wd);
       const float cl = dot3(n, l);
-      if (cl > 0.0f && pl > 0.0f) {
+      if (cl > 0.0f && pl > 0.0f && t.open(wd)) {
         V3 h = v3(l.x, l.y, l.z + 1.0f);
         const float hinv = 1.0f / sqrtf(dot3(h, h));
         h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
@@ -320,10 +328,37 @@ struct LightSampled {
       }
     }
   }
+  template <bool VIEW>
+  __host__ __device__ __forceinline__ void finish(const Principled& p, const ViewRot& rot, V3 n, int lane, int lanes) {
+    table_sum<VIEW>(*this, p, rot, n, lane, lanes);
+  }
 };
 __host__ __device__ __forceinline__ LightSampled light_sampled(const LightTable& lt, int EH, int Q) {
   return LightSampled{lt, {0.0f, 0.0f, 0.0f}, (float)(Q * Q), (float)lt.M, sinf(0.25f * kPi / (float)EH), 0.0f, lt.norm > 0.0f};
 }
+
+// The light technique on the shadowed mesh: both of its sample sets estimate L V f cos, V = 0 along an occluded ray, with the weights of
+// LightSampled (p_L knows nothing of occlusion; the weights of a direction still sum to one, so the estimator stays consistent).  A lobe
+// sample is traced where Occluded traces it, before any texel fetch; a table direction -- a world direction, which is the object-space ray
+// direction, as to_world(rot, l) is for a lobe sample -- is traced after its cheap rejections.  mesh, tree and the table are the pixel's;
+// o and exclude are set per hit sample.
+struct LitOccluded : LightSampled {
+  MeshRef mesh;
+  BvhView tree;
+  float o[3];       // the hit point in object space
+  int32_t exclude;  // the hit face
+  __host__ __device__ __forceinline__ bool open(V3 w) const {
+    const Ray r{{o[0], o[1], o[2]}, {w.x, w.y, w.z}};
+    return !bvh_occluded(mesh, tree, r, exclude);
+  }
+  __host__ __device__ __forceinline__ bool take(const float* __restrict__ env, int EH, int EW, V3 wl, float np, float& w, float L[3]) const {
+    return open(wl) && LightSampled::take(env, EH, EW, wl, np, w, L);
+  }
+  template <bool VIEW>
+  __host__ __device__ __forceinline__ void finish(const Principled& p, const ViewRot& rot, V3 n, int lane, int lanes) {
+    table_sum<VIEW>(*this, p, rot, n, lane, lanes);
+  }
+};
 
 // one lane's share of the radiance a surface point with unit normal n (n.z > -1; the callers pass n.z > 0) reflects toward the viewer at +z:
 // the grid points q = lane, lane + lanes, ... of both lobes, summed in that order into acc (unnormalised).  env == nullptr: white
@@ -332,7 +367,8 @@ __host__ __device__ __forceinline__ LightSampled light_sampled(const LightTable&
 template <bool VIEW, typename TECH>
 __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n,
                                                          int Q, int lane, int lanes, float acc[3], TECH& tech) {
-  static_assert(!(TECH::kNeedsDensity && TECH::kTraces), "the light technique is not traced");
+  static_assert(std::is_same_v<TECH, Plain> || std::is_same_v<TECH, Occluded> || std::is_same_v<TECH, LightSampled> || std::is_same_v<TECH, LitOccluded>,
+                "the techniques: {no light samples, light samples} x {not traced, traced}");
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
@@ -461,6 +497,9 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
 // hits, and the hit fraction.  rec / hits: the workspace halves of launch_mesh_visibility.
 // SHADOW: every lobe direction of a hit sample is traced from the hit point -- the view-space (x_sample, y_sample, z_hit) taken to object
 // space with Rot -- through the BVH in sh, the hit face excluded.  Without it sh is an empty struct and the kernel is the one it always was.
+// LIGHT: li holds the light workspace of the B maps (M samples each; see refmap_render_kernel on why the table is not staged in LDS).  The
+// technique is then the pixel's, not the sample's: its accL runs through the pixel's hit samples in sample order and meets in a second
+// butterfly, as in the sphere's lit kernel.  Without it li is an empty struct.
 struct NoShadowArgs {};
 struct ShadowArgs {
   const float* positions;
@@ -468,12 +507,18 @@ struct ShadowArgs {
   long long V;
   const void* bvh;
 };
-template <bool VIEW, bool SHADOW>
+struct NoLightArgs {};
+struct LightArgs {
+  const char* lws;
+  int M;
+};
+template <bool VIEW, bool SHADOW, bool LIGHT>
 __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
                                                          const float* __restrict__ vnormal, const float* __restrict__ rec, const float* __restrict__ hits,
                                                          float* __restrict__ image, float* __restrict__ normal, float* __restrict__ depth,
                                                          float* __restrict__ alpha, int B, long long F, int H, int W, int EH, int EW, int Q, int S,
-                                                         std::conditional_t<SHADOW, ShadowArgs, NoShadowArgs> sh) {
+                                                         std::conditional_t<SHADOW, ShadowArgs, NoShadowArgs> sh,
+                                                         std::conditional_t<LIGHT, LightArgs, NoLightArgs> li) {
   const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (pix >= (long long)B * H * W) return;  // (wave-uniform)
@@ -488,6 +533,14 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
   float acc[3] = {0.0f, 0.0f, 0.0f};
   float nsum[3] = {0.0f, 0.0f, 0.0f}, dsum = 0.0f;
   int count = 0;
+  [[maybe_unused]] std::conditional_t<LIGHT, std::conditional_t<SHADOW, LitOccluded, LightSampled>, Plain> lit;
+  if constexpr (LIGHT) {
+    static_cast<LightSampled&>(lit) = light_sampled(light_table(li.lws, b, EH, li.M), EH, Q);
+    if constexpr (SHADOW) {
+      lit.mesh = MeshRef{sh.positions, sh.faces, sh.V, F};
+      lit.tree = bvh_view(sh.bvh);
+    }
+  }
   for (int sy = 0; sy < S; ++sy) {
     for (int sx = 0; sx < S; ++sx) {
       const float4 h = hit[((size_t)i * S + sy) * W * S + (size_t)j * S + sx];
@@ -509,22 +562,34 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
       dsum += 1.1f - h.w;
       ++count;
       if (n.z > 0.0f) {
-        std::conditional_t<SHADOW, Occluded, Plain> tech;
-        if constexpr (SHADOW) {
-          const V3 o = to_world<VIEW>(rot, v3(mesh_sample_x(j * S + sx, W * S), mesh_sample_y(i * S + sy, H * S, (float)H / (float)W), h.w));
-          tech = Occluded{{}, MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
+        [[maybe_unused]] V3 o;
+        if constexpr (SHADOW) o = to_world<VIEW>(rot, v3(mesh_sample_x(j * S + sx, W * S), mesh_sample_y(i * S + sy, H * S, (float)H / (float)W), h.w));
+        if constexpr (LIGHT) {
+          if constexpr (SHADOW) {
+            lit.o[0] = o.x;
+            lit.o[1] = o.y;
+            lit.o[2] = o.z;
+            lit.exclude = f;
+          }
+          normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lit);
+        } else {
+          std::conditional_t<SHADOW, Occluded, Plain> tech;
+          if constexpr (SHADOW) tech = Occluded{{}, MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
+          normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
         }
-        normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
       }
     }
   }
   wave_sum3(acc);
+  if constexpr (LIGHT) wave_sum3(lit.accL);
   if (lane == 0) {
     const float inv_s2 = 1.0f / (float)(S * S), scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
     const size_t at = (size_t)i * W + j, plane = (size_t)H * W;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      image[((size_t)b * 3 + c) * plane + at] = acc[c] * scale;
+      float px = acc[c] * scale;
+      if constexpr (LIGHT) px = px + lit.accL[c] * inv_s2;
+      image[((size_t)b * 3 + c) * plane + at] = px;
       if (normal) normal[((size_t)b * 3 + c) * plane + at] = nsum[c] * inv_s2;
     }
     if (depth) depth[(size_t)b * plane + at] = count > 0 ? dsum / (float)count : 0.0f;
@@ -743,11 +808,15 @@ int launch_render_refmap_views(const float* z, int L, const float* env, const fl
   return launch_render_refmap_lit(z, L, env, view, out, B, R, EH, EW, quad, subpixel, flip, 0, nullptr, 0, s);
 }
 
-// the two mesh renders: the same checks and visibility launches; `shadowed` verifies the blob (nothing is launched before that) and shades with it
+// the mesh renders: the same checks and visibility launches; `shadowed` verifies the blob (nothing is launched before that) and shades with it;
+// light_samples > 0 under a map checks the light workspace, builds the tables as the sphere's lit render does and shades with them
 static int render_mesh_impl(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
                             const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
-                            int subpixel, void* workspace, size_t workspace_bytes, bool shadowed, const void* bvh, size_t bvh_bytes, hipStream_t s) {
+                            int subpixel, void* workspace, size_t workspace_bytes, bool shadowed, const void* bvh, size_t bvh_bytes, int light_samples,
+                            void* light_workspace, size_t light_workspace_bytes, hipStream_t s) {
   DRM_REQUIRE(positions && normals && faces && z && image, "render_mesh: null pointer");
+  DRM_REQUIRE(light_samples >= 0, "render_mesh_lit: light_samples >= 0");
+  const bool lit = light_samples > 0 && env;
   DRM_TRY(check_quadrature("render_mesh", quad, subpixel, 0, env, EH, EW));
   const size_t need = render_mesh_workspace_bytes(F, B, H, W, subpixel);
   DRM_REQUIRE(need != 0 && V >= 1 && V <= 0x7fffffffLL,
@@ -758,16 +827,33 @@ static int render_mesh_impl(const float* positions, const float* normals, const 
     set_error("render_mesh: workspace must be 16-byte aligned and hold drm_render_mesh_workspace_bytes = " + std::to_string(need) + " bytes");
     return DRM_ERR_WORKSPACE;
   }
+  char* lws = lit ? static_cast<char*>(light_workspace) : nullptr;
+  if (lit) {
+    DRM_REQUIRE(light_samples_ok(light_samples), "render_mesh_lit: light_samples must be 0 or a power of two in [64, 65536]");
+    const size_t light_need = render_light_workspace_bytes(B, EH, EW, light_samples);
+    DRM_REQUIRE(light_need != 0 && light_workspace && light_workspace_bytes >= light_need && (reinterpret_cast<uintptr_t>(light_workspace) & 7) == 0,
+                "render_mesh_lit: light_workspace must be 8-byte aligned and hold drm_render_light_workspace_bytes = " + std::to_string(light_need) +
+                    " bytes");
+  }
   if (shadowed) DRM_TRY(check_device_bvh(bvh, bvh_bytes, true, F, s, "render_mesh_shadowed"));
   float* records = static_cast<float*>(workspace);
   float* hits = records + (size_t)B * F * kMeshRecordWords;
   DRM_TRY(launch_mesh_visibility(positions, faces, V, F, view, B, H, W, subpixel, records, hits, s));
-  const auto shade = [&](auto kernel, auto sh) {
+  if (lit) {
+    hipLaunchKernelGGL(light_rows_kernel, dim3((unsigned)(EH + 1), (unsigned)B), dim3(256), 0, s, env, lws, EH, EW, light_samples);
+    hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)B), dim3(64), 0, s, lws, EH, EW, light_samples);
+    hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(light_samples / 4), (unsigned)B), dim3(256), 0, s, env, lws, EH, EW, light_samples);
+  }
+  const auto shade = [&](auto kernel, auto sh, auto li) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, view, normals, records, hits, image, normal, depth, alpha, B, F,
-                       H, W, env ? EH : 1, env ? EW : 1, quad, subpixel, sh);
+                       H, W, env ? EH : 1, env ? EW : 1, quad, subpixel, sh, li);
   };
-  if (shadowed) shade(view ? mesh_shade_kernel<true, true> : mesh_shade_kernel<false, true>, ShadowArgs{positions, faces, V, bvh});
-  else shade(view ? mesh_shade_kernel<true, false> : mesh_shade_kernel<false, false>, NoShadowArgs{});
+  const ShadowArgs sh{positions, faces, V, bvh};
+  const LightArgs li{lws, light_samples};
+  if (lit && shadowed) shade(view ? mesh_shade_kernel<true, true, true> : mesh_shade_kernel<false, true, true>, sh, li);
+  else if (lit) shade(view ? mesh_shade_kernel<true, false, true> : mesh_shade_kernel<false, false, true>, NoShadowArgs{}, li);
+  else if (shadowed) shade(view ? mesh_shade_kernel<true, true, false> : mesh_shade_kernel<false, true, false>, sh, NoLightArgs{});
+  else shade(view ? mesh_shade_kernel<true, false, false> : mesh_shade_kernel<false, false, false>, NoShadowArgs{}, NoLightArgs{});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
@@ -776,14 +862,23 @@ int launch_render_mesh(const float* positions, const float* normals, const int32
                        const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
                        int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s) {
   return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
-                          workspace_bytes, false, nullptr, 0, s);
+                          workspace_bytes, false, nullptr, 0, 0, nullptr, 0, s);
 }
 
 int launch_render_mesh_shadowed(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
                                 const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
                                 int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, hipStream_t s) {
   return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
-                          workspace_bytes, true, bvh, bvh_bytes, s);
+                          workspace_bytes, true, bvh, bvh_bytes, 0, nullptr, 0, s);
+}
+
+// bvh == nullptr with bvh_bytes == 0: unshadowed
+int launch_render_mesh_lit(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
+                           const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
+                           int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
+                           void* light_workspace, size_t light_workspace_bytes, hipStream_t s) {
+  return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
+                          workspace_bytes, bvh != nullptr || bvh_bytes != 0, bvh, bvh_bytes, light_samples, light_workspace, light_workspace_bytes, s);
 }
 
 int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {

@@ -6,7 +6,8 @@ Operator surface of the reference's mesh helpers (utils/mitsuba3_utils.py): ``Me
 scripts/preprocess_shape.py:40.  Every visible point is shaded as the reflectance-map renderer shades the sphere point with the same
 normal: direct light from the environment map, no interreflection, black background.  Self-shadowing is opt-in
 (``shadows=True``): shadow rays through a bounding-volume hierarchy built on the host (``build_bvh``; csrc/bvh.hip), also offered on their
-own as ``occluded``.  Loading a mesh, building its BVH and constructing a renderer do not touch the GPU; rendering and ray queries run
+own as ``occluded``.  Light sampling is opt-in too (``light_samples=M``: the light samples of ``render.render``, each traced like a lobe
+direction under ``shadows``), for maps with a sun or a lamp a few texels wide.  Loading a mesh, building its BVH and constructing a renderer do not touch the GPU; rendering and ray queries run
 there (no CPU path).
 """
 from __future__ import annotations
@@ -198,10 +199,14 @@ def occluded(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto") -> torch.Ten
 
 @torch.no_grad()
 def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, image_size, view_from=None,
-                quad: int = QUAD, subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None):
+                quad: int = QUAD, subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None, light_samples: int = 0):
     """One call of drm_render_mesh (``shadows=True``: of drm_render_mesh_shadowed, where parts of the mesh cut light off from other parts;
     ``bvh`` is then the mesh's ``build_bvh`` blob, built here when None): one mesh, lit and seen B ways.  z [B, P], envmaps [B, EH, EW, 3] (or None: white), view_from [B, 3] (or
     None: +z), image_size H or (H, W) -> (image [B, 3, H, W], normal [B, 3, H, W] in the view frame, depth [B, 1, H, W], alpha [B, H, W]).
+    ``light_samples`` = M > 0 (a power of two in [64, 65536]) renders through drm_render_mesh_lit: M directions drawn from each map's own
+    light density join the two lobe quadratures by multiple importance sampling, as in ``render.render``, and with ``shadows`` every light
+    sample is traced like a lobe direction, so the cast shadow of a sun is decided by the sun's own samples.  0, or no envmaps, is the
+    render without them bit for bit.
     GPU only: a ``z`` or ``envmaps`` tensor on the CPU, or a machine without a GPU, is a RuntimeError (the mesh itself and ``view_from`` are
     host data and are brought over)."""
     for name, t in (("z", z), ("envmaps", envmaps)):
@@ -227,11 +232,23 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
+    light_samples = int(light_samples)
+    if light_samples < 0:
+        raise ValueError(f"light_samples must be >= 0, got {light_samples}")
+    light_ws, light_bytes = None, 0
+    if light_samples and env is not None:
+        light_bytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
+        if light_bytes == 0:
+            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+        light_ws = torch.empty(((light_bytes + 7) // 8,), dtype=torch.float64, device=dev)
     args = (pos.data_ptr(), nrm.data_ptr(), faces.data_ptr(), V, F, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(), normal.data_ptr(),
             depth.data_ptr(), alpha.data_ptr(), B, H, W, EH, EW, int(quad), int(subpixel), ws.data_ptr(), nbytes)
     with torch.cuda.device(dev):
-        if shadows:
-            blob = _bvh_on(build_bvh(obj) if bvh is None else bvh, dev)
+        blob = _bvh_on(build_bvh(obj) if bvh is None else bvh, dev) if shadows else None
+        if light_ws is not None:
+            _lib.check(lib.drm_render_mesh_lit(*args, _lib.ptr(blob), 0 if blob is None else int(blob.numel()), light_samples, light_ws.data_ptr(),
+                                               light_bytes, _lib.stream_ptr(dev)))
+        elif shadows:
             _lib.check(lib.drm_render_mesh_shadowed(*args, blob.data_ptr(), int(blob.numel()), _lib.stream_ptr(dev)))
         else:
             _lib.check(lib.drm_render_mesh(*args, _lib.stream_ptr(dev)))
@@ -243,14 +260,18 @@ class MeshRenderer:
     the scene's environment map.  Differences from Mitsuba's ``path`` integrator, all by design: direct light only, no
     interreflection, a black background, and self-shadowing only with ``shadows=True`` (the BVH is built once when a mesh becomes the
     scene's and kept with it; a ``new_scene`` mesh gets one for that call).  The integral is the deterministic quadrature of the reflectance-map
-    renderer, so ``spp`` and ``denoise`` are accepted and ignored.  ``init_view_from`` may be any position off the +-y axis.  The scene
+    renderer, so ``spp`` and ``denoise`` are accepted and ignored.  ``light_samples`` = M > 0 adds M light samples per map (see
+    ``render_mesh``; reachable from a YAML ``params:``); the default 0 renders without them.  ``init_view_from`` may be any position off the +-y axis.  The scene
     state -- environment map, view and mesh -- is kept across ``rendering`` calls as the reference's scene keeps it.  Construction does not
     touch the GPU."""
 
     def __init__(self, image_size, spp: int = 1024, envmap_size=(1000, 2000), denoise: Optional[str] = None, return_normal: bool = False,
                  return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
-                 subpixel: int = SUBPIXEL, shadows: bool = False):
+                 subpixel: int = SUBPIXEL, shadows: bool = False, light_samples: int = 0):
         self.shadows = bool(shadows)
+        self.light_samples = int(light_samples)
+        if self.light_samples and (self.light_samples < 64 or self.light_samples > 65536 or self.light_samples & (self.light_samples - 1)):
+            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
         self.image_size = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(s) for s in image_size)
         self.envmap_size = tuple(int(s) for s in envmap_size)
         self.spp, self.denoise = spp, denoise
@@ -302,7 +323,7 @@ class MeshRenderer:
         z = torch.as_tensor(z).reshape(1, -1).to(dev)
         image, normal, depth, _ = render_mesh(mesh, z, brdf_param_names or self.brdf_param_names, env[None], image_size=self.image_size,
                                               view_from=torch.as_tensor(view).reshape(1, 3), quad=self.quad, subpixel=self.subpixel,
-                                              shadows=self.shadows, bvh=bvh)
+                                              shadows=self.shadows, bvh=bvh, light_samples=self.light_samples)
         outs = [image[0]] + ([normal[0]] if self.return_normal else []) + ([depth[0]] if self.return_depth else [])
         if not channel_first:
             outs = [o.permute(1, 2, 0) for o in outs]

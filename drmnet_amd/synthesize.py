@@ -5,11 +5,12 @@
 writes into D the three files ``estimate`` reads,
 
     image.exr    H x W x 3 radiance of the object (drmnet_amd.mesh.render_mesh: direct light, black background; with ``--shadows`` the
-                 object shadows itself)
+                 object shadows itself; with ``--light_samples M`` a sun or a lamp a few texels wide is resolved, its cast shadow included)
     normal.npy   H x W x 3 float32 shading normals in the view frame (right, up, back)
     mask.png     |normal| > 0.5: the pixels more than half covered
 
 and ``refmap.exr``: the reflectance map RefMapRenderer renders for the same (z, envmap, view), the ground truth the estimate should approach.
+``--light_samples`` applies to both renders, so the image and the map it is judged against resolve the same lights.
 ``--z`` is the canonical row (metallic, base colour R G B, roughness, specular).  The mesh (.obj, or a .pt dict) is scaled to radius 0.9
 so that it fits the film from every view; without ``--envmap`` the environment is white.
 """
@@ -42,6 +43,9 @@ def main(argv=None):
     parser.add_argument("--refmap_res", type=int, default=128, help="resolution of refmap.exr")
     parser.add_argument("--quad", type=int, default=QUAD)
     parser.add_argument("--shadows", action="store_true", help="trace shadow rays: parts of the mesh cut light off from other parts (default: off)")
+    parser.add_argument("--light_samples", type=int, default=0,
+                        help="light samples drawn from the environment map, for image.exr and refmap.exr alike: a power of two in [64, 65536] "
+                        "(default 0: the lobe quadrature alone)")
     parser.add_argument("--output_dir", type=Path, default=Path("./outputs/"))
     args = parser.parse_args(argv)
 
@@ -52,8 +56,9 @@ def main(argv=None):
     z = torch.tensor([args.z], dtype=torch.float32, device=dev)
     env = None if args.envmap is None else file_io.load_exr(args.envmap, as_torch=True).to(dev)[None]
     view = torch.tensor([args.view_from], dtype=torch.float32)
-    image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows)
-    refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view)
+    image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows,
+                                     light_samples=args.light_samples)
+    refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view, light_samples=args.light_samples)
     normal = normal[0].permute(1, 2, 0).cpu().numpy()
     mask = np.linalg.norm(normal, axis=-1) > 0.5
     args.output_dir.mkdir(parents=True, exist_ok=True)

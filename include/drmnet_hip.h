@@ -404,7 +404,7 @@ int drm_render_refmap_lit(const float* z, int L, const float* envmap, const floa
  * and depth AOVs).  Every visible point is shaded exactly as drm_render_refmap_views shades the sphere point with the same normal: direct
  * light from the environment map, NO interreflection (Mitsuba's path integrator has it), and the background is black, not the environment.
  * drm_render_mesh has NO self-shadowing either: it is the model the reflectance map itself assumes.  drm_render_mesh_shadowed (below) adds
- * shadow rays.  Additive: the ABI version is unchanged.
+ * shadow rays, drm_render_mesh_lit the light samples of drm_render_refmap_lit, with or without them.  Additive: the ABI version is unchanged.
  *   One mesh per call, lit and seen B ways: vertex_positions, vertex_normals [V][3], faces [F][3] int32 (smooth shading, no back-face
  *   culling), z [B][6], envmap [B][EH][EW][3] or NULL (white), view [B][9] or NULL (+z).
  *   View frame.  right, up, back are the columns of the row-major Rot = view[b] (the rotation drm_render_refmap_views takes).  Mesh points
@@ -421,7 +421,7 @@ int drm_render_refmap_lit(const float* z, int L, const float* envmap, const floa
  *   Outputs per row b: image [3][H][W] the mean over the S^2 samples of the radiance; normal [3][H][W] the mean of the samples' unit shading
  *   normals, zero for a miss (|normal| > 0.5 is "more than half covered", the mask the reference derives); depth [1][H][W] the mean of
  *   1.1 - z_view over the hit samples, 0 where there are none; alpha [H][W] the hit fraction.  normal, depth and alpha may each be NULL.
- *   Limits: quad in [1, 1024], subpixel in [1, 4], H, W in [1, 4096], 1 <= F < 2^24, V >= 1, 1 <= B <= 65535.  light_samples is not offered.
+ *   Limits: quad in [1, 1024], subpixel in [1, 4], H, W in [1, 4096], 1 <= F < 2^24, V >= 1, 1 <= B <= 65535.  Light samples: drm_render_mesh_lit (below).
  *   workspace: at least drm_render_mesh_workspace_bytes = 80 B F + 16 B (H S) (W S) bytes of device memory, 16-byte aligned: one record per
  *   (row, face) and one hit per film sample, rebuilt by every call.  Three launches (mesh_setup_kernel, mesh_visibility_kernel,
  *   mesh_shade_kernel), no atomics: bitwise reproducible, and a call of B rows equals its rows rendered one by one.
@@ -471,6 +471,35 @@ int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64
 int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
                              const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
                              int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, void* stream);
+/* Light sampling on the object images, for maps with small bright lights: drm_render_mesh / drm_render_mesh_shadowed with the light samples of
+ * drm_render_refmap_lit.  Additive: the ABI version is unchanged.
+ *   Arguments: those of drm_render_mesh_shadowed, where bvh == NULL with bvh_bytes == 0 means unshadowed (any other bvh is checked as
+ *   drm_render_mesh_shadowed checks it); then light_samples, light_workspace, light_workspace_bytes; then stream.
+ *   Estimator (the contract).  For a hit sample with shading normal n (n.z > 0), origin o (the view-space hit point taken to object space with
+ *   Rot) and hit face g the integrand is L(w) V(w) f(w) cos: V(w) = 0 iff the ray (o, w) is occluded by the intersection rule above with
+ *   exclude = g; without a BVH V = 1 everywhere.  Both techniques of drm_render_refmap_lit estimate this one integrand with the SAME weights
+ *   as there (n_s = n_d = quad^2, n_d = 0 for a metal, n_L = light_samples):
+ *     each lobe sample keeps its power-heuristic weight (n p)^2 / ((n p)^2 + (n_L p_L)^2) and contributes only if the ray along Rot l is open;
+ *     it is traced where drm_render_mesh_shadowed traces it, before any texel fetch;
+ *     each light-table entry k keeps its term L_k [f_s cos n_L p_L / ((n_s p_s)^2 + (n_L p_L)^2) + f_d cos n_L p_L / ((n_d p_d)^2 + (n_L p_L)^2)]
+ *     / subpixel^2 and contributes only if the ray along its table direction is open.  The table holds world (environment-frame)
+ *     directions, which in the mesh convention are also the object-space ray directions (as Rot l is for a lobe sample); it enters the
+ *     view frame as Rot^T w_k for the BSDF.  It is traced only after its cheap rejections (n.l_k > 0, p_L > 0).
+ *   p_L knows nothing of occlusion; the weights of a direction still sum to one, so the estimator is consistent for the shadowed integral.
+ *   With a BVH the image is <= the one without in every pixel and channel under a non-negative map.  A map whose tot is 0 renders as
+ *   drm_render_mesh / drm_render_mesh_shadowed render it.
+ *   light_samples: 0, or a power of two in [64, 65536].  0, or envmap == NULL, makes exactly the launches of drm_render_mesh /
+ *   drm_render_mesh_shadowed (the light workspace is not read): the same bytes.
+ *   light_workspace: at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device memory, 8-byte aligned, one table per
+ *   map b, rebuilt by every call (the three light launches of drm_render_refmap_lit, after the visibility launches).
+ *   The lanes keep the per-lane order of the sphere's lit kernel over the pixel's hit samples and meet in its two butterflies: bitwise
+ *   reproducible, and a call of B rows equals its rows rendered one by one.
+ *   DRM_ERR_INVALID for a bad light_samples, a missing, misaligned or short light workspace, a short or damaged blob or bad sizes;
+ *   DRM_ERR_WORKSPACE for the mesh workspace, as in drm_render_mesh: nothing is launched. */
+int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                        const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
+                        int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
+                        void* light_workspace, size_t light_workspace_bytes, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
