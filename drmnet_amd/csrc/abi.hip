@@ -591,6 +591,25 @@ int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_
   });
 }
 
+int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins,
+                         const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, int64_t N, void* stream) {
+  return guarded([&]() -> int {
+    return launch_mesh_closest_hit(vertex_positions, faces, (long long)V, (long long)F, bvh, origins, dirs, exclude, out_face, out_tuv, (long long)N,
+                                   static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                            const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                            int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
+                            void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_mesh_bounced(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B,
+                                      H, W, EH, EW, quad, subpixel, workspace, workspace_bytes, bvh, bvh_bytes, bounce_quad,
+                                      static_cast<hipStream_t>(stream));
+  });
+}
+
 int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
                         const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
                         int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,

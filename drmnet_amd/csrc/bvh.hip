@@ -1,5 +1,6 @@
 // The bounding-volume hierarchy behind the shadow rays of drm_render_mesh_shadowed: the host builder (drm_mesh_bvh_build: no HIP call, usable
-// without a GPU) and the stand-alone any-hit query (drm_mesh_occluded).  The blob layout, the triangle rule and the traversal are in bvh.h.
+// without a GPU) and the stand-alone ray queries: any-hit (drm_mesh_occluded) and closest-hit (drm_mesh_closest_hit).  The blob layout, the
+// triangle rule, the order of the closest hit and the traversal are in bvh.h.
 //
 // Builder.  Over object-space positions, so one tree serves every view of a call.  Kept faces (indices in [0, V), finite vertices, a non-zero
 // fp32 cross product) are split at the median of their centroids along the longest axis of the centroids' box (std::nth_element, ties broken
@@ -98,6 +99,21 @@ __global__ __launch_bounds__(256) void mesh_occluded_kernel(MeshRef m, const voi
   out[k] = (bvh ? bvh_occluded(m, bvh_view(bvh), r, ex) : brute_occluded(m, r, ex)) ? 1 : 0;
 }
 
+// grid ceil(N / 256): thread = ray; out_tuv [N][3] = (t, u, v), zeros where out_face is -1
+__global__ __launch_bounds__(256) void mesh_closest_kernel(MeshRef m, const void* __restrict__ bvh, const float* __restrict__ origins,
+                                                           const float* __restrict__ dirs, const int32_t* __restrict__ exclude,
+                                                           int32_t* __restrict__ out_face, float* __restrict__ out_tuv, long long N) {
+  const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= N) return;
+  const Ray r{{origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]}, {dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]}};
+  const int32_t ex = exclude ? exclude[k] : -1;
+  const Hit h = bvh ? bvh_closest(m, bvh_view(bvh), r, ex) : brute_closest(m, r, ex);
+  out_face[k] = h.face;
+  out_tuv[3 * k] = h.t;
+  out_tuv[3 * k + 1] = h.u;
+  out_tuv[3 * k + 2] = h.v;
+}
+
 bool faces_ok(long long F) { return F >= 1 && F < (1LL << 24); }
 
 }  // namespace
@@ -173,6 +189,19 @@ int launch_mesh_occluded(const float* positions, const int32_t* faces, long long
   if (bvh) DRM_TRY(check_device_bvh(bvh, 0, false, F, s, "mesh_occluded"));
   hipLaunchKernelGGL(mesh_occluded_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, MeshRef{positions, faces, V, F}, bvh, origins, dirs, exclude,
                      out, N);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+int launch_mesh_closest_hit(const float* positions, const int32_t* faces, long long V, long long F, const void* bvh, const float* origins,
+                            const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, long long N, hipStream_t s) {
+  DRM_REQUIRE(N >= 0 && N <= (1LL << 31), "mesh_closest_hit: 0 <= N <= 2^31 rays");
+  DRM_REQUIRE(faces_ok(F) && V >= 1 && V <= 0x7fffffffLL, "mesh_closest_hit: 1 <= F < 2^24 faces, V >= 1 vertices");
+  if (N == 0) return DRM_OK;
+  DRM_REQUIRE(positions && faces && origins && dirs && out_face && out_tuv, "mesh_closest_hit: null pointer");
+  if (bvh) DRM_TRY(check_device_bvh(bvh, 0, false, F, s, "mesh_closest_hit"));
+  hipLaunchKernelGGL(mesh_closest_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, MeshRef{positions, faces, V, F}, bvh, origins, dirs, exclude,
+                     out_face, out_tuv, N);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

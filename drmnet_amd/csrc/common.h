@@ -257,6 +257,11 @@ int launch_render_mesh(const float* positions, const float* normals, const int32
 int launch_render_mesh_shadowed(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
                                 const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
                                 int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, hipStream_t s);
+// the shadowed render with one bounce of interreflection (see drm_render_mesh_bounced): bounce_quad in [1, 16]
+int launch_render_mesh_bounced(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
+                               const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                               int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
+                               hipStream_t s);
 // the same with light samples (see drm_render_mesh_lit): bvh == null with bvh_bytes == 0 is unshadowed; light_samples == 0 or env == null is
 // launch_render_mesh / launch_render_mesh_shadowed; the light workspace is render_light_workspace_bytes(B, EH, EW, light_samples)
 int launch_render_mesh_lit(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,

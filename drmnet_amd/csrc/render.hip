@@ -24,10 +24,11 @@
 // (direct light, no interreflection).  drm_render_mesh_shadowed runs mesh_shade_kernel<VIEW, true, false>, which traces every quadrature
 // direction from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones.  drm_render_mesh_lit runs
 // mesh_shade_kernel<VIEW, SHADOW, true>: the light samples of the sphere's lit render on the mesh, each traced like a lobe direction where
-// there is a BVH.
+// there is a BVH.  drm_render_mesh_bounced runs mesh_shade_kernel<VIEW, true, false, true>: an occluded direction reads the radiance its
+// closest hit reflects back under direct light (one bounce; see Bounced).
 //
 // One statement of the quadrature: normal_lane_sum builds both lobes once and accumulates each in one place; what differs between the
-// renders is its technique parameter (Plain, LightSampled, Occluded, LitOccluded: see "techniques"), which decides per lobe sample whether
+// renders is its technique parameter (Plain, LightSampled, Occluded, LitOccluded, Bounced: see "techniques"), which decides per lobe sample whether
 // it counts, what radiance it reads and what scales its weight.  Every texel fetch is env_taps + bilerp.  Plain holds nothing: the
 // instantiations without light samples and without shadows carry no code and no registers of the others.
 #include <type_traits>
@@ -130,6 +131,25 @@ __host__ __device__ __forceinline__ void principled_eval(const Principled& p, co
   const double kd = (1.0 - m) * cl * diffuse_shape((double)p.r, cl, cv, cd) / kPi;
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) out[ch] = (float)((fd + m * (p.c[ch] + (1.0 - p.c[ch]) * sw)) * k + kd * p.c[ch]);
+}
+
+// principled_eval's expression in fp32 on the same terms, sin^2 passed as |n x .|^2 as the quadrature passes it: what a surface point reflects
+// inside the bounce of Bounced, where a value accurate to fp32 is all the sum around it can use
+__host__ __device__ __forceinline__ void principled_eval32(const Principled& p, V3 n, V3 v, V3 l, float out[3]) {
+  out[0] = out[1] = out[2] = 0.0f;
+  const float cv = dot3(n, v), cl = dot3(n, l);
+  if (!(cv > 0.0f && cl > 0.0f)) return;
+  V3 h = v3(v.x + l.x, v.y + l.y, v.z + l.z);
+  const float inv = 1.0f / sqrtf(dot3(h, h));
+  h = v3(h.x * inv, h.y * inv, h.z * inv);
+  const float nh = dot3(n, h), cd = dot3(h, v), lh = dot3(h, l);
+  const float D = ggx_d(p.a2, nh, cross_sq(n, h));
+  const float G = ggx_g1(p.a2, cv, cross_sq(n, v), cd) * ggx_g1(p.a2, cl, cross_sq(n, l), lh);
+  const float k = D * G / (4.0f * cv);
+  const float fd = (1.0f - p.m) * fresnel_dielectric(cd, p.eta), sw = schlick_weight(cd);
+  const float kd = (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, cd) / kPi;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) out[ch] = (fd + p.m * (p.c[ch] + (1.0f - p.c[ch]) * sw)) * k + kd * p.c[ch];
 }
 
 // radiance toward w: bilinear in the texel grid of an EH x EW map whose texel (i, j) looks along theta = (i + 1/2) pi / EH,
@@ -277,6 +297,80 @@ struct Occluded : Plain {
   }
 };
 
+// One bounce of interreflection on the shadowed mesh: a direction wl that Occluded would drop reads, instead of the map, the radiance L_b
+// its closest hit y = o + t wl on face g' reflects toward -wl under direct light.  With n_y the normalised barycentric mix of the vertex
+// normals of g' in object space (zero or NaN: L_b = 0), w_o = -wl / |wl| (n_y.w_o <= 0: L_b = 0) and the frame of Duff et al. 2017 with its
+// sign term, valid for every unit n: s = 1 where n.z >= 0, else -1, a = -1 / (s + n.z), b = n.x n.y a, t = (1 + s n.x^2 a, s b, -s n.x),
+// bt = (b, s + n.y^2 a, -n.y):
+//   L_b = (pi / K) sum_k V_k L(w_k) E(n_y, w_o, w_k) / cos_k,  K = bounce_quad^2,
+// w_k = cos_k n_y + sqrt(u1) (cos(2 pi u2) t + sin(2 pi u2) bt) the diffuse lobe's cosine-weighted mapping of the midpoint grid
+// (u1, u2) = ((k / bq + 1/2) / bq, (k % bq + 1/2) / bq), cos_k = sqrt(1 - u1); E = principled_eval32 (the BSDF value times cosine);
+// V_k = 0 iff the ray (y, w_k) excluding g' is occluded (any-hit); L the map's bilinear radiance along w_k, an object-space direction being
+// the world direction as for lobe rays, 1 under a white environment.  A direction with E = 0 is neither traced nor looked up.  Each lane
+// runs the K directions of its own bounce serially, in k order.  An open direction is Plain::take: unchanged to the bit.  The weight w is
+// not touched.  One traversal serves both questions: a ray is occluded iff it has a closest hit (the same candidates).
+struct Bounced : Plain {
+  MeshRef mesh;
+  BvhView tree;
+  const float* vnormal;  // [V][3] vertex normals, object space
+  Principled p;          // the row's BSDF, which the hit reflects with as well
+  int bq;                // bounce_quad
+  float o[3];            // the hit point in object space
+  int32_t exclude;       // the hit face
+  __host__ __device__ __forceinline__ void reflected(const float* __restrict__ env, int EH, int EW, const Ray& r, const Hit& h, float L[3]) const {
+    L[0] = L[1] = L[2] = 0.0f;
+    const int32_t* idx = mesh.faces + 3 * (size_t)h.face;  // (a candidate's indices are in [0, V))
+    const float* n0 = vnormal + 3 * (size_t)idx[0];
+    const float* n1 = vnormal + 3 * (size_t)idx[1];
+    const float* n2 = vnormal + 3 * (size_t)idx[2];
+    const float w0 = 1.0f - h.u - h.v;
+    V3 n = v3(w0 * n0[0] + h.u * n1[0] + h.v * n2[0], w0 * n0[1] + h.u * n1[1] + h.v * n2[1], w0 * n0[2] + h.u * n1[2] + h.v * n2[2]);
+    const float len2 = dot3(n, n);
+    if (!(len2 > 0.0f)) return;  // (a NaN mix fails the comparison)
+    const float ninv = 1.0f / sqrtf(len2);
+    n = v3(n.x * ninv, n.y * ninv, n.z * ninv);
+    const V3 d = v3(r.d[0], r.d[1], r.d[2]);
+    const float dinv = 1.0f / sqrtf(dot3(d, d));
+    const V3 wo = v3(-d.x * dinv, -d.y * dinv, -d.z * dinv);
+    if (!(dot3(n, wo) > 0.0f)) return;
+    const float y[3] = {r.o[0] + h.t * r.d[0], r.o[1] + h.t * r.d[1], r.o[2] + h.t * r.d[2]};
+    const float sg = n.z >= 0.0f ? 1.0f : -1.0f;
+    const float ka = -1.0f / (sg + n.z), kb = n.x * n.y * ka;
+    const V3 t = v3(1.0f + sg * n.x * n.x * ka, sg * kb, -sg * n.x), bt = v3(kb, sg + n.y * n.y * ka, -n.y);
+    const float invq = 1.0f / (float)bq;
+    for (int k = 0; k < bq * bq; ++k) {
+      const float u1 = ((float)(k / bq) + 0.5f) * invq, u2 = ((float)(k % bq) + 0.5f) * invq;
+      const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
+      const float rs = sqrtf(u1), ck = sqrtf(1.0f - u1);
+      const V3 l = axpy(ck, n, axpy(rs * sp, bt, v3(rs * cp * t.x, rs * cp * t.y, rs * cp * t.z)));
+      float E[3];
+      principled_eval32(p, n, wo, l, E);
+      if (E[0] == 0.0f && E[1] == 0.0f && E[2] == 0.0f) continue;
+      const Ray s{{y[0], y[1], y[2]}, {l.x, l.y, l.z}};
+      if (bvh_occluded(mesh, tree, s, h.face)) continue;
+      float Lk[3] = {1.0f, 1.0f, 1.0f};
+      if (env) env_lookup(env, EH, EW, l, Lk);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) L[c] += Lk[c] * E[c] / ck;
+    }
+    const float scale = kPi / (float)(bq * bq);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) L[c] *= scale;
+  }
+  __host__ __device__ __forceinline__ bool take(const float* __restrict__ env, int EH, int EW, V3 wl, float np, float& w, float L[3]) const {
+    const Ray r{{o[0], o[1], o[2]}, {wl.x, wl.y, wl.z}};
+    const Hit h = bvh_closest(mesh, tree, r, exclude);
+    if (h.face < 0) {
+      // (normal_lane_sum keeps one L for both lobes of a grid point and Plain::take leaves it alone under a white environment: the specular
+      // lobe's bounce must not reach an open diffuse direction)
+      if (!env) L[0] = L[1] = L[2] = 1.0f;
+      return Plain::take(env, EH, EW, wl, np, w, L);
+    }
+    reflected(env, EH, EW, r, h, L);
+    return true;
+  }
+};
+
 // The light technique: where the map has light (lt.norm > 0) every lobe sample is weighted by the power heuristic against the
 // n_L = lt.M light samples, and finish() lets the lanes stride the light table as they strode the grid, summing into accL (to be
 // normalised by 1 / S^2 only: the weights hold 1 / n).  Needs a map: env is never null here.  The table loop is table_sum, written once for
@@ -367,8 +461,9 @@ struct LitOccluded : LightSampled {
 template <bool VIEW, typename TECH>
 __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n,
                                                          int Q, int lane, int lanes, float acc[3], TECH& tech) {
-  static_assert(std::is_same_v<TECH, Plain> || std::is_same_v<TECH, Occluded> || std::is_same_v<TECH, LightSampled> || std::is_same_v<TECH, LitOccluded>,
-                "the techniques: {no light samples, light samples} x {not traced, traced}");
+  static_assert(std::is_same_v<TECH, Plain> || std::is_same_v<TECH, Occluded> || std::is_same_v<TECH, LightSampled> || std::is_same_v<TECH, LitOccluded> ||
+                    std::is_same_v<TECH, Bounced>,
+                "the techniques: {no light samples, light samples} x {not traced, traced}, and traced with one bounce (no light samples)");
   const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
@@ -500,6 +595,7 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
 // LIGHT: li holds the light workspace of the B maps (M samples each; see refmap_render_kernel on why the table is not staged in LDS).  The
 // technique is then the pixel's, not the sample's: its accL runs through the pixel's hit samples in sample order and meets in a second
 // butterfly, as in the sphere's lit kernel.  Without it li is an empty struct.
+// BOUNCE (with SHADOW, without LIGHT): the technique is Bounced instead of Occluded; bo holds bounce_quad.  Without it bo is an empty struct.
 struct NoShadowArgs {};
 struct ShadowArgs {
   const float* positions;
@@ -512,13 +608,19 @@ struct LightArgs {
   const char* lws;
   int M;
 };
-template <bool VIEW, bool SHADOW, bool LIGHT>
+struct NoBounceArgs {};
+struct BounceArgs {
+  int quad;
+};
+template <bool VIEW, bool SHADOW, bool LIGHT, bool BOUNCE = false>
 __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
                                                          const float* __restrict__ vnormal, const float* __restrict__ rec, const float* __restrict__ hits,
                                                          float* __restrict__ image, float* __restrict__ normal, float* __restrict__ depth,
                                                          float* __restrict__ alpha, int B, long long F, int H, int W, int EH, int EW, int Q, int S,
                                                          std::conditional_t<SHADOW, ShadowArgs, NoShadowArgs> sh,
-                                                         std::conditional_t<LIGHT, LightArgs, NoLightArgs> li) {
+                                                         std::conditional_t<LIGHT, LightArgs, NoLightArgs> li,
+                                                         std::conditional_t<BOUNCE, BounceArgs, NoBounceArgs> bo) {
+  static_assert(!BOUNCE || (SHADOW && !LIGHT), "the bounce needs the BVH and is not combined with light samples");
   const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (pix >= (long long)B * H * W) return;  // (wave-uniform)
@@ -573,8 +675,9 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
           }
           normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, lit);
         } else {
-          std::conditional_t<SHADOW, Occluded, Plain> tech;
-          if constexpr (SHADOW) tech = Occluded{{}, MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
+          std::conditional_t<BOUNCE, Bounced, std::conditional_t<SHADOW, Occluded, Plain>> tech;
+          if constexpr (BOUNCE) tech = Bounced{{}, MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), vnormal, p, bo.quad, {o.x, o.y, o.z}, f};
+          else if constexpr (SHADOW) tech = Occluded{{}, MeshRef{sh.positions, sh.faces, sh.V, F}, bvh_view(sh.bvh), {o.x, o.y, o.z}, f};
           normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
         }
       }
@@ -809,11 +912,12 @@ int launch_render_refmap_views(const float* z, int L, const float* env, const fl
 }
 
 // the mesh renders: the same checks and visibility launches; `shadowed` verifies the blob (nothing is launched before that) and shades with it;
-// light_samples > 0 under a map checks the light workspace, builds the tables as the sphere's lit render does and shades with them
+// light_samples > 0 under a map checks the light workspace, builds the tables as the sphere's lit render does and shades with them;
+// bounce_quad > 0 (the bounced entry's, with `shadowed` and without light samples) shades with one bounce
 static int render_mesh_impl(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
                             const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
                             int subpixel, void* workspace, size_t workspace_bytes, bool shadowed, const void* bvh, size_t bvh_bytes, int light_samples,
-                            void* light_workspace, size_t light_workspace_bytes, hipStream_t s) {
+                            void* light_workspace, size_t light_workspace_bytes, int bounce_quad, hipStream_t s) {
   DRM_REQUIRE(positions && normals && faces && z && image, "render_mesh: null pointer");
   DRM_REQUIRE(light_samples >= 0, "render_mesh_lit: light_samples >= 0");
   const bool lit = light_samples > 0 && env;
@@ -844,16 +948,17 @@ static int render_mesh_impl(const float* positions, const float* normals, const 
     hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)B), dim3(64), 0, s, lws, EH, EW, light_samples);
     hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(light_samples / 4), (unsigned)B), dim3(256), 0, s, env, lws, EH, EW, light_samples);
   }
-  const auto shade = [&](auto kernel, auto sh, auto li) {
+  const auto shade = [&](auto kernel, auto sh, auto li, auto bo) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, view, normals, records, hits, image, normal, depth, alpha, B, F,
-                       H, W, env ? EH : 1, env ? EW : 1, quad, subpixel, sh, li);
+                       H, W, env ? EH : 1, env ? EW : 1, quad, subpixel, sh, li, bo);
   };
   const ShadowArgs sh{positions, faces, V, bvh};
   const LightArgs li{lws, light_samples};
-  if (lit && shadowed) shade(view ? mesh_shade_kernel<true, true, true> : mesh_shade_kernel<false, true, true>, sh, li);
-  else if (lit) shade(view ? mesh_shade_kernel<true, false, true> : mesh_shade_kernel<false, false, true>, NoShadowArgs{}, li);
-  else if (shadowed) shade(view ? mesh_shade_kernel<true, true, false> : mesh_shade_kernel<false, true, false>, sh, NoLightArgs{});
-  else shade(view ? mesh_shade_kernel<true, false, false> : mesh_shade_kernel<false, false, false>, NoShadowArgs{}, NoLightArgs{});
+  if (bounce_quad) shade(view ? mesh_shade_kernel<true, true, false, true> : mesh_shade_kernel<false, true, false, true>, sh, NoLightArgs{}, BounceArgs{bounce_quad});
+  else if (lit && shadowed) shade(view ? mesh_shade_kernel<true, true, true> : mesh_shade_kernel<false, true, true>, sh, li, NoBounceArgs{});
+  else if (lit) shade(view ? mesh_shade_kernel<true, false, true> : mesh_shade_kernel<false, false, true>, NoShadowArgs{}, li, NoBounceArgs{});
+  else if (shadowed) shade(view ? mesh_shade_kernel<true, true, false> : mesh_shade_kernel<false, true, false>, sh, NoLightArgs{}, NoBounceArgs{});
+  else shade(view ? mesh_shade_kernel<true, false, false> : mesh_shade_kernel<false, false, false>, NoShadowArgs{}, NoLightArgs{}, NoBounceArgs{});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
@@ -862,14 +967,24 @@ int launch_render_mesh(const float* positions, const float* normals, const int32
                        const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
                        int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s) {
   return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
-                          workspace_bytes, false, nullptr, 0, 0, nullptr, 0, s);
+                          workspace_bytes, false, nullptr, 0, 0, nullptr, 0, 0, s);
 }
 
 int launch_render_mesh_shadowed(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
                                 const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
                                 int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, hipStream_t s) {
   return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
-                          workspace_bytes, true, bvh, bvh_bytes, 0, nullptr, 0, s);
+                          workspace_bytes, true, bvh, bvh_bytes, 0, nullptr, 0, 0, s);
+}
+
+// the shadowed render with one bounce: bounce_quad^2 directions about every closest hit of an occluded lobe direction
+int launch_render_mesh_bounced(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
+                               const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                               int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
+                               hipStream_t s) {
+  DRM_REQUIRE(bounce_quad >= 1 && bounce_quad <= 16, "render_mesh_bounced: bounce_quad in [1, 16]");
+  return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
+                          workspace_bytes, true, bvh, bvh_bytes, 0, nullptr, 0, bounce_quad, s);
 }
 
 // bvh == nullptr with bvh_bytes == 0: unshadowed
@@ -878,7 +993,7 @@ int launch_render_mesh_lit(const float* positions, const float* normals, const i
                            int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
                            void* light_workspace, size_t light_workspace_bytes, hipStream_t s) {
   return render_mesh_impl(positions, normals, faces, V, F, z, env, view, image, normal, depth, alpha, B, H, W, EH, EW, quad, subpixel, workspace,
-                          workspace_bytes, bvh != nullptr || bvh_bytes != 0, bvh, bvh_bytes, light_samples, light_workspace, light_workspace_bytes, s);
+                          workspace_bytes, bvh != nullptr || bvh_bytes != 0, bvh, bvh_bytes, light_samples, light_workspace, light_workspace_bytes, 0, s);
 }
 
 int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {

@@ -6,7 +6,8 @@ Operator surface of the reference's mesh helpers (utils/mitsuba3_utils.py): ``Me
 scripts/preprocess_shape.py:40.  Every visible point is shaded as the reflectance-map renderer shades the sphere point with the same
 normal: direct light from the environment map, no interreflection, black background.  Self-shadowing is opt-in
 (``shadows=True``): shadow rays through a bounding-volume hierarchy built on the host (``build_bvh``; csrc/bvh.hip), also offered on their
-own as ``occluded``.  Light sampling is opt-in too (``light_samples=M``: the light samples of ``render.render``, each traced like a lobe
+own as ``occluded``.  One bounce of interreflection is opt-in on top of it (``bounces=1``): a lobe direction the mesh cuts off reads the
+light its closest hit reflects back; the closest-hit query is offered on its own as ``closest_hit``.  Light sampling is opt-in too (``light_samples=M``: the light samples of ``render.render``, each traced like a lobe
 direction under ``shadows``), for maps with a sun or a lamp a few texels wide.  Loading a mesh, building its BVH and constructing a renderer do not touch the GPU; rendering and ray queries run
 there (no CPU path).
 """
@@ -168,15 +169,11 @@ def _bvh_on(blob, dev: torch.device) -> torch.Tensor:
     return t.to(dev).contiguous()
 
 
-@torch.no_grad()
-def occluded(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto") -> torch.Tensor:
-    """drm_mesh_occluded: for each of N rays (origins, dirs [N, 3] in object space; dirs of any length) whether some face other than
-    ``exclude`` [N] (int32 face indices; None, or -1, for no exclusion) cuts it off -> bool [N] on the GPU.  The intersection rule is stated
-    in include/drmnet_hip.h.  ``bvh``: "auto" builds the mesh's BVH, a ``build_bvh`` blob is used as it is, None tests every face for every
-    ray (the same answers, slowly).  GPU only: an ``origins`` or ``dirs`` tensor on the CPU is a RuntimeError."""
+def _rays_on(who: str, obj: Mesh, origins, dirs, exclude, bvh):
+    """what the ray queries share: (device, positions, faces, blob or None, origins, dirs, exclude or None, N), everything on the device"""
     for name, t in (("origins", origins), ("dirs", dirs)):
         if isinstance(t, torch.Tensor) and not t.is_cuda:
-            raise RuntimeError(f"occluded runs on the GPU only (drmnet_amd has no CPU path): {name} is on {t.device}")
+            raise RuntimeError(f"{who} runs on the GPU only (drmnet_amd has no CPU path): {name} is on {t.device}")
     dev = _device(origins, dirs)
     o = torch.as_tensor(origins).to(dev, torch.float32).reshape(-1, 3).contiguous()
     d = torch.as_tensor(dirs).to(dev, torch.float32).reshape(-1, 3).contiguous()
@@ -190,6 +187,16 @@ def occluded(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto") -> torch.Ten
             raise ValueError(f"exclude must be [N={N}], got {tuple(ex.shape)}")
     pos, _, faces = _mesh_on(obj, dev)
     blob = None if bvh is None else _bvh_on(build_bvh(obj) if isinstance(bvh, str) and bvh == "auto" else bvh, dev)
+    return dev, pos, faces, blob, o, d, ex, N
+
+
+@torch.no_grad()
+def occluded(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto") -> torch.Tensor:
+    """drm_mesh_occluded: for each of N rays (origins, dirs [N, 3] in object space; dirs of any length) whether some face other than
+    ``exclude`` [N] (int32 face indices; None, or -1, for no exclusion) cuts it off -> bool [N] on the GPU.  The intersection rule is stated
+    in include/drmnet_hip.h.  ``bvh``: "auto" builds the mesh's BVH, a ``build_bvh`` blob is used as it is, None tests every face for every
+    ray (the same answers, slowly).  GPU only: an ``origins`` or ``dirs`` tensor on the CPU is a RuntimeError."""
+    dev, pos, faces, blob, o, d, ex, N = _rays_on("occluded", obj, origins, dirs, exclude, bvh)
     out = torch.zeros(N, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().drm_mesh_occluded(pos.data_ptr(), faces.data_ptr(), int(pos.shape[0]), int(faces.shape[0]), _lib.ptr(blob), o.data_ptr(),
@@ -198,8 +205,39 @@ def occluded(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto") -> torch.Ten
 
 
 @torch.no_grad()
+def closest_hit(obj: Mesh, origins, dirs, exclude=None, *, bvh="auto"):
+    """drm_mesh_closest_hit: for each of N rays what is in the way, and where -> (face int32 [N], t, u, v float32 [N]) on the GPU.  ``face``
+    is the face that ``occluded`` would call a hit and that is least under the order (t, face index), -1 where there is none (t = u = v = 0
+    there); the hit point is origins + t * dirs (t in units of the length of ``dirs``), its barycentric weights (1 - u - v, u, v) on the face's
+    three vertices.  The rule is stated in include/drmnet_hip.h.  Arguments and errors as for ``occluded``; with and without the BVH the
+    answers are the same bits."""
+    dev, pos, faces, blob, o, d, ex, N = _rays_on("closest_hit", obj, origins, dirs, exclude, bvh)
+    face = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    tuv = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_mesh_closest_hit(pos.data_ptr(), faces.data_ptr(), int(pos.shape[0]), int(faces.shape[0]), _lib.ptr(blob), o.data_ptr(),
+                                                   d.data_ptr(), _lib.ptr(ex), face.data_ptr(), tuv.data_ptr(), N, _lib.stream_ptr(dev)))
+    return face, tuv[:, 0].contiguous(), tuv[:, 1].contiguous(), tuv[:, 2].contiguous()
+
+
+def check_bounces(bounces, bounce_quad, shadows, light_samples) -> int:
+    """the ``bounces`` / ``bounce_quad`` arguments of render_mesh and MeshRenderer -> bounces as an int; a ValueError names what is wrong"""
+    if isinstance(bounces, bool) or not isinstance(bounces, (int, np.integer)) or int(bounces) not in (0, 1):
+        raise ValueError(f"bounces must be 0 or 1 (one bounce of interreflection; later bounces are not modelled), got {bounces!r}")
+    if int(bounces) == 1:
+        if not shadows:
+            raise ValueError("bounces=1 needs shadows=True: the bounce replaces what the shadow rays cut off")
+        if int(light_samples) > 0:
+            raise ValueError("bounces=1 is not combined with light_samples > 0: the bounce's inner sum has no light samples")
+        if isinstance(bounce_quad, bool) or not isinstance(bounce_quad, (int, np.integer)) or not 1 <= int(bounce_quad) <= 16:
+            raise ValueError(f"bounce_quad must be an integer in [1, 16], got {bounce_quad!r}")
+    return int(bounces)
+
+
+@torch.no_grad()
 def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, image_size, view_from=None,
-                quad: int = QUAD, subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None, light_samples: int = 0):
+                quad: int = QUAD, subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None, light_samples: int = 0, bounces: int = 0,
+                bounce_quad: int = 4):
     """One call of drm_render_mesh (``shadows=True``: of drm_render_mesh_shadowed, where parts of the mesh cut light off from other parts;
     ``bvh`` is then the mesh's ``build_bvh`` blob, built here when None): one mesh, lit and seen B ways.  z [B, P], envmaps [B, EH, EW, 3] (or None: white), view_from [B, 3] (or
     None: +z), image_size H or (H, W) -> (image [B, 3, H, W], normal [B, 3, H, W] in the view frame, depth [B, 1, H, W], alpha [B, H, W]).
@@ -207,8 +245,12 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     light density join the two lobe quadratures by multiple importance sampling, as in ``render.render``, and with ``shadows`` every light
     sample is traced like a lobe direction, so the cast shadow of a sun is decided by the sun's own samples.  0, or no envmaps, is the
     render without them bit for bit.
+    ``bounces`` = 1 (needs ``shadows``; not combined with ``light_samples``) renders through drm_render_mesh_bounced: a lobe direction the
+    mesh cuts off reads the radiance its closest hit reflects back under direct light, estimated with ``bounce_quad``^2 traced directions
+    (1 <= bounce_quad <= 16); 0 makes exactly the calls above.  A bad combination is a ValueError before anything touches the GPU.
     GPU only: a ``z`` or ``envmaps`` tensor on the CPU, or a machine without a GPU, is a RuntimeError (the mesh itself and ``view_from`` are
     host data and are brought over)."""
+    bounces = check_bounces(bounces, bounce_quad, shadows, light_samples)
     for name, t in (("z", z), ("envmaps", envmaps)):
         if isinstance(t, torch.Tensor) and not t.is_cuda:
             raise RuntimeError(f"render_mesh runs on the GPU only (drmnet_amd has no CPU path): {name} is on {t.device}")
@@ -248,6 +290,8 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
         if light_ws is not None:
             _lib.check(lib.drm_render_mesh_lit(*args, _lib.ptr(blob), 0 if blob is None else int(blob.numel()), light_samples, light_ws.data_ptr(),
                                                light_bytes, _lib.stream_ptr(dev)))
+        elif bounces:
+            _lib.check(lib.drm_render_mesh_bounced(*args, blob.data_ptr(), int(blob.numel()), int(bounce_quad), _lib.stream_ptr(dev)))
         elif shadows:
             _lib.check(lib.drm_render_mesh_shadowed(*args, blob.data_ptr(), int(blob.numel()), _lib.stream_ptr(dev)))
         else:
@@ -261,15 +305,18 @@ class MeshRenderer:
     interreflection, a black background, and self-shadowing only with ``shadows=True`` (the BVH is built once when a mesh becomes the
     scene's and kept with it; a ``new_scene`` mesh gets one for that call).  The integral is the deterministic quadrature of the reflectance-map
     renderer, so ``spp`` and ``denoise`` are accepted and ignored.  ``light_samples`` = M > 0 adds M light samples per map (see
-    ``render_mesh``; reachable from a YAML ``params:``); the default 0 renders without them.  ``init_view_from`` may be any position off the +-y axis.  The scene
+    ``render_mesh``; reachable from a YAML ``params:``); the default 0 renders without them.  ``bounces`` = 1 with ``shadows`` adds one
+    bounce of interreflection (``bounce_quad``^2 directions per bounce; see ``render_mesh``; also reachable from ``params:``), checked here.  ``init_view_from`` may be any position off the +-y axis.  The scene
     state -- environment map, view and mesh -- is kept across ``rendering`` calls as the reference's scene keeps it.  Construction does not
     touch the GPU."""
 
     def __init__(self, image_size, spp: int = 1024, envmap_size=(1000, 2000), denoise: Optional[str] = None, return_normal: bool = False,
                  return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
-                 subpixel: int = SUBPIXEL, shadows: bool = False, light_samples: int = 0):
+                 subpixel: int = SUBPIXEL, shadows: bool = False, light_samples: int = 0, bounces: int = 0, bounce_quad: int = 4):
         self.shadows = bool(shadows)
         self.light_samples = int(light_samples)
+        self.bounces = check_bounces(bounces, bounce_quad, self.shadows, self.light_samples)
+        self.bounce_quad = int(bounce_quad)
         if self.light_samples and (self.light_samples < 64 or self.light_samples > 65536 or self.light_samples & (self.light_samples - 1)):
             raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
         self.image_size = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(s) for s in image_size)
@@ -323,7 +370,8 @@ class MeshRenderer:
         z = torch.as_tensor(z).reshape(1, -1).to(dev)
         image, normal, depth, _ = render_mesh(mesh, z, brdf_param_names or self.brdf_param_names, env[None], image_size=self.image_size,
                                               view_from=torch.as_tensor(view).reshape(1, 3), quad=self.quad, subpixel=self.subpixel,
-                                              shadows=self.shadows, bvh=bvh, light_samples=self.light_samples)
+                                              shadows=self.shadows, bvh=bvh, light_samples=self.light_samples, bounces=self.bounces,
+                                              bounce_quad=self.bounce_quad)
         outs = [image[0]] + ([normal[0]] if self.return_normal else []) + ([depth[0]] if self.return_depth else [])
         if not channel_first:
             outs = [o.permute(1, 2, 0) for o in outs]

@@ -5,7 +5,8 @@
 writes into D the three files ``estimate`` reads,
 
     image.exr    H x W x 3 radiance of the object (drmnet_amd.mesh.render_mesh: direct light, black background; with ``--shadows`` the
-                 object shadows itself; with ``--light_samples M`` a sun or a lamp a few texels wide is resolved, its cast shadow included)
+                 object shadows itself, and with ``--bounces 1`` on top of it the light one part reflects onto another is there (one
+                 bounce); with ``--light_samples M`` a sun or a lamp a few texels wide is resolved, its cast shadow included)
     normal.npy   H x W x 3 float32 shading normals in the view frame (right, up, back)
     mask.png     |normal| > 0.5: the pixels more than half covered
 
@@ -30,7 +31,7 @@ NAMES = ("metallic", "base_color.value.R", "base_color.value.G", "base_color.val
 
 def main(argv=None):
     from . import file_io
-    from .mesh import load_mesh, normalize_mesh, render_mesh
+    from .mesh import check_bounces, load_mesh, normalize_mesh, render_mesh
     from .render import render
 
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -43,11 +44,14 @@ def main(argv=None):
     parser.add_argument("--refmap_res", type=int, default=128, help="resolution of refmap.exr")
     parser.add_argument("--quad", type=int, default=QUAD)
     parser.add_argument("--shadows", action="store_true", help="trace shadow rays: parts of the mesh cut light off from other parts (default: off)")
+    parser.add_argument("--bounces", type=int, default=0, help="1: one bounce of interreflection (needs --shadows; not with --light_samples); default 0")
+    parser.add_argument("--bounce_quad", type=int, default=4, help="the bounce is estimated with bounce_quad^2 directions, 1 .. 16 (default 4)")
     parser.add_argument("--light_samples", type=int, default=0,
                         help="light samples drawn from the environment map, for image.exr and refmap.exr alike: a power of two in [64, 65536] "
                         "(default 0: the lobe quadrature alone)")
     parser.add_argument("--output_dir", type=Path, default=Path("./outputs/"))
     args = parser.parse_args(argv)
+    check_bounces(args.bounces, args.bounce_quad, args.shadows, args.light_samples)
 
     if not torch.cuda.is_available():
         raise RuntimeError("synthesize renders on the GPU (drmnet_amd has no CPU path) and no GPU is visible")
@@ -57,7 +61,7 @@ def main(argv=None):
     env = None if args.envmap is None else file_io.load_exr(args.envmap, as_torch=True).to(dev)[None]
     view = torch.tensor([args.view_from], dtype=torch.float32)
     image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows,
-                                     light_samples=args.light_samples)
+                                     light_samples=args.light_samples, bounces=args.bounces, bounce_quad=args.bounce_quad)
     refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view, light_samples=args.light_samples)
     normal = normal[0].permute(1, 2, 0).cpu().numpy()
     mask = np.linalg.norm(normal, axis=-1) > 0.5

@@ -404,7 +404,8 @@ int drm_render_refmap_lit(const float* z, int L, const float* envmap, const floa
  * and depth AOVs).  Every visible point is shaded exactly as drm_render_refmap_views shades the sphere point with the same normal: direct
  * light from the environment map, NO interreflection (Mitsuba's path integrator has it), and the background is black, not the environment.
  * drm_render_mesh has NO self-shadowing either: it is the model the reflectance map itself assumes.  drm_render_mesh_shadowed (below) adds
- * shadow rays, drm_render_mesh_lit the light samples of drm_render_refmap_lit, with or without them.  Additive: the ABI version is unchanged.
+ * shadow rays, drm_render_mesh_lit the light samples of drm_render_refmap_lit, with or without them, drm_render_mesh_bounced one bounce of
+ * interreflection on top of the shadow rays.  Additive: the ABI version is unchanged.
  *   One mesh per call, lit and seen B ways: vertex_positions, vertex_normals [V][3], faces [F][3] int32 (smooth shading, no back-face
  *   culling), z [B][6], envmap [B][EH][EW][3] or NULL (white), view [B][9] or NULL (+z).
  *   View frame.  right, up, back are the columns of the row-major Rot = view[b] (the rotation drm_render_refmap_views takes).  Mesh points
@@ -463,7 +464,8 @@ int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, 
  *   nothing is multiplied), exclude is the hit face, and every quadrature direction l with a non-zero weight is traced along Rot l, the vector
  *   the environment lookup forms: the specular direction inside its (v.h > 0, n.l > 0, D > 0) branch, the diffuse direction always.  An
  *   occluded direction contributes nothing, an open one exactly what it contributes in drm_render_mesh, so a shadowed image is <= the plain
- *   one in every pixel and channel under a non-negative map.  Interreflection stays out.  Bitwise reproducible; rows are independent. */
+ *   one in every pixel and channel under a non-negative map.  Interreflection stays out of this entry (one bounce: drm_render_mesh_bounced,
+ *   below).  Bitwise reproducible; rows are independent. */
 size_t drm_mesh_bvh_bytes(int64_t F);
 int drm_mesh_bvh_build(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, void* bvh, size_t bytes);
 int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins, const float* dirs,
@@ -500,6 +502,49 @@ int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_norma
                         const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
                         int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
                         void* light_workspace, size_t light_workspace_bytes, void* stream);
+/* One bounce of interreflection for the object images, on a closest-hit ray query of its own.  Additive: the ABI version is unchanged.
+ *   The closest hit.  For a ray (o, d) and an exclude, a face g is a CANDIDATE iff the intersection rule above (drm_mesh_occluded) accepts it:
+ *   its conditions are unchanged, the clause about a zero fp32 cross product included.  A candidate has, in fp32, t = T / det, u = U / det,
+ *   v = V / det, each the correctly rounded quotient (the library is built without any flag that relaxes fp32 division; denormals are kept).
+ *   s T > 0 and a finite non-zero det make t one of +0 .. +inf, never NaN.  The hit is the candidate that is least under the lexicographic
+ *   order (t, g), t compared as an fp32 value: a total order, so the order faces are visited in cannot matter.  Cross-multiplied products are
+ *   not compared (rounded products are not transitive).  No candidate: face -1.  The hit point is o + t d, with barycentric weights
+ *   (1 - u - v, u, v) on the face's vertices (p0, p1, p2).  The BVH never changes an answer: the same face and the same t, u, v bits as
+ *   testing every face.  Its walk is the stackless one of drm_mesh_occluded without the early return; the best t so far also bounds the far
+ *   end of the slab test, under the same 2^-20 of slack.  A ray is occluded iff it has a closest hit.
+ *   drm_mesh_closest_hit: one launch, one thread per ray; the arguments of drm_mesh_occluded with two outputs: out_face [N] int32 (-1: no
+ *   hit) and out_tuv [N][3] float (t, u, v; zeros where there is no hit).  bvh == NULL tests all F faces per ray (the diagnostic path).  The
+ *   header check and the error codes are those of drm_mesh_occluded; nothing is launched on an error.
+ *   drm_render_mesh_bounced: the arguments of drm_render_mesh_shadowed up to bvh_bytes, then bounce_quad in [1, 16], then stream; the
+ *   launches of drm_render_mesh_shadowed with the shading kernel's bounced instantiation in place of the shadowed one.
+ *   Estimator (the contract).  The shadowed render, except for a lobe direction w (object space, non-zero weight) whose ray from the hit
+ *   sample (origin o, exclude = the hit face g) is occluded.  It no longer drops out: in place of the map's radiance it reads
+ *   L_b = the radiance its closest hit reflects toward -w under direct light, traced.  The lobe's weight and everything else about the
+ *   sample are unchanged, and an open direction contributes exactly what it contributes in drm_render_mesh_shadowed, bit for bit.  With
+ *   (g', t, u, v) the closest hit of (o, w) excluding g:
+ *     y = o + t w;  n_y = the normalised barycentric mix (1 - u - v, u, v) of the vertex normals of g', in object space (a zero or NaN mix:
+ *     L_b = 0);  w_o = -w / |w|;  n_y.w_o <= 0: L_b = 0.
+ *     Frame about n = n_y (Duff et al. 2017, with the sign term, valid for every unit n): s = 1 where n.z >= 0, else -1, a = -1 / (s + n.z),
+ *     b = n.x n.y a, t = (1 + s n.x^2 a, s b, -s n.x), bt = (b, s + n.y^2 a, -n.y).
+ *     K = bounce_quad^2 directions w_k, k = k1 bounce_quad + k2, from the diffuse lobe's mapping of the midpoint grid
+ *     (u1, u2) = ((k1 + 1/2) / bounce_quad, (k2 + 1/2) / bounce_quad): cos_k = sqrt(1 - u1),
+ *     w_k = cos_k n + sqrt(u1) (cos(2 pi u2) t + sin(2 pi u2) bt).
+ *     L_b = (pi / K) sum_k V_k L(w_k) E(n_y, w_o, w_k) / cos_k.
+ *     E = the principled BSDF's value times cosine, drm_brdf_eval's expression for the row z[b] evaluated in fp32, with 1 - cos^2 taken as
+ *     |n x .|^2 (0 unless n.w_o > 0 and n.w_k > 0).  V_k = 0 iff the ray (y, w_k) with exclude = g' is occluded (the any-hit rule; a
+ *     direction with E = 0 is not traced).  L(w_k) = the map's bilinear radiance along w_k -- an object-space direction is the world
+ *     direction, as for lobe rays -- or 1 under a NULL map.
+ *   One bounce only; shadows are required (bvh is checked as drm_render_mesh_shadowed checks it); light samples are not combined with it.
+ *   Weights and radiances are non-negative under a non-negative map: a bounced image is >= the shadowed one in every pixel and channel.
+ *   Each lane runs the K directions of its own bounce serially, in k order: bitwise reproducible, and a call of B rows equals its rows alone.
+ *   DRM_ERR_INVALID for a bounce_quad outside [1, 16], a NULL, short or damaged blob or bad sizes, DRM_ERR_WORKSPACE for the mesh workspace,
+ *   as in drm_render_mesh_shadowed: nothing is launched. */
+int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins,
+                         const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, int64_t N, void* stream);
+int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
+                            const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
+                            int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
+                            void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
