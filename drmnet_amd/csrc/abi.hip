@@ -563,8 +563,12 @@ int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, 
                     const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
                     int quad, int subpixel, void* workspace, size_t workspace_bytes, void* stream) {
   return guarded([&]() -> int {
-    return launch_render_mesh(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B, H, W,
-                              EH, EW, quad, subpixel, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    MeshRenderArgs a;
+    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
+    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
+    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -586,8 +590,13 @@ int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_
                              const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
                              int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, void* stream) {
   return guarded([&]() -> int {
-    return launch_render_mesh_shadowed(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B,
-                                       H, W, EH, EW, quad, subpixel, workspace, workspace_bytes, bvh, bvh_bytes, static_cast<hipStream_t>(stream));
+    MeshRenderArgs a;
+    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
+    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
+    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.shadowed = true; a.bvh = bvh; a.bvh_bytes = bvh_bytes;
+    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -604,9 +613,14 @@ int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_n
                             int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
                             void* stream) {
   return guarded([&]() -> int {
-    return launch_render_mesh_bounced(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B,
-                                      H, W, EH, EW, quad, subpixel, workspace, workspace_bytes, bvh, bvh_bytes, bounce_quad,
-                                      static_cast<hipStream_t>(stream));
+    DRM_REQUIRE(bounce_quad >= 1 && bounce_quad <= 16, "render_mesh_bounced: bounce_quad in [1, 16]");
+    MeshRenderArgs a;
+    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
+    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
+    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.shadowed = true; a.bvh = bvh; a.bvh_bytes = bvh_bytes; a.bounce_quad = bounce_quad;
+    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -615,9 +629,15 @@ int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_norma
                         int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
                         void* light_workspace, size_t light_workspace_bytes, void* stream) {
   return guarded([&]() -> int {
-    return launch_render_mesh_lit(vertex_positions, vertex_normals, faces, (long long)V, (long long)F, z, envmap, view, image, normal, depth, alpha, B, H, W,
-                                  EH, EW, quad, subpixel, workspace, workspace_bytes, bvh, bvh_bytes, light_samples, light_workspace,
-                                  light_workspace_bytes, static_cast<hipStream_t>(stream));
+    MeshRenderArgs a;
+    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
+    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
+    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.shadowed = bvh != nullptr || bvh_bytes != 0;  // (bvh null with bvh_bytes 0: unshadowed)
+    a.bvh = bvh; a.bvh_bytes = bvh_bytes;
+    a.light_samples = light_samples; a.light_workspace = light_workspace; a.light_workspace_bytes = light_workspace_bytes;
+    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
   });
 }
 

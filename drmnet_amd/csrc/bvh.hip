@@ -88,14 +88,22 @@ struct Builder {
   }
 };
 
+// ray k of a query and the face it leaves out (exclude null: none)
+__device__ __forceinline__ Ray load_ray(const float* __restrict__ origins, const float* __restrict__ dirs, const int32_t* __restrict__ exclude, long long k,
+                                        int32_t& ex) {
+  const Ray r{{origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]}, {dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]}};
+  ex = exclude ? exclude[k] : -1;
+  return r;
+}
+
 // grid ceil(N / 256): thread = ray
 __global__ __launch_bounds__(256) void mesh_occluded_kernel(MeshRef m, const void* __restrict__ bvh, const float* __restrict__ origins,
                                                             const float* __restrict__ dirs, const int32_t* __restrict__ exclude,
                                                             int32_t* __restrict__ out, long long N) {
   const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
   if (k >= N) return;
-  const Ray r{{origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]}, {dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]}};
-  const int32_t ex = exclude ? exclude[k] : -1;
+  int32_t ex;
+  const Ray r = load_ray(origins, dirs, exclude, k, ex);
   out[k] = (bvh ? bvh_occluded(m, bvh_view(bvh), r, ex) : brute_occluded(m, r, ex)) ? 1 : 0;
 }
 
@@ -105,8 +113,8 @@ __global__ __launch_bounds__(256) void mesh_closest_kernel(MeshRef m, const void
                                                            int32_t* __restrict__ out_face, float* __restrict__ out_tuv, long long N) {
   const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
   if (k >= N) return;
-  const Ray r{{origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]}, {dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]}};
-  const int32_t ex = exclude ? exclude[k] : -1;
+  int32_t ex;
+  const Ray r = load_ray(origins, dirs, exclude, k, ex);
   const Hit h = bvh ? bvh_closest(m, bvh_view(bvh), r, ex) : brute_closest(m, r, ex);
   out_face[k] = h.face;
   out_tuv[3 * k] = h.t;
@@ -180,13 +188,21 @@ int check_device_bvh(const void* bvh, size_t bvh_bytes, bool have_bytes, long lo
   return DRM_OK;
 }
 
+// what both ray queries check before they launch, `who` naming the entry in the messages; `pointers`: the entry's own are all there.  No
+// rays: nothing is dereferenced, so neither the pointers nor the blob are looked at.
+static int check_ray_query(const std::string& who, long long V, long long F, long long N, bool pointers, const void* bvh, hipStream_t s) {
+  DRM_REQUIRE(N >= 0 && N <= (1LL << 31), who + ": 0 <= N <= 2^31 rays");
+  DRM_REQUIRE(faces_ok(F) && V >= 1 && V <= 0x7fffffffLL, who + ": 1 <= F < 2^24 faces, V >= 1 vertices");
+  if (N == 0) return DRM_OK;
+  DRM_REQUIRE(pointers, who + ": null pointer");
+  if (bvh) DRM_TRY(check_device_bvh(bvh, 0, false, F, s, who.c_str()));
+  return DRM_OK;
+}
+
 int launch_mesh_occluded(const float* positions, const int32_t* faces, long long V, long long F, const void* bvh, const float* origins, const float* dirs,
                          const int32_t* exclude, int32_t* out, long long N, hipStream_t s) {
-  DRM_REQUIRE(N >= 0 && N <= (1LL << 31), "mesh_occluded: 0 <= N <= 2^31 rays");
-  DRM_REQUIRE(faces_ok(F) && V >= 1 && V <= 0x7fffffffLL, "mesh_occluded: 1 <= F < 2^24 faces, V >= 1 vertices");
+  DRM_TRY(check_ray_query("mesh_occluded", V, F, N, positions && faces && origins && dirs && out, bvh, s));
   if (N == 0) return DRM_OK;
-  DRM_REQUIRE(positions && faces && origins && dirs && out, "mesh_occluded: null pointer");
-  if (bvh) DRM_TRY(check_device_bvh(bvh, 0, false, F, s, "mesh_occluded"));
   hipLaunchKernelGGL(mesh_occluded_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, MeshRef{positions, faces, V, F}, bvh, origins, dirs, exclude,
                      out, N);
   DRM_HIP_CHECK(hipGetLastError());
@@ -195,11 +211,8 @@ int launch_mesh_occluded(const float* positions, const int32_t* faces, long long
 
 int launch_mesh_closest_hit(const float* positions, const int32_t* faces, long long V, long long F, const void* bvh, const float* origins,
                             const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, long long N, hipStream_t s) {
-  DRM_REQUIRE(N >= 0 && N <= (1LL << 31), "mesh_closest_hit: 0 <= N <= 2^31 rays");
-  DRM_REQUIRE(faces_ok(F) && V >= 1 && V <= 0x7fffffffLL, "mesh_closest_hit: 1 <= F < 2^24 faces, V >= 1 vertices");
+  DRM_TRY(check_ray_query("mesh_closest_hit", V, F, N, positions && faces && origins && dirs && out_face && out_tuv, bvh, s));
   if (N == 0) return DRM_OK;
-  DRM_REQUIRE(positions && faces && origins && dirs && out_face && out_tuv, "mesh_closest_hit: null pointer");
-  if (bvh) DRM_TRY(check_device_bvh(bvh, 0, false, F, s, "mesh_closest_hit"));
   hipLaunchKernelGGL(mesh_closest_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, MeshRef{positions, faces, V, F}, bvh, origins, dirs, exclude,
                      out_face, out_tuv, N);
   DRM_HIP_CHECK(hipGetLastError());

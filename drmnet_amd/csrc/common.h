@@ -250,24 +250,31 @@ size_t render_mesh_workspace_bytes(long long F, int B, int H, int W, int subpixe
 // the two visibility launches: records of every (row, face), then the nearest covering face of every film sample.  view [B][9] or null.
 int launch_mesh_visibility(const float* positions, const int32_t* faces, long long V, long long F, const float* view, int B, int H, int W, int subpixel,
                            float* records, float* hits, hipStream_t s);
-int launch_render_mesh(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
-                       const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
-                       int subpixel, void* workspace, size_t workspace_bytes, hipStream_t s);
-// the same with shadow rays through the blob of drm_mesh_bvh_build (bvh.h): bvh a device pointer to bvh_bytes bytes
-int launch_render_mesh_shadowed(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
-                                const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
-                                int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, hipStream_t s);
-// the shadowed render with one bounce of interreflection (see drm_render_mesh_bounced): bounce_quad in [1, 16]
-int launch_render_mesh_bounced(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z,
-                               const float* env, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
-                               int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
-                               hipStream_t s);
-// the same with light samples (see drm_render_mesh_lit): bvh == null with bvh_bytes == 0 is unshadowed; light_samples == 0 or env == null is
-// launch_render_mesh / launch_render_mesh_shadowed; the light workspace is render_light_workspace_bytes(B, EH, EW, light_samples)
-int launch_render_mesh_lit(const float* positions, const float* normals, const int32_t* faces, long long V, long long F, const float* z, const float* env,
-                           const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW, int quad,
-                           int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
-                           void* light_workspace, size_t light_workspace_bytes, hipStream_t s);
+// One mesh render (the four drm_render_mesh* entries): what every one takes, then the optional parts, each off by default.
+struct MeshRenderArgs {
+  const float* positions = nullptr;  // [V][3]
+  const float* normals = nullptr;    // [V][3]
+  const int32_t* faces = nullptr;    // [F][3]
+  long long V = 0, F = 0;
+  const float* z = nullptr;     // [B][6]
+  const float* env = nullptr;   // [B][EH][EW][3], or null: white
+  const float* view = nullptr;  // [B][9], or null: +z
+  float *image = nullptr, *normal = nullptr, *depth = nullptr, *alpha = nullptr;
+  int B = 0, H = 0, W = 0, EH = 0, EW = 0, quad = 0, subpixel = 0;
+  void* workspace = nullptr;  // render_mesh_workspace_bytes
+  size_t workspace_bytes = 0;
+  // shadow rays through the blob of drm_mesh_bvh_build (bvh.h): bvh a device pointer to bvh_bytes bytes
+  bool shadowed = false;
+  const void* bvh = nullptr;
+  size_t bvh_bytes = 0;
+  // light samples (see drm_render_mesh_lit): 0, or env == null, renders without them; the workspace is render_light_workspace_bytes
+  int light_samples = 0;
+  void* light_workspace = nullptr;
+  size_t light_workspace_bytes = 0;
+  // one bounce of interreflection (see drm_render_mesh_bounced): with shadowed, without light samples; 0: none
+  int bounce_quad = 0;
+};
+int launch_render_mesh(const MeshRenderArgs& a, hipStream_t s);
 // validation losses (losses.hip): see drm_validation_losses
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .render import QUAD, SUBPIXEL, _device, _env_and_view, canonical_rows, view_rotation
+from .render import QUAD, SUBPIXEL, _device, _env_and_view, canonical_rows, check_light_samples, light_samples_error, view_rotation
 
 Mesh = Dict[str, torch.Tensor]
 _KEYS = ("vertex_positions", "vertex_normals", "faces")
@@ -281,7 +281,7 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     if light_samples and env is not None:
         light_bytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
         if light_bytes == 0:
-            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+            raise light_samples_error(light_samples)
         light_ws = torch.empty(((light_bytes + 7) // 8,), dtype=torch.float64, device=dev)
     args = (pos.data_ptr(), nrm.data_ptr(), faces.data_ptr(), V, F, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(), normal.data_ptr(),
             depth.data_ptr(), alpha.data_ptr(), B, H, W, EH, EW, int(quad), int(subpixel), ws.data_ptr(), nbytes)
@@ -314,11 +314,9 @@ class MeshRenderer:
                  return_depth: bool = False, init_view_from=(0, 0, 1.1), brdf_param_names: Optional[List[str]] = None, *, quad: int = QUAD,
                  subpixel: int = SUBPIXEL, shadows: bool = False, light_samples: int = 0, bounces: int = 0, bounce_quad: int = 4):
         self.shadows = bool(shadows)
-        self.light_samples = int(light_samples)
-        self.bounces = check_bounces(bounces, bounce_quad, self.shadows, self.light_samples)
+        self.bounces = check_bounces(bounces, bounce_quad, self.shadows, int(light_samples))
         self.bounce_quad = int(bounce_quad)
-        if self.light_samples and (self.light_samples < 64 or self.light_samples > 65536 or self.light_samples & (self.light_samples - 1)):
-            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+        self.light_samples = check_light_samples(light_samples)
         self.image_size = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(s) for s in image_size)
         self.envmap_size = tuple(int(s) for s in envmap_size)
         self.spp, self.denoise = spp, denoise

@@ -91,6 +91,20 @@ def _env_and_view(envmaps, view_from, B: int, dev: torch.device):
     return env, EH, EW, view
 
 
+def light_samples_error(light_samples) -> ValueError:
+    """what a ``light_samples`` that is neither 0 nor a power of two in [64, 65536] raises, wherever it is found out"""
+    return ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+
+
+def check_light_samples(light_samples) -> int:
+    """``light_samples`` as an int: 0 (none) or a power of two in [64, 65536]; anything else is a ValueError (a renderer's constructor asks this;
+    ``render`` and ``render_mesh`` learn the same from drm_render_light_workspace_bytes, which answers 0 for what the library will not take)"""
+    m = int(light_samples)
+    if m and (m < 64 or m > 65536 or m & (m - 1)):
+        raise light_samples_error(light_samples)
+    return m
+
+
 @torch.no_grad()
 def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD,
            subpixel: int = SUBPIXEL, flip: bool = False, view_from=None, light_samples: int = 0) -> torch.Tensor:
@@ -116,7 +130,7 @@ def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] =
     if light_samples and env is not None:
         nbytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
         if nbytes == 0:
-            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+            raise light_samples_error(light_samples)
         ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
         entry, light_args = lib.drm_render_refmap_lit, (light_samples, ws.data_ptr(), nbytes)
     with torch.cuda.device(dev):
@@ -148,9 +162,7 @@ class RefMapRenderer:
         self.return_normal, self.return_depth = return_normal, return_depth
         self.brdf_param_names = brdf_param_names
         self.quad, self.subpixel = int(quad), int(subpixel)
-        self.light_samples = int(light_samples)
-        if self.light_samples and (self.light_samples < 64 or self.light_samples > 65536 or self.light_samples & (self.light_samples - 1)):
-            raise ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+        self.light_samples = check_light_samples(light_samples)
         self.flip = False
         self._envmap: Optional[torch.Tensor] = None  # the scene's map; None = the initial all-zero bitmap of envmap_size
         self._view_from: Optional[torch.Tensor] = None  # the scene's view; None = the sensor's own (+z)
