@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include "conv_forms.h"
 #include "gn_fold.h"
 
 namespace drm {
@@ -102,10 +103,9 @@ struct ConvArgs {
   const float* in_inv = nullptr;       // split-precision path: [N] per-image 2^-k undoing the input staging factor (launch_act_pow2_scale)
   GnFold gnf;                          // sparse launches (engine.hip gn_params): gn_scale / gn_shift (and a guard table set) are finalised by this launch's own prologue
 };
-// One decision per conv launch: plan_conv (conv_split2.hip) picks the kernel and its instantiation, the split-K form, and whether the 2x2 pool and
+// One decision per conv launch: plan_conv (conv_plan.hip) picks the kernel and its instantiation, the split-K form, and whether the 2x2 pool and
 // the GroupNorm finalise fold into the launch; launch_conv carries it out.  The engine plans every conv once, in sizing and real passes alike.
 enum ConvKernel : unsigned char { CONV_NONE, CONV_IGEMM, CONV_PIPELINE };  // NONE: per-image weights outside the pipeline's rule
-enum ConvTile : unsigned char { TILE_256x256, TILE_256x192, TILE_256x128, TILE_128x128, TILE_256x64, TILE_128x64, TILE_128x32 };  // GEMM rows x channels
 // split-K finish: by the workgroup that arrives last at an output tile (SK instantiation, ConvArgs::tile_ticket), or by a second launch
 // (splitk_reduce_small_kernel) that sums the slabs
 enum SplitFinish : unsigned char { SPLIT_NONE, SPLIT_IN_LAUNCH, SPLIT_REDUCE };
@@ -128,10 +128,10 @@ struct ConvPlan {
 ConvPlan plan_conv(const ConvArgs& a, int precision, bool want_pool = false, bool gn_foldable = false);
 // the weight image a conv with `cin` (padded) input channels reads in `precision`: the pre-split one (launch_pack_conv_weight_split) or plain fp32
 bool conv_split_weights(int precision, int cin);
-// the one launch entry of every conv: validates `a` against the plan; a split-K launch takes its slabs at a.split_ws
+// the one launch entry of every conv (conv.hip): validates `a` against the plan; a split-K launch takes its slabs at a.split_ws
 int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
-// index of the pixel-tile family {TH, TW} that wastes the fewest GEMM rows on an H x W map (ties: the first = larger tile)
-int conv_tile_family(int H, int W, const int (*fam)[2], int n_fam);
+template <int TAPS, int TERMS> int dispatch_s2(const ConvArgs& a, const ConvPlan& p, hipStream_t s);  // the pipeline launches of one DRM_S2_UNITS unit (conv_split2.hip)
+int no_form(const ConvPlan& p);  // the error of a plan without an instantiation
 size_t packed_conv_weight_split_floats(int taps, int CoutP, int CinP);
 // mx: the f16mx image (fp16 hi planes + e4m3 planes of hi and lo) for the 3x3 convs that run with ConvArgs::terms == 2
 int launch_pack_conv_weight_split(const float* w, float* packed, float* scales, unsigned* scratch, int Cout, int Cin, int taps, int CoutP,

@@ -254,10 +254,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
   }
 }
 
-template <int TAPS, int TH, int TW, int WM, int WN, int MT, int NT, int KC>
+template <int TAPS, int TH, int TW, ConvTile T, int KC>
 static int launch_variant(const ConvArgs& a, hipStream_t s) {
-  using C = Cfg<TAPS, TH, TW, WM, WN, MT, NT, KC>;
-  auto kern = conv_igemm_kernel<TAPS, TH, TW, WM, WN, MT, NT, KC>;
+  constexpr TileShape t = tile_shape(T);
+  using C = Cfg<TAPS, TH, TW, t.wm, t.wn, t.mt, t.nt, KC>;
+  auto kern = conv_igemm_kernel<TAPS, TH, TW, t.wm, t.wn, t.mt, t.nt, KC>;
   const size_t lds_bytes = (size_t)C::LDS_F4 * sizeof(float4);
   // the opt-in LDS size is a per-device function attribute: one bit per device ordinal, set idempotently (as in conv_split2.hip)
   const DeviceInfo* di = device_info();
@@ -286,38 +287,21 @@ static int launch_variant(const ConvArgs& a, hipStream_t s) {
 
 template <int TAPS, int TH, int TW, int KC>
 static int launch_igemm_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  if (p.tile == TILE_128x128) return launch_variant<TAPS, TH, TW, 2, 2, 2, 2, KC>(a, s);
-  if (p.tile == TILE_128x64) return launch_variant<TAPS, TH, TW, 2, 2, 2, 1, KC>(a, s);
-  return launch_variant<TAPS, TH, TW, 4, 1, 1, 1, KC>(a, s);
-}
-
-// Pixel-tile family for an H x W map: the one that wastes the fewest GEMM rows on masked edge pixels (ties: the larger tile).  Maps
-// that are whole multiples of a tile (every shipped configuration) pick exactly what they always did; any other size the reference
-// accepts (openaimodel.py:731-768 is fully convolutional) runs with masked edge tiles.
-int conv_tile_family(int H, int W, const int (*fam)[2], int n_fam) {
-  int best = 0;
-  long long best_area = -1;
-  for (int k = 0; k < n_fam; ++k) {
-    const long long th = fam[k][0], tw = fam[k][1];
-    const long long area = ((H + th - 1) / th) * th * ((W + tw - 1) / tw) * tw;
-    if (best_area < 0 || area < best_area) {
-      best = k;
-      best_area = area;
-    }
-  }
-  return best;
+  if (p.tile == TILE_128x128) return launch_variant<TAPS, TH, TW, TILE_128x128, KC>(a, s);
+  if (p.tile == TILE_128x64) return launch_variant<TAPS, TH, TW, TILE_128x64, KC>(a, s);
+  return launch_variant<TAPS, TH, TW, TILE_128x32, KC>(a, s);
 }
 
 template <int TAPS, int KC>
-static int launch_igemm_family(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  if (p.th == 8 && p.tw == 16) return launch_igemm_tile<TAPS, 8, 16, KC>(a, p, s);
-  if (p.th == 8 && p.tw == 8) return launch_igemm_tile<TAPS, 8, 8, KC>(a, p, s);
-  if (p.th == 4 && p.tw == 8) return launch_igemm_tile<TAPS, 4, 8, KC>(a, p, s);
-  return launch_igemm_tile<TAPS, 4, 4, KC>(a, p, s);
+static int launch_igemm_family(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {  // (the families of 128-row tiles)
+#define DRM_X(TH, TW) if constexpr (TH * TW <= 128) if (p.th == TH && p.tw == TW) return launch_igemm_tile<TAPS, TH, TW, KC>(a, p, s);
+  DRM_PIXEL_TILES(DRM_X)
+#undef DRM_X
+  return no_form(p);
 }
 
-// the CONV_IGEMM plans of launch_conv (conv_split2.hip)
-int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+// the CONV_IGEMM plans of launch_conv
+static int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   DRM_REQUIRE(a.Cout % 32 == 0, "conv Cout must be padded to a multiple of 32");
   DRM_REQUIRE((a.C0 + a.C1) % 8 == 0, "conv Cin must be padded to a multiple of 8");
   DRM_REQUIRE((a.gn_scale == nullptr) == (a.gn_shift == nullptr), "gn scale/shift must come together");
@@ -325,6 +309,106 @@ int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   DRM_REQUIRE(a.C0 % 8 == 0, "conv C0 must be a multiple of 8");
   DRM_REQUIRE(a.taps == 9, "1x1 conv needs Cin % 32 == 0");
   return launch_igemm_family<9, 8>(a, p, s);
+}
+
+int no_form(const ConvPlan& p) {  // (a plan that names a form no unit instantiates: a planner bug)
+  set_error("conv plan: form " + std::to_string((int)p.tile) + " on " + std::to_string(p.th) + "x" + std::to_string(p.tw) + (p.ragged ? " ragged" : "") +
+            " pixel tiles, terms " + std::to_string(p.terms) + ", is not instantiated");
+  return DRM_ERR_STATE;
+}
+
+// Second launch of a split-K conv on the smallest maps (H * W < 128, or the wide split: plan_conv says which): out = sum of the slabs in slab order (already
+// un-scaled by their launch) + bias (+ emb[n] + residual), and the per-(image, channel) sums / sums of squares of the result for the next GroupNorm.
+// The whole image sits in ONE block per 16 channel quads -- 16 quads x 16 pixel lanes, the lanes of a channel fold in LDS in lane order and the
+// block's sums ARE the statistics: no partial table, no ticket, no fence, no atomics; 5.8 us at batch 32 on the 4x8 maps.  Larger maps finish inside
+// the conv launch (conv_split2_kernel<..., SK>): there this kernel took 12 us (22 us beyond 256 pixels, in a second kernel with a ticket hand-off).
+__global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* __restrict__ partial, size_t slab_f4, int ks, const float* __restrict__ bias,
+                                                                  const float* __restrict__ emb, int emb_stride, const float* res /* may alias out */,
+                                                                  float4* out, double2* __restrict__ stat, int HW, int Cout) {
+  __shared__ float red[256][8];
+  const int n = blockIdx.y, q4 = Cout >> 2;
+  const int ql = threadIdx.x & 15, pl = threadIdx.x >> 4;
+  const int q = blockIdx.x * 16 + ql;
+  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (q < q4) {
+    if (bias) b = reinterpret_cast<const float4*>(bias)[q];
+    if (emb) {
+      const float4 e = *reinterpret_cast<const float4*>(emb + (size_t)n * emb_stride + 4 * q);
+      b.x += e.x; b.y += e.y; b.z += e.z; b.w += e.w;
+    }
+  }
+  float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int p = pl; p < HW && q < q4; p += 16) {
+    const size_t idx = ((size_t)n * HW + p) * q4 + q;
+    float4 acc = partial[idx];
+    for (int k = 1; k < ks; ++k) {
+      const float4 t = partial[idx + (size_t)k * slab_f4];
+      acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
+    }
+    float4 v = make_float4(acc.x + b.x, acc.y + b.y, acc.z + b.z, acc.w + b.w);
+    if (res) {
+      const float4 r = reinterpret_cast<const float4*>(res)[idx];
+      v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+    }
+    out[idx] = v;
+    s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
+    ss[0] += v.x * v.x; ss[1] += v.y * v.y; ss[2] += v.z * v.z; ss[3] += v.w * v.w;
+  }
+  if (stat) {  // (uniform per launch)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      red[threadIdx.x][k] = s[k];
+      red[threadIdx.x][4 + k] = ss[k];
+    }
+    __syncthreads();
+    if (pl == 0 && q < q4) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        double a = 0.0, c2 = 0.0;
+        for (int j = 0; j < 16; ++j) {  // fixed order
+          a += (double)red[j * 16 + ql][k];
+          c2 += (double)red[j * 16 + ql][4 + k];
+        }
+        double2* d = stat + (size_t)n * Cout + 4 * q + k;
+        *d = make_double2(d->x + a, d->y + c2);
+      }
+    }
+  }
+}
+
+#define DRM_X(TAPS, TERMS) extern template int dispatch_s2<TAPS, TERMS>(const ConvArgs&, const ConvPlan&, hipStream_t);  // (conv_split2.hip, one unit each)
+DRM_S2_UNITS(DRM_X)
+#undef DRM_X
+int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  DRM_REQUIRE(a.taps == 9 || a.taps == 1 || a.taps == 4, "conv taps must be 9, 1 or 4 (the parity form of a 3x3 over a nearest-x2 input)");
+  DRM_REQUIRE(a.taps != 4 || (p.kernel == CONV_PIPELINE && p.finish == SPLIT_NONE), "the parity (4-tap) form runs on the pipeline kernel, un-split");
+  DRM_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv shape");
+  DRM_REQUIRE(!a.up0 || (a.H % 2 == 0 && a.W % 2 == 0), "upsampled source needs even output size");
+  DRM_REQUIRE(a.ksplit == p.ksplit && (p.ksplit == 1 || a.split_ws), "split-K launch without its slab workspace");
+  if (p.kernel == CONV_IGEMM) return launch_igemm(a, p, s);
+  DRM_REQUIRE(p.kernel == CONV_PIPELINE, "no conv kernel takes this shape (per-image weights: split modes, maps of whole 16x16 tiles, 128-channel multiples)");
+  DRM_REQUIRE(a.Cout % 32 == 0 && (a.C0 + a.C1) % 32 == 0 && a.C0 % 32 == 0, "split conv needs channels % 32 == 0");
+  DRM_REQUIRE(a.terms == p.terms, "ConvArgs::terms differs from the plan");
+  DRM_REQUIRE(p.terms != 2 || (a.taps != 1 && a.gn_scale && !a.in_inv && a.w_img_stride_f4 == 0), "f16mx: 3x3 convs on a GroupNorm-ed input only");
+  auto run = [&](const ConvArgs& x) -> int {
+#define DRM_X(TAPS, TERMS) if (a.taps == TAPS && p.terms == TERMS) return dispatch_s2<TAPS, TERMS>(x, p, s);
+    DRM_S2_UNITS(DRM_X)
+#undef DRM_X
+    return no_form(p);
+  };
+  if (p.finish != SPLIT_REDUCE) return run(a);
+  // smallest maps: every split writes its own slab, a fixed-order second launch sums them and applies bias / emb / residual / statistics
+  ConvArgs part = a;
+  part.out = a.split_ws;
+  part.split_ws = nullptr;
+  part.bias = nullptr; part.emb = nullptr; part.res = nullptr; part.stat_out = nullptr;
+  DRM_TRY(run(part));
+  DRM_REQUIRE(a.ksplit > 1 && a.split_stride % 4 == 0 && a.Cout % 4 == 0 && a.H * a.W <= 256, "split-K reduction arguments (maps of more than 256 pixels finish inside the conv launch)");
+  hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((a.Cout / 4 + 15) / 16, a.N), dim3(256), 0, s, reinterpret_cast<const float4*>(a.split_ws),
+                     a.split_stride / 4, a.ksplit, a.bias, a.emb, a.emb_stride, a.res, reinterpret_cast<float4*>(a.out), a.stat_out, a.H * a.W, a.Cout);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

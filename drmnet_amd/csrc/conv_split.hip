@@ -1,4 +1,4 @@
-// Split-precision arithmetic of the fused GroupNorm+SiLU+conv implicit GEMM -- weight pre-split (the kernel and its planner: conv_split2.hip):
+// Split-precision arithmetic of the fused GroupNorm+SiLU+conv implicit GEMM -- weight pre-split (the kernel: conv_split2.hip, its planner: conv_plan.hip):
 // fp32-accurate products on the gfx950 f16 matrix cores.
 //
 // Every fp32 operand x is split as x = hi + lo with hi = fp16(x), lo = fp16(x - hi) (22 significant bits together),

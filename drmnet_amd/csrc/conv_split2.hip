@@ -1465,313 +1465,40 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
   return DRM_OK;
 }
 
-static int no_form(const ConvPlan& p) {  // (a plan that names a form no unit instantiates: a planner bug)
-  set_error("conv plan: form " + std::to_string((int)p.tile) + " on " + std::to_string(p.th) + "x" + std::to_string(p.tw) + (p.ragged ? " ragged" : "") +
-            " pixel tiles, terms " + std::to_string(p.terms) + ", is not instantiated");
-  return DRM_ERR_STATE;
+// The one step from a plan to its instantiation: the kernels a unit instantiates are exactly the forms s2_form (conv_forms.h) states.
+template <int TAPS, int TERMS, int TH, int TW, ConvTile T, bool RAG, bool SK, bool POOL>
+static int launch_s2_form(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  constexpr S2Form f = s2_form(TAPS, TERMS, TH, TW, T, RAG, SK, POOL);
+  constexpr TileShape t = tile_shape(T);
+  if constexpr (f.exists) return launch_s2<TAPS, TH, TW, t.wm, t.wn, t.mt, t.nt, f.ring, f.tps, TERMS, RAG, SK, POOL>(a, s);
+  return no_form(p);
 }
 
-// The instantiations of one (TAPS, TERMS) unit on one pixel tile, by GEMM tile.  3x3: one barrier per kernel ROW (3 taps, 48 KB of weights per
-// step, double-buffered); 1x1: one tap per step, ring of 4.  3x3 256-row tiles of 4-row pixel tiles (4x8 / 4x4 maps) do not exist: their
-// multi-image halo tiles leave no room for 96 KB of weights.
-template <int TAPS, int TH, int TW, int TERMS>
+template <int TAPS, int TERMS, int TH, int TW, ConvTile T>
+static int launch_s2_variant(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.ragged) return launch_s2_form<TAPS, TERMS, TH, TW, T, true, false, false>(a, p, s);
+  if (p.pool) return launch_s2_form<TAPS, TERMS, TH, TW, T, false, false, true>(a, p, s);
+  if (p.finish == SPLIT_IN_LAUNCH) return launch_s2_form<TAPS, TERMS, TH, TW, T, false, true, false>(a, p, s);
+  return launch_s2_form<TAPS, TERMS, TH, TW, T, false, false, false>(a, p, s);
+}
+
+template <int TAPS, int TERMS, int TH, int TW>
 static int launch_s2_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  constexpr int TPS = (TAPS == 9) ? 3 : (TAPS == 4 ? 2 : 1), RG = (TAPS == 1) ? 4 : 2;
-  constexpr bool T16 = TH == 16 && TW == 16, ROWS256 = TAPS == 1 || TH >= 8;
-  if constexpr (TAPS == 4) {
-    // the parity form of a 3x3 conv over a nearest-x2 input: one window ROW (2 taps) per step and barrier, ring of 2, on every GEMM tile of the
-    // 3x3 form (two-tap groups fit next to the halo tile where three-tap groups did not: 192-wide and 128x128 tiles); never ragged, split or pooled
-    if (p.ragged || p.pool || p.ksplit > 1) return no_form(p);
-    if (p.tile == TILE_256x192) {
-      if constexpr (T16 && (TERMS == 3 || TERMS == 2)) return launch_s2<TAPS, TH, TW, 4, 2, 2, 3, RG, TPS, TERMS>(a, s);
-    } else if (p.tile == TILE_256x128) {
-      if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS>(a, s);
-    } else if (p.tile == TILE_128x128) {
-      if constexpr (!ROWS256) return launch_s2<TAPS, TH, TW, 2, 2, 2, 2, RG, TPS, TERMS>(a, s);
-    } else if (p.tile == TILE_256x64) {
-      if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 1, RG, TPS, TERMS>(a, s);
-    } else if constexpr (!T16) {
-      if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS>(a, s);
-      if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS>(a, s);
-    }
-    return no_form(p);
-  } else if (p.ragged) {
-    if constexpr (TERMS != 0 && !T16 && !(TH == 4 && TW == 8)) {  // (the ragged families; fp32 runs ragged maps on conv_igemm_kernel)
-      if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS, true>(a, s);
-      if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS, true>(a, s);
-    }
-  } else if (p.tile == TILE_256x256) {
-    if constexpr (TAPS == 1 && T16 && TERMS == 3) return launch_s2<TAPS, TH, TW, 4, 2, 2, 4, 2, 1, TERMS>(a, s);
-  } else if (p.tile == TILE_256x192) {
-    if constexpr (T16 && (TERMS == 3 || (TAPS == 9 && TERMS == 2))) return launch_s2<TAPS, TH, TW, 4, 2, 2, 3, 3, 1, TERMS>(a, s);
-  } else if (p.tile == TILE_256x128 && p.pool) {
-    if constexpr (TAPS == 9 && T16) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS, false, false, true>(a, s);
-  } else if (p.tile == TILE_256x128) {
-    if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 2, RG, TPS, TERMS>(a, s);
-  } else if (p.tile == TILE_128x128) {
-    if constexpr (!ROWS256) return launch_s2<TAPS, TH, TW, 2, 2, 2, 2, 3, 1, TERMS>(a, s);
-  } else if (p.tile == TILE_256x64) {
-    if constexpr (ROWS256) return launch_s2<TAPS, TH, TW, 4, 2, 2, 1, RG, TPS, TERMS>(a, s);
-  } else if constexpr (!T16) {  // 128-row tiles
-    if (p.tile == TILE_128x64) return launch_s2<TAPS, TH, TW, 2, 2, 2, 1, RG, TPS, TERMS>(a, s);
-    if (p.tile == TILE_128x32 && p.finish == SPLIT_IN_LAUNCH) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS, false, true>(a, s);
-    if (p.tile == TILE_128x32) return launch_s2<TAPS, TH, TW, 4, 1, 1, 1, RG, TPS, TERMS>(a, s);
-  }
+#define DRM_X(name, wm, wn, mt, nt) if (p.tile == name) return launch_s2_variant<TAPS, TERMS, TH, TW, name>(a, p, s);
+  DRM_CONV_TILES(DRM_X)
+#undef DRM_X
   return no_form(p);
 }
 
 template <int TAPS, int TERMS>
 int dispatch_s2(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  if (p.th == 16 && p.tw == 16) return launch_s2_tile<TAPS, 16, 16, TERMS>(a, p, s);
-  if (p.th == 8 && p.tw == 16) return launch_s2_tile<TAPS, 8, 16, TERMS>(a, p, s);
-  if (p.th == 8 && p.tw == 8) return launch_s2_tile<TAPS, 8, 8, TERMS>(a, p, s);
-  if (p.th == 4 && p.tw == 8) return launch_s2_tile<TAPS, 4, 8, TERMS>(a, p, s);
-  if (p.th == 4 && p.tw == 4) return launch_s2_tile<TAPS, 4, 4, TERMS>(a, p, s);
+#define DRM_X(TH, TW) if (p.th == TH && p.tw == TW) return launch_s2_tile<TAPS, TERMS, TH, TW>(a, p, s);
+  DRM_PIXEL_TILES(DRM_X)
+#undef DRM_X
   return no_form(p);
 }
 
-// Build units: this file is compiled once per (TAPS, TERMS) pair with -DDRM_S2_UNIT=<10 * TAPS + TERMS> (the kernel instantiations of that pair,
-// in parallel: drmnet_amd/build.py) and once without (the host-side rest below, which only declares them).
-#ifdef DRM_S2_UNIT
+// Build units: compiled once per (TAPS, TERMS) pair of DRM_S2_UNITS, -DDRM_S2_UNIT=<10 * TAPS + TERMS> (drmnet_amd/build.py); launch_conv picks the unit
 template int dispatch_s2<DRM_S2_UNIT / 10, DRM_S2_UNIT % 10>(const ConvArgs&, const ConvPlan&, hipStream_t);
-#else
-extern template int dispatch_s2<9, 0>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<1, 0>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<9, 1>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<1, 1>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<9, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<1, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<9, 2>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<9, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<4, 0>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<4, 1>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<4, 2>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<4, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<4, 4>(const ConvArgs&, const ConvPlan&, hipStream_t);
-extern template int dispatch_s2<1, 3>(const ConvArgs&, const ConvPlan&, hipStream_t);
-int launch_igemm(const ConvArgs& a, const ConvPlan& p, hipStream_t s);  // (conv.hip)
-
-constexpr long long S2_MIN_WIDE_TILES = 176;  // 256 x 128 tiles are used from this many workgroups on (of 256 CUs)
-// On sparse launches (few images) the conv finalises its input's GroupNorm tables in its own prologue (ConvArgs::gnf, gn_fold.h) and no
-// gn_finalize launch is made: at batch 1 a ~5 us launch per GroupNorm was 111 launches = a tenth of the DRMNet step.
-constexpr int GN_FOLD_MAX_N = 4;
-
-bool conv_split_weights(int precision, int cin) { return precision != PREC_FP32 && cin % 32 == 0; }
-
-ConvPlan plan_conv(const ConvArgs& a, int precision, bool want_pool, bool gn_foldable) {
-  ConvPlan p;
-  const int Ctot = a.C0 + a.C1, hw = a.H * a.W;
-  const bool split = precision != PREC_FP32, chunks = Ctot % 32 == 0 && a.C0 % 32 == 0;
-  const long long rows = (long long)a.N * hw;
-  auto wgs = [&](int bm, int bn) { return ((rows + bm - 1) / bm) * (a.Cout / bn); };
-  if (a.w_img_stride_f4 != 0) {
-    // per-image weights (the attention GEMMs, attn.hip): split modes, one image per tile (maps of whole 16 x 16 tiles), 128-channel multiples
-    if (!split || a.H % 16 != 0 || a.W % 16 != 0 || a.Cout % 128 != 0 || Ctot % 128 != 0) return p;
-  }
-  // The pipeline kernel (LDS-DMA weight ring, persistent tiles, fused output statistics) takes every conv whose channel counts are whole 32-chunks:
-  // the split modes on any map, exact fp32 (TERMS = 0) on maps that are a whole number of 4x4 tiles.  The rest -- odd channel counts of the
-  // per-module entry points, ragged maps in fp32 -- runs on conv_igemm_kernel (conv.hip): 128-row tiles, edge tiles masked.
-  if (!chunks || (!split && (a.H % 4 != 0 || a.W % 4 != 0))) {
-    static const int fam[4][2] = {{8, 16}, {8, 8}, {4, 8}, {4, 4}};
-    const int f = conv_tile_family(a.H, a.W, fam, 4);
-    p.kernel = CONV_IGEMM;
-    p.th = fam[f][0]; p.tw = fam[f][1];
-    p.tile = a.Cout % 128 == 0 ? TILE_128x128 : (a.Cout % 64 == 0 ? TILE_128x64 : TILE_128x32);
-    p.kc = chunks ? 32 : 8;
-    return p;
-  }
-  p.kernel = CONV_PIPELINE;
-  p.terms = (precision == PREC_F16MX && a.mx_site) ? 2 : precision_terms(precision);
-  p.gn_fold = gn_foldable && a.N <= GN_FOLD_MAX_N;
-  // pixel-tile family: 256-row tiles of TH x TW pixels per image, 128-row tiles of TH4 x TW4
-  static const int whole[5][4] = {{16, 16, 8, 16}, {8, 16, 8, 16}, {8, 8, 8, 8}, {4, 8, 4, 8}, {4, 4, 4, 4}};
-  const int* fw = nullptr;
-  for (const auto& f : whole)
-    if (!fw && a.H % f[0] == 0 && a.W % f[1] == 0) fw = f;
-  if (!fw) {
-    // Maps that are not a whole number of tiles (any H, W the reference accepts other than the shipped sizes): 128-row tiles on 4 waves,
-    // 64 or 32 channels wide, in three pixel-tile families, edge tiles masked (no split-K, no per-image weights)
-    static const int fam[3][2] = {{8, 16}, {8, 8}, {4, 4}};
-    const int f = conv_tile_family(a.H, a.W, fam, 3);
-    p.th = fam[f][0]; p.tw = fam[f][1];
-    p.ragged = true;
-    p.tile = a.Cout % 64 == 0 ? TILE_128x64 : TILE_128x32;
-    return p;
-  }
-  // Split-K.  Deep levels (maps of at most 128 pixels: the 8x16 and 4x8 levels of a batch-32 step): too few GEMM rows for the 128-channel-wide
-  // tiles to fill the chip, and the narrow tiles that do fill it re-stage (GroupNorm + SiLU + split) every activation tile once per 32 or 64 output
-  // channels.  Split-K over the WIDE tiles instead: every split writes its slab, splitk_reduce_small_kernel finishes (two-launch form).
-  // (1x1 convs of these levels on the same form measured neutral: 5.86 -> 5.54 ms of 1x1 time per step, given back by the reduction launches)
-  int wide = 1;
-  if (a.taps == 9 && !a.out_nchw && a.w_img_stride_f4 == 0 && a.Cout % 128 == 0 && hw <= 128 &&
-      ((a.H % 8 == 0 && a.W % 16 == 0) || (a.H % 4 == 0 && a.W % 8 == 0)) && rows >= 1024) {  // (sparse launches keep the narrow tiles: a batch-1 step would fill half a wide tile)
-    const int bm = (a.taps == 1 || (a.H % 8 == 0 && a.W % 16 == 0)) ? 256 : 128;  // (3x3 on 4x8 maps: 128-pixel x 128-channel tiles on 4 waves)
-    const long long tiles = ((rows + bm - 1) / bm) * (a.Cout / 128);
-    if (tiles < S2_MIN_WIDE_TILES) wide = (int)std::max<long long>(std::min<long long>(std::min<long long>(8, Ctot / 32 / 2), std::max<long long>(1, 256 / tiles)), 1);
-  }
-  // Deep U-Net levels (4x8 .. 8x16 maps) have few GEMM rows: with 256x128 tiles they launch far fewer workgroups than the chip has CUs.  Shrink
-  // the tile (128 rows, then 64 / 32 channels) until the grid covers the 256 CUs.
-  const bool t16 = fw[0] == 16 && fw[1] == 16, rows256 = a.taps == 1 || fw[0] >= 8;
-  auto tile = [&](ConvTile t, bool r256) {
-    p.tile = t;
-    p.th = r256 ? fw[0] : fw[2];
-    p.tw = r256 ? fw[1] : fw[3];
-  };
-  if (a.taps == 1 && t16 && p.terms == 3 && a.Cout % 256 == 0 && wgs(256, 256) >= 512) {
-    // 1x1 on big maps with Cout a multiple of 256: 256 output channels per tile (64 x 128 per wave, weight ring of 2).  The 1x1 form pays
-    // its activation staging and its barrier once per 24 MFMAs of a wave; here per 48 (the 64x128-map skip convs: 11-15 % faster).  The
-    // 1x1 kernel has the registers for it (176 -> 256 VGPRs, 2 spilled); the 3x3 kernel does not.
-    tile(TILE_256x256, true);
-  } else if (t16 && (p.terms == 3 || (a.taps != 1 && p.terms == 2)) && a.Cout % 192 == 0 && wgs(256, 192) >= 512) {
-    // 192 output channels per tile (64 x 96 per wave, one-tap weight ring of 3).  1x1 for Cout = 384 / 1152 / 1536 ...: qkv 512->1536 @16x32 and
-    // the 32x64-map skip convs 12-16 % faster.  3x3 (f16x3, f16mx; the three-tap groups would not fit next to the halo tile) for Cout = 384 on
-    // big maps: 12 fragment reads per 18 MFMA products instead of 8 per 12 -- 5 % faster there.  Fits since the scalar-base DMA addressing took
-    // the kernel from 256 to 207 VGPRs.
-    tile(TILE_256x192, true);
-  } else if (a.Cout % 128 == 0 && (wgs(256, 128) >= S2_MIN_WIDE_TILES || wide > 1)) {
-    // (one round of 128-wide tiles on >= 176 of the 256 CUs beats two rounds of the less efficient 64-wide ones: qkv 640->1920 @8x16 27 %,
-    //  512->1536 @8x16 24 %, 3x3 384->384 @16x32 12 % faster than with the old "fill every CU" rule)
-    tile(rows256 ? TILE_256x128 : TILE_128x128, rows256);
-    // the Downsample behind a 3x3 conv on 16 x 16 pixel tiles, from its epilogue (split modes)
-    p.pool = want_pool && split && a.taps == 9 && t16 && !a.out_nchw;
-  } else if (a.Cout % 64 == 0 && wgs(256, 64) >= 256) {
-    tile(rows256 ? TILE_256x64 : TILE_128x64, rows256);
-  } else if (a.Cout % 64 == 0 && wgs(128, 64) >= 256) {
-    // ([r4] 128 x 32 tiles from 512 workgroups on -- two workgroups per CU on the batch-1 step's top level instead of one: 4.74 vs 4.755 ms there,
-    //  780 vs 800 steps/s at batch 32 -- not adopted: co-resident workgroups do not hide what a sparse launch waits for)
-    tile(TILE_128x64, false);
-  } else {
-    // ([r4] a ring of 4 three-tap groups on these sparse-launch tiles: 5.31 vs 5.38 ms on the batch-1 step, later 5.06 vs 5.08 -- not adopted)
-    tile(TILE_128x32, false);
-  }
-  // Split-K factor: the wide split above, else only the 128-row x 32-channel tiles qualify, when their grid leaves most of the 256 CUs idle and
-  // the reduction is long.  (1x1 convs too [r3]: on the deep, small maps a K = 768 .. 1536 reduction is 24 .. 48 serial one-chunk steps of a
-  // handful of workgroups -- 30 us at batch 1 whatever the map; split, they are ~5 chunks each plus the small-map reduction.)
-  // ([r4] with the cheaper hand-off: splits of >= 2 chunks up to 1024 workgroups measured 5.13 vs 5.08 ms on the batch-1 step -- not adopted)
-  p.ksplit = wide;
-  if (wide == 1 && p.tile == TILE_128x32 && !a.out_nchw && a.w_img_stride_f4 == 0)
-    p.ksplit = (int)std::max<long long>(std::min<long long>(std::min<long long>(8, Ctot / 32 / 4), 640 / std::max<long long>(wgs(128, 32), 1)), 1);
-  if (p.ksplit > 1) {
-    // Who finishes a split-K conv.  Maps of at least 128 pixels: the launch itself -- the workgroup that arrives last at an output tile sums the
-    // slabs in slab order and runs the full epilogue (SK instantiation; the hand-off costs ~10 us whatever the shape).  Smaller maps:
-    // splitk_reduce_small_kernel in a second launch (5.8 us on the 4x8 maps of the batch-32 step, where the fused finish measured 1 % slower on
-    // the whole step; at batch 1 the maps of 128 .. 1024 pixels are where the second launch cost 12 .. 22 us: 6.64 -> 6.0 ms per step with the
-    // fused finish).  ([r4] with the agent-scope hand-off the fused finish was tried on the smaller maps too: batch 1 4.79 vs 4.755 ms, batch 32
-    // 759 vs 763 steps/s -- the second launch stays)
-    p.finish = (hw >= 128 && wide == 1) ? SPLIT_IN_LAUNCH : SPLIT_REDUCE;
-    // one arrival counter per output tile (128 GEMM rows x 32 channels; an upper bound over the pixel-tile families)
-    if (p.finish == SPLIT_IN_LAUNCH) p.tickets = ((size_t)a.N * hw / 128 + (size_t)hw / 16 + 2) * (size_t)(a.Cout / 32);
-  }
-  return p;
-}
-
-// Second launch of a split-K conv on the smallest maps (H * W < 128, or the wide split: plan_conv says which): out = sum of the slabs in slab order (already
-// un-scaled by their launch) + bias (+ emb[n] + residual), and the per-(image, channel) sums / sums of squares of the result for the next GroupNorm.
-// The whole image sits in ONE block per 16 channel quads -- 16 quads x 16 pixel lanes, the lanes of a channel fold in LDS in lane order and the
-// block's sums ARE the statistics: no partial table, no ticket, no fence, no atomics; 5.8 us at batch 32 on the 4x8 maps.  Larger maps finish inside
-// the conv launch (conv_split2_kernel<..., SK>): there this kernel took 12 us (22 us beyond 256 pixels, in a second kernel with a ticket hand-off).
-__global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* __restrict__ partial, size_t slab_f4, int ks, const float* __restrict__ bias,
-                                                                  const float* __restrict__ emb, int emb_stride, const float* res /* may alias out */,
-                                                                  float4* out, double2* __restrict__ stat, int HW, int Cout) {
-  __shared__ float red[256][8];
-  const int n = blockIdx.y, q4 = Cout >> 2;
-  const int ql = threadIdx.x & 15, pl = threadIdx.x >> 4;
-  const int q = blockIdx.x * 16 + ql;
-  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (q < q4) {
-    if (bias) b = reinterpret_cast<const float4*>(bias)[q];
-    if (emb) {
-      const float4 e = *reinterpret_cast<const float4*>(emb + (size_t)n * emb_stride + 4 * q);
-      b.x += e.x; b.y += e.y; b.z += e.z; b.w += e.w;
-    }
-  }
-  float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int p = pl; p < HW && q < q4; p += 16) {
-    const size_t idx = ((size_t)n * HW + p) * q4 + q;
-    float4 acc = partial[idx];
-    for (int k = 1; k < ks; ++k) {
-      const float4 t = partial[idx + (size_t)k * slab_f4];
-      acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
-    }
-    float4 v = make_float4(acc.x + b.x, acc.y + b.y, acc.z + b.z, acc.w + b.w);
-    if (res) {
-      const float4 r = reinterpret_cast<const float4*>(res)[idx];
-      v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-    }
-    out[idx] = v;
-    s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
-    ss[0] += v.x * v.x; ss[1] += v.y * v.y; ss[2] += v.z * v.z; ss[3] += v.w * v.w;
-  }
-  if (stat) {  // (uniform per launch)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      red[threadIdx.x][k] = s[k];
-      red[threadIdx.x][4 + k] = ss[k];
-    }
-    __syncthreads();
-    if (pl == 0 && q < q4) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        double a = 0.0, c2 = 0.0;
-        for (int j = 0; j < 16; ++j) {  // fixed order
-          a += (double)red[j * 16 + ql][k];
-          c2 += (double)red[j * 16 + ql][4 + k];
-        }
-        double2* d = stat + (size_t)n * Cout + 4 * q + k;
-        *d = make_double2(d->x + a, d->y + c2);
-      }
-    }
-  }
-}
-
-static int launch_splitk_reduce(const ConvArgs& a, const float* partial, hipStream_t s) {
-  const int HW = a.H * a.W;
-  DRM_REQUIRE(a.ksplit > 1 && a.split_stride % 4 == 0 && a.Cout % 4 == 0 && HW <= 256, "split-K reduction arguments (maps of more than 256 pixels finish inside the conv launch)");
-  hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((a.Cout / 4 + 15) / 16, a.N), dim3(256), 0, s, reinterpret_cast<const float4*>(partial),
-                     a.split_stride / 4, a.ksplit, a.bias, a.emb, a.emb_stride, a.res, reinterpret_cast<float4*>(a.out), a.stat_out, HW, a.Cout);
-  DRM_HIP_CHECK(hipGetLastError());
-  return DRM_OK;
-}
-
-int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
-  DRM_REQUIRE(a.taps == 9 || a.taps == 1 || a.taps == 4, "conv taps must be 9, 1 or 4 (the parity form of a 3x3 over a nearest-x2 input)");
-  DRM_REQUIRE(a.taps != 4 || (p.kernel == CONV_PIPELINE && p.finish == SPLIT_NONE), "the parity (4-tap) form runs on the pipeline kernel, un-split");
-  DRM_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0, "conv shape");
-  DRM_REQUIRE(!a.up0 || (a.H % 2 == 0 && a.W % 2 == 0), "upsampled source needs even output size");
-  DRM_REQUIRE(a.ksplit == p.ksplit && (p.ksplit == 1 || a.split_ws), "split-K launch without its slab workspace");
-  if (p.kernel == CONV_IGEMM) return launch_igemm(a, p, s);
-  DRM_REQUIRE(p.kernel == CONV_PIPELINE, "no conv kernel takes this shape (per-image weights: split modes, maps of whole 16x16 tiles, 128-channel multiples)");
-  DRM_REQUIRE(a.Cout % 32 == 0 && (a.C0 + a.C1) % 32 == 0 && a.C0 % 32 == 0, "split conv needs channels % 32 == 0");
-  DRM_REQUIRE(a.terms == p.terms, "ConvArgs::terms differs from the plan");
-  DRM_REQUIRE(p.terms != 2 || (a.taps != 1 && a.gn_scale && !a.in_inv && a.w_img_stride_f4 == 0), "f16mx: 3x3 convs on a GroupNorm-ed input only");
-  auto run = [&](const ConvArgs& x) -> int {
-    if (a.taps == 4) switch (p.terms) {
-      case 0: return dispatch_s2<4, 0>(x, p, s);
-      case 1: return dispatch_s2<4, 1>(x, p, s);
-      case 2: return dispatch_s2<4, 2>(x, p, s);
-      case 3: return dispatch_s2<4, 3>(x, p, s);
-      case 4: return dispatch_s2<4, 4>(x, p, s);
-      default: return no_form(p);
-    }
-    switch (p.terms) {
-      case 0: return a.taps == 9 ? dispatch_s2<9, 0>(x, p, s) : dispatch_s2<1, 0>(x, p, s);  // exact fp32 operands (DRM_PREC_FP32)
-      case 1: return a.taps == 9 ? dispatch_s2<9, 1>(x, p, s) : dispatch_s2<1, 1>(x, p, s);  // plain fp16 operands, one MFMA per product (DRM_PREC_F16)
-      case 2: return dispatch_s2<9, 2>(x, p, s);  // fp16 hi*hi + block-scaled fp8 cross terms (DRM_PREC_F16MX): the GroupNorm-fed 3x3 convs only
-      case 3: return a.taps == 9 ? dispatch_s2<9, 3>(x, p, s) : dispatch_s2<1, 3>(x, p, s);  // fp16 hi / lo, three MFMAs per product
-      case 4: return a.taps == 9 ? dispatch_s2<9, 4>(x, p, s) : dispatch_s2<1, 4>(x, p, s);  // plain bf16 operands (DRM_PREC_BF16)
-    }
-    return no_form(p);
-  };
-  if (p.finish != SPLIT_REDUCE) return run(a);
-  // smallest maps: every split writes its own slab, a fixed-order second launch sums them and applies bias / emb / residual / statistics
-  ConvArgs part = a;
-  part.out = a.split_ws;
-  part.split_ws = nullptr;
-  part.bias = nullptr; part.emb = nullptr; part.res = nullptr; part.stat_out = nullptr;
-  DRM_TRY(run(part));
-  return launch_splitk_reduce(a, a.split_ws, s);
-}
-#endif  // DRM_S2_UNIT
 
 }  // namespace drm

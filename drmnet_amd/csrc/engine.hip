@@ -469,8 +469,7 @@ static UpconvSplit plan_upconv_split(const Ctx& c, const ResLayer& r, const Conv
   u.p4 = plan_conv(u.a4, c.precision);
   u.p9 = plan_conv(u.b9, c.precision);
   if (!plain(u.p4) || !plain(u.p9)) return u;
-  static const int tile_bn[] = {256, 192, 128, 128, 64, 64, 32};  // (ConvTile order) a Cout tile of A lies inside one parity
-  if (r.cout % tile_bn[u.p4.tile] != 0) return u;
+  if (r.cout % tile_shape(u.p4.tile).bn() != 0) return u;  // a Cout tile of A lies inside one parity
   // The rule (mode 1).  Measured on the five decoder levels of the batch-32 step, f16mx, single launch -> A + B, two interleaved rounds on one
   // device (profiles/upconv_split_shapes.txt): 128x256 1.755 -> 1.419 ms, 64x128 1.409 -> 1.105, 32x64 0.700 -> 0.544, 16x32 0.310 -> 0.254,
   // round-to-round spread of a shape 0.2 .. 3 %: every level where the form applies wins by 18 .. 22 %, all of them on 256-row tiles at least 128
