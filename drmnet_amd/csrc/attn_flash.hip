@@ -23,7 +23,6 @@
 // Work: per 128-key tile and workgroup 2 x 1152 MFMAs (q k^T and P v at C = 384); k, v and the workgroup's q are re-read from L2 / the
 // Infinity Cache per key tile (the q / k / v images of a batch-32 pass are 300 MB).
 #include <algorithm>
-#include <atomic>
 #include <utility>
 
 #include "common.h"
@@ -434,20 +433,17 @@ int launch_attention_flash(const AttnPlan& p, const AttnTables& t, const float* 
   const size_t lds_bytes = (size_t)FA_SLOTS * FA_SLOT_F4 * sizeof(float4);
   const DeviceInfo* di = device_info();
   if (!di) return DRM_ERR_STATE;
-  auto go = [&](auto kern) -> int {
-    static std::atomic<uint64_t> attr_mask{0};
-    if (!(attr_mask.load(std::memory_order_acquire) >> di->ordinal & 1)) {
-      DRM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-      attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
-    }
+  auto go = [&](auto tag) -> int {
+    constexpr auto kern = decltype(tag)::kernel;
+    DRM_TRY(opt_in_lds<kern>(lds_bytes, di));
     hipLaunchKernelGGL(kern, dim3((unsigned)(N * (T / FA_QT))), dim3(256), lds_bytes, s, reinterpret_cast<const float4*>(t.wq), reinterpret_cast<const float4*>(t.wk),
                        reinterpret_cast<const float4*>(t.wv), x, out, t.qk_inv, t.k_inv, t.v_inv, N, T);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;
   };
-  if (terms == 4) return go(attn_flash_kernel<384, 4>);
-  if (terms == 1) return go(attn_flash_kernel<384, 1>);
-  return go(attn_flash_kernel<384, 3>);
+  if (terms == 4) return go(KernelTag<attn_flash_kernel<384, 4>>{});
+  if (terms == 1) return go(KernelTag<attn_flash_kernel<384, 1>>{});
+  return go(KernelTag<attn_flash_kernel<384, 3>>{});
 }
 
 }  // namespace drm

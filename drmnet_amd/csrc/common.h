@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include <string>
 #include "conv_forms.h"
 #include "gn_fold.h"
@@ -54,6 +55,26 @@ struct DeviceInfo {
   size_t lds_per_cu = 0;  // 163840
 };
 const DeviceInfo* device_info();
+// The opt-in LDS size (above 48 KiB) is a per-device function attribute: one bit per device ordinal and KERNEL instantiation (a template
+// argument, so kernels that share a function type keep separate state), set idempotently -- a racing second thread at worst repeats the
+// call -- so the entry points stay re-entrant across streams, threads and devices.
+template <auto KERNEL>
+int opt_in_lds(size_t bytes, const DeviceInfo* di) {
+  static std::atomic<uint64_t> attr_mask{0};
+  if (bytes > 48 * 1024 && !(attr_mask.load(std::memory_order_acquire) >> di->ordinal & 1)) {
+    DRM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
+  }
+  return DRM_OK;
+}
+template <auto KERNEL>  // (a kernel as an argument of a generic launch lambda: opt_in_lds<KERNEL> needs it as a constant)
+struct KernelTag { static constexpr auto kernel = KERNEL; };
+// Logical tile ids are dealt to the 8 XCDs in contiguous ranges (workgroups b and b + 8 share an XCD and its L2): the range of XCD `xcd` of `total`
+struct XcdRange { int start, count; };
+__host__ __device__ __forceinline__ XcdRange xcd_range(int total, int xcd) {
+  const int q8 = total >> 3, r8 = total & 7;
+  return {xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8, q8 + (xcd < r8 ? 1 : 0)};
+}
 
 // ---------------------------------------------------------------------------------------------
 // Activation layout: NHWC fp32 ("pixels x channels", channels contiguous) everywhere inside the
@@ -103,6 +124,16 @@ struct ConvArgs {
   const float* in_inv = nullptr;       // split-precision path: [N] per-image 2^-k undoing the input staging factor (launch_act_pow2_scale)
   GnFold gnf;                          // sparse launches (engine.hip gn_params): gn_scale / gn_shift (and a guard table set) are finalised by this launch's own prologue
 };
+// The launch profiler's work of a conv: 2 FLOP per MAC on un-padded channels; bytes = input read once + output written once (+ the residual) +
+// weights once.  (the parity form, taps == 4, reports the algorithmic FLOPs of the conv it replaces: 9 taps at 4 x the pixels on a quarter
+// of its GEMM columns)
+struct ConvWork { double flops, bytes; };
+inline ConvWork conv_work(const ConvArgs& a, int taps) {
+  const double cin = a.cin_real > 0 ? a.cin_real : (a.C0 + a.C1), cout = a.out_nchw ? a.cout_valid : a.Cout;
+  const double px = (double)a.N * a.H * a.W;
+  const double px_in = (double)a.N * ((a.H >> a.up0) * (a.W >> a.up0)) * a.C0 + px * a.C1;
+  return {2.0 * px * (taps == 4 ? 9 : taps) * cin * cout, 4.0 * (px_in + px * cout * (a.res ? 2 : 1) + (double)taps * cin * cout)};
+}
 // One decision per conv launch: plan_conv (conv_plan.hip) picks the kernel and its instantiation, the split-K form, and whether the 2x2 pool and
 // the GroupNorm finalise fold into the launch; launch_conv carries it out.  The engine plans every conv once, in sizing and real passes alike.
 enum ConvKernel : unsigned char { CONV_NONE, CONV_IGEMM, CONV_PIPELINE };  // NONE: per-image weights outside the pipeline's rule

@@ -16,7 +16,6 @@
 // double-buffered [kgroup][cout][4] LDS tile, one tap at a time, prefetched into registers under the MFMAs.
 // Math: v_mfma_f32_32x32x2_f32 (exact fp32, 256 FLOP/clk/CU); each wave holds MT x NT 32x32 accumulators.
 // K order inside a chunk is permuted (lane half h takes k-groups 2j+h) so one b128 read feeds 4 MFMAs.
-#include <atomic>
 
 #include "common.h"
 #include "profiler.h"
@@ -62,12 +61,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
   //      ids are the Cout tiles of one pixel tile, then its spatial neighbours)
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;  // edge tiles of a map that is not a multiple of the tile are masked
   const int n_tiles = a.Cout / C::BN;
-  int logical;
-  {
-    const int id = blockIdx.x, nwg = gridDim.x;
-    const int q = nwg >> 3, rr = nwg & 7, xcd = id & 7;
-    logical = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (id >> 3);
-  }
+  const int logical = xcd_range((int)gridDim.x, (int)blockIdx.x & 7).start + ((int)blockIdx.x >> 3);
   const int n_tile = logical % n_tiles;
   int m_tile = logical / n_tiles;
   const int tx = m_tile % tiles_x;
@@ -258,27 +252,18 @@ template <int TAPS, int TH, int TW, ConvTile T, int KC>
 static int launch_variant(const ConvArgs& a, hipStream_t s) {
   constexpr TileShape t = tile_shape(T);
   using C = Cfg<TAPS, TH, TW, t.wm, t.wn, t.mt, t.nt, KC>;
-  auto kern = conv_igemm_kernel<TAPS, TH, TW, t.wm, t.wn, t.mt, t.nt, KC>;
+  constexpr auto kern = conv_igemm_kernel<TAPS, TH, TW, t.wm, t.wn, t.mt, t.nt, KC>;
   const size_t lds_bytes = (size_t)C::LDS_F4 * sizeof(float4);
-  // the opt-in LDS size is a per-device function attribute: one bit per device ordinal, set idempotently (as in conv_split2.hip)
   const DeviceInfo* di = device_info();
   if (!di) return DRM_ERR_STATE;
-  static std::atomic<uint64_t> attr_mask{0};
-  if (lds_bytes > 48 * 1024 && !(attr_mask.load(std::memory_order_acquire) >> di->ordinal & 1)) {
-    DRM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
-  }
+  DRM_TRY(opt_in_lds<kern>(lds_bytes, di));
   const int groups = (a.N + C::TN - 1) / C::TN;
   const long long blocks = (long long)groups * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW) * (a.Cout / C::BN);
   DRM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv grid size");
   {
-    // algorithmic work: 2 FLOP per MAC on un-padded channels; bytes = input read once + output written once + weights once
-    const double cin = a.cin_real > 0 ? a.cin_real : (a.C0 + a.C1), cout = a.out_nchw ? a.cout_valid : a.Cout;
-    const double px = (double)a.N * a.H * a.W;
-    const double px_in = (double)a.N * ((a.H >> a.up0) * (a.W >> a.up0)) * a.C0 + px * a.C1;
+    const ConvWork work = conv_work(a, TAPS);
     prof_tag(a.N, a.H, a.W, a.C0 + a.C1, a.Cout);
-    ProfScope ps(TAPS == 9 ? PROF_CONV3 : PROF_CONV1, 2.0 * px * TAPS * cin * cout,
-                 4.0 * (px_in + px * cout * (a.res ? 2 : 1) + (double)TAPS * cin * cout), s);
+    ProfScope ps(TAPS == 9 ? PROF_CONV3 : PROF_CONV1, work.flops, work.bytes, s);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, s, a);
   }
   DRM_HIP_CHECK(hipGetLastError());

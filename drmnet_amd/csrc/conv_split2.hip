@@ -22,13 +22,13 @@
 // written); 0 = exact fp32 (v_mfma_f32_32x32x2_f32) -- all on this one pipeline.
 // Split-K (deep, small maps): every split writes its own slab; SK instantiations finish the tile inside the launch (last-arriving workgroup).
 #include <algorithm>
-#include <atomic>
 #include <utility>
 #include <vector>
 #include <cstdio>
 #include <string>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "profiler.h"
 
 // Diagnostic build only (tools/stamp_probe.sh, -DDRM_S2_STAMP, a separate .so): one workgroup records an s_memtime timeline of
@@ -217,52 +217,11 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
 // Activation loads are issued from inline asm as well: a compiler-visible load makes hipcc put s_waitcnt vmcnt(0) in front
 // of its first use, which also drains every LDS-DMA weight group in flight (measured: ~1.2 us stall per 32-channel chunk).
 // The destinations are tied to the counted wait that precedes their first use (tie_regs) -- cdna_hip_programming.md 5.7.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void gload16x2(f32x4& d0, f32x4& d1, const void* p) {
   asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:16" : "=&v"(d0), "=&v"(d1) : "v"(p) : "memory");
 }
 __device__ __forceinline__ void tie_regs(f32x4& x0, f32x4& x1) { asm volatile("" : "+v"(x0), "+v"(x1)::"memory"); }
-// Agent-scope accesses of the fused split-K hand-off (sc1: coherent across the 8 XCD-private L2s by themselves, the way relaxed agent-scope atomics
-// are -- LLVM AMDGPU memory model, gfx942 rows "load / store atomic monotonic agent").  The slabs move only through these, so the hand-off needs
-// ordering (s_waitcnt vmcnt(0) before the ticket) but no L2 write-back / invalidate: MI355X_MICROARCH.md "Valid forms", first row of its table
-// (one lane of each storing workgroup adds to ONE counter after every storing wave's vmcnt(0) wait and a barrier; the workgroup whose add came
-// last loads after a barrier that lane joins; every store and every load of the bytes is a 16-byte global sc1 access).  Checked on this shape
-// of hand-off by tools/probes/sc1_handoff_probe.hip: 0 stale values in 2 x 400 launches with the splits of a tile on one XCD and on different
-// XCDs (plain accesses without the fences: 358 M stale values across XCDs), 9 / 15 us per launch against 33 / 57 us with the fences.
-// (s_nop 1: a store of more than 8 bytes reads its data registers after issue -- the wait states the compiler inserts before it overwrites them
-//  are invisible to it inside asm; without them the next quad transpose corrupted the slab)
-// -DDRM_SK_FENCED=1: the conservative form of the same hand-off, kept compilable for A/Bs and as the switch to throw should a stale slab
-// ever show -- plain slab stores / loads around an agent-scope release fence (one lane, before the ticket) and acquire fences (every wave of the
-// finishing workgroup, after it): the LLVM memory model's documented release / acquire pair instead of per-access sc1 coherence.  19 vs 7 us per
-// hand-off at the 64x64 level of the batch-1 step (profiles/r04_sc1_handoff_probe.txt); tools/skab.sh compares the two builds.
-#ifdef DRM_SK_FENCED
-__device__ __forceinline__ void gstore16_agent(void* p, const f32x4& v) { asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory"); }
-__device__ __forceinline__ void gload16_agent(f32x4& d, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(d) : "v"(p) : "memory"); }
-#else
-__device__ __forceinline__ void gstore16_agent(void* p, const f32x4& v) { asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory"); }
-__device__ __forceinline__ void gload16_agent(f32x4& d, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(d) : "v"(p) : "memory"); }
-#endif
 __device__ __forceinline__ void tie_reg(f32x4& x) { asm volatile("" : "+v"(x)::"memory"); }
-
-// 4 x 4 transpose across the four lanes of a quad: in, lane q holds x_k = M[q][k]; out, lane q holds x_k = M[k][q].
-// Two butterfly stages (lane bit 0 with register pairs (0,1), (2,3); lane bit 1 with pairs (0,2), (1,3)); each moves one register
-// per pair through a DPP quad permute and selects by lane parity.
-template <int CTRL>
-__device__ __forceinline__ float quad_perm(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ void quad_transpose(float& x0, float& x1, float& x2, float& x3, int lane) {
-  const bool b0 = lane & 1, b1 = lane & 2;
-  float t;
-  t = quad_perm<0xB1>(b0 ? x0 : x1);  // [1,0,3,2]
-  if (b0) x0 = t; else x1 = t;
-  t = quad_perm<0xB1>(b0 ? x2 : x3);
-  if (b0) x2 = t; else x3 = t;
-  t = quad_perm<0x4E>(b1 ? x0 : x2);  // [2,3,0,1]
-  if (b1) x0 = t; else x2 = t;
-  t = quad_perm<0x4E>(b1 ? x1 : x3);
-  if (b1) x1 = t; else x3 = t;
-}
 
 template <int... I, typename F>
 __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
@@ -316,9 +275,8 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
   const int n_tiles = a.Cout / C::BN;
   const int total = ((a.N + C::TN - 1) / C::TN) * tiles_y * tiles_x * n_tiles;
   const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-  const int q8 = total >> 3, r8 = total & 7;
-  const int x_start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int x_count = q8 + (xcd < r8 ? 1 : 0);
+  const XcdRange xr = xcd_range(total, xcd);
+  const int x_start = xr.start, x_count = xr.count;
   const int J = ((int)gridDim.x - xcd + 7) >> 3;  // workgroups living on this XCD
   auto decode = [&](int logical) {
     TilePos t;
@@ -796,14 +754,19 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
     };
     // group R-1 steps ahead of tile-local group index gi0: inside this tile, else the matching group of the next tile
     // (else a harmless re-read)
-    auto issue_ahead = [&](int gi0) {
-      int gi = gi0 + (R - 1);
-      long long co0 = cur.wofs;
+    auto group_ahead = [&](int gi0, int& gi, long long& co0) {
+      gi = gi0 + (R - 1);
+      co0 = cur.wofs;
       if (gi >= NGT) {
         gi -= NGT;
         if (gi >= NGT) gi %= NGT;
         co0 = nxt.wofs;
       }
+    };
+    auto issue_ahead = [&](int gi0) {
+      int gi;
+      long long co0;
+      group_ahead(gi0, gi, co0);
       issue_G(gseq, gi, co0);
       ++gseq;
     };
@@ -852,14 +815,9 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
       static_for(std::make_integer_sequence<int, C::NG>{}, [&](auto gc) {
         constexpr int g = decltype(gc)::value;
         constexpr bool last_g = (g == C::NG - 1);
-        // group R-1 steps ahead: inside this tile, else the matching group of the next tile (else a harmless re-read)
-        int d_gi = chunk * C::NG + g + (R - 1);
-        long long d_co0 = cur.wofs;
-        if (d_gi >= NGT) {
-          d_gi -= NGT;
-          if (d_gi >= NGT) d_gi %= NGT;
-          d_co0 = nxt.wofs;
-        }
+        int d_gi;
+        long long d_co0;
+        group_ahead(chunk * C::NG + g, d_gi, d_co0);
         const int d_seq = gseq++;
         const bool a_req = (g == A_G) && a_next;
         // Hook points of a step: 2 per tap (one per 16-channel slab).  The DMA instructions go to the first hook points,
@@ -946,6 +904,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 
     S2_STAMP(9);  // epilogue start
     [[maybe_unused]] bool fused_last = false;  // fused split-K: this workgroup arrived last at its tile and ran the full epilogue
+    constexpr int MT_EPI = (TAPS == 4) ? 0 : MT;  // (the pixel-shuffle epilogue of the parity form follows the loop below; declared ahead of the diagnostic build's `if`)
 #ifdef DRM_S2_STAMP
     // timing experiments of the diagnostic build (tools/epi_cost.sh): stamp_block bit 16 = no output stores, bit 17 = no epilogue at all
     const bool skip_epilogue = a.stamp_block & 0x20000;
@@ -969,7 +928,6 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
     // (i, g).  Loads are issued unconditionally on clamped addresses (batched ahead of the math); stores are predicated
     // and fire-and-forget: they drain while the next tile's main loop runs (they are OLDER than every vector-memory operation
     // the next tile counts, so their number does not enter the counted waits).
-    constexpr int MT_EPI = (TAPS == 4) ? 0 : MT;  // (the pixel-shuffle epilogue of the parity form follows this loop)
 #pragma unroll
     for (int i = 0; i < MT_EPI; ++i) {
       size_t pixb[4];
@@ -1008,7 +966,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
           for (int e = 0; e < 16; ++e) {
             const int g = e >> 2, k = e & 3;
             const bool ok = (okp >> e) & 1u;
-            float v = acc[i][c][e] * ((a.w_inv_img ? a.w_inv_img[nimg[g]] : inv_scale) * (a.in_inv ? a.in_inv[nimg[g]] : 1.0f)) + bias;
+            float v = acc[i][c][e] * epi_scale(a, nimg[g], inv_scale) + bias;  // (the value rule's terms in its order; emb and res only where the pixel exists)
             acc[i][c][e] = 0.f;
             if (!ok) continue;
             const size_t pix = pixb[g] + k;
@@ -1054,8 +1012,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           ev[g] = (a.emb && first) ? a.emb[(size_t)nimg[g] * a.emb_stride + co] : 0.f;
-          // weight and (per image) input staging factors, all 2^-k (attention GEMMs: the "weights" are per image, and in_inv carries alpha)
-          sv[g] = (a.w_inv_img ? a.w_inv_img[nimg[g]] : inv_scale) * (a.in_inv ? a.in_inv[nimg[g]] : 1.0f);
+          sv[g] = epi_scale(a, nimg[g], inv_scale);
         }
 #ifdef DRM_S2_STAMP
         const bool abl_noload = a.stamp_block & 0x200000;  // timing experiments (tools/epi_ablate.sh): no residual loads
@@ -1074,7 +1031,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int g = e >> 2;
-          v[e] = acc[i][c][e] * sv[g] + bias + ev[g] + rv[e];
+          v[e] = epi_value(acc[i][c][e] * sv[g], bias, ev[g], rv[e]);
           acc[i][c][e] = 0.f;  // ready for the next tile
 #ifdef DRM_S2_STAMP
           if (a.stamp_block & 0x100000) continue;  // timing experiment: no statistics arithmetic
@@ -1261,7 +1218,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
               const int g = e >> 2;
-              const float x = v[e] + bias + ev[g] + rv[e];  // (the order of the one-launch epilogue)
+              const float x = epi_value(v[e], bias, ev[g], rv[e]);  // (the slab sum is already scaled)
               v[e] = x;
               if (okg[g]) {
                 if (e < 8) { s0 += x; q0 += x * x; } else { s1 += x; q1 += x * x; }
@@ -1374,7 +1331,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 template <int TAPS, int TH, int TW, int WM, int WN, int MT, int NT, int R, int TPS, int TERMS = 3, bool RAG = false, bool SK = false, bool POOL = false>
 static int launch_s2(const ConvArgs& a, hipStream_t s) {
   using C = S2Cfg<TAPS, TH, TW, WM, WN, MT, NT, R, TPS, TERMS>;
-  auto kern = conv_split2_kernel<TAPS, TH, TW, WM, WN, MT, NT, R, TPS, TERMS, RAG, SK, POOL>;
+  constexpr auto kern = conv_split2_kernel<TAPS, TH, TW, WM, WN, MT, NT, R, TPS, TERMS, RAG, SK, POOL>;
   DRM_REQUIRE(RAG || (a.H % TH == 0 && a.W % TW == 0), "conv tile does not divide the map");
   DRM_REQUIRE(POOL == (a.pool_out != nullptr), "pooled output: only launches plan_conv pools");
   DRM_REQUIRE(!POOL || (a.pool_stat && a.stat_out && a.ksplit <= 1 && !a.out_nchw), "pooled output: needs both statistics tables, no split-K");
@@ -1388,13 +1345,7 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
   static_assert((C::LDS_F4 + (POOL ? C::ST_F4 : 0)) * 16 <= 160 * 1024, "LDS budget");
   const DeviceInfo* di = device_info();  // fails loudly on anything that is not an MI355X-shaped gfx950 (256 CUs, 160 KiB LDS)
   if (!di) return DRM_ERR_STATE;
-  // the opt-in LDS size is a per-device function attribute: one bit per device ordinal, set idempotently (a racing second
-  // thread at worst repeats the call), so the entry points stay re-entrant across streams, threads and devices
-  static std::atomic<uint64_t> attr_mask{0};
-  if (lds_bytes > 48 * 1024 && !(attr_mask.load(std::memory_order_acquire) >> di->ordinal & 1)) {
-    DRM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
-  }
+  DRM_TRY(opt_in_lds<kern>(lds_bytes, di));
   const int groups = (a.N + C::TN - 1) / C::TN;
   const long long tiles = (long long)groups * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW) * (a.Cout / C::BN);
   DRM_REQUIRE(tiles > 0 && tiles < (1ll << 31), "conv grid size");
@@ -1409,9 +1360,6 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
               "split-K launch contract");
   if (tiles < grid || ngt < R - 1 || (TAPS == 1 && ngt < 2) || ks > 1) grid = tiles;  // (a prefetch may only reach into the NEXT tile)
   {
-    const double cin = a.cin_real > 0 ? a.cin_real : (a.C0 + a.C1), cout = a.out_nchw ? a.cout_valid : a.Cout;
-    const double px = (double)a.N * a.H * a.W;
-    const double px_in = (double)a.N * ((a.H >> a.up0) * (a.W >> a.up0)) * a.C0 + px * a.C1;
     prof_tag(a.N, a.H, a.W, a.C0 + a.C1, a.Cout);
     if (prof_enabled()) {  // the instantiation's name as rocprofv3 prints it: per-variant totals next to the per-family ones
       static const std::string vname = [] {
@@ -1423,10 +1371,8 @@ static int launch_s2(const ConvArgs& a, hipStream_t s) {
       prof_variant(vname.c_str());
     }
     DRM_REQUIRE(a.w_img_stride_f4 == 0 || (C::TN == 1 && ks == 1), "per-image weights need one image per tile (H*W a multiple of the 256-pixel tile)");
-    // (the parity form reports the algorithmic FLOPs of the conv it replaces: 9 taps at 4 x the pixels on a quarter of its GEMM columns)
-    constexpr int ALG_TAPS = (TAPS == 4) ? 9 : TAPS;
-    ProfScope ps(a.prof_kind == PROF_KINDS ? -1 : (a.prof_kind >= 0 ? a.prof_kind : (TAPS != 1 ? PROF_CONV3 : PROF_CONV1)), 2.0 * px * ALG_TAPS * cin * cout,
-                 4.0 * (px_in + px * cout * (a.res ? 2 : 1) + (double)TAPS * cin * cout), s);
+    const ConvWork work = conv_work(a, TAPS);
+    ProfScope ps(a.prof_kind == PROF_KINDS ? -1 : (a.prof_kind >= 0 ? a.prof_kind : (TAPS != 1 ? PROF_CONV3 : PROF_CONV1)), work.flops, work.bytes, s);
 #ifdef DRM_S2_STAMP
     // DRM_S2_STAMP_FILE=<path> [DRM_S2_STAMP_BLOCK=<workgroup>] [DRM_S2_STAMP_TILE0=<first recorded tile>]: appends one record
     // per 8-wave launch that has the 7.5 KiB of LDS to spare

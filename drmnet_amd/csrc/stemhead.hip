@@ -12,9 +12,9 @@
 // (The head keeps the generic pipeline kernel: a kernel of its own -- one pixel per lane, exact fp32 FMAs -- measured 0.36 ms against 0.31 ms and
 //  lives in tools/experiments/head_conv_kernel_r5.hip.txt, not in the library.)
 #include <algorithm>
-#include <atomic>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "profiler.h"
 
 namespace drm {
@@ -34,24 +34,6 @@ union ShF4H8 {
   float4 f4;
   sh_f16x8 h8;
 };
-
-template <int DPP_CTRL>
-__device__ __forceinline__ float sh_quad_perm(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), DPP_CTRL, 0xF, 0xF, false));
-}
-// 4 x 4 transpose across the lanes of a quad (conv_split2.hip quad_transpose)
-__device__ __forceinline__ void sh_quad_transpose(float& x0, float& x1, float& x2, float& x3, int lane) {
-  const bool b0 = lane & 1, b1 = lane & 2;
-  float t;
-  t = sh_quad_perm<0xB1>(b0 ? x0 : x1);
-  if (b0) x0 = t; else x1 = t;
-  t = sh_quad_perm<0xB1>(b0 ? x2 : x3);
-  if (b0) x2 = t; else x3 = t;
-  t = sh_quad_perm<0x4E>(b1 ? x0 : x2);
-  if (b1) x0 = t; else x2 = t;
-  t = sh_quad_perm<0x4E>(b1 ? x1 : x3);
-  if (b1) x1 = t; else x3 = t;
-}
 
 // GEMM row of a tile (0 .. 127) -> pixel inside the 8 x 16 tile: 32-row blocks are 4 x 8 patches, so the rows 8g + 4h + k a lane holds of an
 // accumulator block are four consecutive pixels of one image row
@@ -290,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
         const int cq = (wn * 2 + c) * 32 + (r & ~3);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          sh_quad_transpose(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], r);
+          quad_transpose(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], r);
           const int y = ty0 + py0 + g, xx = tx0 + px0 + (r & 3);
           if (y < H && xx < W)
             *reinterpret_cast<float4*>(out + (((size_t)n * H + y) * W + xx) * STEM_COUT + cq) = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
@@ -385,20 +367,15 @@ int launch_stem_conv(const float* x, int Cx, const float* cond, int Cc, const in
   const int grid = (int)std::min<long long>(tiles, 2ll * di->cus);
   prof_tag(N, H, W, Cin, Cout);
   ProfScope ps(PROF_CONV3, 2.0 * N * H * W * 9.0 * Cin * Cout, 4.0 * ((double)N * H * W * (Cin + Cout) + 9.0 * Cin * Cout), s);
-  // one opt-in mask PER kernel variant (all four share a function-pointer type, so a static inside the generic lambda would be shared: ADVICE r5)
-  static std::atomic<uint64_t> attr_masks[4];
-  auto go = [&](auto kern, int variant) -> int {
-    std::atomic<uint64_t>& attr_mask = attr_masks[variant];
-    if (!(attr_mask.load(std::memory_order_acquire) >> di->ordinal & 1)) {
-      DRM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_mask.fetch_or(uint64_t(1) << di->ordinal, std::memory_order_release);
-    }
+  auto go = [&](auto tag) -> int {  // (one opt-in state per kernel variant, though all four share a function type: opt_in_lds)
+    constexpr auto kern = decltype(tag)::kernel;
+    DRM_TRY(opt_in_lds<kern>(lds, di));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, x, Cx, cond, Cc, rows, wimg, bias, out, stat, N, H, W);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;
   };
-  if (Cin == 4) return exact ? go(stem_conv_kernel<4, true>, 0) : go(stem_conv_kernel<4, false>, 1);
-  return exact ? go(stem_conv_kernel<6, true>, 2) : go(stem_conv_kernel<6, false>, 3);
+  if (Cin == 4) return exact ? go(KernelTag<stem_conv_kernel<4, true>>{}) : go(KernelTag<stem_conv_kernel<4, false>>{});
+  return exact ? go(KernelTag<stem_conv_kernel<6, true>>{}) : go(KernelTag<stem_conv_kernel<6, false>>{});
 }
 
 }  // namespace drm
