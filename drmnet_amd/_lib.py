@@ -43,6 +43,7 @@ SYMBOLS = [
     "drm_render_mesh_workspace_bytes", "drm_render_mesh",
     "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed", "drm_render_mesh_lit",
     "drm_mesh_closest_hit", "drm_render_mesh_bounced",
+    "drm_render_normals", "drm_image_from_refmap",
     "drm_obs_forward_process", "drm_diffusion_losses",
 ]
 
@@ -215,7 +216,9 @@ def lib() -> C.CDLL:
     L.drm_mesh_closest_hit.argtypes = [fp, vp, C.c_int64, C.c_int64, vp, fp, fp, vp, vp, fp, C.c_int64, vp]
     L.drm_render_mesh_bounced.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t,
                                           vp, C.c_size_t, i32, vp]
-    L.drm_validation_losses.argtypes = [fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
+    L.drm_render_normals.argtypes = [fp, u8p, i32, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
+    L.drm_image_from_refmap.argtypes = [fp, u8p, i32, i32, fp, u8p, i32, fp, fp, i32, i32, i32, vp]
+    L.drm_validation_losses.argtypes =[fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]
     L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     L.drm_diffusion_losses.argtypes = [fp, fp, fp, vp, fp, fp, i32, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t, fp, fp, vp]

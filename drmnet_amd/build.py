@@ -26,7 +26,7 @@ def units():
     """(source, object name, extra flags) of every object of the library"""
     out = [("conv_split2.hip", f"conv_split2_u{u}.o", [f"-DDRM_S2_UNIT={u}"]) for u in S2_UNITS]
     return out + [(src, src.replace(".hip", ".o"), []) for src in SOURCES]
-HEADERS = ["common.h", "conv_forms.h", "conv_epilogue.h", "gn_fold.h", "engine.h", "samplers.h", "philox.h", "profiler.h", "bvh.h", os.path.join("..", "..", "include", "drmnet_hip.h")]
+HEADERS = ["common.h", "conv_forms.h", "conv_epilogue.h", "gn_fold.h", "engine.h", "samplers.h", "philox.h", "profiler.h", "bvh.h", "normal_map.h", os.path.join("..", "..", "include", "drmnet_hip.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-ffp-contract=off"]
 

@@ -641,6 +641,22 @@ int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_norma
   });
 }
 
+int drm_render_normals(const float* normals, const uint8_t* mask, int Bn, const float* z, const float* envmap, const float* view, float* image,
+                       float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
+                       size_t light_workspace_bytes, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_normals(normals, mask, Bn, z, envmap, view, image, alpha, B, H, W, EH, EW, quad, light_samples, light_workspace,
+                                 light_workspace_bytes, static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_image_from_refmap(const float* refmap, const uint8_t* refmask, int Br, int R, const float* normals, const uint8_t* mask, int Bn, float* image,
+                          float* alpha, int B, int H, int W, void* stream) {
+  return guarded([&]() -> int {
+    return launch_image_from_refmap(refmap, refmask, Br, R, normals, mask, Bn, image, alpha, B, H, W, static_cast<hipStream_t>(stream));
+  });
+}
+
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream) {
   return guarded([&]() -> int { return launch_brdf_eval(z, z_rows, n, v, l, out, (long long)N, static_cast<hipStream_t>(stream)); });
 }

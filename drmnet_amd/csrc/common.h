@@ -207,6 +207,9 @@ size_t refmap_workspace_bytes(long long n, int res, float thr);
 int launch_refmap_mask_make(const float* colors, const float* normals, long long n, int C, int res, float thr, int min_points, float* refmap,
                             unsigned char* refmask, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_erode_mask(const unsigned char* mask, int H, int W, int k, unsigned char* out, hipStream_t s);
+// the inverse of the gather (see drm_image_from_refmap): refmap [Br][3][R][R] read at the normals of normals [Bn][H][W][3]
+int launch_image_from_refmap(const float* refmap, const unsigned char* refmask, int Br, int R, const float* normals, const unsigned char* mask, int Bn,
+                             float* image, float* alpha, int B, int H, int W, hipStream_t s);
 // attention (attn.hip): qkv [N][T][3C] (v thirds = proj_out folded into v: launch_fold_attn_params), x [N][T][C] the block's input
 // -> out = x + softmax(q k^T) v [N][T][C] and out_stat [N][C] += per-channel (sum, sum of squares) of out (zeroed by the caller);
 // scores workspace [group][T][T].
@@ -306,6 +309,10 @@ struct MeshRenderArgs {
   int bounce_quad = 0;
 };
 int launch_render_mesh(const MeshRenderArgs& a, hipStream_t s);
+// a normal map shaded B ways (see drm_render_normals): normals [Bn][H][W][3] in the view frame, mask uint8 [Bn][H][W] or null
+int launch_render_normals(const float* normals, const unsigned char* mask, int Bn, const float* z, const float* env, const float* view, float* image,
+                          float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
+                          size_t light_workspace_bytes, hipStream_t s);
 // validation losses (losses.hip): see drm_validation_losses
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,

@@ -8,10 +8,13 @@
 // verbatim on the neighbouring rows / columns -- and one wave per texel selects the lower median of the colour sums by
 // rank counting.  HBM-bound: 24 B read per pixel, a few atomics, 13 B written per texel.
 //   count -> exclusive scan -> fill -> select      (all on the caller's stream; one host read-back validates capacity)
+//
+// And the scatter direction, reflectance map -> image at a normal map's normals: image_from_refmap_kernel below.
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
+#include "normal_map.h"
 
 namespace drm {
 
@@ -223,6 +226,65 @@ int launch_erode_mask(const unsigned char* mask, int H, int W, int k, unsigned c
     return DRM_OK;
   }
   hipLaunchKernelGGL(erode_mask_kernel, dim3((unsigned)((H * W + 255) / 256)), dim3(256), 0, s, mask, H, W, k, out);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+// The inverse of the gather: the image a normal map would show if the reflectance-map model held exactly (drm_image_from_refmap).  One
+// thread per pixel (b, i, j); normal and mask as in normals_shade_kernel (normal_map_pixel).  The unit normal n is taken to texel
+// coordinates by the inverse of the sensor's parametrisation n = (cos b sin a, sin b, cos b cos a) (render.hip sensor_normal, flip 0):
+//   a = atan2f(n.x, n.z), b = asinf(min(max(n.y, -1), 1));  tj = (a / pi + 0.5) R - 0.5,  ti = (0.5 - b / pi) R - 0.5
+// and the map is read bilinearly over the taps (i0, i1) x (j0, j1) = (floor ti, floor ti + 1) x (floor tj, floor tj + 1), each index
+// clamped to [0, R - 1], with fy = ti - floor ti, fx = tj - floor tj, in this order of additions (fp32, no contraction):
+//   top = (1 - fx) v[i0][j0] + fx v[i0][j1];  bot = (1 - fx) v[i1][j0] + fx v[i1][j1];  value = (1 - fy) top + fy bot.
+// refmask: the pixel is valid iff all four clamped taps are observed, whatever their weights -- a rule of floor ti and floor tj alone.
+__global__ __launch_bounds__(256) void image_from_refmap_kernel(const float* __restrict__ refmap, const unsigned char* __restrict__ refmask, int Br,
+                                                                const float* __restrict__ normals, const unsigned char* __restrict__ mask, int Bn,
+                                                                float* __restrict__ image, float* __restrict__ alpha, int B, int H, int W, int R) {
+  const long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= (long long)B * H * W) return;
+  const size_t plane = (size_t)H * W, texels = (size_t)R * R;
+  const int b = (int)(pix / ((long long)H * W));
+  const size_t at = (size_t)(pix - (long long)b * H * W);
+  V3 n = v3(0.0f, 0.0f, 0.0f);
+  bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);
+  float px[3] = {0.0f, 0.0f, 0.0f};
+  if (drawn) {
+    const float kPi = 3.14159265358979323846f;
+    const float a = atan2f(n.x, n.z), e = asinf(fminf(fmaxf(n.y, -1.0f), 1.0f));
+    const float tj = (a / kPi + 0.5f) * (float)R - 0.5f, ti = (0.5f - e / kPi) * (float)R - 0.5f;
+    const float fj = floorf(tj), fi = floorf(ti);
+    const float fx = tj - fj, fy = ti - fi;
+    const int j0 = min(max((int)fj, 0), R - 1), j1 = min(max((int)fj + 1, 0), R - 1);
+    const int i0 = min(max((int)fi, 0), R - 1), i1 = min(max((int)fi + 1, 0), R - 1);
+    const size_t br = Br == 1 ? 0 : (size_t)b;
+    if (refmask) {
+      const unsigned char* m = refmask + br * texels;
+      drawn = m[(size_t)i0 * R + j0] && m[(size_t)i0 * R + j1] && m[(size_t)i1 * R + j0] && m[(size_t)i1 * R + j1];
+    }
+    if (drawn) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float* v = refmap + (br * 3 + c) * texels;
+        const float top = (1.0f - fx) * v[(size_t)i0 * R + j0] + fx * v[(size_t)i0 * R + j1];
+        const float bot = (1.0f - fx) * v[(size_t)i1 * R + j0] + fx * v[(size_t)i1 * R + j1];
+        px[c] = (1.0f - fy) * top + fy * bot;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) image[((size_t)b * 3 + c) * plane + at] = px[c];
+  if (alpha) alpha[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
+}
+
+int launch_image_from_refmap(const float* refmap, const unsigned char* refmask, int Br, int R, const float* normals, const unsigned char* mask, int Bn,
+                             float* image, float* alpha, int B, int H, int W, hipStream_t s) {
+  DRM_REQUIRE(refmap && normals && image, "image_from_refmap: null pointer");
+  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && R >= 1 && R <= 8192 && (Bn == 1 || Bn == B) && (Br == 1 || Br == B),
+              "image_from_refmap: 1 <= B <= 65535 rows, H and W in [1, 4096], 1 <= R <= 8192, Bn and Br = 1 or B");
+  const long long blocks = ((long long)B * H * W + 255) / 256;
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "image_from_refmap: B H W too large for one launch");
+  hipLaunchKernelGGL(image_from_refmap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, refmap, refmask, Br, normals, mask, Bn, image, alpha, B, H, W, R);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -27,6 +27,9 @@
 // there is a BVH.  drm_render_mesh_bounced runs mesh_shade_kernel<VIEW, true, false, true>: an occluded direction reads the radiance its
 // closest hit reflects back under direct light (one bounce; see Bounced).
 //
+// Object images of a normal map (drm_render_normals): normals_shade_kernel runs the same per-normal body on the normals of a normal map,
+// the input estimate's user has, with Plain or LightSampled: no mesh, no shadows.
+//
 // One statement of the quadrature: normal_lane_sum builds both lobes once and accumulates each in one place; what differs between the
 // renders is its technique parameter (Plain, LightSampled, Occluded, LitOccluded, Bounced: see "techniques"), which decides per lobe sample whether
 // it counts, what radiance it reads and what scales its weight.  Every texel fetch is env_taps + bilerp.  Plain holds nothing: the
@@ -40,6 +43,7 @@
 
 #include "bvh.h"
 #include "common.h"
+#include "normal_map.h"
 
 namespace drm {
 
@@ -48,11 +52,7 @@ namespace {
 constexpr float kPi = 3.14159265358979323846f;
 constexpr int kRenderWaves = 4;  // pixels (one wave each) per 256-thread workgroup
 
-struct V3 {
-  float x, y, z;
-};
-__host__ __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__host__ __device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+// (V3, v3, dot3 and unit_or_zero: normal_map.h)
 __host__ __device__ __forceinline__ V3 axpy(float s, V3 a, V3 b) { return v3(s * a.x + b.x, s * a.y + b.y, s * a.z + b.z); }
 // |a x b|^2: sin^2 of the angle between unit vectors without the cancellation of 1 - cos^2 near 0
 __host__ __device__ __forceinline__ float cross_sq(V3 a, V3 b) {
@@ -60,12 +60,6 @@ __host__ __device__ __forceinline__ float cross_sq(V3 a, V3 b) {
   return cx * cx + cy * cy + cz * cz;
 }
 __host__ __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-// the unit vector along n, or zero where its length is zero or NaN (a NaN fails the comparison)
-__host__ __device__ __forceinline__ V3 unit_or_zero(V3 n) {
-  const float len2 = dot3(n, n);
-  const float ninv = len2 > 0.0f ? 1.0f / sqrtf(len2) : 0.0f;
-  return len2 > 0.0f ? v3(n.x * ninv, n.y * ninv, n.z * ninv) : v3(0.0f, 0.0f, 0.0f);
-}
 // the barycentric mix (1 - u - v, u, v) of three vertex normals, not normalised: the shading normal of a point of a face, in object space
 __host__ __device__ __forceinline__ V3 mix_normals(const float* n0, const float* n1, const float* n2, float u, float v) {
   const float w0 = 1.0f - u - v;
@@ -875,6 +869,49 @@ __global__ __launch_bounds__(256) void brdf_eval_kernel(const float* __restrict_
   }
 }
 
+// Shading of a normal map (drm_render_normals): the image estimate's user has, normal map -> image, with no mesh behind it.  grid:
+// ceil(B H W / 4) workgroups of 4 waves; wave = pixel (row b, i, j), lit by env[b] and seen through view[b] (which turns the environment
+// lookups only: the normals are already in the view frame).  The wave reads the normal of map bn = (Bn == 1 ? 0 : b) through one address (a
+// broadcast), normalises it (normal_map_pixel) and, where the pixel is drawn, runs the sphere's normal_lane_sum once: the Q x Q grids,
+// per-lane order, butterfly and finish of refmap_render_kernel with S = 1, so a pixel is shaded exactly as the sphere point and the mesh
+// hit with that normal.  A pixel that is not drawn gets image 0 and alpha 0 (wave-uniform).  LIGHT: lws is the light workspace of the B
+// maps (M samples each), as in refmap_render_kernel.  No LDS, no scratch, no atomics.
+template <bool VIEW, bool LIGHT>
+__global__ __launch_bounds__(256) void normals_shade_kernel(const float* __restrict__ normals, const unsigned char* __restrict__ mask, int Bn,
+                                                            const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
+                                                            float* __restrict__ image, float* __restrict__ alpha, int B, int H, int W, int EH, int EW, int Q,
+                                                            const char* __restrict__ lws, int M) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
+  const size_t plane = (size_t)H * W;
+  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
+  const size_t at = (size_t)(pix - (long long)b * H * W);
+  V3 n = v3(0.0f, 0.0f, 0.0f);
+  const bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);  // (wave-uniform: every lane read the same pixel)
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  std::conditional_t<LIGHT, LightSampled, Plain> tech;
+  if constexpr (LIGHT) tech = light_sampled(light_table(lws, b, EH, M), EH, Q);
+  if (drawn) {
+    const Principled p = principled(z + 6 * (size_t)b);
+    const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+    const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+    normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
+    wave_sum3(acc);
+    if constexpr (LIGHT) wave_sum3(tech.accL);
+  }
+  if (lane == 0) {
+    const float scale = 1.0f / (float)(Q * Q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float px = acc[c] * scale;
+      if constexpr (LIGHT) px = px + tech.accL[c];
+      image[((size_t)b * 3 + c) * plane + at] = drawn ? px : 0.0f;
+    }
+    if (alpha) alpha[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
+  }
+}
+
 }  // namespace
 
 // What every launch of a pixel kernel checks of its quadrature and environment (`who` names the entry in the message; subpixel_max = 0: the
@@ -991,6 +1028,37 @@ int launch_render_mesh(const MeshRenderArgs& a, hipStream_t s) {
   };
   if (a.view) shade(std::true_type{});
   else shade(std::false_type{});
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+// A normal map shaded B ways (see drm_render_normals): the checks launch_render_mesh makes of what the two share; light_samples > 0 under
+// a map builds the tables as the lit renders do and shades with them.
+int launch_render_normals(const float* normals, const unsigned char* mask, int Bn, const float* z, const float* env, const float* view, float* image,
+                          float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
+                          size_t light_workspace_bytes, hipStream_t s) {
+  DRM_REQUIRE(normals && z && image, "render_normals: null pointer");
+  DRM_REQUIRE(light_samples >= 0, "render_normals: light_samples >= 0");
+  const bool lit = light_samples > 0 && env;
+  DRM_TRY(check_quadrature("render_normals", quad, 1, 0, env, EH, EW));
+  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
+              "render_normals: 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
+  const long long blocks = pixel_blocks((long long)B * H * W);
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_normals: B H W too large for one launch");
+  char* lws = lit ? static_cast<char*>(light_workspace) : nullptr;
+  if (lit) {
+    DRM_REQUIRE(light_samples_ok(light_samples), "render_normals: light_samples must be 0 or a power of two in [64, 65536]");
+    const std::string fault = light_workspace_fault("render_normals: light_workspace", light_workspace, light_workspace_bytes,
+                                                    render_light_workspace_bytes(B, EH, EW, light_samples));
+    DRM_REQUIRE(fault.empty(), fault);
+    launch_light_tables(env, lws, B, EH, EW, light_samples, s);
+  }
+  // (a view only turns the environment: under a white one it changes nothing and is not read)
+  const bool with_view = env && view;
+  const auto kernel = lit ? (with_view ? normals_shade_kernel<true, true> : normals_shade_kernel<false, true>)
+                          : (with_view ? normals_shade_kernel<true, false> : normals_shade_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, z, env, with_view ? view : nullptr, image, alpha, B, H,
+                     W, env ? EH : 1, env ? EW : 1, quad, lws, lit ? light_samples : 0);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -7,7 +7,9 @@
 mask erosion + refmap_mask_make (csrc/refmap.hip), ObsNet DDIM inpainting and the DRMNet reverse loop (device loops behind
 the C ABI).  The keyword-only `hooks` let tests inject the random draws the reference takes from torch's global generator.
 `main` writes the reference's two images (sample_env.png, and sample_brdf.png through visualize_bsdf on csrc/render.hip) and also saves
-and prints the BRDF parameters.
+and prints the BRDF parameters.  With `--rerender` (off by default) it also shades the estimate back onto the input's normal map
+(drmnet_amd/relight.py) and reports how far that image, and the image ObsNet's inpainted reflectance map stands for, are from the input:
+sample_rerender.exr / .png, sample_refmap_image.exr, sample_errors.json.
 """
 from __future__ import annotations
 
@@ -117,13 +119,9 @@ def save_brdf_png(path, zK, brdf_param_names) -> None:
     file_io.save_png(path, hdr2ldr(fig), mask=mask)
 
 
-def main(argv=None):
+def parser() -> argparse.ArgumentParser:
     # Provenance: this entry point deliberately mirrors the reference's command line (scripts/estimate.py:105-142: the same options, defaults, mask
     # rule and output files -- SURVEY 2 #20 keeps it as the user-facing surface); everything it calls is this package's own code over the HIP library.
-    from . import file_io
-    from .config import instantiate_from_config, load_config
-    from .transform import hdr2ldr
-
     parser = argparse.ArgumentParser()
     parser.add_argument("--input_img", type=Path, help="The path of HDR image for an object (.exr)")
     parser.add_argument("--input_normal", type=Path, help="The path of normal map for an object (.npy)")
@@ -131,14 +129,49 @@ def main(argv=None):
     parser.add_argument("--obsnet_base_path", type=Path, help="the config path for obsnet", default=Path("./configs/obsnet/eval_obsnet.yaml"))
     parser.add_argument("--drmnet_base_path", type=Path, help="the config path for drmnet", default=Path("./configs/drmnet/eval_drmnet.yaml"))
     parser.add_argument("--output_dir", type=Path, help="the output directory", default=Path("./outputs/"))
-    args = parser.parse_args(argv)
+    parser.add_argument("--rerender", action="store_true",
+                        help="also re-render the estimate on the input's normal map and report how far it is from the input image (default: off)")
+    return parser
 
-    obsnet_base_config = load_config(args.obsnet_base_path)
-    obsnet_model = instantiate_from_config(obsnet_base_config["model"]).cuda()
-    obsnet_model.ds = instantiate_from_config(obsnet_base_config["data"]["params"]["predict"])
-    drmnet_base_config = load_config(args.drmnet_base_path)
-    drmnet_model = instantiate_from_config(drmnet_base_config["model"]).cuda()
-    drmnet_model.ds = instantiate_from_config(drmnet_base_config["data"]["params"]["predict"])
+
+def write_rerender(output_dir: Path, drmnet_model, Lr0_sample, zK_est, inpaint, input_img, input_normal, mask) -> dict:
+    """What ``--rerender`` adds: sample_rerender.exr / .png, the estimate shaded on the input's normal map (relight.rerender);
+    sample_refmap_image.exr, ObsNet's inpainted reflectance map read at every pixel's normal (relight.image_from_refmap); and
+    sample_errors.json, both against the input image on the un-eroded mask: "estimate" is the whole loop, "inpainted_refmap" what the
+    reflectance-map model itself cannot explain (shadows, interreflection, a BRDF that varies), before any estimate is made."""
+    import json
+
+    from . import file_io
+    from .relight import image_errors, image_from_refmap, rerender, save_image
+
+    image, _ = rerender(drmnet_model, Lr0_sample, zK_est, input_normal, mask)
+    save_image(output_dir / "sample_rerender", image[0], mask)
+    lookup, _ = image_from_refmap(inpaint, input_normal, mask=mask)
+    file_io.save_exr(output_dir / "sample_refmap_image.exr", lookup[0].permute(1, 2, 0))
+    errors = {"estimate": image_errors(image[0].permute(1, 2, 0), input_img, mask),
+              "inpainted_refmap": image_errors(lookup[0].permute(1, 2, 0), input_img, mask)}
+    (output_dir / "sample_errors.json").write_text(json.dumps(errors, indent=1) + "\n")
+    return errors
+
+
+def main(argv=None, *, models=None, hooks: Optional[dict] = None):
+    """``models`` = (DRMNet_model, ObsNet_model), already on the GPU with their ``ds``, stands in for the two configs, and ``hooks`` are
+    ``estimate``'s: tests run the command line on small networks with injected draws."""
+    from . import file_io
+    from .config import instantiate_from_config, load_config
+    from .transform import hdr2ldr
+
+    args = parser().parse_args(argv)
+
+    if models is not None:
+        drmnet_model, obsnet_model = models
+    else:
+        obsnet_base_config = load_config(args.obsnet_base_path)
+        obsnet_model = instantiate_from_config(obsnet_base_config["model"]).cuda()
+        obsnet_model.ds = instantiate_from_config(obsnet_base_config["data"]["params"]["predict"])
+        drmnet_base_config = load_config(args.drmnet_base_path)
+        drmnet_model = instantiate_from_config(drmnet_base_config["model"]).cuda()
+        drmnet_model.ds = instantiate_from_config(drmnet_base_config["data"]["params"]["predict"])
 
     input_img = file_io.load_exr(args.input_img, as_torch=True).cuda()
     input_normal = torch.from_numpy(np.load(args.input_normal)).cuda()
@@ -151,13 +184,19 @@ def main(argv=None):
     else:
         mask = normal_mask
 
-    Lr0_sample, zK_est = estimate(drmnet_model, obsnet_model, input_img, input_normal, mask)
+    hooks = dict(hooks or {})
+    if args.rerender:
+        hooks.setdefault("stages", {})
+    Lr0_sample, zK_est = estimate(drmnet_model, obsnet_model, input_img, input_normal, mask, hooks=hooks)
     envmap_est = drmnet_model.r0toenvmap(Lr0_sample[None], (drmnet_model.image_size, drmnet_model.image_size * 2))[0]  # [H, W, 3]
     args.output_dir.mkdir(exist_ok=True)
     file_io.save_png(args.output_dir / "sample_env.png", hdr2ldr(envmap_est.cpu().numpy()))
     save_brdf_png(args.output_dir / "sample_brdf.png", zK_est, drmnet_model.brdf_param_names)
     np.save(args.output_dir / "sample_brdf.npy", zK_est.cpu().numpy())
     print("estimated BRDF parameters", dict(zip(drmnet_model.brdf_param_names, zK_est.tolist())))
+    if args.rerender:
+        errors = write_rerender(args.output_dir, drmnet_model, Lr0_sample, zK_est, hooks["stages"]["inpaint"], input_img, input_normal, mask)
+        print("re-rendered estimate against the input image", errors)
 
 
 if __name__ == "__main__":

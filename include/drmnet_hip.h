@@ -545,6 +545,43 @@ int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_n
                             const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
                             int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
                             void* stream);
+/* Object images from a normal map: the forward model pointed at the inputs of the estimate (an object image, its normal map, a mask), with
+ * no mesh behind it.  The two entries complement MitsubaOrthoRenderer (utils/mitsuba3_utils.py:433-564), which needs the mesh, and
+ * DRMNet.reconstruct (models/drmnet.py:943-953), which renders the estimate back onto the sphere only.  Additive: the ABI version is unchanged.
+ *   normals [Bn][H][W][3]: channel-last, as normal.npy holds them, in the view frame (right, up, back); mask [Bn][H][W] uint8 or NULL;
+ *   Bn = 1 (one normal map for all B rows: one object relit B ways) or B.  n = the normal divided by its length (any length is taken).
+ *   A pixel is not drawn -- image 0, alpha 0 -- where the mask is 0, where the normal is zero or has a NaN or infinite component, and
+ *   where n.z <= 0 (it does not face the viewer at +z).  image [B][3][H][W]; alpha [B][H][W], 1.0 where drawn, may be NULL.
+ *   Limits: 1 <= B <= 65535, H and W in [1, 4096].
+ * drm_render_normals (csrc/render.hip, normals_shade_kernel): every drawn pixel is the radiance its normal reflects toward +z under row b's
+ *   BSDF z[b] (z [B][6]) and envmap[b] ([B][EH][EW][3] or NULL: white), exactly as drm_render_refmap_views shades the sphere point and
+ *   drm_render_mesh the mesh hit with that normal: one wave per pixel, the same quad x quad grids, per-lane order and butterfly, subpixel = 1.
+ *   view [B][9] or NULL: the rotations of drm_render_refmap_views.  They turn the environment lookups only (a lobe direction l is looked up
+ *   at Rot l); the normals are already in the view frame.  Under a NULL map the view is not read.
+ *   light_samples > 0 with a map: the light samples of drm_render_refmap_lit (the same tables, built by the same three launches, the same
+ *   estimator with subpixel = 1) on light_workspace, at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device
+ *   memory, 8-byte aligned.  light_samples = 0, or envmap == NULL, makes exactly the launch without them (the workspace is not read).
+ *   Bitwise reproducible; a call of B rows equals its rows alone, and Bn = 1 equals the normal map repeated B times.
+ *   DRM_ERR_INVALID for Bn outside {1, B}, sizes outside the limits, quad outside [1, 1024], a bad light_samples, or a missing, misaligned
+ *   or short light workspace: nothing is launched.
+ * drm_image_from_refmap (csrc/refmap.hip, image_from_refmap_kernel): every drawn pixel reads a given reflectance map at its normal -- what
+ *   the image would be if the reflectance-map model held exactly; the inverse of drm_refmap_mask_make's gather.  One thread per pixel.
+ *   refmap [Br][3][R][R] channel-first, as drm_render_refmap writes it and the networks return it; refmask [Br][R][R] uint8 or NULL;
+ *   Br = 1 or B; 1 <= R <= 8192.
+ *   Texel coordinates: the inverse of the sensor's n = (cos b sin a, sin b, cos b cos a) (drm_render_refmap, flip = 0), which is also the
+ *   parametrisation of drm_refmap_mask_make (theta from +y, phi = atan2(n.z, -n.x)):  a = atan2f(n.x, n.z), b = asinf(n.y) (n.y clamped to
+ *   [-1, 1]);  tj = (a / pi + 0.5) R - 0.5, ti = (0.5 - b / pi) R - 0.5: texel (i, j)'s centre maps to (ti, tj) = (i, j).
+ *   Bilinear over the taps (i0, i1) x (j0, j1) = (floor ti, floor ti + 1) x (floor tj, floor tj + 1), every index clamped to [0, R - 1], with
+ *   fy = ti - floor ti, fx = tj - floor tj, added in this order (fp32, no contraction):
+ *     top = (1 - fx) v[i0][j0] + fx v[i0][j1];  bot = (1 - fx) v[i1][j0] + fx v[i1][j1];  value = (1 - fy) top + fy bot.
+ *   With a refmask a pixel is drawn only if all four clamped taps are observed (non-zero), whatever their weights: the rule depends on
+ *   floor ti and floor tj alone, so it changes only where a coordinate crosses an integer.
+ *   DRM_ERR_INVALID for Bn or Br outside {1, B} or sizes outside the limits: nothing is launched. */
+int drm_render_normals(const float* normals, const uint8_t* mask, int Bn, const float* z, const float* envmap, const float* view, float* image,
+                       float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
+                       size_t light_workspace_bytes, void* stream);
+int drm_image_from_refmap(const float* refmap, const uint8_t* refmask, int Br, int R, const float* normals, const uint8_t* mask, int Bn, float* image,
+                          float* alpha, int B, int H, int W, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */

@@ -5,7 +5,7 @@
 
 OLD / NEW: a library (libdrmnet_hip.so), an object file, or a directory of objects (csrc/_obj).  Every device code object inside them is
 disassembled with the ROCm llvm-objdump; a kernel is IDENTICAL when its whole instruction text (mnemonics, registers, immediates, branch
-offsets) is the same on both sides.  For a kernel that differs: instructions on each side, and VGPRs, AGPRs, scratch bytes and the waves
+offsets) is the same on both sides; the padding between its last instruction and the next symbol is not part of it.  For a kernel that differs: instructions on each side, and VGPRs, AGPRs, scratch bytes and the waves
 per SIMD the register count allows, from the code object's metadata.  Exit status 1 when anything differs or exists on one side only.
 """
 from __future__ import annotations
@@ -82,6 +82,11 @@ def kernels(path: str):
                         sym = None
                 elif sym and line.startswith("\t"):
                     res[sym][0].append(line.split("//")[0].strip())
+    for ins, _ in res.values():
+        # what follows a kernel's last instruction is the section's padding up to the next symbol's alignment (s_nop, or zero bytes that
+        # objdump prints as "..."): it belongs to the layout, which moves when a kernel is added after this one, not to the kernel
+        while ins and ins[-1] in ("s_nop 0", "..."):
+            ins.pop()
     return res
 
 
