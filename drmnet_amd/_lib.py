@@ -44,6 +44,7 @@ SYMBOLS = [
     "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed", "drm_render_mesh_lit",
     "drm_mesh_closest_hit", "drm_render_mesh_bounced",
     "drm_render_normals", "drm_image_from_refmap",
+    "drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap_table", "drm_render_normals_table",
     "drm_obs_forward_process", "drm_diffusion_losses",
 ]
 
@@ -218,6 +219,10 @@ def lib() -> C.CDLL:
                                           vp, C.c_size_t, i32, vp]
     L.drm_render_normals.argtypes = [fp, u8p, i32, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
     L.drm_image_from_refmap.argtypes = [fp, u8p, i32, i32, fp, u8p, i32, fp, fp, i32, i32, i32, vp]
+    L.drm_brdf_to_merl.argtypes = [fp, i32, fp, vp]
+    L.drm_merl_eval.argtypes = [fp, i32, vp, fp, fp, fp, fp, C.c_int64, i32, vp]
+    L.drm_render_refmap_table.argtypes = [fp, i32, vp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_render_normals_table.argtypes = [fp, u8p, i32, fp, i32, vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.drm_validation_losses.argtypes =[fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]
     L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]

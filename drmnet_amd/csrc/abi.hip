@@ -661,6 +661,34 @@ int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, co
   return guarded([&]() -> int { return launch_brdf_eval(z, z_rows, n, v, l, out, (long long)N, static_cast<hipStream_t>(stream)); });
 }
 
+// ------------------------------------------------------------------------------------------------ measured BRDFs (brdf_table.hip)
+
+int drm_brdf_to_merl(const float* z, int rows, float* tables_out, void* stream) {
+  return guarded([&]() -> int { return launch_brdf_to_merl(z, rows, tables_out, static_cast<hipStream_t>(stream)); });
+}
+
+int drm_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, int64_t N, int linear,
+                  void* stream) {
+  return guarded([&]() -> int { return launch_merl_eval(tables, NT, table_of, n, v, l, out, (long long)N, linear, static_cast<hipStream_t>(stream)); });
+}
+
+int drm_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* envmap, const float* view, float* out,
+                            int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_refmap_table(tables, NT, table_of, alpha, envmap, view, out, B, R, EH, EW, quad, subpixel, flip, linear,
+                                      static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_render_normals_table(const float* normals, const uint8_t* mask, int Bn, const float* tables, int NT, const int32_t* table_of, const float* alpha,
+                             const float* envmap, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH, int EW, int quad,
+                             int linear, void* stream) {
+  return guarded([&]() -> int {
+    return launch_render_normals_table(normals, mask, Bn, tables, NT, table_of, alpha, envmap, view, image, alpha_out, B, H, W, EH, EW, quad, linear,
+                                       static_cast<hipStream_t>(stream));
+  });
+}
+
 // ------------------------------------------------------------------------------------------------ validation losses (losses.hip)
 
 int drm_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,

@@ -1,0 +1,370 @@
+// Measured BRDFs: a material given as a MERL table instead of a principled row.  Replaces, on the inference side (paths relative to the
+// reference root):
+//   bsdf_to_merl (a BSDF sampled on the MERL grid)                    utils/mitsuba3_utils.py:602-638
+//   eval_bsdf / visualize_bsdf for a measured material               utils/mitsuba3_utils.py:641-690
+//   MitsubaRefMapRenderer.rendering with a measured BSDF              utils/mitsuba3_utils.py:324-430
+// A table is [90][90][180] entries over (theta_h, theta_d, phi_d) of Rusinkiewicz's half-vector parametrisation, node (i, j, k) standing for
+// theta_h = (i / 90)^2 pi / 2, theta_d = j pi / 180, phi_d = k pi / 180.  On the device an entry is one float4 (r, g, b, 0), so a lookup
+// corner is one 16-byte load; an entry without a measurement (below the horizon) is (-1, -1, -1, 0).  One table is 23 MB: it is read from
+// memory (the Infinity Cache holds it), never staged in LDS.
+//
+// Stated once here: table_coords (the coordinates of a direction pair, fp32 in the renders and fp64 in drm_merl_eval), table_lookup (both
+// modes) and table_lane_sum, the per-normal body of both renders.  A table has no analytic lobe, so table_lane_sum cannot split the
+// integrand as normal_lane_sum does: both of its sample sets -- the Q x Q grid mapped to the GGX visible normals of the table's proxy
+// roughness alpha, and the same grid mapped to cosine-weighted directions, exactly normal_lane_sum's two constructions -- estimate the whole
+// integrand L f (n.l), combined with the balance heuristic: a sample l of either set adds L(l) f(n, v, l) (n.l) / (Q^2 (p_s(l) + p_d(l))),
+// p_s = G1(v) D(h) / (4 n.v) at h = normalize(v + l), p_d = (n.l) / pi.  The weights of a direction sum to one, so the rule is consistent
+// for any alpha; alpha only decides where the accuracy goes.  One wave owns one pixel, its lanes split the grid, keep their partial sums in a
+// fixed order and meet in wave_sum3: bitwise reproducible, no atomics, no LDS.
+#include <vector>
+
+#include "common.h"
+#include "normal_map.h"
+#include "render_shared.h"
+
+namespace drm {
+
+namespace {
+
+constexpr int kNH = 90, kND = 90, kNP = 180;
+constexpr long long kTableEntries = (long long)kNH * kND * kNP;  // float4 each
+constexpr double kPi64 = 3.14159265358979323846;
+constexpr double kSnap = 1e-12;  // a cosine of the export grid below this is the rounding of an exact zero (theta_h + theta_d = pi / 2, phi_d = 0)
+
+// The continuous table coordinates x = (90 sqrt(theta_h / (pi / 2)), 90 theta_d / (pi / 2), 180 phi_d / pi) of unit n, v (toward the
+// viewer) and l (toward the light): h = normalize(v + l), theta_h = atan2(|n x h|, n.h), theta_d = atan2(|l x h|, l.h) (never acos of a dot
+// product near 1), and MERL's azimuth: in the half-vector frame the normal lies at azimuth pi, x_h = -normalize(n - (n.h) h), y_h = h x x_h,
+// phi_d = atan2(v.y_h, v.x_h) mod pi (reciprocity gives the other half); 0 where |n - (n.h) h| < 1e-6.
+template <typename T>
+__device__ __forceinline__ void table_coords(const T* n, const T* v, const T* l, T x[3]) {
+  const T pi = T(kPi64);
+  T h[3] = {v[0] + l[0], v[1] + l[1], v[2] + l[2]};
+  const T hl = sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+  h[0] = h[0] / hl; h[1] = h[1] / hl; h[2] = h[2] / hl;
+  const T nh = n[0] * h[0] + n[1] * h[1] + n[2] * h[2], lh = l[0] * h[0] + l[1] * h[1] + l[2] * h[2];
+  T cx = n[1] * h[2] - n[2] * h[1], cy = n[2] * h[0] - n[0] * h[2], cz = n[0] * h[1] - n[1] * h[0];
+  const T th = atan2(sqrt(cx * cx + cy * cy + cz * cz), nh);
+  cx = l[1] * h[2] - l[2] * h[1]; cy = l[2] * h[0] - l[0] * h[2]; cz = l[0] * h[1] - l[1] * h[0];
+  const T td = atan2(sqrt(cx * cx + cy * cy + cz * cz), lh);
+  const T p[3] = {n[0] - nh * h[0], n[1] - nh * h[1], n[2] - nh * h[2]};
+  const T pl = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+  T ph = T(0);
+  if (pl >= T(1e-6)) {
+    const T xh[3] = {-p[0] / pl, -p[1] / pl, -p[2] / pl};
+    const T yh[3] = {h[1] * xh[2] - h[2] * xh[1], h[2] * xh[0] - h[0] * xh[2], h[0] * xh[1] - h[1] * xh[0]};
+    ph = atan2(v[0] * yh[0] + v[1] * yh[1] + v[2] * yh[2], v[0] * xh[0] + v[1] * xh[1] + v[2] * xh[2]);
+    if (ph < T(0)) ph = ph + pi;
+    if (ph >= pi) ph = ph - pi;
+  }
+  x[0] = T(90) * sqrt(th / (pi / T(2)));
+  x[1] = T(90) * td / (pi / T(2));
+  x[2] = T(180) * ph / pi;
+}
+
+__device__ __forceinline__ int clampi(int a, int lo, int hi) { return a < lo ? lo : (a > hi ? hi : a); }
+__device__ __forceinline__ size_t entry_at(int i, int j, int k) { return ((size_t)i * kND + j) * kNP + k; }
+
+// f_table at the coordinates x.  nearest (the MERL distribution reader's rule): floor, clamp to [0, 89] x [0, 89] x [0, 179], a negative
+// entry reads 0.  linear: trilinear between floor and floor + 1, clamped at 89 in theta_h and theta_d and wrapping 179 -> 0 in phi_d; a
+// corner whose entry is negative is dropped and the remaining weights renormalised, 0 where all eight are.  Every index is clamped after
+// the conversion, so a NaN coordinate reads inside the table too.  The eight corner loads are issued together.
+template <typename T>
+__device__ __forceinline__ void table_lookup(const float4* __restrict__ tab, const T x[3], int linear, T f[3]) {
+  const T fh = floor(x[0]), fd = floor(x[1]), fp = floor(x[2]);
+  const int ih = (int)fh, id = (int)fd, ip = (int)fp;
+  if (!linear) {
+    const float4 e = tab[entry_at(clampi(ih, 0, kNH - 1), clampi(id, 0, kND - 1), clampi(ip, 0, kNP - 1))];
+    const bool ok = !(e.x < 0.0f);
+    f[0] = ok ? T(e.x) : T(0);
+    f[1] = ok ? T(e.y) : T(0);
+    f[2] = ok ? T(e.z) : T(0);
+    return;
+  }
+  const int i0 = clampi(ih, 0, kNH - 1), i1 = clampi(ih + 1, 0, kNH - 1);
+  const int j0 = clampi(id, 0, kND - 1), j1 = clampi(id + 1, 0, kND - 1);
+  int k0 = clampi(ip, 0, 2 * kNP - 1) % kNP;
+  const int k1 = k0 + 1 == kNP ? 0 : k0 + 1;
+  float4 e[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) e[c] = tab[entry_at(c & 4 ? i1 : i0, c & 2 ? j1 : j0, c & 1 ? k1 : k0)];
+  const T th = x[0] - fh, td = x[1] - fd, tp = x[2] - fp;
+  T num[3] = {T(0), T(0), T(0)}, den = T(0);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const T w = e[c].x < 0.0f ? T(0) : (c & 4 ? th : T(1) - th) * (c & 2 ? td : T(1) - td) * (c & 1 ? tp : T(1) - tp);
+    num[0] += w * T(e[c].x);
+    num[1] += w * T(e[c].y);
+    num[2] += w * T(e[c].z);
+    den += w;
+  }
+  const bool ok = den > T(0);
+  f[0] = ok ? num[0] / den : T(0);
+  f[1] = ok ? num[1] / den : T(0);
+  f[2] = ok ? num[2] / den : T(0);
+}
+
+// one thread per entry of every row's table: the half-vector frame has h = +z and n = (-sin theta_h, 0, cos theta_h); the viewer is
+// wo = (sin theta_d cos phi_d, sin theta_d sin phi_d, cos theta_d), the light wi = wo (-1, -1, 1); entry = principled_eval / (n.wi) in
+// fp64; -1 where n.wo < 0 or n.wi < 0, 0 where a cosine is exactly 0 (kSnap).
+__global__ __launch_bounds__(256) void brdf_to_merl_kernel(const float* __restrict__ z, float4* __restrict__ out, long long total) {
+  for (long long at = (long long)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += (long long)gridDim.x * blockDim.x) {
+    const long long row = at / kTableEntries;
+    const int rem = (int)(at - row * kTableEntries);
+    const int i = rem / (kND * kNP), j = (rem / kNP) % kND, k = rem % kNP;
+    const double t = (double)i / 90.0;
+    const double th = t * t * (kPi64 / 2), td = (double)j * (kPi64 / 180), pd = (double)k * (kPi64 / 180);
+    const double n[3] = {-sin(th), 0.0, cos(th)};
+    const double wo[3] = {sin(td) * cos(pd), sin(td) * sin(pd), cos(td)};
+    const double wi[3] = {-wo[0], -wo[1], wo[2]};
+    double co = n[0] * wo[0] + n[1] * wo[1] + n[2] * wo[2], ci = n[0] * wi[0] + n[1] * wi[1] + n[2] * wi[2];
+    if (fabs(co) < kSnap) co = 0.0;
+    if (fabs(ci) < kSnap) ci = 0.0;
+    float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (co < 0.0 || ci < 0.0) {
+      e.x = e.y = e.z = -1.0f;
+    } else if (co > 0.0 && ci > 0.0) {
+      const Principled p = principled(z + 6 * row);
+      float f[3];
+      principled_eval(p, n, wo, wi, f);
+      e.x = (float)((double)f[0] / ci);
+      e.y = (float)((double)f[1] / ci);
+      e.z = (float)((double)f[2] / ci);
+    }
+    out[at] = e;
+  }
+}
+
+// one thread per element: out[k] = f_table(n[k], v[k], l[k]) (n.l) under table table_of[k] (null: table 0), coordinates in fp64
+__global__ __launch_bounds__(256) void merl_eval_kernel(const float4* __restrict__ tables, const int32_t* __restrict__ table_of, const float* __restrict__ n,
+                                                        const float* __restrict__ v, const float* __restrict__ l, float* __restrict__ out, long long N,
+                                                        int linear) {
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < N; k += (long long)gridDim.x * blockDim.x) {
+    const double nn[3] = {n[3 * k], n[3 * k + 1], n[3 * k + 2]}, vv[3] = {v[3 * k], v[3 * k + 1], v[3 * k + 2]};
+    const double ll[3] = {l[3 * k], l[3 * k + 1], l[3 * k + 2]};
+    const double cv = nn[0] * vv[0] + nn[1] * vv[1] + nn[2] * vv[2], cl = nn[0] * ll[0] + nn[1] * ll[1] + nn[2] * ll[2];
+    double f[3] = {0.0, 0.0, 0.0};
+    if (cv > 0.0 && cl > 0.0) {
+      double x[3];
+      table_coords(nn, vv, ll, x);
+      table_lookup(tables + (size_t)(table_of ? table_of[k] : 0) * kTableEntries, x, linear, f);
+    }
+    out[3 * k] = (float)(f[0] * cl);
+    out[3 * k + 1] = (float)(f[1] * cl);
+    out[3 * k + 2] = (float)(f[2] * cl);
+  }
+}
+
+// One sample of either set: a direction l above the surface (cl = n.l > 0) with its balance weight w = (n.l) / (p_s + p_d).  The table is
+// asked first -- the eight corner loads go out together, ahead of the environment's four -- then the radiance is read along to_world(rot, l).
+template <bool VIEW>
+__device__ __forceinline__ void table_sample(const float4* __restrict__ tab, int linear, const float* __restrict__ env, const ViewRot& rot, int EH, int EW,
+                                             V3 n, V3 l, float w, float acc[3]) {
+  const float nn[3] = {n.x, n.y, n.z}, vv[3] = {0.0f, 0.0f, 1.0f}, ll[3] = {l.x, l.y, l.z};
+  float x[3], f[3], L[3] = {1.0f, 1.0f, 1.0f};
+  table_coords(nn, vv, ll, x);
+  table_lookup(tab, x, linear, f);
+  if (env) env_lookup(env, EH, EW, to_world<VIEW>(rot, l), L);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) acc[c] += L[c] * f[c] * w;
+}
+
+// one lane's share of the radiance a surface point with unit normal n (n.z > 0) reflects toward the viewer at +z under a table: the grid
+// points q = lane, lane + lanes, ... of both sample sets, in that order, summed into acc (to be divided by Q^2).  The constructions of the
+// directions are normal_lane_sum's, with the table's proxy roughness alpha in the place of the row's.
+template <bool VIEW>
+__device__ __forceinline__ void table_lane_sum(const float4* __restrict__ tab, float alpha, int linear, const float* __restrict__ env, const ViewRot& rot,
+                                               int EH, int EW, V3 n, int Q, int lane, int lanes, float acc[3]) {
+  const V3 v = v3(0.0f, 0.0f, 1.0f);
+  const float invQ = 1.0f / (float)Q, a2 = alpha * alpha;
+  const float cv = n.z;
+  const Frame f = duff_frame(n, 1.0f);
+  float Vx = -alpha * n.x, Vy = -alpha * n.y, Vz = cv;
+  const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
+  Vx *= vinv; Vy *= vinv; Vz *= vinv;
+  const float lensq = Vx * Vx + Vy * Vy;
+  const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
+  const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
+  const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
+  const float vs = 0.5f * (1.0f + Vz);
+  const float g1v = ggx_g1(a2, n.z, n.x * n.x + n.y * n.y, 1.0f);  // G1(v): v.h > 0 wherever it is used
+  for (int q = lane; q < Q * Q; q += lanes) {
+    const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
+    const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
+    // the GGX set: h from the visible normals seen from v, l = reflect(v, h); p_s from the h it was built from
+    {
+      const float rs = sqrtf(u1), t1 = rs * cp;
+      const float t2 = (1.0f - vs) * sqrtf(1.0f - t1 * t1) + vs * rs * sp;
+      const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
+      const float hx = alpha * (t1 * T1x + t2 * T2x + tz * Vx), hy = alpha * (t1 * T1y + t2 * T2y + tz * Vy);
+      const float hz = fmaxf(t2 * T2z + tz * Vz, 0.0f);
+      const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
+      const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
+      const V3 h = axpy(nh, n, axpy(hy * hinv, f.bt, v3(hx * hinv * f.t.x, hx * hinv * f.t.y, hx * hinv * f.t.z)));
+      const float vh = dot3(v, h);
+      const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
+      const float cl = dot3(n, l);
+      const float D = ggx_d(a2, nh, s2h);
+      if (vh > 0.0f && cl > 0.0f && D > 0.0f) {
+        const float ps = g1v * D / (4.0f * cv), pd = cl * (1.0f / kPi);
+        table_sample<VIEW>(tab, linear, env, rot, EH, EW, n, l, cl / (ps + pd), acc);
+      }
+    }
+    // the cosine set: p_s at h = normalize(v + l)
+    {
+      float cl;
+      const V3 l = cosine_direction(n, f, u1, sp, cp, cl);
+      V3 h = v3(l.x, l.y, l.z + 1.0f);
+      const float hinv = 1.0f / sqrtf(dot3(h, h));
+      h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
+      const float ps = g1v * ggx_d(a2, dot3(n, h), cross_sq(n, h)) / (4.0f * cv), pd = cl * (1.0f / kPi);
+      if (cl > 0.0f) table_sample<VIEW>(tab, linear, env, rot, EH, EW, n, l, cl / (ps + pd), acc);
+    }
+  }
+}
+
+// The sphere of refmap_render_kernel under tables.  grid: ceil(B R^2 / 4) workgroups of 4 waves; wave = pixel (row b, i, j), lit by env[b], seen
+// through view[b], under table table_of[b] (null: table 0) with alpha[table].  out [B][3][R][R].
+template <bool VIEW>
+__global__ __launch_bounds__(256) void refmap_table_kernel(const float4* __restrict__ tables, const int32_t* __restrict__ table_of,
+                                                           const float* __restrict__ alpha, const float* __restrict__ env, const float* __restrict__ view,
+                                                           float* __restrict__ out, int B, int R, int EH, int EW, int Q, int S, int flip, int linear) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)B * R * R) return;  // (wave-uniform)
+  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)R * R)));
+  const int rem = (int)(pix - (long long)b * R * R);
+  const int i = rem / R, j = rem - (rem / R) * R;
+  const int t = table_of ? table_of[b] : 0;
+  const float4* tab = tables + (size_t)t * kTableEntries;
+  const float a = alpha[t];
+  const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+  const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  for (int sy = 0; sy < S; ++sy) {
+    for (int sx = 0; sx < S; ++sx) {
+      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
+      table_lane_sum<VIEW>(tab, a, linear, e, rot, EH, EW, n, Q, lane, 64, acc);
+    }
+  }
+  wave_sum3(acc);
+  if (lane == 0) {
+    const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(((size_t)b * 3 + c) * R + i) * R + j] = acc[c] * scale;
+  }
+}
+
+// normals_shade_kernel under tables: the same reading of the normal map (normal_map_pixel), the same drawn mask, and table_lane_sum once
+// per drawn pixel (S = 1).  image [B][3][H][W], alpha_out [B][H][W] or null.
+template <bool VIEW>
+__global__ __launch_bounds__(256) void normals_table_kernel(const float* __restrict__ normals, const unsigned char* __restrict__ mask, int Bn,
+                                                            const float4* __restrict__ tables, const int32_t* __restrict__ table_of,
+                                                            const float* __restrict__ alpha, const float* __restrict__ env, const float* __restrict__ view,
+                                                            float* __restrict__ image, float* __restrict__ alpha_out, int B, int H, int W, int EH, int EW,
+                                                            int Q, int linear) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
+  const size_t plane = (size_t)H * W;
+  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
+  const size_t at = (size_t)(pix - (long long)b * H * W);
+  V3 n = v3(0.0f, 0.0f, 0.0f);
+  const bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);  // (wave-uniform: every lane read the same pixel)
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  if (drawn) {
+    const int t = table_of ? table_of[b] : 0;
+    const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+    const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+    table_lane_sum<VIEW>(tables + (size_t)t * kTableEntries, alpha[t], linear, e, rot, EH, EW, n, Q, lane, 64, acc);
+    wave_sum3(acc);
+  }
+  if (lane == 0) {
+    const float scale = 1.0f / (float)(Q * Q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) image[((size_t)b * 3 + c) * plane + at] = drawn ? acc[c] * scale : 0.0f;
+    if (alpha_out) alpha_out[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
+  }
+}
+
+}  // namespace
+
+// What every entry that reads tables checks of them before anything is launched: the pointers, NT, every table_of value (brought to the
+// host: `count` of them; null stands for table 0 everywhere) and, where the entry renders, every alpha.  `who` names the entry.
+static int check_tables(const std::string& who, const void* tables, int NT, const int32_t* table_of, long long count, const float* alpha, bool renders,
+                        hipStream_t s) {
+  DRM_REQUIRE(tables && (reinterpret_cast<uintptr_t>(tables) & 15) == 0, who + ": tables must be a 16-byte aligned device pointer");
+  DRM_REQUIRE(NT >= 1 && NT <= 4096, who + ": NT in [1, 4096] tables");
+  DRM_REQUIRE(!renders || alpha, who + ": alpha is null");
+  std::vector<int32_t> of(table_of ? (size_t)count : 0);
+  std::vector<float> al(renders ? (size_t)NT : 0);
+  if (!of.empty()) DRM_HIP_CHECK(hipMemcpyAsync(of.data(), table_of, of.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (!al.empty()) DRM_HIP_CHECK(hipMemcpyAsync(al.data(), alpha, al.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (!of.empty() || !al.empty()) DRM_HIP_CHECK(hipStreamSynchronize(s));
+  for (size_t k = 0; k < of.size(); ++k)
+    DRM_REQUIRE(of[k] >= 0 && of[k] < NT, who + ": table_of[" + std::to_string(k) + "] = " + std::to_string(of[k]) + " is outside [0, NT = " +
+                                              std::to_string(NT) + ")");
+  for (size_t k = 0; k < al.size(); ++k)
+    DRM_REQUIRE(al[k] >= 0.005f && al[k] <= 1.0f, who + ": alpha[" + std::to_string(k) + "] must be a finite value in [0.005, 1]");  // (a NaN fails both)
+  return DRM_OK;
+}
+
+int launch_brdf_to_merl(const float* z, int rows, float* tables_out, hipStream_t s) {
+  DRM_REQUIRE(z && tables_out, "brdf_to_merl: null pointer");
+  DRM_REQUIRE((reinterpret_cast<uintptr_t>(tables_out) & 15) == 0, "brdf_to_merl: tables_out must be 16-byte aligned");
+  DRM_REQUIRE(rows >= 1 && rows <= 4096, "brdf_to_merl: rows in [1, 4096]");
+  const long long total = (long long)rows * kTableEntries;
+  const long long blocks = std::min<long long>((total + 255) / 256, 65536);
+  hipLaunchKernelGGL(brdf_to_merl_kernel, dim3((unsigned)blocks), dim3(256), 0, s, z, reinterpret_cast<float4*>(tables_out), total);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+int launch_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, long long N,
+                     int linear, hipStream_t s) {
+  DRM_REQUIRE(N >= 0 && N <= (1LL << 31), "merl_eval: 0 <= N <= 2^31");
+  if (N == 0) return DRM_OK;
+  DRM_REQUIRE(n && v && l && out, "merl_eval: null pointer");
+  DRM_TRY(check_tables("merl_eval", tables, NT, table_of, N, nullptr, false, s));
+  const long long blocks = std::min<long long>((N + 255) / 256, 65536);
+  hipLaunchKernelGGL(merl_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(tables), table_of, n, v, l, out, N,
+                     linear ? 1 : 0);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+int launch_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* env, const float* view, float* out,
+                               int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, hipStream_t s) {
+  DRM_REQUIRE(out, "render_refmap_table: out is null");
+  DRM_REQUIRE(B >= 1 && B <= 65535 && R > 0 && R <= 8192, "render_refmap_table: 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192");
+  DRM_TRY(check_quadrature("render_refmap_table", quad, subpixel, 16, env, EH, EW));
+  const long long blocks = pixel_blocks((long long)B * R * R);
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap_table: B R^2 too large for one launch");
+  DRM_TRY(check_tables("render_refmap_table", tables, NT, table_of, B, alpha, true, s));
+  // (a view only turns the environment: under a white one it changes nothing and is not read)
+  const bool with_view = env && view;
+  const auto kernel = with_view ? refmap_table_kernel<true> : refmap_table_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, reinterpret_cast<const float4*>(tables), table_of, alpha, env,
+                     with_view ? view : nullptr, out, B, R, env ? EH : 1, env ? EW : 1, quad, subpixel, flip ? 1 : 0, linear ? 1 : 0);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+int launch_render_normals_table(const float* normals, const unsigned char* mask, int Bn, const float* tables, int NT, const int32_t* table_of,
+                                const float* alpha, const float* env, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH,
+                                int EW, int quad, int linear, hipStream_t s) {
+  DRM_REQUIRE(normals && image, "render_normals_table: null pointer");
+  DRM_TRY(check_quadrature("render_normals_table", quad, 1, 0, env, EH, EW));
+  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
+              "render_normals_table: 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
+  const long long blocks = pixel_blocks((long long)B * H * W);
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_normals_table: B H W too large for one launch");
+  DRM_TRY(check_tables("render_normals_table", tables, NT, table_of, B, alpha, true, s));
+  const bool with_view = env && view;
+  const auto kernel = with_view ? normals_table_kernel<true> : normals_table_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, reinterpret_cast<const float4*>(tables), table_of,
+                     alpha, env, with_view ? view : nullptr, image, alpha_out, B, H, W, env ? EH : 1, env ? EW : 1, quad, linear ? 1 : 0);
+  DRM_HIP_CHECK(hipGetLastError());
+  return DRM_OK;
+}
+
+}  // namespace drm

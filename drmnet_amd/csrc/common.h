@@ -326,6 +326,15 @@ int launch_diffusion_losses(const float* model_out, const float* target, const f
                             size_t ws_bytes, float* out, float* rows_out, hipStream_t s);
 // principled eval (f times n.l) of N (n, v, l) triples; z [1 or N][6]; out [N][3]
 int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s);
+// measured BRDFs (brdf_table.hip): tables [NT][90][90][180][4] packed (r, g, b, 0) entries; table_of int32 per row / element or null (table 0)
+int launch_brdf_to_merl(const float* z, int rows, float* tables_out, hipStream_t s);
+int launch_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, long long N,
+                     int linear, hipStream_t s);
+int launch_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* env, const float* view, float* out,
+                               int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, hipStream_t s);
+int launch_render_normals_table(const float* normals, const unsigned char* mask, int Bn, const float* tables, int NT, const int32_t* table_of,
+                                const float* alpha, const float* env, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH,
+                                int EW, int quad, int linear, hipStream_t s);
 
 // misc kernels (misc.hip)
 // absmax_bits (optional): [N][pack_input_absmax_parts(H, W)] words, every one written: max |element| of one block of a packed image as fp32 bits

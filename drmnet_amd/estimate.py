@@ -9,7 +9,8 @@ the C ABI).  The keyword-only `hooks` let tests inject the random draws the refe
 `main` writes the reference's two images (sample_env.png, and sample_brdf.png through visualize_bsdf on csrc/render.hip) and also saves
 and prints the BRDF parameters.  With `--rerender` (off by default) it also shades the estimate back onto the input's normal map
 (drmnet_amd/relight.py) and reports how far that image, and the image ObsNet's inpainted reflectance map stands for, are from the input:
-sample_rerender.exr / .png, sample_refmap_image.exr, sample_errors.json.
+sample_rerender.exr / .png, sample_refmap_image.exr, sample_errors.json.  With `--save_merl` (off by default) it also writes
+sample_brdf.binary, the estimated BRDF as a MERL table (drmnet_amd/merl.py).
 """
 from __future__ import annotations
 
@@ -131,7 +132,17 @@ def parser() -> argparse.ArgumentParser:
     parser.add_argument("--output_dir", type=Path, help="the output directory", default=Path("./outputs/"))
     parser.add_argument("--rerender", action="store_true",
                         help="also re-render the estimate on the input's normal map and report how far it is from the input image (default: off)")
+    parser.add_argument("--save_merl", action="store_true",
+                        help="also write sample_brdf.binary, the estimated BRDF as a MERL table (default: off)")
     return parser
+
+
+def save_brdf_merl(path, zK, brdf_param_names) -> None:
+    """the estimated BRDF exported as a MERL file (merl.bsdf_to_merl, merl.save_merl): what other tools and BRDF error metrics consume"""
+    from .merl import MeasuredBSDF, save_merl
+    from .render import get_bsdf
+
+    save_merl(MeasuredBSDF.from_principled(get_bsdf(zK, brdf_param_names), alpha=1.0).table, path)
 
 
 def write_rerender(output_dir: Path, drmnet_model, Lr0_sample, zK_est, inpaint, input_img, input_normal, mask) -> dict:
@@ -193,6 +204,8 @@ def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     file_io.save_png(args.output_dir / "sample_env.png", hdr2ldr(envmap_est.cpu().numpy()))
     save_brdf_png(args.output_dir / "sample_brdf.png", zK_est, drmnet_model.brdf_param_names)
     np.save(args.output_dir / "sample_brdf.npy", zK_est.cpu().numpy())
+    if args.save_merl:
+        save_brdf_merl(args.output_dir / "sample_brdf.binary", zK_est, drmnet_model.brdf_param_names)
     print("estimated BRDF parameters", dict(zip(drmnet_model.brdf_param_names, zK_est.tolist())))
     if args.rerender:
         errors = write_rerender(args.output_dir, drmnet_model, Lr0_sample, zK_est, hooks["stages"]["inpaint"], input_img, input_normal, mask)

@@ -1,8 +1,8 @@
 """Object images from a normal map -- the forward model pointed at ``estimate``'s own inputs -- on normals_shade_kernel (csrc/render.hip)
 and image_from_refmap_kernel (csrc/refmap.hip).
 
-    python -m drmnet_amd.relight --input_normal N.npy [--input_mask M.png] [--envmap E.exr] --z m R G B r s [--view_from x y z]
-        [--quad Q] [--light_samples M] [--input_img I.exr] --output_dir D
+    python -m drmnet_amd.relight --input_normal N.npy [--input_mask M.png] [--envmap E.exr] (--z m R G B r s | --merl material.binary)
+        [--view_from x y z] [--quad Q] [--light_samples M] [--input_img I.exr] --output_dir D
 
 ``estimate`` turns an object image, its normal map and a mask into an illumination map and a BRDF; nothing in the reference turns those
 back into an image of the same object without its mesh (MitsubaOrthoRenderer, utils/mitsuba3_utils.py:433-564, needs the mesh;
@@ -13,6 +13,8 @@ there is on a photograph, which has no ground-truth reflectance map), relights t
 ``image_from_refmap`` reads a reflectance map at every pixel's normal instead: the image the reflectance-map model itself stands for, the
 inverse of ``img2refmap.refmap_mask_make``.  ``image_errors`` reports how far two images are apart on a mask.  The command line writes
 ``image.exr`` and the tone-mapped ``image.png`` (the mask as alpha), and with ``--input_img`` also ``errors.json`` against that image.
+``render_normals_measured`` (``--merl``) shades the normal map under a measured BRDF, a MERL table (``merl.MeasuredBSDF``), instead of a
+principled row; light samples under a table are not built.
 Rendering runs on the GPU (no CPU path); argument errors are raised before it is touched.
 """
 from __future__ import annotations
@@ -101,6 +103,43 @@ def render_normals(normals, z, brdf_param_names: Sequence[str], envmaps: Optiona
                                           alpha.data_ptr(), B, H, W, EH, EW, int(quad), light_samples if light_ws is not None else 0,
                                           _lib.ptr(light_ws), light_bytes, _lib.stream_ptr(dev)))
     return image, alpha
+
+
+@torch.no_grad()
+def render_normals_measured(normals, bsdfs, envmaps: Optional[torch.Tensor] = None, *, mask=None, view_from=None, quad: int = QUAD, lookup: str = "linear"):
+    """One call of drm_render_normals_table: ``render_normals`` under measured BRDFs.  ``bsdfs`` is one merl.MeasuredBSDF, shared by all rows,
+    or a list of B (equal objects share one device table); B is the number of envmaps [B, EH, EW, 3], or of bsdfs under a white environment
+    (None).  normals, mask and view_from as in ``render_normals``; ``lookup`` is "linear" or "nearest" -> (image [B, 3, H, W], alpha [B, H, W]),
+    what ``render_normals`` returns.  There are no light samples under a table."""
+    from .merl import MeasuredBSDF, device_tables, lookup_mode
+
+    linear = lookup_mode(lookup)
+    if isinstance(envmaps, torch.Tensor):
+        if envmaps.dim() != 4 or envmaps.shape[3] != 3:
+            raise ValueError(f"envmaps must be [B, H, W, 3], got {tuple(envmaps.shape)}")
+        B = int(envmaps.shape[0])
+    else:
+        B = 1 if isinstance(bsdfs, MeasuredBSDF) else len(list(bsdfs))
+    if not 1 <= B <= 65535:
+        raise ValueError(f"render_normals_measured: B = {B} rows in [1, 65535]")
+    Bn, H, W = _normal_maps("render_normals_measured", normals, mask, B)
+    if isinstance(quad, bool) or not 1 <= int(quad) <= 1024:
+        raise ValueError(f"render_normals_measured: quad in [1, 1024], got {quad!r}")
+    if view_from is not None and view_rotation(view_from).shape[0] != B:
+        raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
+    _gpu_only("render_normals_measured", normals=normals, envmaps=envmaps)
+    dev = _device(normals, envmaps)
+    tables, table_of, alpha = device_tables(bsdfs, B, dev)
+    nrm = normals.to(dev, torch.float32).reshape(Bn, H, W, 3).contiguous()
+    m8 = _mask_on(mask, Bn, H, W, dev)
+    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    drawn = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_render_normals_table(nrm.data_ptr(), _lib.ptr(m8), Bn, tables.data_ptr(), int(tables.shape[0]), table_of.data_ptr(),
+                                                       alpha.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(), drawn.data_ptr(), B, H, W,
+                                                       EH, EW, int(quad), linear, _lib.stream_ptr(dev)))
+    return image, drawn
 
 
 @torch.no_grad()
@@ -201,12 +240,13 @@ def save_image(stem: Path, image: torch.Tensor, mask: torch.Tensor) -> None:
 
 
 def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="shade a normal map under an environment map with a principled BRDF")
+    p = argparse.ArgumentParser(description="shade a normal map under an environment map with a principled or a measured BRDF")
     p.add_argument("--input_normal", type=Path, required=True, help="normal map of the object (.npy, H x W x 3, view frame)")
     p.add_argument("--input_mask", type=Path, default=None, help="mask of the object (.png); default: |normal| > 0.5 alone")
     p.add_argument("--envmap", type=Path, default=None, help="lat-long environment map (.exr); default: white")
-    p.add_argument("--z", type=float, nargs=6, required=True, metavar=("m", "R", "G", "B", "r", "s"),
-                   help="metallic, base colour R G B, roughness, specular")
+    material = p.add_mutually_exclusive_group(required=True)
+    material.add_argument("--z", type=float, nargs=6, metavar=("m", "R", "G", "B", "r", "s"), help="metallic, base colour R G B, roughness, specular")
+    material.add_argument("--merl", type=Path, default=None, help="a measured BRDF instead: a MERL table (.binary), read trilinearly")
     p.add_argument("--view_from", type=float, nargs=3, default=None, metavar=("x", "y", "z"),
                    help="viewer position the environment is turned for (off the +-y axis); default: +z")
     p.add_argument("--quad", type=int, default=QUAD)
@@ -219,7 +259,10 @@ def parser() -> argparse.ArgumentParser:
 def main(argv=None):
     from . import file_io
 
-    args = parser().parse_args(argv)
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.merl is not None and args.light_samples != 0:
+        ap.error("--light_samples with --merl: light samples under a table are not built")
     check_light_samples(args.light_samples)
     if not 1 <= args.quad <= 1024:
         raise ValueError(f"quad in [1, 1024], got {args.quad}")
@@ -237,8 +280,14 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("relight renders on the GPU (drmnet_amd has no CPU path) and no GPU is visible")
     dev = torch.device("cuda", torch.cuda.current_device())
-    image, _ = render_normals(normal.to(dev), torch.tensor([args.z], dtype=torch.float32, device=dev), NAMES, None if env is None else env.to(dev)[None],
-                              mask=mask.to(dev), view_from=view, quad=args.quad, light_samples=args.light_samples)
+    if args.merl is not None:
+        from .merl import MeasuredBSDF
+
+        image, _ = render_normals_measured(normal.to(dev), MeasuredBSDF.from_file(args.merl), None if env is None else env.to(dev)[None],
+                                           mask=mask.to(dev), view_from=view, quad=args.quad)
+    else:
+        image, _ = render_normals(normal.to(dev), torch.tensor([args.z], dtype=torch.float32, device=dev), NAMES, None if env is None else env.to(dev)[None],
+                                  mask=mask.to(dev), view_from=view, quad=args.quad, light_samples=args.light_samples)
     args.output_dir.mkdir(parents=True, exist_ok=True)
     save_image(args.output_dir / "image", image[0], mask.to(dev))
     print(f"wrote image.exr and image.png ({int(mask.sum())} of {mask.numel()} pixels) to {args.output_dir}")

@@ -224,22 +224,61 @@ def get_bsdf(z, brdf_param_names: Sequence[str]) -> PrincipledBSDF:
 def _as_rows(a, n: int) -> np.ndarray:
     a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     a = np.asarray(a, dtype=np.float32).reshape(-1, 3)
-    return np.array(np.broadcast_to(a, (n, 3)))
+    # (a row-major copy, as the kernels read it: copied in "K" order a broadcast view keeps its axis order and comes out column-major)
+    return np.array(np.broadcast_to(a, (n, 3)), order="C")
 
 
 @torch.no_grad()
-def eval_bsdf(bsdf: PrincipledBSDF, normal, wo, wi) -> np.ndarray:
+def eval_bsdf(bsdf, normal, wo, wi, *, lookup: str = "nearest") -> np.ndarray:
     """utils/mitsuba3_utils.py:610-626: f(wi, wo) (n.wo) of Mitsuba's eval for wi toward the viewer and wo toward the light; each of
-    normal / wo / wi is one vector [3] or N vectors [N, 3] (unit length).  Returns [N, 3] (numpy), evaluated by drm_brdf_eval."""
+    normal / wo / wi is one vector [3] or N vectors [N, 3] (unit length).  Returns [N, 3] (numpy), evaluated by drm_brdf_eval for a
+    PrincipledBSDF and by drm_merl_eval for a merl.MeasuredBSDF, whose table is read as ``lookup`` says: "nearest" (the default: the MERL
+    distribution reader's rule) or "linear"."""
+    from .merl import MeasuredBSDF, lookup_mode
+
     n = max(int(np.size(a) // 3) for a in (normal, wo, wi))
     arrs = [torch.from_numpy(_as_rows(a, n)) for a in (normal, wi, wo)]
+    measured = isinstance(bsdf, MeasuredBSDF)
+    linear = lookup_mode(lookup) if measured else 0
     dev = _device()
     nrm, v, l = (a.to(dev) for a in arrs)
-    z = torch.tensor(bsdf.row, dtype=torch.float32, device=dev)
     out = torch.empty((n, 3), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().drm_brdf_eval(z.data_ptr(), 1, nrm.data_ptr(), v.data_ptr(), l.data_ptr(), out.data_ptr(), n, _lib.stream_ptr(dev)))
+        if measured:
+            table = bsdf.device_table(dev)
+            _lib.check(_lib.lib().drm_merl_eval(table.data_ptr(), 1, None, nrm.data_ptr(), v.data_ptr(), l.data_ptr(), out.data_ptr(), n, linear,
+                                                _lib.stream_ptr(dev)))
+        else:
+            z = torch.tensor(bsdf.row, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib().drm_brdf_eval(z.data_ptr(), 1, nrm.data_ptr(), v.data_ptr(), l.data_ptr(), out.data_ptr(), n, _lib.stream_ptr(dev)))
     return out.cpu().numpy()
+
+
+@torch.no_grad()
+def render_table(bsdfs, envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD, subpixel: int = SUBPIXEL, flip: bool = False,
+                 view_from=None, lookup: str = "linear") -> torch.Tensor:
+    """One launch of drm_render_refmap_table: the sphere of ``render`` under measured BRDFs.  ``bsdfs`` is one merl.MeasuredBSDF, shared by
+    all rows, or a list of B (equal objects share one device table); envmaps [B, H, W, 3] (or None: white, and then B = len(bsdfs), 1 for a
+    single one); view_from [B, 3] (or None: +z) -> reflectance maps [B, 3, res, res].  Each table is sampled with its own proxy roughness
+    (``MeasuredBSDF.alpha``) and read as ``lookup`` says ("linear" or "nearest")."""
+    from .merl import MeasuredBSDF, device_tables, lookup_mode
+
+    linear = lookup_mode(lookup)
+    dev = _device(envmaps)
+    if envmaps is not None:
+        B = int(envmaps.shape[0])
+    else:
+        B = 1 if isinstance(bsdfs, MeasuredBSDF) else len(list(bsdfs))
+    if not 1 <= B <= 65535:
+        raise ValueError(f"render_table: B = {B} rows in [1, 65535]")
+    tables, table_of, alpha = device_tables(bsdfs, B, dev)
+    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    out = torch.empty((B, 3, res, res), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_render_refmap_table(tables.data_ptr(), int(tables.shape[0]), table_of.data_ptr(), alpha.data_ptr(), _lib.ptr(env),
+                                                      _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad), int(subpixel), int(bool(flip)),
+                                                      linear, _lib.stream_ptr(dev)))
+    return out
 
 
 def visualize_layout(increment_deg: float = 30, imsize=(512, 512), angle_start: float = 0):
@@ -268,10 +307,10 @@ def visualize_layout(increment_deg: float = 30, imsize=(512, 512), angle_start: 
     return normal, light, mask
 
 
-def visualize_bsdf(bsdf: PrincipledBSDF, increment_deg: float = 30, imsize=(512, 512), angle_start: float = 0):
-    """utils/mitsuba3_utils.py:629-660: the BSDF on the spheres of visualize_layout, seen along -z (wi = [0, 0, -1]).  Returns
-    (fig [H, W, 3] float32, mask [H, W] bool)."""
+def visualize_bsdf(bsdf, increment_deg: float = 30, imsize=(512, 512), angle_start: float = 0, *, lookup: str = "nearest"):
+    """utils/mitsuba3_utils.py:629-660: the BSDF (a PrincipledBSDF or a merl.MeasuredBSDF, read as ``lookup`` says) on the spheres of
+    visualize_layout, seen along -z (wi = [0, 0, -1]).  Returns (fig [H, W, 3] float32, mask [H, W] bool)."""
     normal, light, mask = visualize_layout(increment_deg, imsize, angle_start)
     fig = np.zeros(normal.shape, dtype=np.float32)
-    fig[mask] = eval_bsdf(bsdf, normal[mask], light[mask], (0.0, 0.0, -1.0))
+    fig[mask] = eval_bsdf(bsdf, normal[mask], light[mask], (0.0, 0.0, -1.0), lookup=lookup)
     return fig, mask

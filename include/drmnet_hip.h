@@ -587,6 +587,53 @@ int drm_image_from_refmap(const float* refmap, const uint8_t* refmask, int Br, i
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream);
 
+/* Measured BRDFs (csrc/brdf_table.hip): a material given as a MERL table instead of a principled row.  Additive: the ABI version is unchanged.
+ * Layout "packed table": one table is [90][90][180][4] fp32 = (theta_h, theta_d, phi_d, (r, g, b, 0)), 23 328 000 bytes, 16-byte aligned, so
+ *   a lookup corner is one 16-byte load; `tables` is [NT] such blocks back to back.  Node (i, j, k) stands for theta_h = (i / 90)^2 pi / 2,
+ *   theta_d = j pi / 180, phi_d = k pi / 180.  An entry without a measurement (below the horizon) has r = g = b = -1.  The values are
+ *   BRDF values (load_merl's, the colour scales applied), not BRDF times cosine.  1 <= NT <= 4096.
+ * The lookup f_table(n, v, l), unit n, v (toward the viewer), l (toward the light); 0 unless n.v > 0 and n.l > 0:
+ *   h = normalize(v + l); theta_h = atan2(|n x h|, n.h); theta_d = atan2(|l x h|, l.h);
+ *   x_h = -normalize(n - (n.h) h), y_h = h x x_h, phi_d = atan2(v.y_h, v.x_h) taken mod pi (MERL's convention: in the half-vector frame the
+ *   normal lies at azimuth pi; reciprocity gives the other half); phi_d = 0 where |n - (n.h) h| < 1e-6;
+ *   coordinates (90 sqrt(theta_h / (pi / 2)), 90 theta_d / (pi / 2), 180 phi_d / pi).
+ *   linear = 0 ("nearest", the MERL distribution reader's rule): floor each, clamp to [0, 89], [0, 89], [0, 179]; a negative entry reads 0.
+ *   linear != 0: trilinear between floor and floor + 1, clamped at 89 in theta_h and theta_d, wrapping 179 -> 0 in phi_d; corners whose
+ *   entry is negative are dropped and the remaining weights renormalised; 0 where all eight are dropped.
+ * table_of: int32 device array naming the table of every row / element, or NULL: table 0 for all.  It is brought to the host and checked
+ *   (one stream synchronisation) before anything is launched, as is alpha.
+ * DRM_ERR_INVALID, with drm_last_error naming the argument and no output touched: a NULL where data is required, tables not 16-byte aligned,
+ *   NT outside [1, 4096], a table_of value outside [0, NT), an alpha outside [0.005, 1] or not finite, a bad quad / subpixel / map size.
+ *
+ * drm_brdf_to_merl (replaces bsdf_to_merl, utils/mitsuba3_utils.py:602-638): one packed table per principled row z [rows][6],
+ *   1 <= rows <= 4096, one thread per entry, in fp64 (drm_brdf_eval's expression): in the half-vector frame h = +z,
+ *   n = (-sin theta_h, 0, cos theta_h), wo = (sin theta_d cos phi_d, sin theta_d sin phi_d, cos theta_d) (the viewer), wi = wo (-1, -1, 1)
+ *   (the light); entry = eval(n, wo, wi) / (n.wi); -1 where n.wo < 0 or n.wi < 0; 0 where a cosine is exactly 0 (|cos| < 1e-12: the grid's
+ *   exact zeros, theta_h + theta_d = pi / 2 at phi_d = 0, as fp64 rounds them). */
+int drm_brdf_to_merl(const float* z, int rows, float* tables_out, void* stream);
+/* drm_merl_eval (eval_bsdf / visualize_bsdf for a measured material, utils/mitsuba3_utils.py:641-690): out [N][3] = f_table(n, v, l) (n.l)
+ *   -- Mitsuba's eval convention, as drm_brdf_eval -- for N triples n, v, l [N][3]; coordinates and interpolation in fp64. */
+int drm_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, int64_t N, int linear,
+                  void* stream);
+/* drm_render_refmap_table (MitsubaRefMapRenderer.rendering with a measured BSDF, utils/mitsuba3_utils.py:324-430): the sphere of
+ *   drm_render_refmap_views under tables: the same sensor, sub-pixel normals, one wave per pixel, fixed per-lane order and butterfly, no
+ *   atomics: bitwise reproducible, and a batch equals its rows rendered alone.  Row b is lit by envmap[b] ([B][EH][EW][3] or NULL: white),
+ *   seen through view[b] ([B][9] or NULL: +z), under table table_of[b].  out [B][3][R][R].  1 <= B <= 65535, 1 <= R <= 8192.
+ *   alpha [NT] (device): the proxy roughness of each table, in [0.005, 1].  The quadrature per normal n (v = +z): the quad x quad midpoint
+ *   grid mapped to the GGX visible normals of roughness alpha seen from v with l = reflect(v, h), and the same grid mapped to cosine-weighted
+ *   directions (the two constructions of drm_render_refmap); a sample l of either set with n.l > 0 (a GGX sample also v.h > 0 and D > 0) adds
+ *     L(Rot l) f_table(n, v, l) (n.l) / (quad^2 (p_s(l) + p_d(l))),  p_s = G1(v) D(h) / (4 n.v) at h = normalize(v + l),  p_d = (n.l) / pi
+ *   (the balance heuristic over both sets: consistent for any alpha, which only decides where the accuracy goes); the pixel is the sum
+ *   over both sets and the subpixel^2 normals, divided by subpixel^2.  All in fp32. */
+int drm_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* envmap, const float* view, float* out,
+                            int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, void* stream);
+/* drm_render_normals_table: drm_render_normals with (tables, NT, table_of, alpha, linear) in place of z and without light samples: the same
+ *   reading of the normal map and drawn mask, and the per-normal sum of drm_render_refmap_table with subpixel = 1 (a pixel whose normal is a
+ *   sphere normal equals that render's pixel bit for bit).  image [B][3][H][W]; alpha_out [B][H][W] or NULL. */
+int drm_render_normals_table(const float* normals, const uint8_t* mask, int Bn, const float* tables, int NT, const int32_t* table_of, const float* alpha,
+                             const float* envmap, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH, int EW, int quad,
+                             int linear, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The validation losses (csrc/losses.hip).
  * ------------------------------------------------------------------------------------------- */
