@@ -48,6 +48,7 @@ __device__ __forceinline__ f32x16 fa_mma(const F4H8& a, const F4H8& b, f32x16 c)
 
 constexpr int FA_QT = 128;          // queries per workgroup: 4 waves x 32
 constexpr int FA_KT = 128;          // keys per tile
+static_assert(FA_QT == ATTN_FLASH_TILE && FA_KT == ATTN_FLASH_TILE, "the planner's rule (attn_plan.hip) divides T by this tile");
 constexpr int FA_SLOT_F4 = 2048;    // 32 KiB ring slot
 constexpr int FA_SLOTS = 4;
 constexpr int FA_AHEAD = 3;         // DMA runs this many steps ahead of the MFMAs (a step is confirmed one step before its first fragment read)
@@ -411,13 +412,6 @@ __global__ __launch_bounds__(256) void pack_attn_v_perm_kernel(const float* __re
     dp[((size_t)kc * 8 + 4 + seg) * C + c] = lo.f4;
   }
 }
-
-// (T = 512 -- RefNet's 16x32 level at the metric shape, 128 workgroups at batch 32 -- measured 0.106 ms per core against 0.114 ms for the
-//  conv-pipeline form: the three packing launches and the half-empty chip eat the kernel's advantage; from T = 1024 it is 0.224 vs ~0.45 ms)
-#ifndef FA_MIN_T
-#define FA_MIN_T 1024
-#endif
-bool attention_flash_applicable(int T, int C, int terms) { return (terms == 3 || terms == 1 || terms == 4) && C == 384 && T % FA_KT == 0 && T >= FA_MIN_T; }
 
 // The tail of the single-kernel form (launch_attention_core, attn.hip, has written the factor tables and the row-major images of q and k): v^T in
 // the kernel's key order, then the kernel.  qkv [N][T][3C], x [N][T][C], out = x + P v [N][T][C].

@@ -243,8 +243,13 @@ struct AttnTables {
 // scores: plan.scores_floats, ws: plan.ws_floats floats; out_stat (zeroed by the caller) where plan.out_stats
 int launch_attention_core(const AttnPlan& p, const float* qkv, const double2* qkv_mom, const float* x, float* scores, float* out, double2* out_stat,
                           float* ws, hipStream_t s);
-// attn_flash.hip, for launch_attention_core alone (no other caller): the rule of ATTN_FLASH, and its tail once the tables and the row-major images of
-// q and k are written (v^T pack + the kernel)
+// attn_plan.hip (host code only), for the launchers of attn.hip: a GEMM of the conv-pipeline form as a 1x1 conv with per-image weights, and the one
+// walk over a core's workspace (null ws: sizes only; *end = the floats it spans)
+ConvArgs attention_gemm(int nb, int H, int W, int cin, int cout);
+AttnTables attention_tables(const AttnPlan& p, float* ws, size_t* end = nullptr);
+// the rule of ATTN_FLASH (attn_plan.hip; queries per workgroup = keys per tile = ATTN_FLASH_TILE), and, in attn_flash.hip for launch_attention_core
+// alone (no other caller), its tail once the tables and the row-major images of q and k are written (v^T pack + the kernel)
+constexpr int ATTN_FLASH_TILE = 128;
 bool attention_flash_applicable(int T, int C, int terms);
 int launch_attention_flash(const AttnPlan& p, const AttnTables& t, const float* qkv, const float* x, float* out, hipStream_t s);
 

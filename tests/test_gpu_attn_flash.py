@@ -40,9 +40,10 @@ def test_attention_block_384_at_32x32_vs_reference_golden(dev, precision):
 
 
 @pytest.mark.parametrize("precision", ["f16x3", "f16", "bf16"])
-@pytest.mark.parametrize("n,h,w", [(3, 32, 64), (8, 32, 32), (5, 32, 32)])
+@pytest.mark.parametrize("n,h,w", [(3, 32, 64), (8, 32, 32), (5, 32, 32), (3, 24, 48)])
 def test_attention_block_vs_oracle_metric_shape(dev, n, h, w, precision):
-    """T = 2048 (the 3x128x256 metric shape's ds = 4 level) and T = 1024; N * T / 128 a multiple of 8 (XCD-grouped query tiles) and not"""
+    """T = 2048 (the 3x128x256 metric shape's ds = 4 level), T = 1024 and T = 1152; N * T / 128 workgroups: 48, 64 and 40 are multiples of 8
+    (XCD-grouped query tiles), the 27 of 3 x 24x48 are not (the unswizzled order)"""
     gen = torch.Generator().manual_seed(100 + n + h + w)
     x = torch.randn((n, 384, h, w), generator=gen)
     x[0] *= 3.0  # images of different scale in one batch: the per-image factors of q / k / v differ
