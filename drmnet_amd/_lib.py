@@ -46,6 +46,7 @@ SYMBOLS = [
     "drm_render_normals", "drm_image_from_refmap",
     "drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap_table", "drm_render_normals_table",
     "drm_obs_forward_process", "drm_diffusion_losses",
+    "drm_envmap2mirmap", "drm_rotate_envmap", "drm_mirimg2envmap", "drm_refmap2refimg",
 ]
 
 
@@ -227,6 +228,10 @@ def lib() -> C.CDLL:
                                         fp, vp]
     L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     L.drm_diffusion_losses.argtypes = [fp, fp, fp, vp, fp, fp, i32, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t, fp, fp, vp]
+    L.drm_envmap2mirmap.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_rotate_envmap.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_mirimg2envmap.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_refmap2refimg.argtypes = [fp, fp, u8p, i32, i32, i32, i32, i32, i32, vp]
     if L.drm_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libdrmnet_hip.so ABI version {L.drm_abi_version()} != {ABI_VERSION}: rebuild with `python -m drmnet_amd.build`")
     _lib = L

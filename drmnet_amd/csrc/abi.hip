@@ -530,6 +530,32 @@ int drm_resize(const float* x, float* out, int planes, int IH, int IW, int OH, i
   return guarded([&]() -> int { return launch_resize(x, out, planes, IH, IW, OH, OW, mode, static_cast<hipStream_t>(stream)); });
 }
 
+// ------------------------------------------------------------------------------------------------ sphere / envmap warps (sphere_warp.hip)
+
+int drm_envmap2mirmap(const float* envmap, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int mitigate_aliasing,
+                      int log_scale_interpolation, int channels_last_in, void* stream) {
+  return guarded([&]() -> int {
+    return launch_envmap2mirmap(envmap, frames, out, B, C, H, W, OH, OW, mitigate_aliasing, log_scale_interpolation, channels_last_in,
+                                static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_rotate_envmap(const float* envmap, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int channels_last_in,
+                      void* stream) {
+  return guarded([&]() -> int { return launch_rotate_envmap(envmap, frames, out, B, C, H, W, OH, OW, channels_last_in, static_cast<hipStream_t>(stream)); });
+}
+
+int drm_mirimg2envmap(const float* refimg, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int log_scale_interpolation,
+                      int channels_last_in, void* stream) {
+  return guarded([&]() -> int {
+    return launch_mirimg2envmap(refimg, frames, out, B, C, H, W, OH, OW, log_scale_interpolation, channels_last_in, static_cast<hipStream_t>(stream));
+  });
+}
+
+int drm_refmap2refimg(const float* refmap, float* out, uint8_t* mask, int B, int C, int H, int W, int radius, int channels_last_in, void* stream) {
+  return guarded([&]() -> int { return launch_refmap2refimg(refmap, out, mask, B, C, H, W, radius, channels_last_in, static_cast<hipStream_t>(stream)); });
+}
+
 // ------------------------------------------------------------------------------------------------ forward model (render.hip)
 
 int drm_render_refmap(const float* z, const float* envmap, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, void* stream) {

@@ -263,6 +263,15 @@ int launch_mirmap2envmap(const float* mir, const float* basis, float* out, int B
 int launch_hdr2ldr(const float* x, const unsigned char* mask, int HW, float alpha, float gamma, float* out, hipStream_t s);
 int launch_resize(const float* x, float* out, int planes, int IH, int IW, int OH, int OW, int mode, hipStream_t s);
 
+// the sphere / envmap warp family (sphere_warp.hip; see drm_envmap2mirmap and its neighbours): in [B][C][H][W], or [B][H][W][C] with nhwc_in,
+// frames [B][k][3] fp32 on the device, out [B][C][OH][OW]
+int launch_envmap2mirmap(const float* env, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int mitigate_aliasing,
+                         int log_interp, int nhwc_in, hipStream_t s);
+int launch_rotate_envmap(const float* env, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int nhwc_in, hipStream_t s);
+int launch_mirimg2envmap(const float* img, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int log_interp, int nhwc_in,
+                         hipStream_t s);
+int launch_refmap2refimg(const float* refmap, float* out, unsigned char* mask, int B, int C, int H, int W, int radius, int nhwc_in, hipStream_t s);
+
 // reflectance-map forward model (render.hip): z [B][6] canonical principled rows, env [B][EH][EW][3] or null (white), out [B][3][R][R]
 int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s);
 // the same kernel on L stacked sets of rows: z [L][B][6], out [L][B][3][R][R]; row (l, b) under env[b], seen through view[b] ([B][9] row-major

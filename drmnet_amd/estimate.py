@@ -10,7 +10,10 @@ the C ABI).  The keyword-only `hooks` let tests inject the random draws the refe
 and prints the BRDF parameters.  With `--rerender` (off by default) it also shades the estimate back onto the input's normal map
 (drmnet_amd/relight.py) and reports how far that image, and the image ObsNet's inpainted reflectance map stands for, are from the input:
 sample_rerender.exr / .png, sample_refmap_image.exr, sample_errors.json.  With `--save_merl` (off by default) it also writes
-sample_brdf.binary, the estimated BRDF as a MERL table (drmnet_amd/merl.py).
+sample_brdf.binary, the estimated BRDF as a MERL table (drmnet_amd/merl.py).  With `--gt_envmap E.exr --gt_view_from x y z` (a pair, off by
+default: the `--envmap` and `--view_from` `synthesize` was given) it also judges the estimated illumination against the true one
+(drmnet_amd/groundtruth.py): sample_gt_mirmap.exr, the mirror reflectance map Lr0 should equal; sample_gt_env.exr, the true map in the
+camera frame the estimated map is in; sample_Lr0.exr; and sample_gt_errors.json.
 """
 from __future__ import annotations
 
@@ -134,7 +137,20 @@ def parser() -> argparse.ArgumentParser:
                         help="also re-render the estimate on the input's normal map and report how far it is from the input image (default: off)")
     parser.add_argument("--save_merl", action="store_true",
                         help="also write sample_brdf.binary, the estimated BRDF as a MERL table (default: off)")
+    parser.add_argument("--gt_envmap", type=Path, default=None,
+                        help="the true lat-long environment map (.exr, world frame): also report the estimated illumination's error; needs --gt_view_from")
+    parser.add_argument("--gt_view_from", type=float, nargs=3, default=None, metavar=("x", "y", "z"),
+                        help="the viewer position the object image was taken from (off the +-y axis); needs --gt_envmap")
     return parser
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """the command line, with the one rule argparse cannot state: --gt_envmap and --gt_view_from come as a pair"""
+    p = parser()
+    args = p.parse_args(argv)
+    if (args.gt_envmap is None) != (args.gt_view_from is None):
+        p.error("--gt_envmap and --gt_view_from come as a pair: the true map is in the world frame, the estimate in the camera's")
+    return args
 
 
 def save_brdf_merl(path, zK, brdf_param_names) -> None:
@@ -165,6 +181,25 @@ def write_rerender(output_dir: Path, drmnet_model, Lr0_sample, zK_est, inpaint, 
     return errors
 
 
+def write_groundtruth(output_dir: Path, Lr0_sample, envmap_est, envmap_gt, view_from) -> dict:
+    """What ``--gt_envmap`` adds: sample_gt_mirmap.exr and sample_gt_env.exr, the true illumination as the mirror reflectance map and as
+    the camera-frame environment map (groundtruth.gt_mirror_map / gt_camera_envmap); sample_Lr0.exr, the estimated mirror map they are
+    compared with (the estimated environment map is sample_env.png's); and sample_gt_errors.json: "mirror_map" and "envmap", each the
+    estimate against the truth over every texel (relight.image_errors: the scaled figures allow for the scale ambiguity)."""
+    import json
+
+    from . import file_io
+    from .groundtruth import illumination_errors
+
+    maps = {}
+    errors = illumination_errors(Lr0_sample, envmap_est, envmap_gt, view_from, maps=maps)
+    file_io.save_exr(output_dir / "sample_gt_mirmap.exr", maps["mirror_map"].permute(1, 2, 0))
+    file_io.save_exr(output_dir / "sample_gt_env.exr", maps["envmap"])
+    file_io.save_exr(output_dir / "sample_Lr0.exr", Lr0_sample.permute(1, 2, 0))
+    (output_dir / "sample_gt_errors.json").write_text(json.dumps(errors, indent=1) + "\n")
+    return errors
+
+
 def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     """``models`` = (DRMNet_model, ObsNet_model), already on the GPU with their ``ds``, stands in for the two configs, and ``hooks`` are
     ``estimate``'s: tests run the command line on small networks with injected draws."""
@@ -172,7 +207,11 @@ def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     from .config import instantiate_from_config, load_config
     from .transform import hdr2ldr
 
-    args = parser().parse_args(argv)
+    args = parse_args(argv)
+    if args.gt_view_from is not None:
+        from .render import view_rotation
+
+        view_rotation(args.gt_view_from)  # (a view along +-y is a ValueError here, before any work)
 
     if models is not None:
         drmnet_model, obsnet_model = models
@@ -210,6 +249,10 @@ def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     if args.rerender:
         errors = write_rerender(args.output_dir, drmnet_model, Lr0_sample, zK_est, hooks["stages"]["inpaint"], input_img, input_normal, mask)
         print("re-rendered estimate against the input image", errors)
+    if args.gt_envmap is not None:
+        envmap_gt = file_io.load_exr(args.gt_envmap, as_torch=True).cuda()
+        errors = write_groundtruth(args.output_dir, Lr0_sample, envmap_est, envmap_gt, args.gt_view_from)
+        print("estimated illumination against the ground truth", errors)
 
 
 if __name__ == "__main__":

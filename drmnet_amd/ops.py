@@ -395,3 +395,71 @@ def resize(x, size, mode: str = "bilinear"):
     with _dev(x):
         _lib.check(_lib.lib().drm_resize(x.data_ptr(), out.data_ptr(), planes, ih, iw, oh, ow, RESIZE_MODES[mode], _lib.stream_ptr(x.device)))
     return out
+
+
+def _warp_input(x, name: str, channels_last: bool):
+    """x [B, C, H, W] (or [B, H, W, C] with channels_last) on the GPU -> (x, B, C, H, W)"""
+    x = _lib.require_gpu_tensor(x, name)
+    if x.ndim != 4:
+        raise RuntimeError(f"{name} must be [B, C, H, W]" + (" ([B, H, W, C] with channels_last)" if channels_last else "") + f", got {tuple(x.shape)}")
+    b, c, h, w = (x.shape[0], x.shape[3], x.shape[1], x.shape[2]) if channels_last else x.shape
+    return x, int(b), int(c), int(h), int(w)
+
+
+def _warp_frames(frames, b: int, k: int, dev):
+    f = torch.as_tensor(frames, dtype=torch.float32)
+    if tuple(f.shape) != (b, k, 3):
+        raise RuntimeError(f"frames must be [B={b}, {k}, 3], got {tuple(f.shape)}")
+    return f.to(dev).contiguous()
+
+
+@torch.no_grad()
+def envmap2mirmap(envmap, output_shape, frames, mitigate_aliasing=True, log_scale_interpolation=False, channels_last=False):
+    """drm_envmap2mirmap (utils/transform.py:201-242) on frames [B, 6, 3] (include/drmnet_hip.h names the rows) -> [B, C, OH, OW]"""
+    envmap, b, c, h, w = _warp_input(envmap, "envmap", channels_last)
+    oh, ow = int(output_shape[0]), int(output_shape[1])
+    frames = _warp_frames(frames, b, 6, envmap.device)
+    out = torch.empty((b, c, oh, ow), dtype=torch.float32, device=envmap.device)
+    with _dev(envmap):
+        _lib.check(_lib.lib().drm_envmap2mirmap(envmap.data_ptr(), frames.data_ptr(), out.data_ptr(), b, c, h, w, oh, ow, int(bool(mitigate_aliasing)),
+                                                int(bool(log_scale_interpolation)), int(bool(channels_last)), _lib.stream_ptr(envmap.device)))
+    return out
+
+
+@torch.no_grad()
+def rotate_envmap(envmap, output_shape, frames, channels_last=False):
+    """drm_rotate_envmap (utils/transform.py:317-363) on frames [B, 6, 3] -> [B, C, OH, OW]"""
+    envmap, b, c, h, w = _warp_input(envmap, "envmap", channels_last)
+    oh, ow = int(output_shape[0]), int(output_shape[1])
+    frames = _warp_frames(frames, b, 6, envmap.device)
+    out = torch.empty((b, c, oh, ow), dtype=torch.float32, device=envmap.device)
+    with _dev(envmap):
+        _lib.check(_lib.lib().drm_rotate_envmap(envmap.data_ptr(), frames.data_ptr(), out.data_ptr(), b, c, h, w, oh, ow, int(bool(channels_last)),
+                                                _lib.stream_ptr(envmap.device)))
+    return out
+
+
+@torch.no_grad()
+def mirimg2envmap(refimg, output_shape, frames, log_scale_interpolation=False, channels_last=False):
+    """drm_mirimg2envmap (utils/transform.py:245-284) on frames [B, 7, 3] -> [B, C, OH, OW]"""
+    refimg, b, c, h, w = _warp_input(refimg, "refimg", channels_last)
+    oh, ow = int(output_shape[0]), int(output_shape[1])
+    frames = _warp_frames(frames, b, 7, refimg.device)
+    out = torch.empty((b, c, oh, ow), dtype=torch.float32, device=refimg.device)
+    with _dev(refimg):
+        _lib.check(_lib.lib().drm_mirimg2envmap(refimg.data_ptr(), frames.data_ptr(), out.data_ptr(), b, c, h, w, oh, ow, int(bool(log_scale_interpolation)),
+                                                int(bool(channels_last)), _lib.stream_ptr(refimg.device)))
+    return out
+
+
+@torch.no_grad()
+def refmap2refimg(refmap, radius: int, channels_last=False):
+    """drm_refmap2refimg (utils/transform.py:170-198) -> (image [B, C, 2 radius, 2 radius], zero outside the disc; mask [2 radius, 2 radius] bool)"""
+    refmap, b, c, h, w = _warp_input(refmap, "refmap", channels_last)
+    res = 2 * int(radius)
+    out = torch.empty((b, c, res, res), dtype=torch.float32, device=refmap.device)
+    mask = torch.empty((res, res), dtype=torch.uint8, device=refmap.device)
+    with _dev(refmap):
+        _lib.check(_lib.lib().drm_refmap2refimg(refmap.data_ptr(), out.data_ptr(), mask.data_ptr(), b, c, h, w, int(radius), int(bool(channels_last)),
+                                                _lib.stream_ptr(refmap.device)))
+    return out, mask.bool()

@@ -351,6 +351,39 @@ int drm_hdr2ldr(const float* x, const uint8_t* mask, int HW, float alpha, float 
 int drm_resize(const float* x, float* out, int planes, int IH, int IW, int OH, int OW, int mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The rest of the reference's sphere / environment-map warps (csrc/sphere_warp.hip): one gather-and-pool kernel, a map per warp.
+ * Common to the four entries: the input is [B][C][H][W], or [B][H][W][C] when channels_last_in (what the EXR reader and the renderers
+ * give); the output is always [B][C][OH][OW]; every fetch is torch.nn.functional.grid_sample(bilinear, padding_mode="border",
+ * align_corners=False) arithmetic, so the azimuth seam is clamped, not wrapped, as in the reference.  `frames` is a device array
+ * [B][k][3] fp32, one set of frame vectors per item, built by the caller the way the reference builds them: a binormal is
+ * cross(normal, tangent), negated where the reference passes reverse_phi.  The vectors are used as given (the reference's
+ * assume_normalized): a frame that is not orthonormal warps accordingly.  Item b depends on its own input and frame alone, and the
+ * results are deterministic.  DRM_ERR_INVALID for a NULL pointer, B or C < 1 or a side outside [1, 16384]: nothing is launched.
+ * ------------------------------------------------------------------------------------------- */
+/* envmap2mirmap (utils/transform.py:201-242): a lat-long environment map and a viewer position -> the mirror reflectance map.
+ * frames [B][6][3]: top (re-orthogonalised against view_from by the caller, :217-218), view_from, cross(top, view_from) (negated for
+ * flip_horizontal); envmap_zenith, envmap_left_edge, cross(zenith, left_edge) (negated for reverse_azimuth_envmap).
+ * With mitigate_aliasing the reference samples an S x S grid (S = min(H, W) if OH < H, else max(OH, OW)) and reduces it with
+ * adaptive_avg_pool2d; here each output pixel averages its own pool window [floor(i S / OH), ceil((i + 1) S / OH)) directly and the
+ * S x S intermediate never exists: one wave per pixel when every window holds 64 samples or more, one thread per pixel otherwise.
+ * log_scale_interpolation: taps are log(max(t, 1e-7)), the mean is taken in the log domain, exp follows the pool. */
+int drm_envmap2mirmap(const float* envmap, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int mitigate_aliasing,
+                      int log_scale_interpolation, int channels_last_in, void* stream);
+/* rotate_envmap (utils/transform.py:317-363): a lat-long map re-expressed in another frame.  frames [B][6][3]: tgt_envmap_zenith,
+ * tgt_envmap_left_edge, -cross(of the two); src_envmap_zenith, src_envmap_left_edge, -cross(of the two). */
+int drm_rotate_envmap(const float* envmap, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int channels_last_in,
+                      void* stream);
+/* mirimg2envmap (utils/transform.py:245-284): an orthographic mirror-ball image -> the lat-long map.  frames [B][7][3]: envmap_zenith,
+ * envmap_left_edge, cross(of the two) (negated for reverse_azimuth); top (re-orthogonalised, :264-265), t = cross(view_from, top),
+ * cross(top, t); view_from. */
+int drm_mirimg2envmap(const float* refimg, const float* frames, float* out, int B, int C, int H, int W, int OH, int OW, int log_scale_interpolation,
+                      int channels_last_in, void* stream);
+/* refmap2refimg_torch (utils/transform.py:170-198, with gen_sphere_normals_realcentering :147-167): a reflectance map in the (theta, phi)
+ * parametrisation -> the ball image out [B][C][2 radius][2 radius]; pixels outside the disc are written 0.  mask uint8 [2 radius][2 radius]
+ * (1 inside the disc) or NULL.  radius in [1, 8192]. */
+int drm_refmap2refimg(const float* refmap, float* out, uint8_t* mask, int B, int C, int H, int W, int radius, int channels_last_in, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The forward model DRMNet inverts: reflectance maps of a sphere lit by an environment map (csrc/render.hip).
  * ------------------------------------------------------------------------------------------- */
 /* A BSDF row is canonical: z[6] = (metallic, base colour R, G, B, roughness, specular), each clipped to [0, 1] by the kernels.  The BSDF is
