@@ -10,12 +10,13 @@
 //
 // Stated once here: table_coords (the coordinates of a direction pair, fp32 in the renders and fp64 in drm_merl_eval), table_lookup (both
 // modes) and table_lane_sum, the per-normal body of both renders.  A table has no analytic lobe, so table_lane_sum cannot split the
-// integrand as normal_lane_sum does: both of its sample sets -- the Q x Q grid mapped to the GGX visible normals of the table's proxy
-// roughness alpha, and the same grid mapped to cosine-weighted directions, exactly normal_lane_sum's two constructions -- estimate the whole
+// integrand as normal_lane_sum does: both sample sets of render_shared.h -- the Q x Q grid mapped to the GGX visible normals of the table's
+// proxy roughness alpha (ggx_sample), and the same grid mapped to cosine-weighted directions (cosine_direction) -- estimate the whole
 // integrand L f (n.l), combined with the balance heuristic: a sample l of either set adds L(l) f(n, v, l) (n.l) / (Q^2 (p_s(l) + p_d(l))),
 // p_s = G1(v) D(h) / (4 n.v) at h = normalize(v + l), p_d = (n.l) / pi.  The weights of a direction sum to one, so the rule is consistent
-// for any alpha; alpha only decides where the accuracy goes.  One wave owns one pixel, its lanes split the grid, keep their partial sums in a
-// fixed order and meet in wave_sum3: bitwise reproducible, no atomics, no LDS.
+// for any alpha; alpha only decides where the accuracy goes.  No direction is constructed in this file.  The renders are the pixel kernels of
+// render_shared.h instantiated with TableMaterial: one wave owns one pixel, its lanes split the grid, keep their partial sums in a fixed order
+// and meet in wave_sum3: bitwise reproducible, no atomics, no LDS.
 #include <vector>
 
 #include "common.h"
@@ -169,122 +170,63 @@ __device__ __forceinline__ void table_sample(const float4* __restrict__ tab, int
 }
 
 // one lane's share of the radiance a surface point with unit normal n (n.z > 0) reflects toward the viewer at +z under a table: the grid
-// points q = lane, lane + lanes, ... of both sample sets, in that order, summed into acc (to be divided by Q^2).  The constructions of the
-// directions are normal_lane_sum's, with the table's proxy roughness alpha in the place of the row's.
+// points q = lane, lane + lanes, ... of both sample sets of render_shared.h, in that order, summed into acc (to be divided by Q^2), with
+// the table's proxy roughness alpha in the place of the row's; what is stated here is the balance weight of each.
 template <bool VIEW>
 __device__ __forceinline__ void table_lane_sum(const float4* __restrict__ tab, float alpha, int linear, const float* __restrict__ env, const ViewRot& rot,
                                                int EH, int EW, V3 n, int Q, int lane, int lanes, float acc[3]) {
-  const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q, a2 = alpha * alpha;
   const float cv = n.z;
   const Frame f = duff_frame(n, 1.0f);
-  float Vx = -alpha * n.x, Vy = -alpha * n.y, Vz = cv;
-  const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
-  Vx *= vinv; Vy *= vinv; Vz *= vinv;
-  const float lensq = Vx * Vx + Vy * Vy;
-  const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
-  const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
-  const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
-  const float vs = 0.5f * (1.0f + Vz);
+  const VisibleFrame vf = visible_frame(n, alpha);
   const float g1v = ggx_g1(a2, n.z, n.x * n.x + n.y * n.y, 1.0f);  // G1(v): v.h > 0 wherever it is used
   for (int q = lane; q < Q * Q; q += lanes) {
-    const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
-    const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
-    // the GGX set: h from the visible normals seen from v, l = reflect(v, h); p_s from the h it was built from
+    const GridPoint g = grid_point(q, Q, invQ);
+    // the GGX set: p_s from the h the sample was built from
     {
-      const float rs = sqrtf(u1), t1 = rs * cp;
-      const float t2 = (1.0f - vs) * sqrtf(1.0f - t1 * t1) + vs * rs * sp;
-      const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
-      const float hx = alpha * (t1 * T1x + t2 * T2x + tz * Vx), hy = alpha * (t1 * T1y + t2 * T2y + tz * Vy);
-      const float hz = fmaxf(t2 * T2z + tz * Vz, 0.0f);
-      const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
-      const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
-      const V3 h = axpy(nh, n, axpy(hy * hinv, f.bt, v3(hx * hinv * f.t.x, hx * hinv * f.t.y, hx * hinv * f.t.z)));
-      const float vh = dot3(v, h);
-      const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
-      const float cl = dot3(n, l);
-      const float D = ggx_d(a2, nh, s2h);
-      if (vh > 0.0f && cl > 0.0f && D > 0.0f) {
-        const float ps = g1v * D / (4.0f * cv), pd = cl * (1.0f / kPi);
-        table_sample<VIEW>(tab, linear, env, rot, EH, EW, n, l, cl / (ps + pd), acc);
+      const GgxSample s = ggx_sample(vf, alpha, n, f, g);
+      const float D = ggx_d(a2, s.nh, s.s2h);
+      if (s.vh > 0.0f && s.cl > 0.0f && D > 0.0f) {
+        const float ps = visible_density(g1v, D, cv), pd = s.cl * (1.0f / kPi);
+        table_sample<VIEW>(tab, linear, env, rot, EH, EW, n, s.l, s.cl / (ps + pd), acc);
       }
     }
     // the cosine set: p_s at h = normalize(v + l)
     {
       float cl;
-      const V3 l = cosine_direction(n, f, u1, sp, cp, cl);
-      V3 h = v3(l.x, l.y, l.z + 1.0f);
-      const float hinv = 1.0f / sqrtf(dot3(h, h));
-      h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
-      const float ps = g1v * ggx_d(a2, dot3(n, h), cross_sq(n, h)) / (4.0f * cv), pd = cl * (1.0f / kPi);
+      const V3 l = cosine_direction(n, f, g.u1, g.sp, g.cp, cl);
+      const V3 h = half_vector(l);
+      const float ps = visible_density(g1v, ggx_d(a2, dot3(n, h), cross_sq(n, h)), cv), pd = cl * (1.0f / kPi);
       if (cl > 0.0f) table_sample<VIEW>(tab, linear, env, rot, EH, EW, n, l, cl / (ps + pd), acc);
     }
   }
 }
 
-// The sphere of refmap_render_kernel under tables.  grid: ceil(B R^2 / 4) workgroups of 4 waves; wave = pixel (row b, i, j), lit by env[b], seen
-// through view[b], under table table_of[b] (null: table 0) with alpha[table].  out [B][3][R][R].
-template <bool VIEW>
-__global__ __launch_bounds__(256) void refmap_table_kernel(const float4* __restrict__ tables, const int32_t* __restrict__ table_of,
-                                                           const float* __restrict__ alpha, const float* __restrict__ env, const float* __restrict__ view,
-                                                           float* __restrict__ out, int B, int R, int EH, int EW, int Q, int S, int flip, int linear) {
-  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (pix >= (long long)B * R * R) return;  // (wave-uniform)
-  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)R * R)));
-  const int rem = (int)(pix - (long long)b * R * R);
-  const int i = rem / R, j = rem - (rem / R) * R;
-  const int t = table_of ? table_of[b] : 0;
-  const float4* tab = tables + (size_t)t * kTableEntries;
-  const float a = alpha[t];
-  const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
-  const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  for (int sy = 0; sy < S; ++sy) {
-    for (int sx = 0; sx < S; ++sx) {
-      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
-      table_lane_sum<VIEW>(tab, a, linear, e, rot, EH, EW, n, Q, lane, 64, acc);
-    }
+// The material of the pixel kernels (render_shared.h) for a table: row b is table table_of[b] (null: table 0) with alpha[table]; nothing joins.
+struct TableArgs {
+  const float4* tables;
+  const int32_t* table_of;
+  const float* alpha;
+  int linear;
+};
+struct TableMaterial {
+  using Args = TableArgs;
+  static constexpr bool kStacked = false;  // rows = B
+  const float4* tab;
+  float alpha;
+  int linear;
+  __device__ __forceinline__ TableMaterial(const Args& a, int, int b, int, int) : linear(a.linear) {
+    const int t = a.table_of ? a.table_of[b] : 0;
+    tab = a.tables + (size_t)t * kTableEntries;
+    alpha = a.alpha[t];
   }
-  wave_sum3(acc);
-  if (lane == 0) {
-    const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[(((size_t)b * 3 + c) * R + i) * R + j] = acc[c] * scale;
+  template <bool VIEW>
+  __device__ __forceinline__ void lane_sum(const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n, int Q, int lane, int lanes, float acc[3]) {
+    table_lane_sum<VIEW>(tab, alpha, linear, env, rot, EH, EW, n, Q, lane, lanes, acc);
   }
-}
-
-// normals_shade_kernel under tables: the same reading of the normal map (normal_map_pixel), the same drawn mask, and table_lane_sum once
-// per drawn pixel (S = 1).  image [B][3][H][W], alpha_out [B][H][W] or null.
-template <bool VIEW>
-__global__ __launch_bounds__(256) void normals_table_kernel(const float* __restrict__ normals, const unsigned char* __restrict__ mask, int Bn,
-                                                            const float4* __restrict__ tables, const int32_t* __restrict__ table_of,
-                                                            const float* __restrict__ alpha, const float* __restrict__ env, const float* __restrict__ view,
-                                                            float* __restrict__ image, float* __restrict__ alpha_out, int B, int H, int W, int EH, int EW,
-                                                            int Q, int linear) {
-  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
-  const size_t plane = (size_t)H * W;
-  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
-  const size_t at = (size_t)(pix - (long long)b * H * W);
-  V3 n = v3(0.0f, 0.0f, 0.0f);
-  const bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);  // (wave-uniform: every lane read the same pixel)
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  if (drawn) {
-    const int t = table_of ? table_of[b] : 0;
-    const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
-    const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
-    table_lane_sum<VIEW>(tables + (size_t)t * kTableEntries, alpha[t], linear, e, rot, EH, EW, n, Q, lane, 64, acc);
-    wave_sum3(acc);
-  }
-  if (lane == 0) {
-    const float scale = 1.0f / (float)(Q * Q);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) image[((size_t)b * 3 + c) * plane + at] = drawn ? acc[c] * scale : 0.0f;
-    if (alpha_out) alpha_out[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
-  }
-}
+  __device__ __forceinline__ void meet() {}
+  __device__ __forceinline__ float joined(int, float px, float) const { return px; }
+};
 
 }  // namespace
 
@@ -337,14 +279,12 @@ int launch_render_refmap_table(const float* tables, int NT, const int32_t* table
   DRM_REQUIRE(out, "render_refmap_table: out is null");
   DRM_REQUIRE(B >= 1 && B <= 65535 && R > 0 && R <= 8192, "render_refmap_table: 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192");
   DRM_TRY(check_quadrature("render_refmap_table", quad, subpixel, 16, env, EH, EW));
-  const long long blocks = pixel_blocks((long long)B * R * R);
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap_table: B R^2 too large for one launch");
+  PixelLaunch pl;
+  DRM_TRY(plan_pixel_launch("render_refmap_table", "B R^2", (long long)B * R * R, env, view, EH, EW, pl));
   DRM_TRY(check_tables("render_refmap_table", tables, NT, table_of, B, alpha, true, s));
-  // (a view only turns the environment: under a white one it changes nothing and is not read)
-  const bool with_view = env && view;
-  const auto kernel = with_view ? refmap_table_kernel<true> : refmap_table_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, reinterpret_cast<const float4*>(tables), table_of, alpha, env,
-                     with_view ? view : nullptr, out, B, R, env ? EH : 1, env ? EW : 1, quad, subpixel, flip ? 1 : 0, linear ? 1 : 0);
+  const TableArgs margs{reinterpret_cast<const float4*>(tables), table_of, alpha, linear ? 1 : 0};
+  const auto kernel = pl.view ? sphere_pixel_kernel<true, TableMaterial> : sphere_pixel_kernel<false, TableMaterial>;
+  hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, env, pl.view, out, B, B, R, pl.EH, pl.EW, quad, subpixel, flip ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
@@ -353,16 +293,12 @@ int launch_render_normals_table(const float* normals, const unsigned char* mask,
                                 const float* alpha, const float* env, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH,
                                 int EW, int quad, int linear, hipStream_t s) {
   DRM_REQUIRE(normals && image, "render_normals_table: null pointer");
-  DRM_TRY(check_quadrature("render_normals_table", quad, 1, 0, env, EH, EW));
-  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
-              "render_normals_table: 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
-  const long long blocks = pixel_blocks((long long)B * H * W);
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_normals_table: B H W too large for one launch");
+  PixelLaunch pl;
+  DRM_TRY(check_normals_launch("render_normals_table", B, H, W, Bn, quad, env, EH, EW, view, pl));
   DRM_TRY(check_tables("render_normals_table", tables, NT, table_of, B, alpha, true, s));
-  const bool with_view = env && view;
-  const auto kernel = with_view ? normals_table_kernel<true> : normals_table_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, reinterpret_cast<const float4*>(tables), table_of,
-                     alpha, env, with_view ? view : nullptr, image, alpha_out, B, H, W, env ? EH : 1, env ? EW : 1, quad, linear ? 1 : 0);
+  const TableArgs margs{reinterpret_cast<const float4*>(tables), table_of, alpha, linear ? 1 : 0};
+  const auto kernel = pl.view ? normals_pixel_kernel<true, TableMaterial> : normals_pixel_kernel<false, TableMaterial>;
+  hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, normals, mask, Bn, env, pl.view, image, alpha_out, B, H, W, pl.EH, pl.EW, quad);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -1,5 +1,5 @@
 // torch.nn.functional.grid_sample(mode="bilinear", padding_mode="border", align_corners=False) on one sample position, stated once for
-// the sphere / envmap warps of sphere_warp.hip (mirmap2envmap_kernel in transform.hip carries its own copy of the same arithmetic).
+// the sphere / envmap warps of sphere_warp.hip and for mirmap2envmap_kernel in transform.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
-// Three-vectors and the reading of a normal map, shared by the kernels that go from a normal map to an image: normals_shade_kernel
-// (render.hip), which shades every pixel's normal, and image_from_refmap_kernel (refmap.hip), which looks it up in a reflectance map.
+// Three-vectors and the reading of a normal map, shared by the kernels that go from a normal map to an image: normals_pixel_kernel
+// (render_shared.h), which shades every pixel's normal, and image_from_refmap_kernel (refmap.hip), which looks it up in a reflectance map.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -231,7 +231,7 @@ int launch_erode_mask(const unsigned char* mask, int H, int W, int k, unsigned c
 }
 
 // The inverse of the gather: the image a normal map would show if the reflectance-map model held exactly (drm_image_from_refmap).  One
-// thread per pixel (b, i, j); normal and mask as in normals_shade_kernel (normal_map_pixel).  The unit normal n is taken to texel
+// thread per pixel (b, i, j); normal and mask as in normals_pixel_kernel (normal_map_pixel).  The unit normal n is taken to texel
 // coordinates by the inverse of the sensor's parametrisation n = (cos b sin a, sin b, cos b cos a) (render.hip sensor_normal, flip 0):
 //   a = atan2f(n.x, n.z), b = asinf(min(max(n.y, -1), 1));  tj = (a / pi + 0.5) R - 0.5,  ti = (0.5 - b / pi) R - 0.5
 // and the map is read bilinearly over the taps (i0, i1) x (j0, j1) = (floor ti, floor ti + 1) x (floor tj, floor tj + 1), each index

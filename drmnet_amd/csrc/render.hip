@@ -27,8 +27,8 @@
 // there is a BVH.  drm_render_mesh_bounced runs mesh_shade_kernel<VIEW, true, false, true>: an occluded direction reads the radiance its
 // closest hit reflects back under direct light (one bounce; see Bounced).
 //
-// Object images of a normal map (drm_render_normals): normals_shade_kernel runs the same per-normal body on the normals of a normal map,
-// the input estimate's user has, with Plain or LightSampled: no mesh, no shadows.
+// Object images of a normal map (drm_render_normals): normals_pixel_kernel (render_shared.h) with Plain, or normals_lit_kernel with
+// LightSampled, runs the same per-normal body on the normals of a normal map, the input estimate's user has: no mesh, no shadows.
 //
 // One statement of the quadrature: normal_lane_sum builds both lobes once and accumulates each in one place; what differs between the
 // renders is its technique parameter (Plain, LightSampled, Occluded, LitOccluded, Bounced: see "techniques"), which decides per lobe sample whether
@@ -40,8 +40,9 @@
 // hit and the bounce's; mesh_technique builds the technique of a mesh pixel; on the host every mesh render is launch_render_mesh over one
 // MeshRenderArgs, and both lit renders share light_workspace_fault and launch_light_tables.
 //
-// The vector, frame, BSDF-term, environment-lookup, sensor, view and butterfly helpers, and the launch checks, live in render_shared.h: the
-// renders under a measured table (brdf_table.hip) use the same ones.
+// Shared with the renders under a measured table (brdf_table.hip), in render_shared.h: the vector, frame, BSDF-term, environment-lookup,
+// sensor, view and butterfly helpers; the sample sets (grid_point, visible_frame, ggx_sample, visible_density, half_vector), so that
+// normal_lane_sum holds only the lobe weights and the technique calls; the two pixel kernels, instantiated here with RowMaterial; their checks.
 #include <type_traits>
 
 #include "bvh.h"
@@ -163,9 +164,9 @@ struct Bounced : Plain {
     const Frame f = duff_frame(n, n.z >= 0.0f ? 1.0f : -1.0f);
     const float invq = 1.0f / (float)bq;
     for (int k = 0; k < bq * bq; ++k) {
-      const float u1 = ((float)(k / bq) + 0.5f) * invq, u2 = ((float)(k % bq) + 0.5f) * invq;
+      const GridPoint g = grid_point(k, bq, invq);
       float ck;
-      const V3 l = cosine_direction(n, f, u1, sinf(2.0f * kPi * u2), cosf(2.0f * kPi * u2), ck);
+      const V3 l = cosine_direction(n, f, g.u1, g.sp, g.cp, ck);
       float E[3];
       principled_eval32(p, n, wo, l, E);
       if (E[0] == 0.0f && E[1] == 0.0f && E[2] == 0.0f) continue;
@@ -227,12 +228,9 @@ struct LightSampled {
       const V3 l = from_world<VIEW>(rot, wd);
       const float cl = dot3(n, l);
       if (cl > 0.0f && pl > 0.0f && t.open(wd)) {
-        V3 h = v3(l.x, l.y, l.z + 1.0f);
-        const float hinv = 1.0f / sqrtf(dot3(h, h));
-        h = v3(h.x * hinv, h.y * hinv, h.z * hinv);
+        const V3 h = half_vector(l);
         const float vh = h.z, nh = dot3(n, h);
-        const float D = ggx_d(p.a2, nh, cross_sq(n, h));
-        const float ps = g1v * D / (4.0f * cv);
+        const float ps = visible_density(g1v, ggx_d(p.a2, nh, cross_sq(n, h)), cv);
         const float ks = ps * ggx_g1(p.a2, cl, cross_sq(n, l), dot3(l, h));  // D G / (4 n.v)
         const float kd = diffuse ? (1.0f - p.m) * cl * diffuse_shape(p.r, cl, cv, vh) * (1.0f / kPi) : 0.0f;
         const float a = nlight * pl, as = nlobe * ps, ad = diffuse ? nlobe * cl * (1.0f / kPi) : 0.0f;
@@ -270,7 +268,7 @@ struct LitOccluded : LightSampled {
 
 // one lane's share of the radiance a surface point with unit normal n (n.z > -1; the callers pass n.z > 0) reflects toward the viewer at +z:
 // the grid points q = lane, lane + lanes, ... of both lobes, summed in that order into acc (unnormalised).  env == nullptr: white
-// environment (L = 1).  The sphere (pixel_lane_sum) and the mesh (mesh_shade_kernel) share this body; TECH (above) is asked about every
+// environment (L = 1).  The pixel kernels (RowMaterial) and the mesh (mesh_shade_kernel) share this body; TECH (above) is asked about every
 // lobe sample with a non-zero weight, along to_world(rot, l), the vector the environment lookup forms.
 template <bool VIEW, typename TECH>
 __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n,
@@ -278,45 +276,24 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
   static_assert(std::is_same_v<TECH, Plain> || std::is_same_v<TECH, Occluded> || std::is_same_v<TECH, LightSampled> || std::is_same_v<TECH, LitOccluded> ||
                     std::is_same_v<TECH, Bounced>,
                 "the techniques: {no light samples, light samples} x {not traced, traced}, and traced with one bounce (no light samples)");
-  const V3 v = v3(0.0f, 0.0f, 1.0f);
   const float invQ = 1.0f / (float)Q;
   const bool diffuse = p.m < 1.0f;
   const float cv = n.z;  // n.v for v = +z
   // orthonormal frame (t, bt, n) (n.z > 0 on the whole film: the sign term is the literal 1); v = (-n.x, -n.y, n.z) in it
   const Frame f = duff_frame(n, 1.0f);
-  // visible-normal sampling frame: V = normalize(alpha v_t, alpha v_b, v_n), T1 = normalize(z x V) (x if V = z), T2 = V x T1
-  float Vx = -p.alpha * n.x, Vy = -p.alpha * n.y, Vz = cv;
-  const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
-  Vx *= vinv; Vy *= vinv; Vz *= vinv;
-  const float lensq = Vx * Vx + Vy * Vy;
-  const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
-  const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
-  const float T2x = -Vz * T1y, T2y = Vz * T1x, T2z = Vx * T1y - Vy * T1x;
-  const float vs = 0.5f * (1.0f + Vz);
+  const VisibleFrame vf = visible_frame(n, p.alpha);
   tech.begin(p, n);
   for (int q = lane; q < Q * Q; q += lanes) {
-    const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
-    const float sp = sinf(2.0f * kPi * u2), cp = cosf(2.0f * kPi * u2);
+    const GridPoint g = grid_point(q, Q, invQ);
     float L[3] = {1.0f, 1.0f, 1.0f};
-    // specular lobe: h from the GGX distribution of visible normals (Heitz 2018) seen from v, l = reflect(v, h); weight F G1(l)
+    // specular lobe: the GGX sample; weight F G1(l)
     {
-      const float rs = sqrtf(u1), t1 = rs * cp;
-      const float t2 = (1.0f - vs) * sqrtf(1.0f - t1 * t1) + vs * rs * sp;
-      const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
-      const float hx = p.alpha * (t1 * T1x + t2 * T2x + tz * Vx), hy = p.alpha * (t1 * T1y + t2 * T2y + tz * Vy);
-      const float hz = fmaxf(t2 * T2z + tz * Vz, 0.0f);
-      const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
-      const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
-      const V3 h = axpy(nh, n, axpy(hy * hinv, f.bt, v3(hx * hinv * f.t.x, hx * hinv * f.t.y, hx * hinv * f.t.z)));
-      const float vh = dot3(v, h);
-      const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
-      const float cl = dot3(n, l);
-      if (vh > 0.0f && cl > 0.0f && ggx_d(p.a2, nh, s2h) > 0.0f) {
-        float w = ggx_g1(p.a2, cl, cross_sq(n, l), vh), np = 0.0f;
-        const float fd = (1.0f - p.m) * fresnel_dielectric(vh, p.eta), sw = schlick_weight(vh);
-        // p_s(l) = G1(v) D(h) / (4 n.v): the density of l under the visible-normal sampling above
-        if constexpr (TECH::kNeedsDensity) np = tech.nlobe * (tech.g1v * ggx_d(p.a2, nh, s2h) / (4.0f * cv));
-        if (tech.take(env, EH, EW, to_world<VIEW>(rot, l), np, w, L)) {
+      const GgxSample s = ggx_sample(vf, p.alpha, n, f, g);
+      if (s.vh > 0.0f && s.cl > 0.0f && ggx_d(p.a2, s.nh, s.s2h) > 0.0f) {
+        float w = ggx_g1(p.a2, s.cl, cross_sq(n, s.l), s.vh), np = 0.0f;
+        const float fd = (1.0f - p.m) * fresnel_dielectric(s.vh, p.eta), sw = schlick_weight(s.vh);
+        if constexpr (TECH::kNeedsDensity) np = tech.nlobe * visible_density(tech.g1v, ggx_d(p.a2, s.nh, s.s2h), cv);
+        if (tech.take(env, EH, EW, to_world<VIEW>(rot, s.l), np, w, L)) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) acc[c] += (fd + p.m * (p.c[c] + (1.0f - p.c[c]) * sw)) * w * L[c];
         }
@@ -325,8 +302,9 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
     // diffuse lobe: cosine-weighted l; weight pi diff / (n.l) = (1 - m) c shape
     if (diffuse) {
       float cl;
-      const V3 l = cosine_direction(n, f, u1, sp, cp, cl);
-      V3 h = v3(l.x, l.y, l.z + 1.0f);
+      const V3 l = cosine_direction(n, f, g.u1, g.sp, g.cp, cl);
+      // (not half_vector(l).z: this lobe divides h.z by |h| where half_vector multiplies by 1 / |h|, another rounding, and a render's bits stay)
+      const V3 h = v3(l.x, l.y, l.z + 1.0f);
       const float cd = h.z / sqrtf(dot3(h, h));  // h.v for h = normalize(v + l)
       float w = (1.0f - p.m) * diffuse_shape(p.r, cl, cv, cd), np = 0.0f;
       if constexpr (TECH::kNeedsDensity) np = tech.nlobe * cl * (1.0f / kPi);  // p_d(l) = n.l / pi
@@ -339,52 +317,72 @@ __host__ __device__ __forceinline__ void normal_lane_sum(const Principled& p, co
   tech.template finish<VIEW>(p, rot, n, lane, lanes);
 }
 
-// one lane's share of pixel (i, j) of the sphere: normal_lane_sum at every sub-pixel normal, in sub-pixel order
-template <bool VIEW, typename TECH>
-__host__ __device__ __forceinline__ void pixel_lane_sum(const Principled& p, const float* __restrict__ env, const ViewRot& rot, int EH, int EW, int R,
-                                                        int i, int j, int Q, int S, int flip, int lane, int lanes, float acc[3], TECH& tech) {
-  for (int sy = 0; sy < S; ++sy) {
-    for (int sx = 0; sx < S; ++sx) {
-      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
-      normal_lane_sum<VIEW>(p, env, rot, EH, EW, n, Q, lane, lanes, acc, tech);
-    }
+// The material of the pixel kernels of render_shared.h for a principled row: row `row` of z [rows][6] under Plain, or, LIGHT, under
+// LightSampled with the light table of map b (lws: the light workspace of the B maps, M samples each), which every pixel of the map's rows
+// reads from memory, a wave's loads contiguous: it is not staged in LDS.  (Staging would tie the four waves of a workgroup, which may
+// belong to different maps and may have left at the bounds check, to barriers, and a table of M = 65536 samples, 1.8 MB, does not fit; the
+// 28 KB of M = 1024 stay cache-resident.)  accL joins the pixel after the butterfly, divided by S^2 only.  Without LIGHT: the row alone.
+struct RowArgs {
+  const float* z;
+};
+struct LitRowArgs {
+  const float* z;
+  const char* lws;
+  int M;
+};
+template <bool LIGHT>
+struct RowMaterial {
+  using Args = std::conditional_t<LIGHT, LitRowArgs, RowArgs>;
+  static constexpr bool kStacked = true;  // rows = L B
+  Principled p;
+  std::conditional_t<LIGHT, LightSampled, Plain> tech;
+  __device__ __forceinline__ RowMaterial(const Args& a, int row, int b, int EH, int Q) : p(principled(a.z + 6 * (size_t)row)) {
+    if constexpr (LIGHT) tech = light_sampled(light_table(a.lws, b, EH, a.M), EH, Q);
   }
-}
+  template <bool VIEW>
+  __device__ __forceinline__ void lane_sum(const float* __restrict__ env, const ViewRot& rot, int EH, int EW, V3 n, int Q, int lane, int lanes, float acc[3]) {
+    normal_lane_sum<VIEW>(p, env, rot, EH, EW, n, Q, lane, lanes, acc, tech);
+  }
+  __device__ __forceinline__ void meet() {
+    if constexpr (LIGHT) wave_sum3(tech.accL);
+  }
+  __device__ __forceinline__ float joined(int c, float px, float inv_s2) const {
+    if constexpr (LIGHT) return px + tech.accL[c] * inv_s2;
+    else return px;
+  }
+};
 
-// grid: ceil(L B R^2 / 4) workgroups of 4 waves; wave = pixel (row, i, j), row = l B + b lit by env[b] and seen through view[b];
-// z [L][B][6], out [L][B][3][R][R].  Every row runs the same per-lane order whatever L is, so a stacked render equals its rows rendered alone.
-// LIGHT: lws is the light workspace of the B maps (M samples each).  The table of map b is read from memory by every pixel of its L rows, a
-// wave's loads contiguous: it is not staged in LDS.  (Staging would tie the four waves of a workgroup, which may belong to different maps
-// and may have left at the bounds check, to barriers, and a table of M = 65536 samples, 1.8 MB, does not fit; the 28 KB of M = 1024 stay
-// cache-resident across the map's pixels.)
-template <bool VIEW, bool LIGHT>
-__global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
-                                                            float* __restrict__ out, int rows, int B, int R, int EH, int EW, int Q, int S, int flip,
-                                                            const char* __restrict__ lws, int M) {
+// The lit normal map keeps a kernel of its own: normals_pixel_kernel's pixel (render_shared.h: the same reading of the normal map, drawn rule
+// and stores) with LightSampled, the light table's header read ahead of the drawn test and the row inside it.  As an instantiation of the
+// shared kernel it measured 0.05 .. 0.17 % slower than this in every run, more than two copies of one library differ.
+template <bool VIEW>
+__global__ __launch_bounds__(256) void normals_lit_kernel(const float* __restrict__ normals, const unsigned char* __restrict__ mask, int Bn,
+                                                          const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
+                                                          float* __restrict__ image, float* __restrict__ alpha, int B, int H, int W, int EH, int EW, int Q,
+                                                          const char* __restrict__ lws, int M) {
   const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (pix >= (long long)rows * R * R) return;  // (wave-uniform)
-  const int row = (int)(pix / ((long long)R * R));
-  const int rem = (int)(pix - (long long)row * R * R);
-  const int i = rem / R, j = rem - (rem / R) * R;
-  const int b = __builtin_amdgcn_readfirstlane(row % B);  // (a wave is one pixel: the map and the view matrix are fetched through scalar loads)
-  const Principled p = principled(z + 6 * (size_t)row);
-  const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
-  const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
+  const size_t plane = (size_t)H * W;
+  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
+  const size_t at = (size_t)(pix - (long long)b * H * W);
+  V3 n = v3(0.0f, 0.0f, 0.0f);
+  const bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);  // (wave-uniform: every lane read the same pixel)
   float acc[3] = {0.0f, 0.0f, 0.0f};
-  std::conditional_t<LIGHT, LightSampled, Plain> tech;
-  if constexpr (LIGHT) tech = light_sampled(light_table(lws, b, EH, M), EH, Q);
-  pixel_lane_sum<VIEW>(p, e, rot, EH, EW, R, i, j, Q, S, flip, lane, 64, acc, tech);
-  wave_sum3(acc);
-  if constexpr (LIGHT) wave_sum3(tech.accL);
+  LightSampled tech = light_sampled(light_table(lws, b, EH, M), EH, Q);
+  if (drawn) {
+    const Principled p = principled(z + 6 * (size_t)b);
+    const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+    const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+    normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
+    wave_sum3(acc);
+    wave_sum3(tech.accL);
+  }
   if (lane == 0) {
-    const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
+    const float scale = 1.0f / (float)(Q * Q);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float px = acc[c] * scale;
-      if constexpr (LIGHT) px = px + tech.accL[c] * (1.0f / (float)(S * S));
-      out[(((size_t)row * 3 + c) * R + i) * R + j] = px;
-    }
+    for (int c = 0; c < 3; ++c) image[((size_t)b * 3 + c) * plane + at] = drawn ? acc[c] * scale + tech.accL[c] : 0.0f;
+    if (alpha) alpha[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
   }
 }
 
@@ -399,7 +397,7 @@ __global__ __launch_bounds__(256) void refmap_render_kernel(const float* __restr
 // the sphere's lit kernel.
 // SHADOW: every direction of a hit sample is traced from the hit point -- the view-space (x_sample, y_sample, z_hit) taken to object
 // space with Rot -- through the BVH in sh, the hit face excluded.  Without it sh is an empty struct and the kernel is the one it always was.
-// LIGHT: li holds the light workspace of the B maps (M samples each; see refmap_render_kernel on why the table is not staged in LDS).
+// LIGHT: li holds the light workspace of the B maps (M samples each; see RowMaterial on why the table is not staged in LDS).
 // Without it li is an empty struct.
 // BOUNCE (with SHADOW, without LIGHT): the technique is Bounced instead of Occluded; bo holds bounce_quad.  Without it bo is an empty struct.
 struct NoShadowArgs {};
@@ -658,49 +656,6 @@ __global__ __launch_bounds__(256) void brdf_eval_kernel(const float* __restrict_
   }
 }
 
-// Shading of a normal map (drm_render_normals): the image estimate's user has, normal map -> image, with no mesh behind it.  grid:
-// ceil(B H W / 4) workgroups of 4 waves; wave = pixel (row b, i, j), lit by env[b] and seen through view[b] (which turns the environment
-// lookups only: the normals are already in the view frame).  The wave reads the normal of map bn = (Bn == 1 ? 0 : b) through one address (a
-// broadcast), normalises it (normal_map_pixel) and, where the pixel is drawn, runs the sphere's normal_lane_sum once: the Q x Q grids,
-// per-lane order, butterfly and finish of refmap_render_kernel with S = 1, so a pixel is shaded exactly as the sphere point and the mesh
-// hit with that normal.  A pixel that is not drawn gets image 0 and alpha 0 (wave-uniform).  LIGHT: lws is the light workspace of the B
-// maps (M samples each), as in refmap_render_kernel.  No LDS, no scratch, no atomics.
-template <bool VIEW, bool LIGHT>
-__global__ __launch_bounds__(256) void normals_shade_kernel(const float* __restrict__ normals, const unsigned char* __restrict__ mask, int Bn,
-                                                            const float* __restrict__ z, const float* __restrict__ env, const float* __restrict__ view,
-                                                            float* __restrict__ image, float* __restrict__ alpha, int B, int H, int W, int EH, int EW, int Q,
-                                                            const char* __restrict__ lws, int M) {
-  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
-  const size_t plane = (size_t)H * W;
-  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
-  const size_t at = (size_t)(pix - (long long)b * H * W);
-  V3 n = v3(0.0f, 0.0f, 0.0f);
-  const bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);  // (wave-uniform: every lane read the same pixel)
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  std::conditional_t<LIGHT, LightSampled, Plain> tech;
-  if constexpr (LIGHT) tech = light_sampled(light_table(lws, b, EH, M), EH, Q);
-  if (drawn) {
-    const Principled p = principled(z + 6 * (size_t)b);
-    const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
-    const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
-    normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
-    wave_sum3(acc);
-    if constexpr (LIGHT) wave_sum3(tech.accL);
-  }
-  if (lane == 0) {
-    const float scale = 1.0f / (float)(Q * Q);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float px = acc[c] * scale;
-      if constexpr (LIGHT) px = px + tech.accL[c];
-      image[((size_t)b * 3 + c) * plane + at] = drawn ? px : 0.0f;
-    }
-    if (alpha) alpha[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
-  }
-}
-
 }  // namespace
 
 static bool light_samples_ok(int M) { return M >= 64 && M <= 65536 && (M & (M - 1)) == 0; }
@@ -743,15 +698,15 @@ int launch_render_refmap_lit(const float* z, int L, const float* env, const floa
       return DRM_ERR_WORKSPACE;
     }
   }
-  const long long blocks = pixel_blocks((long long)L * B * R * R);
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_refmap: L B R^2 too large for one launch");
+  PixelLaunch pl;
+  DRM_TRY(plan_pixel_launch("render_refmap", "L B R^2", (long long)L * B * R * R, env, view, EH, EW, pl));
   if (lit) launch_light_tables(env, ws, B, EH, EW, light_samples, s);
-  // (a view only turns the environment: under a white one it changes nothing and is not read)
-  const bool with_view = env && view;
-  const auto kernel = lit ? (with_view ? refmap_render_kernel<true, true> : refmap_render_kernel<false, true>)
-                          : (with_view ? refmap_render_kernel<true, false> : refmap_render_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, z, env, with_view ? view : nullptr, out, L * B, B, R, env ? EH : 1,
-                     env ? EW : 1, quad, subpixel, flip ? 1 : 0, ws, lit ? light_samples : 0);
+  const auto launch = [&](auto kernel, auto margs) {
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, env, pl.view, out, L * B, B, R, pl.EH, pl.EW, quad, subpixel,
+                       flip ? 1 : 0);
+  };
+  if (lit) launch(pl.view ? sphere_pixel_kernel<true, RowMaterial<true>> : sphere_pixel_kernel<false, RowMaterial<true>>, LitRowArgs{z, ws, light_samples});
+  else launch(pl.view ? sphere_pixel_kernel<true, RowMaterial<false>> : sphere_pixel_kernel<false, RowMaterial<false>>, RowArgs{z});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
@@ -819,11 +774,8 @@ int launch_render_normals(const float* normals, const unsigned char* mask, int B
   DRM_REQUIRE(normals && z && image, "render_normals: null pointer");
   DRM_REQUIRE(light_samples >= 0, "render_normals: light_samples >= 0");
   const bool lit = light_samples > 0 && env;
-  DRM_TRY(check_quadrature("render_normals", quad, 1, 0, env, EH, EW));
-  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
-              "render_normals: 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
-  const long long blocks = pixel_blocks((long long)B * H * W);
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_normals: B H W too large for one launch");
+  PixelLaunch pl;
+  DRM_TRY(check_normals_launch("render_normals", B, H, W, Bn, quad, env, EH, EW, view, pl));
   char* lws = lit ? static_cast<char*>(light_workspace) : nullptr;
   if (lit) {
     DRM_REQUIRE(light_samples_ok(light_samples), "render_normals: light_samples must be 0 or a power of two in [64, 65536]");
@@ -832,12 +784,15 @@ int launch_render_normals(const float* normals, const unsigned char* mask, int B
     DRM_REQUIRE(fault.empty(), fault);
     launch_light_tables(env, lws, B, EH, EW, light_samples, s);
   }
-  // (a view only turns the environment: under a white one it changes nothing and is not read)
-  const bool with_view = env && view;
-  const auto kernel = lit ? (with_view ? normals_shade_kernel<true, true> : normals_shade_kernel<false, true>)
-                          : (with_view ? normals_shade_kernel<true, false> : normals_shade_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, z, env, with_view ? view : nullptr, image, alpha, B, H,
-                     W, env ? EH : 1, env ? EW : 1, quad, lws, lit ? light_samples : 0);
+  if (lit) {
+    const auto kernel = pl.view ? normals_lit_kernel<true> : normals_lit_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, z, env, pl.view, image, alpha, B, H, W, pl.EH, pl.EW, quad,
+                       lws, light_samples);
+  } else {
+    const auto kernel = pl.view ? normals_pixel_kernel<true, RowMaterial<false>> : normals_pixel_kernel<false, RowMaterial<false>>;
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, RowArgs{z}, normals, mask, Bn, env, pl.view, image, alpha, B, H, W, pl.EH, pl.EW,
+                       quad);
+  }
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -1,8 +1,8 @@
 // What the per-normal sums of render.hip (normal_lane_sum: a principled row) and brdf_table.hip (table_lane_sum: a measured table) share:
-// the three-vector helpers, the frame about a normal and the cosine-weighted direction, the principled row with its GGX, Fresnel and diffuse
-// terms and their eval, the environment lookup (env_taps + bilerp), the sensor's normals, the view rotation, the wave butterfly, and the
-// checks and grid of a pixel kernel's launch.  Everything device-side sits in an unnamed namespace, as it did inside render.hip: every
-// translation unit gets its own copy, and render.hip's kernels compile to the instructions they had.
+// the three-vector helpers, the frame about a normal and the cosine-weighted direction, the sample sets (the grid point, the visible-normal
+// frame, the GGX sample, its density, the half vector), the principled row with its GGX, Fresnel and diffuse terms and their eval, the
+// environment lookup (env_taps + bilerp), the sensor's normals, the view rotation and the wave butterfly; the two pixel kernels, templates
+// over the material that each source instantiates with its own; and the checks and grid of their launches.  (Device side: unnamed namespace.)
 #pragma once
 #include <string>
 
@@ -45,6 +45,57 @@ __host__ __device__ __forceinline__ V3 cosine_direction(V3 n, const Frame& f, fl
   const float rs = sqrtf(u1);
   cl = sqrtf(1.0f - u1);
   return axpy(cl, n, axpy(rs * sp, f.bt, v3(rs * cp * f.t.x, rs * cp * f.t.y, rs * cp * f.t.z)));
+}
+
+// The sample sets of a normal seen from v = +z, for normal_lane_sum and table_lane_sum; every operation and its order is part of a render's bits.
+// the point of index q of a Q x Q midpoint grid, (u1, u2) = ((q / Q + 1/2) / Q, (q % Q + 1/2) / Q), as (u1, sin 2 pi u2, cos 2 pi u2); invQ = 1 / Q
+struct GridPoint {
+  float u1, sp, cp;
+};
+__host__ __device__ __forceinline__ GridPoint grid_point(int q, int Q, float invQ) {
+  const float u1 = ((float)(q / Q) + 0.5f) * invQ, u2 = ((float)(q % Q) + 0.5f) * invQ;
+  return GridPoint{u1, sinf(2.0f * kPi * u2), cosf(2.0f * kPi * u2)};
+}
+// visible-normal sampling frame about (n, alpha): V = normalize(alpha v_t, alpha v_b, v_n), T1 = normalize(z x V) (x if V = z), T2 = V x T1
+struct VisibleFrame {
+  float Vx, Vy, Vz, T1x, T1y, T2x, T2y, T2z, vs;
+};
+__host__ __device__ __forceinline__ VisibleFrame visible_frame(V3 n, float alpha) {
+  float Vx = -alpha * n.x, Vy = -alpha * n.y, Vz = n.z;
+  const float vinv = 1.0f / sqrtf(Vx * Vx + Vy * Vy + Vz * Vz);
+  Vx *= vinv; Vy *= vinv; Vz *= vinv;
+  const float lensq = Vx * Vx + Vy * Vy;
+  const float tinv = lensq > 0.0f ? 1.0f / sqrtf(lensq) : 0.0f;
+  const float T1x = lensq > 0.0f ? -Vy * tinv : 1.0f, T1y = lensq > 0.0f ? Vx * tinv : 0.0f;
+  return VisibleFrame{Vx, Vy, Vz, T1x, T1y, -Vz * T1y, Vz * T1x, Vx * T1y - Vy * T1x, 0.5f * (1.0f + Vz)};
+}
+// The GGX sample of a grid point: h from the distribution of visible normals (Heitz 2018) seen from v = +z, l = reflect(v, h); nh = n.h,
+// s2h = 1 - nh^2 from the components (no cancellation), vh = v.h, cl = n.l.  f = duff_frame(n, 1).  The caller keeps it where vh > 0, cl > 0, D > 0.
+struct GgxSample {
+  V3 l;
+  float nh, s2h, vh, cl;
+};
+__host__ __device__ __forceinline__ GgxSample ggx_sample(const VisibleFrame& vf, float alpha, V3 n, const Frame& f, const GridPoint& g) {
+  const V3 v = v3(0.0f, 0.0f, 1.0f);
+  const float rs = sqrtf(g.u1), t1 = rs * g.cp;
+  const float t2 = (1.0f - vf.vs) * sqrtf(1.0f - t1 * t1) + vf.vs * rs * g.sp;
+  const float tz = sqrtf(fmaxf(1.0f - t1 * t1 - t2 * t2, 0.0f));
+  const float hx = alpha * (t1 * vf.T1x + t2 * vf.T2x + tz * vf.Vx), hy = alpha * (t1 * vf.T1y + t2 * vf.T2y + tz * vf.Vy);
+  const float hz = fmaxf(t2 * vf.T2z + tz * vf.Vz, 0.0f);
+  const float hinv = 1.0f / sqrtf(hx * hx + hy * hy + hz * hz);
+  const float nh = hz * hinv, s2h = (hx * hx + hy * hy) * hinv * hinv;
+  const V3 h = axpy(nh, n, axpy(hy * hinv, f.bt, v3(hx * hinv * f.t.x, hx * hinv * f.t.y, hx * hinv * f.t.z)));
+  const float vh = dot3(v, h);
+  const V3 l = axpy(2.0f * vh, h, v3(-v.x, -v.y, -v.z));
+  return GgxSample{l, nh, s2h, vh, dot3(n, l)};
+}
+// p_s(l) = G1(v) D(h) / (4 n.v): the density of l = reflect(v, h) under the visible-normal sampling
+__host__ __device__ __forceinline__ float visible_density(float g1v, float D, float cv) { return g1v * D / (4.0f * cv); }
+// normalize(v + l) for v = +z, in the form (v + l) * (1 / |v + l|)
+__host__ __device__ __forceinline__ V3 half_vector(V3 l) {
+  const V3 h = v3(l.x, l.y, l.z + 1.0f);
+  const float hinv = 1.0f / sqrtf(dot3(h, h));
+  return v3(h.x * hinv, h.y * hinv, h.z * hinv);
 }
 
 // canonical row (metallic, base colour R G B, roughness, specular), clipped to [0, 1] as get_bsdf / _render_scene clip
@@ -230,6 +281,80 @@ __device__ __forceinline__ void wave_sum3(float a[3]) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ pixel kernels
+// The two pixel kernels, stated once for every material.  One wave owns one pixel: its lanes split the Q x Q grid, keep their partial sums in
+// a fixed order and meet in wave_sum3.  MAT is what a row is and how one lane shades one normal under it (RowMaterial in render.hip: a
+// principled row with Plain or LightSampled; TableMaterial in brdf_table.hip): MAT::Args, its launch arguments, one small struct passed by
+// value; MAT(args, row, b, EH, Q), the material of row `row` lit by map b; lane_sum<VIEW>(...), one lane's share of normal n summed into acc
+// (unnormalised); meet(), the butterfly of what it summed beside acc, if anything; joined(c, px, inv_s2), channel c of the pixel with that
+// sum joined to px = acc[c] / (S^2 Q^2).  Every difference between materials is a type: no kernel holds state or a branch of another's.
+
+// The sphere.  grid: ceil(rows R^2 / 4) workgroups of 4 waves; wave = pixel (row, i, j), row = l B + b lit by env[b], seen through view[b];
+// out [rows][3][R][R].  Every row runs the same per-lane order whatever L is: a stacked render (rows = L B) equals its rows rendered alone.
+template <bool VIEW, typename MAT>
+__global__ __launch_bounds__(256) void sphere_pixel_kernel(typename MAT::Args margs, const float* __restrict__ env, const float* __restrict__ view,
+                                                           float* __restrict__ out, int rows, int B, int R, int EH, int EW, int Q, int S, int flip) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)rows * R * R) return;  // (wave-uniform)
+  // (a wave is one pixel: the map and the view matrix are fetched through scalar loads.  A material without stacks, rows = B, has row = b:
+  // it pays for no modulo and its row is wave-uniform too, as in the kernel it had of its own)
+  const int at = (int)(pix / ((long long)R * R));
+  const int row = MAT::kStacked ? at : __builtin_amdgcn_readfirstlane(at);
+  const int b = MAT::kStacked ? __builtin_amdgcn_readfirstlane(at % B) : row;
+  const int rem = (int)(pix - (long long)row * R * R);
+  const int i = rem / R, j = rem - (rem / R) * R;
+  MAT mat(margs, row, b, EH, Q);
+  const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+  const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  for (int sy = 0; sy < S; ++sy) {
+    for (int sx = 0; sx < S; ++sx) {
+      const V3 n = sensor_normal(((float)j + ((float)sx + 0.5f) / (float)S) / (float)R, ((float)i + ((float)sy + 0.5f) / (float)S) / (float)R, flip);
+      mat.template lane_sum<VIEW>(e, rot, EH, EW, n, Q, lane, 64, acc);
+    }
+  }
+  wave_sum3(acc);
+  mat.meet();
+  if (lane == 0) {
+    const float scale = 1.0f / ((float)(S * S) * (float)(Q * Q));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(((size_t)row * 3 + c) * R + i) * R + j] = mat.joined(c, acc[c] * scale, 1.0f / (float)(S * S));
+  }
+}
+
+// A normal map (no mesh behind it).  grid: ceil(B H W / 4) workgroups of 4 waves; wave = pixel (row b, i, j), lit by env[b]; view[b] turns
+// the environment lookups only (the normals are in the view frame).  The wave reads the normal of map (Bn == 1 ? 0 : b) through one address
+// (normal_map_pixel) and, where the pixel is drawn, runs lane_sum once: the sphere's pixel with S = 1.  Not drawn: image 0, alpha 0 (wave-uniform).
+template <bool VIEW, typename MAT>
+__global__ __launch_bounds__(256) void normals_pixel_kernel(typename MAT::Args margs, const float* __restrict__ normals, const unsigned char* __restrict__ mask,
+                                                            int Bn, const float* __restrict__ env, const float* __restrict__ view, float* __restrict__ image,
+                                                            float* __restrict__ alpha, int B, int H, int W, int EH, int EW, int Q) {
+  const long long pix = (long long)blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pix >= (long long)B * H * W) return;  // (wave-uniform)
+  const size_t plane = (size_t)H * W;
+  const int b = __builtin_amdgcn_readfirstlane((int)(pix / ((long long)H * W)));
+  const size_t at = (size_t)(pix - (long long)b * H * W);
+  V3 n = v3(0.0f, 0.0f, 0.0f);
+  const bool drawn = normal_map_pixel(normals, mask, (Bn == 1 ? 0 : (size_t)b * plane) + at, n);  // (wave-uniform: every lane read the same pixel)
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  MAT mat(margs, b, b, EH, Q);  // (ahead of the drawn test: what the material reads is under way while the normal is)
+  if (drawn) {
+    const float* e = env ? env + (size_t)b * EH * EW * 3 : nullptr;
+    const ViewRot rot = view_rot(VIEW ? view + 9 * (size_t)b : nullptr);
+    mat.template lane_sum<VIEW>(e, rot, EH, EW, n, Q, lane, 64, acc);
+    wave_sum3(acc);
+    mat.meet();
+  }
+  if (lane == 0) {
+    const float scale = 1.0f / (float)(Q * Q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) image[((size_t)b * 3 + c) * plane + at] = drawn ? mat.joined(c, acc[c] * scale, 1.0f) : 0.0f;
+    if (alpha) alpha[(size_t)b * plane + at] = drawn ? 1.0f : 0.0f;
+  }
+}
+
 }  // namespace
 
 // What every launch of a pixel kernel checks of its quadrature and environment (`who` names the entry in the message; subpixel_max = 0: the
@@ -241,5 +366,28 @@ static inline int check_quadrature(const std::string& who, int quad, int subpixe
   return DRM_OK;
 }
 static inline long long pixel_blocks(long long pixels) { return (pixels + kRenderWaves - 1) / kRenderWaves; }
+
+// What the launches of a pixel kernel share whatever the material: the grid, and the environment as the kernel sees it (a view only turns
+// it, so under a white one, nominally 1 x 1, view is null and the kernel the one without it).  `size` names the pixel count in the message.
+struct PixelLaunch {
+  unsigned blocks;
+  const float* view;
+  int EH, EW;
+};
+static inline int plan_pixel_launch(const std::string& who, const char* size, long long pixels, const float* env, const float* view, int EH, int EW,
+                                    PixelLaunch& pl) {
+  const long long blocks = pixel_blocks(pixels);
+  DRM_REQUIRE(blocks <= 0x7fffffffLL, who + ": " + size + " too large for one launch");
+  pl = PixelLaunch{(unsigned)blocks, env ? view : nullptr, env ? EH : 1, env ? EW : 1};
+  return DRM_OK;
+}
+// the normal-map kernel's launches (the sphere's two bound their rows differently and say so in their own words: they share plan_pixel_launch)
+static inline int check_normals_launch(const std::string& who, int B, int H, int W, int Bn, int quad, const float* env, int EH, int EW, const float* view,
+                                       PixelLaunch& pl) {
+  DRM_TRY(check_quadrature(who, quad, 1, 0, env, EH, EW));
+  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
+              who + ": 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
+  return plan_pixel_launch(who, "B H W", (long long)B * H * W, env, view, EH, EW, pl);
+}
 
 }  // namespace drm

@@ -9,6 +9,7 @@
 // One launch applies a whole chain of maps per element (the reference makes one pass over the tensor per map); the two
 // data-dependent pieces -- the masked min/max of `normalizedLogarithmic` and the luminance mean -- are one workgroup per image.
 #include "common.h"
+#include "grid_sample.h"
 
 namespace drm {
 
@@ -180,8 +181,8 @@ int launch_luminance_scale(const float* x, int B, int HW, float scaler, float* s
 // ------------------------------------------------------------------------------------------------ mirror map -> envmap
 // mirmap2envmap (utils/transform.py:106-144) with view = +z, top = +y, zenith = +y, left edge = -z, reverse_azimuth: the
 // envmap texel (i, j) looks along d(theta_i, phi_j); the mirror ball shows it at the pixel whose normal is the half vector
-// n = normalize(d + view); (theta, phi) of n about (top, view) give the sample position, fetched with torch's
-// grid_sample(bilinear, padding_mode="border", align_corners=False) arithmetic.  Optionally divides by basis_r0 first
+// n = normalize(d + view); (theta, phi) of n about (top, view) give the sample position, fetched through grid_sample_taps
+// (grid_sample.h: torch's grid_sample(bilinear, padding_mode="border", align_corners=False) arithmetic).  Optionally divides by basis_r0 first
 // (DRMNet.r0toenvmap, models/drmnet.py:931-941) and stores channels-last ([B,OH,OW,C], what r0toenvmap returns).
 __global__ __launch_bounds__(256) void mirmap2envmap_kernel(const float* __restrict__ mir, const float* __restrict__ basis, float* __restrict__ out,
                                                             int B, int C, int H, int W, int OH, int OW, int log_interp, int nhwc) {
@@ -197,28 +198,22 @@ __global__ __launch_bounds__(256) void mirmap2envmap_kernel(const float* __restr
   nx /= len; ny /= len; nz /= len;
   const float u = atan2f(nx, nz) * (2.0f / PI);
   const float v = acosf(ny) * (2.0f / PI) - 1.0f;
-  // grid_sample: unnormalise (align_corners = False), clip to the border, bilinear
-  float ix = ((u + 1.0f) * (float)W - 1.0f) / 2.0f, iy = ((v + 1.0f) * (float)H - 1.0f) / 2.0f;
-  ix = fminf((float)(W - 1), fmaxf(ix, 0.0f));
-  iy = fminf((float)(H - 1), fmaxf(iy, 0.0f));
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-  const float wx1 = ix - fx, wy1 = iy - fy, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
-  const float w00 = wx0 * wy0, w01 = wx1 * wy0, w10 = wx0 * wy1, w11 = wx1 * wy1;  // (nw, ne, sw, se)
+  const BilinearTaps t = grid_sample_taps(u, v, H, W);
+  const int x0 = t.x0, y0 = t.y0, x1 = x0 + 1, y1 = y0 + 1;
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
     for (int c = 0; c < C; ++c) {
       const float* p = mir + ((size_t)b * C + c) * H * W;
       const float* q = basis ? basis + (size_t)c * H * W : nullptr;
       auto at = [&](int y, int x) {
-        float t = p[y * W + x];
-        if (q) t = t / q[y * W + x];
-        return log_interp ? logf(fmaxf(t, 1e-7f)) : t;
+        float m = p[y * W + x];
+        if (q) m = m / q[y * W + x];
+        return log_interp ? logf(fmaxf(m, 1e-7f)) : m;
       };
       float acc = 0.f;
-      acc += at(y0, x0) * w00;
-      if (x1 < W) acc += at(y0, x1) * w01;
-      if (y1 < H) acc += at(y1, x0) * w10;
-      if (x1 < W && y1 < H) acc += at(y1, x1) * w11;
+      acc += at(y0, x0) * t.w00;
+      if (t.has_x1) acc += at(y0, x1) * t.w01;
+      if (t.has_y1) acc += at(y1, x0) * t.w10;
+      if (t.has_x1 && t.has_y1) acc += at(y1, x1) * t.w11;
       if (log_interp) acc = expf(acc);
       if (nhwc) out[(((size_t)b * OH + i) * OW + j) * C + c] = acc;
       else out[(((size_t)b * C + c) * OH + i) * OW + j] = acc;

@@ -1,4 +1,4 @@
-"""Object images from a normal map -- the forward model pointed at ``estimate``'s own inputs -- on normals_shade_kernel (csrc/render.hip)
+"""Object images from a normal map -- the forward model pointed at ``estimate``'s own inputs -- on normals_pixel_kernel (csrc/render_shared.h)
 and image_from_refmap_kernel (csrc/refmap.hip).
 
     python -m drmnet_amd.relight --input_normal N.npy [--input_mask M.png] [--envmap E.exr] (--z m R G B r s | --merl material.binary)

@@ -586,7 +586,7 @@ int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_n
  *   A pixel is not drawn -- image 0, alpha 0 -- where the mask is 0, where the normal is zero or has a NaN or infinite component, and
  *   where n.z <= 0 (it does not face the viewer at +z).  image [B][3][H][W]; alpha [B][H][W], 1.0 where drawn, may be NULL.
  *   Limits: 1 <= B <= 65535, H and W in [1, 4096].
- * drm_render_normals (csrc/render.hip, normals_shade_kernel): every drawn pixel is the radiance its normal reflects toward +z under row b's
+ * drm_render_normals (csrc/render_shared.h, normals_pixel_kernel): every drawn pixel is the radiance its normal reflects toward +z under row b's
  *   BSDF z[b] (z [B][6]) and envmap[b] ([B][EH][EW][3] or NULL: white), exactly as drm_render_refmap_views shades the sphere point and
  *   drm_render_mesh the mesh hit with that normal: one wave per pixel, the same quad x quad grids, per-lane order and butterfly, subpixel = 1.
  *   view [B][9] or NULL: the rotations of drm_render_refmap_views.  They turn the environment lookups only (a lobe direction l is looked up

@@ -1,4 +1,4 @@
-"""float64 numpy restatement of the normal-map images (drm_render_normals: normals_shade_kernel in drmnet_amd/csrc/render.hip;
+"""float64 numpy restatement of the normal-map images (drm_render_normals: normals_pixel_kernel in drmnet_amd/csrc/render_shared.h;
 drm_image_from_refmap: image_from_refmap_kernel in csrc/refmap.hip), written from include/drmnet_hip.h.  No new physics: shading is
 mesh_ref.sample_radiance on the unit normals, the lit form light_ref._mis_rows with light_ref.light_table, and the lookup is the header's
 formulas.  Used by tests/test_relight_cpu.py and tests/test_gpu_relight.py; nothing here touches a GPU.

@@ -1,4 +1,4 @@
-"""Object images from a normal map on the GPU (drm_render_normals: normals_shade_kernel in csrc/render.hip; drm_image_from_refmap:
+"""Object images from a normal map on the GPU (drm_render_normals: normals_pixel_kernel in csrc/render_shared.h; drm_image_from_refmap:
 image_from_refmap_kernel in csrc/refmap.hip; through drmnet_amd.relight and the two command lines) against the float64 restatement
 tests/relight_ref.py.
 

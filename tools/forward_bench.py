@@ -7,6 +7,11 @@
         stacked entry point, e.g. the parent commit's built with tools/build_variant.sh, runs the expanded form only).
         --light_samples M also times the same stacked rows through drm_render_refmap_lit (the density and table launches included; under
         `rocprofv3 --kernel-trace --stats` the three light kernels and the render show on their own).
+    python tools/forward_bench.py render --entries --libs - A.so B.so [--reps 10 --rounds 2] [--mesh_batch 4] [--match table normals]
+        one call each of drm_render_refmap_views / _lit / _table, drm_render_normals (plain and lit) / _table and the four mesh entries at
+        B rows, 128 x 128, maps 128 x 256, quad 32, subpixel 2, M = 1024, a mesh of 20 480 faces; device events, the libraries alternating
+        in every round, and whether every library wrote the same bits.  Two copies of one library under two names give the spread that a
+        difference between two libraries has to exceed.
     python tools/forward_bench.py step [--batch 20]
         one DRMNet.validation_step at full width (synthetic weights, 128 x 128, 128 x 256 maps) split into forward process (renders +
         transforms), networks and loss by device events.  Run it under `rocprofv3 --kernel-trace --stats -- python ...` for the kernel table.
@@ -44,6 +49,8 @@ def timed(fn, reps):
 def bench_render(args):
     from drmnet_amd import _lib
 
+    if args.entries:
+        return bench_entries(args)
     dev = torch.device("cuda:0")
     L, B, R = args.stack, args.batch, 128
     libs = []
@@ -98,6 +105,99 @@ def bench_render(args):
             ms = sorted(ms)
             print(f"maps {EH}x{EW} L={L} B={B} R={R}  [{name}] {form}: median {ms[len(ms) // 2]:.2f} ms  min {ms[0]:.2f}  max {ms[-1]:.2f}  (n={len(ms)})", flush=True)
         del env
+
+
+def bench_entries(args):
+    """render --entries: the table, normal-map and mesh entries (and the sphere's, plain and lit), per library, alternating in every round"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mesh_ref
+
+    from drmnet_amd import _lib
+    from drmnet_amd.merl import MeasuredBSDF, device_tables
+    from drmnet_amd.mesh import build_bvh
+    from drmnet_amd.render import get_bsdf, view_rotation
+
+    dev = torch.device("cuda:0")
+    B, Bm, R, EH, EW, Q, S, M = args.batch, args.mesh_batch or args.batch, 128, 128, 256, 32, 2, args.light_samples or 1024
+    names = ["metallic.value", "base_color.value.R", "base_color.value.G", "base_color.value.B", "roughness.value", "specular"]
+    libs = [(path, C.CDLL(_lib.LIB_PATH if path == "-" else os.path.join(ROOT, path))) for path in args.libs]
+    g = torch.Generator().manual_seed(1)
+    z = torch.rand((B, 6), generator=g).to(dev)
+    env = (torch.rand((B, EH, EW, 3), generator=g) + 0.05).to(dev)
+    phi = torch.rand((B,), generator=g) * 6.2831853
+    view = view_rotation(torch.stack([torch.sin(phi), 0.3 * torch.ones(B), torch.cos(phi)], dim=-1)).to(dev)
+    nrm = torch.randn((B, R, R, 3), generator=g)
+    nrm[..., 2] = nrm[..., 2].abs() + 0.1
+    nrm = nrm.to(dev)
+    measured = [MeasuredBSDF.from_principled(get_bsdf(row, names)) for row in ([0.0, 0.7, 0.5, 0.3, 0.5, 0.6], [1.0, 0.7, 0.5, 0.3, 0.3, 0.6])]
+    tables, table_of, alpha = device_tables([measured[b % 2] for b in range(B)], B, dev)
+    # 20 480 faces that shadow and light one another: a body and three balls, icosphere(4) each (the scene of shadow_ref.two_spheres, finer)
+    _, d, f = mesh_ref.icosphere(4)
+    centres = [(0.0, 0.0, 0.0, 0.5), (0.40, 0.35, 0.30, 0.2), (-0.45, 0.30, 0.25, 0.2), (0.10, -0.50, 0.30, 0.2)]
+    obj = {"vertex_positions": torch.tensor(np.concatenate([r * d + np.array([x, y, zc]) for x, y, zc, r in centres]), dtype=torch.float32),
+           "vertex_normals": torch.tensor(np.concatenate([d] * 4), dtype=torch.float32),
+           "faces": torch.tensor(np.concatenate([f + k * len(d) for k in range(4)]), dtype=torch.int32)}
+    pos, vn, faces = (obj[k].to(dev).contiguous() for k in ("vertex_positions", "vertex_normals", "faces"))
+    blob = build_bvh(obj).to(dev)
+    V, F = C.c_int64(pos.shape[0]), C.c_int64(faces.shape[0])
+    first = libs[0][1]
+    for fn in ("drm_render_light_workspace_bytes", "drm_render_mesh_workspace_bytes"):
+        getattr(first, fn).restype = C.c_size_t
+    lbytes = first.drm_render_light_workspace_bytes(B, EH, EW, M)
+    mbytes = first.drm_render_mesh_workspace_bytes(F, Bm, R, R, S)
+    assert lbytes > 0 and mbytes > 0
+    lws = torch.empty(((lbytes + 7) // 8,), dtype=torch.float64, device=dev)
+    mws = torch.empty(((mbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
+    out = torch.empty((B, 3, R, R), device=dev)
+    drawn = torch.empty((B, R, R), device=dev)
+    mesh_out = [torch.empty((Bm, c, R, R), device=dev) for c in (3, 3, 1, 1)]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    vp, sz = (lambda t: C.c_void_p(t.data_ptr())), C.c_size_t
+
+    def entries(lib):
+        mesh_args = (vp(pos), vp(vn), vp(faces), V, F, vp(z), vp(env), vp(view), *(vp(t) for t in mesh_out), Bm, R, R, EH, EW, Q, S, vp(mws), sz(mbytes))
+        bvh = (vp(blob), sz(blob.numel()))
+        return {
+            "drm_render_refmap_views": ([out], lambda: lib.drm_render_refmap_views(vp(z), 1, vp(env), vp(view), vp(out), B, R, EH, EW, Q, S, 0, stream)),
+            f"drm_render_refmap_lit M={M}": ([out], lambda: lib.drm_render_refmap_lit(vp(z), 1, vp(env), vp(view), vp(out), B, R, EH, EW, Q, S, 0, M, vp(lws),
+                                                                                      sz(lbytes), stream)),
+            "drm_render_refmap_table": ([out], lambda: lib.drm_render_refmap_table(vp(tables), int(tables.shape[0]), vp(table_of), vp(alpha), vp(env), vp(view),
+                                                                                  vp(out), B, R, EH, EW, Q, S, 0, 1, stream)),
+            "drm_render_normals": ([out, drawn], lambda: lib.drm_render_normals(vp(nrm), None, B, vp(z), vp(env), vp(view), vp(out), vp(drawn), B, R, R, EH, EW, Q,
+                                                                               0, None, sz(0), stream)),
+            f"drm_render_normals M={M}": ([out, drawn], lambda: lib.drm_render_normals(vp(nrm), None, B, vp(z), vp(env), vp(view), vp(out), vp(drawn), B, R, R, EH,
+                                                                                     EW, Q, M, vp(lws), sz(lbytes), stream)),
+            "drm_render_normals_table": ([out, drawn], lambda: lib.drm_render_normals_table(vp(nrm), None, B, vp(tables), int(tables.shape[0]), vp(table_of),
+                                                                                           vp(alpha), vp(env), vp(view), vp(out), vp(drawn), B, R, R, EH, EW, Q, 1,
+                                                                                           stream)),
+            f"drm_render_mesh B={Bm}": (mesh_out, lambda: lib.drm_render_mesh(*mesh_args, stream)),
+            f"drm_render_mesh_shadowed B={Bm}": (mesh_out, lambda: lib.drm_render_mesh_shadowed(*mesh_args, *bvh, stream)),
+            f"drm_render_mesh_lit B={Bm} M={M}": (mesh_out, lambda: lib.drm_render_mesh_lit(*mesh_args, None, sz(0), M, vp(lws), sz(lbytes), stream)),
+            f"drm_render_mesh_bounced B={Bm}": (mesh_out, lambda: lib.drm_render_mesh_bounced(*mesh_args, *bvh, 4, stream)),
+        }
+
+    results, bits = {}, {}
+    for rep in range(args.rounds):
+        for name, lib in libs:
+            for entry, (outs, call) in entries(lib).items():
+                if args.match and not any(m in entry for m in args.match):
+                    continue
+
+                def run():
+                    assert call() == 0
+
+                results.setdefault((entry, name), []).extend(timed(run, args.reps))
+                torch.cuda.synchronize()
+                bits.setdefault(entry, []).append((name, [t.clone() for t in outs]))
+    for entry, seen in bits.items():
+        same = all(torch.equal(a, b) for _, o in seen[1:] for a, b in zip(seen[0][1], o))
+        print(f"{entry}: every library, every round, bitwise equal outputs: {same}", flush=True)
+    for (entry, name), ms in results.items():
+        ms = sorted(ms)
+        print(f"B={B} {R}x{R} maps {EH}x{EW} Q={Q} S={S}  {entry}  [{name}]: median {ms[len(ms) // 2]:.3f} ms  min {ms[0]:.3f}  max {ms[-1]:.3f}  (n={len(ms)})",
+              flush=True)
 
 
 def bench_step(args):
@@ -217,5 +317,8 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="f16mx")
     ap.add_argument("--light_samples", type=int, default=0, help="render: also time drm_render_refmap_lit with this many light samples per map")
+    ap.add_argument("--entries", action="store_true", help="render: time the sphere, table, normal-map and mesh entries per library instead")
+    ap.add_argument("--mesh_batch", type=int, default=0, help="render --entries: rows of the mesh entries (default: --batch)")
+    ap.add_argument("--match", nargs="*", default=[], help="render --entries: only the entries whose name contains one of these")
     a = ap.parse_args()
     {"render": bench_render, "step": bench_step, "obs_step": bench_obs_step}[a.what](a)

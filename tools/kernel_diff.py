@@ -2,6 +2,7 @@
 """Compare the gfx950 kernels of two builds, symbol by symbol (no GPU needed).
 
     python tools/kernel_diff.py OLD NEW [--match SUBSTRING ...] [--list-identical]
+    python tools/kernel_diff.py --list BUILD [--match SUBSTRING ...]      the counts of one build's kernels, for kernels whose names changed
 
 OLD / NEW: a library (libdrmnet_hip.so), an object file, or a directory of objects (csrc/_obj).  Every device code object inside them is
 disassembled with the ROCm llvm-objdump; a kernel is IDENTICAL when its whole instruction text (mnemonics, registers, immediates, branch
@@ -95,6 +96,11 @@ def waves(m) -> int:
     return min(8, 512 // max(8, (regs + 7) // 8 * 8))
 
 
+def counts(ins, m) -> str:
+    return (f"{len(ins)} instructions, {m.get('vgpr_count', 0)} VGPRs, {m.get('agpr_count', 0)} AGPRs, {m.get('sgpr_count', 0)} SGPRs, "
+            f"{m.get('private_segment_fixed_size', 0)} B scratch, {waves(m)} waves/SIMD by registers")
+
+
 def demangle(names):
     for tool in (llvm("llvm-cxxfilt"), "c++filt"):  # (whichever is installed; the mangled names otherwise)
         try:
@@ -109,11 +115,20 @@ def demangle(names):
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("old")
-    ap.add_argument("new")
+    ap.add_argument("old", nargs="?")
+    ap.add_argument("new", nargs="?")
+    ap.add_argument("--list", metavar="BUILD", help="print the counts of every kernel of this one build instead of comparing two")
     ap.add_argument("--match", action="append", default=[], help="only kernels whose demangled name contains this (repeatable)")
     ap.add_argument("--list-identical", action="store_true", help="print the identical kernels too, not only their count")
     a = ap.parse_args()
+    if a.list:
+        ks = kernels(a.list)
+        for sym, name in demangle(sorted(ks)).items():
+            if not a.match or any(s in name for s in a.match):
+                print(f"{counts(*ks[sym])}  {name}")
+        return 0
+    if not a.old or not a.new:
+        ap.error("OLD and NEW, or --list BUILD")
     ko, kn = kernels(a.old), kernels(a.new)
     names = demangle(sorted(set(ko) | set(kn)))
     same = diff = 0
@@ -131,8 +146,7 @@ def main() -> int:
             diff += 1
             print(f"DIFFERENT  {name}")
             for tag, (ins, m) in (("old", ko[sym]), ("new", kn[sym])):
-                print(f"    {tag}: {len(ins)} instructions, {m.get('vgpr_count', 0)} VGPRs, {m.get('agpr_count', 0)} AGPRs, "
-                      f"{m.get('private_segment_fixed_size', 0)} B scratch, {waves(m)} waves/SIMD by registers")
+                print(f"    {tag}: {counts(ins, m)}")
     print(f"{same} identical, {diff} different")
     return 1 if diff else 0
 
