@@ -310,7 +310,7 @@ int no_form(const ConvPlan& p) {  // (a plan that names a form no unit instantia
 __global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* __restrict__ partial, size_t slab_f4, int ks, const float* __restrict__ bias,
                                                                   const float* __restrict__ emb, int emb_stride, const float* res /* may alias out */,
                                                                   float4* out, double2* __restrict__ stat, int HW, int Cout) {
-  __shared__ float red[256][8];
+  __shared__ double red[256][8];
   const int n = blockIdx.y, q4 = Cout >> 2;
   const int ql = threadIdx.x & 15, pl = threadIdx.x >> 4;
   const int q = blockIdx.x * 16 + ql;
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* 
       b.x += e.x; b.y += e.y; b.z += e.z; b.w += e.w;
     }
   }
-  float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};  // (double, as gn.hip: E[x^2] - E[x]^2 cancels badly in fp32 when |mean| >> std)
 #pragma unroll 4
   for (int p = pl; p < HW && q < q4; p += 16) {
     const size_t idx = ((size_t)n * HW + p) * q4 + q;
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* 
     }
     out[idx] = v;
     s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
-    ss[0] += v.x * v.x; ss[1] += v.y * v.y; ss[2] += v.z * v.z; ss[3] += v.w * v.w;
+    ss[0] += (double)v.x * v.x; ss[1] += (double)v.y * v.y; ss[2] += (double)v.z * v.z; ss[3] += (double)v.w * v.w;
   }
   if (stat) {  // (uniform per launch)
 #pragma unroll
@@ -352,8 +352,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_small_kernel(const float4* 
       for (int k = 0; k < 4; ++k) {
         double a = 0.0, c2 = 0.0;
         for (int j = 0; j < 16; ++j) {  // fixed order
-          a += (double)red[j * 16 + ql][k];
-          c2 += (double)red[j * 16 + ql][4 + k];
+          a += red[j * 16 + ql][k];
+          c2 += red[j * 16 + ql][4 + k];
         }
         double2* d = stat + (size_t)n * Cout + 4 * q + k;
         *d = make_double2(d->x + a, d->y + c2);

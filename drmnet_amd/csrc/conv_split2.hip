@@ -150,6 +150,16 @@ struct S2Cfg {
 // v * sigmoid(v) with v_rcp_f32 (1 ulp) in place of the IEEE division sequence (11 VALU instructions per value inside the
 // activation staging, which runs on the same SIMDs as the MFMAs); the hi/lo fp16 split that follows keeps 22 bits anyway.
 __device__ __forceinline__ float silu2(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+// Output statistics of a lane, about a pivot.  E[x^2] - E[x]^2 cancels badly when |mean| >> std (gn.hip squares in double for that reason), and an
+// output channel does carry an offset: bias and emb are added right here.  Sums of x and x * x in fp32 lose the variance's low bits to the
+// offset's square (2^6 on unit noise: eleven bits); sums of d = x - p and d * d about one of the lane's own values p are the size of the
+// spread whatever the offset, so fp32 keeps them, and the pivot is put back exactly, in double, once per lane and row half:
+//   sum x = sum d + n p,   sum x^2 = sum d^2 + p (2 sum d + n p).
+__device__ __forceinline__ void stat_unpivot(float s, float q, float p, int n, double& S, double& Q) {
+  const double pd = (double)p, sd = (double)s, np = (double)n * pd;
+  S = sd + np;
+  Q = (double)q + pd * (2.0 * sd + np);
+}
 __device__ __forceinline__ void split2(float v, _Float16& hi, _Float16& lo) {
   const float c = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
   hi = (_Float16)c;
@@ -961,7 +971,8 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
           // masked edge tiles: plain per-element form (residual read, store and statistics under the pixel's own predicate)
           const bool first = ks == 1;
           const float bias = (a.bias && first) ? a.bias[co] : 0.f;
-          float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
+          float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f, p0 = 0.f, p1 = 0.f;  // (sums about the half's first live value: stat_unpivot)
+          int n0 = 0, n1 = 0;
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int g = e >> 2, k = e & 3;
@@ -979,26 +990,33 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
               out_s[pix * a.Cout + co] = v;
             }
             if (e < 8) {
-              s0 += v;
-              q0 += v * v;
+              if (n0++ == 0) p0 = v;
+              const float dv = v - p0;
+              s0 += dv;
+              q0 += dv * dv;
             } else {
-              s1 += v;
-              q1 += v * v;
+              if (n1++ == 0) p1 = v;
+              const float dv = v - p1;
+              s1 += dv;
+              q1 += dv * dv;
             }
           }
           if (st) {
             const int row0 = (wm * MT + i) * 32;
+            double S0, Q0, S1, Q1;
+            stat_unpivot(s0, q0, p0, n0, S0, Q0);
+            stat_unpivot(s1, q1, p1, n1, S1, Q1);
             if (PPI >= 32) {
-              s0 += s1;
-              q0 += q1;
+              S0 += S1;
+              Q0 += Q1;
             }
             double* d = lst + ((size_t)(row0 / PPI) * C::BN + col) * 2;
-            atomicAdd(d, (double)s0);
-            atomicAdd(d + 1, (double)q0);
+            atomicAdd(d, S0);
+            atomicAdd(d + 1, Q0);
             if (PPI < 32) {
               double* d2 = lst + ((size_t)((row0 + 16) / PPI) * C::BN + col) * 2;
-              atomicAdd(d2, (double)s1);
-              atomicAdd(d2 + 1, (double)q1);
+              atomicAdd(d2, S1);
+              atomicAdd(d2 + 1, Q1);
             }
           }
           continue;
@@ -1026,23 +1044,27 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 #pragma unroll
           for (int e = 0; e < 16; ++e) rv[e] = 0.f;
         }
-        float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;  // rows 0-15 / 16-31 of this tile (two images when PPI == 16)
+        float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;  // rows 0-15 / 16-31 of this tile (two images when PPI == 16), about p0 / p1 (stat_unpivot)
         float v[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int g = e >> 2;
-          v[e] = epi_value(acc[i][c][e] * sv[g], bias, ev[g], rv[e]);
+          v[e] = epi_value(acc[i][c][e] * sv[e >> 2], bias, ev[e >> 2], rv[e]);
           acc[i][c][e] = 0.f;  // ready for the next tile
+        }
+        const float p0 = okg[0] ? v[0] : (okg[1] ? v[4] : 0.f), p1 = okg[2] ? v[8] : (okg[3] ? v[12] : 0.f);  // a live value of each half
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
 #ifdef DRM_S2_STAMP
           if (a.stamp_block & 0x100000) continue;  // timing experiment: no statistics arithmetic
 #endif
-          if (okg[g]) {
+          if (okg[e >> 2]) {
+            const float dv = v[e] - (e < 8 ? p0 : p1);
             if (e < 8) {
-              s0 += v[e];
-              q0 += v[e] * v[e];
+              s0 += dv;
+              q0 += dv * dv;
             } else {
-              s1 += v[e];
-              q1 += v[e] * v[e];
+              s1 += dv;
+              q1 += dv * dv;
             }
           }
         }
@@ -1056,9 +1078,12 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
           for (int q = 0; q < 4; ++q) {
             const int gy = q >> 1, kx = q & 1;
             pv[q] = (v[8 * gy + 2 * kx] + v[8 * gy + 2 * kx + 1] + v[8 * gy + 4 + 2 * kx] + v[8 * gy + 4 + 2 * kx + 1]) * 0.25f;
-            ps += pv[q];
-            pq += pv[q] * pv[q];
+            const float dv = pv[q] - pv[0];  // (about the first pooled value: stat_unpivot)
+            ps += dv;
+            pq += dv * dv;
           }
+          double PS, PQ;
+          stat_unpivot(ps, pq, pv[0], 4, PS, PQ);
           quad_transpose(pv[0], pv[1], pv[2], pv[3], r);  // -> pooled pixel (r & 3) of this lane's four channels
           {
             const int row0 = (wm * MT + i) * 32;
@@ -1070,8 +1095,8 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
             const int n = cur.n0;
             *reinterpret_cast<float4*>(&a.pool_out[(((size_t)n * (a.H >> 1) + ppy) * (a.W >> 1) + ppx) * a.Cout + cq4]) = make_float4(pv[0], pv[1], pv[2], pv[3]);
             double* d2 = lst2 + (size_t)col * 2;
-            atomicAdd(d2, (double)ps);
-            atomicAdd(d2 + 1, (double)pq);
+            atomicAdd(d2, PS);
+            atomicAdd(d2 + 1, PQ);
           }
         }
         if (a.out_nchw) {
@@ -1121,17 +1146,20 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
 #endif
         if (st && first && !abl_noatom) {
           const int row0 = (wm * MT + i) * 32;
+          double S0, Q0, S1, Q1;
+          stat_unpivot(s0, q0, p0, 4 * ((int)okg[0] + (int)okg[1]), S0, Q0);
+          stat_unpivot(s1, q1, p1, 4 * ((int)okg[2] + (int)okg[3]), S1, Q1);
           if (PPI >= 32) {
-            s0 += s1;
-            q0 += q1;
+            S0 += S1;
+            Q0 += Q1;
           }
           double* d = lst + ((size_t)(row0 / PPI) * C::BN + col) * 2;
-          atomicAdd(d, (double)s0);
-          atomicAdd(d + 1, (double)q0);
+          atomicAdd(d, S0);
+          atomicAdd(d + 1, Q0);
           if (PPI < 32) {
             double* d2 = lst + ((size_t)((row0 + 16) / PPI) * C::BN + col) * 2;
-            atomicAdd(d2, (double)s1);
-            atomicAdd(d2 + 1, (double)q1);
+            atomicAdd(d2, S1);
+            atomicAdd(d2 + 1, Q1);
           }
         }
         S2_STAMP(23 + 4 * (i * NT + c));  // statistics atomics issued
@@ -1214,14 +1242,15 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
               sum_groups(I2{}, I2{}, I8{});
             }
             S2_STAMP(74);  // slabs summed
-            float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
+            float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;  // (about p0 / p1: stat_unpivot)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) v[e] = epi_value(v[e], bias, ev[e >> 2], rv[e]);  // (the slab sum is already scaled)
+            const float p0 = okg[0] ? v[0] : (okg[1] ? v[4] : 0.f), p1 = okg[2] ? v[8] : (okg[3] ? v[12] : 0.f);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-              const int g = e >> 2;
-              const float x = epi_value(v[e], bias, ev[g], rv[e]);  // (the slab sum is already scaled)
-              v[e] = x;
-              if (okg[g]) {
-                if (e < 8) { s0 += x; q0 += x * x; } else { s1 += x; q1 += x * x; }
+              if (okg[e >> 2]) {
+                const float dv = v[e] - (e < 8 ? p0 : p1);
+                if (e < 8) { s0 += dv; q0 += dv * dv; } else { s1 += dv; q1 += dv * dv; }
               }
             }
 #pragma unroll
@@ -1231,17 +1260,20 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_split2_kernel(ConvArgs a)
             }
             if (st) {  // LDS fold like every full epilogue; the global fold below runs for this workgroup
               const int row0 = wm * 32;
+              double S0, Q0, S1, Q1;
+              stat_unpivot(s0, q0, p0, 4 * ((int)okg[0] + (int)okg[1]), S0, Q0);
+              stat_unpivot(s1, q1, p1, 4 * ((int)okg[2] + (int)okg[3]), S1, Q1);
               if (PPI >= 32) {
-                s0 += s1;
-                q0 += q1;
+                S0 += S1;
+                Q0 += Q1;
               }
               double* d = lst + ((size_t)(row0 / PPI) * C::BN + col) * 2;
-              atomicAdd(d, (double)s0);
-              atomicAdd(d + 1, (double)q0);
+              atomicAdd(d, S0);
+              atomicAdd(d + 1, Q0);
               if (PPI < 32) {
                 double* d2 = lst + ((size_t)((row0 + 16) / PPI) * C::BN + col) * 2;
-                atomicAdd(d2, (double)s1);
-                atomicAdd(d2 + 1, (double)q1);
+                atomicAdd(d2, S1);
+                atomicAdd(d2 + 1, Q1);
               }
             }
             fused_last = true;

@@ -10,6 +10,11 @@ The block and network cases pass through fp64 atomics whose order is not fixed; 
 reproduced (the JSON holds null otherwise).  An unpinned case is compared with the fp64 torch reference instead, at the tolerance of the existing test
 of its form (tests/test_gpu_upconv.py: 1e-5 per block, 2e-5 for f16mx; conftest.NET_TOL for the network).  Cases that fell back when the digests were
 recorded: none -- all eight reproduced (FELL_BACK below).
+
+The four block and network digests were recorded again, by the same recorder, when the epilogue's output statistics changed their arithmetic on
+purpose (sums about a per-lane pivot instead of fp32 sums of x and x * x: DESIGN.md "GroupNorm checks"): the next GroupNorm's tables move in their
+last bits, and with them every byte behind it.  The four conv cases, whose output no statistics feed, kept their digests from the earlier commit;
+what the new statistics are held to is tests/test_gpu_groupnorm.py's elementwise bound against fp64.
 """
 import hashlib
 import json
