@@ -19,11 +19,18 @@ ABI_VERSION = 3
 MAX_LEVELS = 8
 LOSS_WORKSPACE_BYTES = 2048  # DRM_LOSS_WORKSPACE_BYTES
 DIFFUSION_LOSS_MAX_PARTS = 32  # DRM_DIFFUSION_LOSS_MAX_PARTS
+BRDF_ERROR_SUMS = 9  # DRM_BRDF_ERROR_SUMS
+BRDF_ERROR_PARTS = 128  # DRM_BRDF_ERROR_PARTS
 
 
 def diffusion_loss_workspace_bytes(B: int) -> int:
     """DRM_DIFFUSION_LOSS_WORKSPACE_BYTES(B)"""
     return int(B) * DIFFUSION_LOSS_MAX_PARTS * 2 * 8
+
+
+def brdf_error_workspace_bytes(C: int) -> int:
+    """DRM_BRDF_ERROR_WORKSPACE_BYTES(C)"""
+    return int(C) * BRDF_ERROR_PARTS * BRDF_ERROR_SUMS * 8
 
 
 # every symbol include/drmnet_hip.h declares (tests check the .so exports all of them)
@@ -44,7 +51,7 @@ SYMBOLS = [
     "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed", "drm_render_mesh_lit",
     "drm_mesh_closest_hit", "drm_render_mesh_bounced",
     "drm_render_normals", "drm_image_from_refmap",
-    "drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap_table", "drm_render_normals_table",
+    "drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap_table", "drm_render_normals_table", "drm_brdf_error_sums",
     "drm_obs_forward_process", "drm_diffusion_losses",
     "drm_envmap2mirmap", "drm_rotate_envmap", "drm_mirimg2envmap", "drm_refmap2refimg",
 ]
@@ -224,6 +231,7 @@ def lib() -> C.CDLL:
     L.drm_merl_eval.argtypes = [fp, i32, vp, fp, fp, fp, fp, C.c_int64, i32, vp]
     L.drm_render_refmap_table.argtypes = [fp, i32, vp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     L.drm_render_normals_table.argtypes = [fp, u8p, i32, fp, i32, vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_brdf_error_sums.argtypes = [fp, i32, fp, fp, vp, C.c_size_t, vp, vp]
     L.drm_validation_losses.argtypes =[fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]
     L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]

@@ -715,6 +715,13 @@ int drm_render_normals_table(const float* normals, const uint8_t* mask, int Bn, 
   });
 }
 
+int drm_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* workspace, size_t workspace_bytes, double* sums,
+                        void* stream) {
+  return guarded([&]() -> int {
+    return launch_brdf_error_sums(z, C, table, z_target, workspace, workspace_bytes, sums, static_cast<hipStream_t>(stream));
+  });
+}
+
 // ------------------------------------------------------------------------------------------------ validation losses (losses.hip)
 
 int drm_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "merl_grid.h"
 #include "normal_map.h"
 #include "render_shared.h"
 
@@ -27,11 +28,7 @@ namespace drm {
 
 namespace {
 
-constexpr int kNH = 90, kND = 90, kNP = 180;
-constexpr long long kTableEntries = (long long)kNH * kND * kNP;  // float4 each
-constexpr double kPi64 = 3.14159265358979323846;
-constexpr double kSnap = 1e-12;  // a cosine of the export grid below this is the rounding of an exact zero (theta_h + theta_d = pi / 2, phi_d = 0)
-
+// (the grid's sizes, kPi64 and the export's node geometry and entry value: merl_grid.h)
 // The continuous table coordinates x = (90 sqrt(theta_h / (pi / 2)), 90 theta_d / (pi / 2), 180 phi_d / pi) of unit n, v (toward the
 // viewer) and l (toward the light): h = normalize(v + l), theta_h = atan2(|n x h|, n.h), theta_d = atan2(|l x h|, l.h) (never acos of a dot
 // product near 1), and MERL's azimuth: in the half-vector frame the normal lies at azimuth pi, x_h = -normalize(n - (n.h) h), y_h = h x x_h,
@@ -104,32 +101,21 @@ __device__ __forceinline__ void table_lookup(const float4* __restrict__ tab, con
   f[2] = ok ? num[2] / den : T(0);
 }
 
-// one thread per entry of every row's table: the half-vector frame has h = +z and n = (-sin theta_h, 0, cos theta_h); the viewer is
-// wo = (sin theta_d cos phi_d, sin theta_d sin phi_d, cos theta_d), the light wi = wo (-1, -1, 1); entry = principled_eval / (n.wi) in
-// fp64; -1 where n.wo < 0 or n.wi < 0, 0 where a cosine is exactly 0 (kSnap).
+// one thread per entry of every row's table: the node's directions and the entry's value are merl_grid.h's (merl_node, merl_entry); -1 where
+// n.wo < 0 or n.wi < 0, 0 where a cosine is exactly 0 (kSnap).
 __global__ __launch_bounds__(256) void brdf_to_merl_kernel(const float* __restrict__ z, float4* __restrict__ out, long long total) {
   for (long long at = (long long)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += (long long)gridDim.x * blockDim.x) {
     const long long row = at / kTableEntries;
-    const int rem = (int)(at - row * kTableEntries);
-    const int i = rem / (kND * kNP), j = (rem / kNP) % kND, k = rem % kNP;
-    const double t = (double)i / 90.0;
-    const double th = t * t * (kPi64 / 2), td = (double)j * (kPi64 / 180), pd = (double)k * (kPi64 / 180);
-    const double n[3] = {-sin(th), 0.0, cos(th)};
-    const double wo[3] = {sin(td) * cos(pd), sin(td) * sin(pd), cos(td)};
-    const double wi[3] = {-wo[0], -wo[1], wo[2]};
-    double co = n[0] * wo[0] + n[1] * wo[1] + n[2] * wo[2], ci = n[0] * wi[0] + n[1] * wi[1] + n[2] * wi[2];
-    if (fabs(co) < kSnap) co = 0.0;
-    if (fabs(ci) < kSnap) ci = 0.0;
+    const MerlNode nd = merl_node((int)(at - row * kTableEntries));
     float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (co < 0.0 || ci < 0.0) {
+    if (merl_node_below(nd)) {
       e.x = e.y = e.z = -1.0f;
-    } else if (co > 0.0 && ci > 0.0) {
-      const Principled p = principled(z + 6 * row);
+    } else if (merl_node_lit(nd)) {
       float f[3];
-      principled_eval(p, n, wo, wi, f);
-      e.x = (float)((double)f[0] / ci);
-      e.y = (float)((double)f[1] / ci);
-      e.z = (float)((double)f[2] / ci);
+      merl_entry(principled(z + 6 * row), nd, f);
+      e.x = f[0];
+      e.y = f[1];
+      e.z = f[2];
     }
     out[at] = e;
   }

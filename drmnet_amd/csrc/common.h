@@ -349,6 +349,8 @@ int launch_render_refmap_table(const float* tables, int NT, const int32_t* table
 int launch_render_normals_table(const float* normals, const unsigned char* mask, int Bn, const float* tables, int NT, const int32_t* table_of,
                                 const float* alpha, const float* env, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH,
                                 int EW, int quad, int linear, hipStream_t s);
+// BRDF-space error sums of C principled rows against a packed table or a principled row (brdf_error.hip): see drm_brdf_error_sums
+int launch_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* ws, size_t ws_bytes, double* sums, hipStream_t s);
 
 // misc kernels (misc.hip)
 // absmax_bits (optional): [N][pack_input_absmax_parts(H, W)] words, every one written: max |element| of one block of a packed image as fp32 bits

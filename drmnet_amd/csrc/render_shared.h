@@ -155,17 +155,31 @@ __host__ __device__ __forceinline__ T diffuse_shape(T r, T cl, T cv, T cd) {
 
 // Mitsuba's eval (f times n.l) per channel, in fp64; n, v (toward the viewer), l (toward the light) unit vectors, given as fp32
 // (drm_brdf_eval) or as fp64 (drm_brdf_to_merl, whose grid directions are formed in fp64): S
+// in two halves, so that a kernel that scores many rows on one direction triple (brdf_error.hip) forms the first half once: EvalGeom, the
+// cosines of the triple, which no row enters, and principled_eval_at, the terms a row enters.  principled_eval is the two in sequence.
+struct EvalGeom {
+  double cv, cl, nh, cd, lh;  // n.v, n.l, n.h, h.v, h.l at h = normalize(v + l); nh, cd, lh are set only where cv > 0 and cl > 0
+};
 template <typename S>
-__host__ __device__ __forceinline__ void principled_eval(const Principled& p, const S* n, const S* v, const S* l, float out[3]) {
-  out[0] = out[1] = out[2] = 0.0f;
+__host__ __device__ __forceinline__ EvalGeom eval_geom(const S* n, const S* v, const S* l) {
+  EvalGeom g;
   const double nx = n[0], ny = n[1], nz = n[2];
-  const double cv = nx * v[0] + ny * v[1] + nz * v[2], cl = nx * l[0] + ny * l[1] + nz * l[2];
-  if (!(cv > 0.0 && cl > 0.0)) return;
+  g.cv = nx * v[0] + ny * v[1] + nz * v[2];
+  g.cl = nx * l[0] + ny * l[1] + nz * l[2];
+  g.nh = g.cd = g.lh = 0.0;
+  if (!(g.cv > 0.0 && g.cl > 0.0)) return g;
   double hx = (double)v[0] + l[0], hy = (double)v[1] + l[1], hz = (double)v[2] + l[2];
   const double inv = 1.0 / sqrt(hx * hx + hy * hy + hz * hz);
   hx *= inv; hy *= inv; hz *= inv;
-  const double nh = nx * hx + ny * hy + nz * hz;  // > 0: v and l are both above the surface
-  const double cd = hx * v[0] + hy * v[1] + hz * v[2], lh = hx * l[0] + hy * l[1] + hz * l[2];
+  g.nh = nx * hx + ny * hy + nz * hz;  // > 0: v and l are both above the surface
+  g.cd = hx * v[0] + hy * v[1] + hz * v[2];
+  g.lh = hx * l[0] + hy * l[1] + hz * l[2];
+  return g;
+}
+__host__ __device__ __forceinline__ void principled_eval_at(const Principled& p, const EvalGeom& g, float out[3]) {
+  out[0] = out[1] = out[2] = 0.0f;
+  const double cv = g.cv, cl = g.cl, nh = g.nh, cd = g.cd, lh = g.lh;
+  if (!(cv > 0.0 && cl > 0.0)) return;
   const double a2 = (double)p.alpha * p.alpha, m = p.m;
   // sin^2 as 1 - cos^2 (in fp64 the cancellation costs nothing, and this is the definition's form for inputs that are unit only to fp32)
   const double D = ggx_d(a2, nh, 1.0 - nh * nh);
@@ -175,6 +189,10 @@ __host__ __device__ __forceinline__ void principled_eval(const Principled& p, co
   const double kd = (1.0 - m) * cl * diffuse_shape((double)p.r, cl, cv, cd) / kPi;
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) out[ch] = (float)((fd + m * (p.c[ch] + (1.0 - p.c[ch]) * sw)) * k + kd * p.c[ch]);
+}
+template <typename S>
+__host__ __device__ __forceinline__ void principled_eval(const Principled& p, const S* n, const S* v, const S* l, float out[3]) {
+  principled_eval_at(p, eval_geom(n, v, l), out);
 }
 
 // principled_eval's expression in fp32 on the same terms, sin^2 passed as |n x .|^2 as the quadrature passes it: what a surface point reflects

@@ -13,7 +13,10 @@ sample_rerender.exr / .png, sample_refmap_image.exr, sample_errors.json.  With `
 sample_brdf.binary, the estimated BRDF as a MERL table (drmnet_amd/merl.py).  With `--gt_envmap E.exr --gt_view_from x y z` (a pair, off by
 default: the `--envmap` and `--view_from` `synthesize` was given) it also judges the estimated illumination against the true one
 (drmnet_amd/groundtruth.py): sample_gt_mirmap.exr, the mirror reflectance map Lr0 should equal; sample_gt_env.exr, the true map in the
-camera frame the estimated map is in; sample_Lr0.exr; and sample_gt_errors.json.
+camera frame the estimated map is in; sample_Lr0.exr; and sample_gt_errors.json.  With `--gt_z m R G B r s` (the `--z` `synthesize` rendered
+with) or `--gt_merl M.binary` (the table `relight --merl` rendered under; the two exclude each other) it also judges the estimated BRDF in
+BRDF space (drmnet_amd/reflectance.py): sample_gt_errors.json gains "brdf", and under a measured truth "brdf_fit", the best principled fit of
+the table, the floor the estimate is to be read against.
 """
 from __future__ import annotations
 
@@ -141,15 +144,22 @@ def parser() -> argparse.ArgumentParser:
                         help="the true lat-long environment map (.exr, world frame): also report the estimated illumination's error; needs --gt_view_from")
     parser.add_argument("--gt_view_from", type=float, nargs=3, default=None, metavar=("x", "y", "z"),
                         help="the viewer position the object image was taken from (off the +-y axis); needs --gt_envmap")
+    parser.add_argument("--gt_z", type=float, nargs=6, default=None, metavar=("m", "R", "G", "B", "r", "s"),
+                        help="the true principled row (metallic, base colour R G B, roughness, specular): also report the estimated BRDF's error")
+    parser.add_argument("--gt_merl", type=Path, default=None,
+                        help="the true measured BRDF (a MERL .binary): also report the estimated BRDF's error and the best principled fit of the table")
     return parser
 
 
 def parse_args(argv=None) -> argparse.Namespace:
-    """the command line, with the one rule argparse cannot state: --gt_envmap and --gt_view_from come as a pair"""
+    """the command line, with the two rules argparse cannot state: --gt_envmap and --gt_view_from come as a pair, and --gt_z and --gt_merl
+    exclude each other"""
     p = parser()
     args = p.parse_args(argv)
     if (args.gt_envmap is None) != (args.gt_view_from is None):
         p.error("--gt_envmap and --gt_view_from come as a pair: the true map is in the world frame, the estimate in the camera's")
+    if args.gt_z is not None and args.gt_merl is not None:
+        p.error("--gt_z and --gt_merl exclude each other: the true reflectance is one principled row or one measured table")
     return args
 
 
@@ -200,9 +210,28 @@ def write_groundtruth(output_dir: Path, Lr0_sample, envmap_est, envmap_gt, view_
     return errors
 
 
+def write_groundtruth_brdf(output_dir: Path, zK_est, brdf_param_names, truth, errors: Optional[dict] = None, fit_options: Optional[dict] = None) -> dict:
+    """What ``--gt_z`` / ``--gt_merl`` add to sample_gt_errors.json (created when ``--gt_envmap`` did not write it; ``errors`` is what it
+    wrote): "brdf" = reflectance.brdf_errors(the estimated row, truth), the scaled figures allowing for the scale ambiguity; and, for a
+    measured truth (a merl.MeasuredBSDF), "brdf_fit" = reflectance.fit_principled(truth) with its ``z``: the best any principled row can do,
+    the floor the estimate is to be read against.  ``fit_options`` are fit_principled's keywords."""
+    import json
+
+    from .merl import MeasuredBSDF
+    from .reflectance import brdf_errors, fit_principled
+    from .render import get_bsdf
+
+    errors = dict(errors or {})
+    errors["brdf"] = brdf_errors(get_bsdf(zK_est, brdf_param_names), truth)
+    if isinstance(truth, MeasuredBSDF):
+        errors["brdf_fit"] = fit_principled(truth, **(fit_options or {}))
+    (output_dir / "sample_gt_errors.json").write_text(json.dumps(errors, indent=1) + "\n")
+    return errors
+
+
 def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     """``models`` = (DRMNet_model, ObsNet_model), already on the GPU with their ``ds``, stands in for the two configs, and ``hooks`` are
-    ``estimate``'s: tests run the command line on small networks with injected draws."""
+    ``estimate``'s: tests run the command line on small networks with injected draws.  hooks["fit"]: keywords for the fit of ``--gt_merl``."""
     from . import file_io
     from .config import instantiate_from_config, load_config
     from .transform import hdr2ldr
@@ -249,10 +278,17 @@ def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     if args.rerender:
         errors = write_rerender(args.output_dir, drmnet_model, Lr0_sample, zK_est, hooks["stages"]["inpaint"], input_img, input_normal, mask)
         print("re-rendered estimate against the input image", errors)
+    gt_errors = None
     if args.gt_envmap is not None:
         envmap_gt = file_io.load_exr(args.gt_envmap, as_torch=True).cuda()
-        errors = write_groundtruth(args.output_dir, Lr0_sample, envmap_est, envmap_gt, args.gt_view_from)
-        print("estimated illumination against the ground truth", errors)
+        gt_errors = write_groundtruth(args.output_dir, Lr0_sample, envmap_est, envmap_gt, args.gt_view_from)
+        print("estimated illumination against the ground truth", gt_errors)
+    if args.gt_z is not None or args.gt_merl is not None:
+        from .merl import MeasuredBSDF
+
+        truth = np.clip(args.gt_z, 0.0, 1.0) if args.gt_z is not None else MeasuredBSDF.from_file(args.gt_merl, alpha=1.0)
+        gt_errors = write_groundtruth_brdf(args.output_dir, zK_est, drmnet_model.brdf_param_names, truth, gt_errors, hooks.get("fit"))
+        print("estimated BRDF against the ground truth", {k: gt_errors[k] for k in ("brdf", "brdf_fit") if k in gt_errors})
 
 
 if __name__ == "__main__":

@@ -2,15 +2,20 @@
 
     python -m drmnet_amd.merl --z m R G B r s --output est.binary        # a principled row exported as a MERL file
     python -m drmnet_amd.merl --input a.binary --figure a.png            # the visualize_bsdf figure of a measured BRDF
+    python -m drmnet_amd.merl --input a.binary --fit [--objective log1p|l2] [--output fitted.binary] [--figure f.png]
+                                                                         # the closest principled row, as one JSON line
+    python -m drmnet_amd.merl --input a.binary --compare --z m R G B r s # the BRDF-space errors of a row against a table, as JSON
+    python -m drmnet_amd.merl --compare --z m R G B r s --against a.binary   # the same
 
 Operator surface of the reference: ``load_merl`` / ``save_merl`` (utils/file_io.py:59-103) and ``bsdf_to_merl``
 (utils/mitsuba3_utils.py:602-638) keep their names, shapes and file format.  ``MeasuredBSDF`` is the measured counterpart of
 ``render.PrincipledBSDF``: ``render.eval_bsdf`` / ``render.visualize_bsdf`` take either, ``render.render_table`` renders the sphere and
 ``relight.render_normals_measured`` an object image from a normal map under it.  The file format and the packing are host numpy;
-export, evaluation and rendering run on the GPU (no CPU path).
+export, evaluation and rendering run on the GPU (no CPU path).  Fitting principled parameters to a table and the BRDF-space error metrics are
+drmnet_amd/reflectance.py (csrc/brdf_error.hip); ``--fit`` and ``--compare`` are its command lines.
 
-Out of scope: mesh renders under a table (with or without shadows or bounces), light samples under a table, anisotropic tables, fitting
-principled parameters to a table, and BRDF-space error metrics.
+Out of scope: mesh renders under a table (with or without shadows or bounces), light samples under a table, anisotropic tables, and
+table-against-table errors.
 """
 from __future__ import annotations
 
@@ -190,21 +195,70 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--input", type=Path, default=None, help="a MERL file (.binary) to draw")
     p.add_argument("--figure", type=Path, default=None, help="the visualize_bsdf figure (.png) of --input (or of the exported --z)")
     p.add_argument("--lookup", choices=("nearest", "linear"), default="nearest", help="how the figure reads the table (default: MERL's own reader rule)")
+    p.add_argument("--fit", action="store_true", help="fit a principled row to --input and print it with its errors as one JSON line; "
+                   "--output writes the fitted row's table, --figure draws it")
+    p.add_argument("--objective", choices=("log1p", "l2"), default="log1p", help="what --fit minimises (default: rmse_log1p)")
+    p.add_argument("--compare", action="store_true", help="print the BRDF-space errors of the row --z against the table --input (or --against) as JSON")
+    p.add_argument("--against", type=Path, default=None, help="the MERL file (.binary) --compare holds --z against")
     return p
 
 
-def main(argv=None):
+def parse_args(argv=None) -> argparse.Namespace:
+    """the command line with the rules between its options"""
     ap = parser()
     args = ap.parse_args(argv)
+    if args.fit and args.compare:
+        ap.error("--fit and --compare exclude each other")
+    if args.fit:
+        if args.input is None:
+            ap.error("--fit needs --input, the measured BRDF to fit")
+        if args.z is not None or args.against is not None:
+            ap.error("--fit takes --input alone (no --z, no --against)")
+        return args
+    if args.compare:
+        if args.z is None:
+            if args.input is not None and args.against is not None:
+                ap.error("--compare: table-versus-table comparison is out of scope: the first BRDF must be a principled row, given as --z")
+            ap.error("--compare needs the row --z and one table, --input or --against")
+        if (args.input is None) == (args.against is None):
+            ap.error("--compare needs exactly one table to hold --z against: --input or --against")
+        return args
+    if args.against is not None:
+        ap.error("--against belongs to --compare")
     if (args.z is None) == (args.input is None):
         ap.error("exactly one of --z and --input")
     if args.z is not None and args.output is None:
         ap.error("--z needs --output")
     if args.input is not None and args.figure is None:
         ap.error("--input needs --figure")
-    from .render import PrincipledBSDF, visualize_bsdf
+    return args
 
-    if args.z is not None:
+
+def main(argv=None, *, fit_options: Optional[dict] = None):
+    """``fit_options``: keywords for reflectance.fit_principled under ``--fit`` (tests pass a small ``starts``)"""
+    import json
+
+    args = parse_args(argv)
+    from .render import CANONICAL, PrincipledBSDF, visualize_bsdf
+
+    if args.compare:
+        from .reflectance import brdf_errors
+
+        target = MeasuredBSDF.from_file(args.input if args.input is not None else args.against, alpha=1.0)
+        print(json.dumps(brdf_errors(np.clip(args.z, 0.0, 1.0), target)))
+        return
+    if args.fit:
+        from .reflectance import fit_principled
+
+        fit = fit_principled(MeasuredBSDF.from_file(args.input, alpha=1.0), objective=args.objective, **(fit_options or {}))
+        print(json.dumps({"z": dict(zip(CANONICAL, fit["z"])), "objective": fit["objective"], "errors": fit["errors"], "rounds": fit["rounds"],
+                          "evaluations": fit["evaluations"]}))
+        if args.output is None and args.figure is None:
+            return
+        args.z, args.input = fit["z"], None  # (what follows exports and draws the fitted row)
+    if args.z is not None and args.output is None:
+        bsdf = MeasuredBSDF.from_principled(PrincipledBSDF(np.clip(args.z, 0.0, 1.0)))
+    elif args.z is not None:
         bsdf = MeasuredBSDF.from_principled(PrincipledBSDF(np.clip(args.z, 0.0, 1.0)))
         save_merl(bsdf.table, args.output)
         print(f"wrote {args.output} (proxy alpha {bsdf.alpha:.4g})")

@@ -666,6 +666,37 @@ int drm_render_refmap_table(const float* tables, int NT, const int32_t* table_of
 int drm_render_normals_table(const float* normals, const uint8_t* mask, int Bn, const float* tables, int NT, const int32_t* table_of, const float* alpha,
                              const float* envmap, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH, int EW, int quad,
                              int linear, void* stream);
+/* drm_brdf_error_sums (csrc/brdf_error.hip; serves drmnet_amd/reflectance.py: brdf_errors, fit_principled, estimate --gt_z / --gt_merl and
+ *   merl --fit / --compare.  Additive: the ABI version is unchanged): C candidate rows z [C][6], 1 <= C <= 4096, scored against ONE target on
+ *   the MERL grid in one pass.  The target is `table` (one packed table, 16-byte aligned) or `z_target` (one principled row [6]); exactly one
+ *   of the two is non-NULL.  At a node, a = the candidate's value there = the entry drm_brdf_to_merl stores (the same device function), b =
+ *   the target's entry (a principled target's formed the same way), ci = n.wi.  A node counts where drm_brdf_to_merl stores a BRDF value
+ *   (n.wo > 0 and n.wi > 0 after the 1e-12 snap) and the target entry has no negative channel; every counting node weighs one (the MERL-sample
+ *   convention, no solid-angle weight) and the three channels are pooled.  sums [C][DRM_BRDF_ERROR_SUMS] fp64, over the channel values of the
+ *   counting nodes:
+ *     [DRM_BRDF_ERROR_N]      their count n                       [DRM_BRDF_ERROR_N_LOG]   the count with a > 0 and b > 0
+ *     [DRM_BRDF_ERROR_D]      sum of d = log10 a - log10 b        [DRM_BRDF_ERROR_DD]      sum of d^2         (both over the n_log values)
+ *     [DRM_BRDF_ERROR_LOG1P]  sum of (log1p(a ci) - log1p(b ci))^2
+ *     [DRM_BRDF_ERROR_L2]     sum of ((a - b) ci)^2
+ *     [DRM_BRDF_ERROR_AA], [DRM_BRDF_ERROR_AB], [DRM_BRDF_ERROR_BB]   sums of (a ci)^2, (a ci)(b ci), (b ci)^2
+ *   Element arithmetic and sums are fp64, added in a fixed order without atomics: two calls are bitwise equal, and a row's sums do not depend
+ *   on C or on its place among the candidates.  Two launches, no host synchronisation.  workspace: DRM_BRDF_ERROR_WORKSPACE_BYTES(C) of device
+ *   memory, 8-byte aligned, contents irrelevant.  DRM_ERR_INVALID with drm_last_error naming the entry: both or neither target, C outside
+ *   [1, 4096], a misaligned table, a NULL z / workspace / sums, a workspace too small. */
+#define DRM_BRDF_ERROR_SUMS 9
+#define DRM_BRDF_ERROR_N 0
+#define DRM_BRDF_ERROR_N_LOG 1
+#define DRM_BRDF_ERROR_D 2
+#define DRM_BRDF_ERROR_DD 3
+#define DRM_BRDF_ERROR_LOG1P 4
+#define DRM_BRDF_ERROR_L2 5
+#define DRM_BRDF_ERROR_AA 6
+#define DRM_BRDF_ERROR_AB 7
+#define DRM_BRDF_ERROR_BB 8
+#define DRM_BRDF_ERROR_PARTS 128
+#define DRM_BRDF_ERROR_WORKSPACE_BYTES(C) ((size_t)(C) * DRM_BRDF_ERROR_PARTS * DRM_BRDF_ERROR_SUMS * sizeof(double))
+int drm_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* workspace, size_t workspace_bytes, double* sums,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The validation losses (csrc/losses.hip).
