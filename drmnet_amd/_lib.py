@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DRM_LIB_PATH: an explicitly named alternative build (tools/stamp_probe.sh uses it for its diagnostic library); never set by the product
 LIB_PATH = os.environ.get("DRM_LIB_PATH") or os.path.join(_HERE, "csrc", "libdrmnet_hip.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 MAX_LEVELS = 8
 LOSS_WORKSPACE_BYTES = 2048  # DRM_LOSS_WORKSPACE_BYTES
 DIFFUSION_LOSS_MAX_PARTS = 32  # DRM_DIFFUSION_LOSS_MAX_PARTS
@@ -40,18 +40,16 @@ SYMBOLS = [
     "drm_unet_workspace_bytes", "drm_unet_forward",
     "drm_linear_forward", "drm_timestep_embedding", "drm_op_norm_act_conv", "drm_op_resblock", "drm_op_attention_block",
     "drm_drmnet_create", "drm_drmnet_destroy", "drm_drmnet_workspace_bytes", "drm_drmnet_set_batch_parts", "drm_drmnet_set_batch_part_min", "drm_drmnet_step", "drm_drmnet_sample",
-    "drm_sampler_workspace_bytes", "drm_ddim_sample", "drm_ddim_sample_logged", "drm_ddpm_sample", "drm_ddim_sample_ex", "drm_ddpm_sample_ex", "drm_randn",
+    "drm_sampler_workspace_bytes", "drm_ddim_sample", "drm_ddpm_sample", "drm_randn",
     "drm_profile_enable", "drm_profile_reset", "drm_profile_collect", "drm_unet_set_precision", "drm_set_op_precision",
     "drm_refmap_workspace_bytes", "drm_refmap_mask_make", "drm_erode_mask",
     "drm_unet_load_params_set", "drm_unet_use_set", "drm_set_graph_replay", "drm_set_upconv_split", "drm_graph_launches",
     "drm_map_chain", "drm_masked_log_range", "drm_luminance_scale", "drm_mirmap2envmap", "drm_hdr2ldr", "drm_resize", "drm_profile_variants",
-    "drm_render_refmap", "drm_brdf_eval", "drm_render_refmap_views", "drm_validation_losses",
-    "drm_render_refmap_lit", "drm_render_light_workspace_bytes",
+    "drm_render_refmap", "drm_brdf_eval", "drm_validation_losses", "drm_render_light_workspace_bytes",
     "drm_render_mesh_workspace_bytes", "drm_render_mesh",
-    "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed", "drm_render_mesh_lit",
-    "drm_mesh_closest_hit", "drm_render_mesh_bounced",
+    "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_mesh_closest_hit",
     "drm_render_normals", "drm_image_from_refmap",
-    "drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap_table", "drm_render_normals_table", "drm_brdf_error_sums",
+    "drm_brdf_to_merl", "drm_merl_eval", "drm_brdf_error_sums",
     "drm_obs_forward_process", "drm_diffusion_losses",
     "drm_envmap2mirmap", "drm_rotate_envmap", "drm_mirimg2envmap", "drm_refmap2refimg",
 ]
@@ -65,12 +63,40 @@ class UNetDesc(C.Structure):
     ]
 
 
+def sized(struct_type, **fields):
+    """a zeroed ``struct_type`` with struct_bytes = its sizeof (what the library checks first) and ``fields`` set"""
+    s = struct_type(struct_bytes=C.sizeof(struct_type))
+    for name, value in fields.items():
+        setattr(s, name, value)
+    return s
+
+
 class MaskBlend(C.Structure):  # drm_mask_blend
-    _fields_ = [("mask", C.c_void_p), ("mask_channels", C.c_int32), ("x0", C.c_void_p), ("qcoef", C.POINTER(C.c_float)), ("qnoise", C.c_void_p), ("when", C.c_int32)]
+    _fields_ = [("struct_bytes", C.c_uint32), ("mask", C.c_void_p), ("mask_channels", C.c_int32), ("x0", C.c_void_p), ("qcoef", C.POINTER(C.c_float)),
+                ("qnoise", C.c_void_p), ("when", C.c_int32)]
 
 
 class SamplerOptions(C.Structure):  # drm_sampler_options
-    _fields_ = [("blend", C.POINTER(MaskBlend)), ("uncond", C.c_void_p), ("guidance_scale", C.c_float), ("noise_dropout", C.c_float), ("dropout_keep", C.c_void_p)]
+    _fields_ = [("struct_bytes", C.c_uint32), ("blend", C.POINTER(MaskBlend)), ("uncond", C.c_void_p), ("guidance_scale", C.c_float),
+                ("noise_dropout", C.c_float), ("dropout_keep", C.c_void_p)]
+
+
+class ChainLog(C.Structure):  # drm_chain_log
+    _fields_ = [("struct_bytes", C.c_uint32), ("every_t", C.c_int32), ("x", C.c_void_p), ("pred_x0", C.c_void_p), ("slots", C.c_int32),
+                ("n_logged", C.POINTER(C.c_int32))]
+
+
+class Shading(C.Structure):  # drm_shading
+    _fields_ = [("struct_bytes", C.c_uint32), ("B", C.c_int32), ("z", C.c_void_p), ("tables", C.c_void_p), ("NT", C.c_int32), ("table_of", C.c_void_p),
+                ("table_alpha", C.c_void_p), ("table_linear", C.c_int32), ("envmap", C.c_void_p), ("EH", C.c_int32), ("EW", C.c_int32), ("view", C.c_void_p),
+                ("quad", C.c_int32), ("light_samples", C.c_int32), ("light_workspace", C.c_void_p), ("light_workspace_bytes", C.c_size_t)]
+
+
+class MeshRender(C.Structure):  # drm_mesh_render
+    _fields_ = [("struct_bytes", C.c_uint32), ("vertex_positions", C.c_void_p), ("vertex_normals", C.c_void_p), ("faces", C.c_void_p), ("V", C.c_int64),
+                ("F", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("subpixel", C.c_int32), ("image", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p), ("alpha", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("shadows", C.c_int32),
+                ("bvh", C.c_void_p), ("bvh_bytes", C.c_size_t), ("bounces", C.c_int32), ("bounce_quad", C.c_int32)]
 
 
 class DrmnetCfg(C.Structure):
@@ -98,7 +124,7 @@ def make_mask_blend(mask, x0, qcoef, qnoise, when: int, img_shape):
     qn = None if qnoise is None else require_gpu_tensor(qnoise, "mask_noise").float().contiguous()
     if qn is not None and tuple(qn.shape) != (qc.shape[0],) + tuple(img_shape):
         raise RuntimeError(f"mask_noise must be [steps={qc.shape[0]}, N, C, H, W]")
-    b = MaskBlend()
+    b = sized(MaskBlend)
     b.mask, b.mask_channels, b.x0 = mask.data_ptr(), int(mask.shape[1]), x0.data_ptr()
     b.qcoef = qc.ctypes.data_as(C.POINTER(C.c_float))
     b.qnoise = None if qn is None else qn.data_ptr()
@@ -109,7 +135,7 @@ def make_mask_blend(mask, x0, qcoef, qnoise, when: int, img_shape):
 def make_sampler_options(img_shape, steps, blend=None, uncond=None, guidance_scale=1.0, noise_dropout=0.0, dropout_keep=None):
     """drm_sampler_options for a chain on `img_shape`: blend = (struct, keep-alive) of make_mask_blend or None; uncond [N,C,H,W]; dropout_keep
     [steps,N,C,H,W] 0 / 1 or None.  Returns (struct, keep-alive tuple)."""
-    o = SamplerOptions()
+    o = sized(SamplerOptions)
     keep = [blend]
     if blend is not None:
         o.blend = C.pointer(blend[0])
@@ -128,6 +154,35 @@ def make_sampler_options(img_shape, steps, blend=None, uncond=None, guidance_sca
         o.dropout_keep = k.data_ptr()
         keep.append(k)
     return o, tuple(keep)
+
+
+def light_samples_error(light_samples) -> ValueError:
+    """what a ``light_samples`` that is neither 0 nor a power of two in [64, 65536] raises, wherever it is found out"""
+    return ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+
+
+def make_shading(B: int, *, z=None, tables=None, env=None, view=None, quad: int, light_samples: int = 0):
+    """drm_shading of B rows: z [.., 6] canonical rows, or tables = (tables [NT, ...], table_of, alpha, linear) of merl.device_tables; env
+    [B, EH, EW, 3] or None (white); view [B, 3, 3] or None (+z); everything on one device.  ``light_samples`` > 0 under a map allocates the
+    light workspace (a size of 0 from the library means a count it will not take: ValueError).  Returns (struct, keep-alive tuple)."""
+    sh = sized(Shading, B=int(B), z=ptr(z), envmap=ptr(env), view=ptr(view), quad=int(quad))
+    keep = [z, tables, env, view]
+    if tables is not None:
+        t, table_of, alpha, linear = tables
+        sh.tables, sh.NT, sh.table_of, sh.table_alpha, sh.table_linear = t.data_ptr(), int(t.shape[0]), ptr(table_of), ptr(alpha), int(linear)
+    if env is not None:
+        sh.EH, sh.EW = int(env.shape[1]), int(env.shape[2])
+    light_samples = int(light_samples)
+    if light_samples < 0:
+        raise ValueError(f"light_samples must be >= 0, got {light_samples}")
+    if light_samples and env is not None:
+        nbytes = int(lib().drm_render_light_workspace_bytes(sh.B, sh.EH, sh.EW, light_samples))
+        if nbytes == 0:
+            raise light_samples_error(light_samples)
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=env.device)
+        sh.light_samples, sh.light_workspace, sh.light_workspace_bytes = light_samples, ws.data_ptr(), nbytes
+        keep.append(ws)
+    return sh, tuple(keep)
 
 
 _lib: Optional[C.CDLL] = None
@@ -175,13 +230,9 @@ def lib() -> C.CDLL:
     L.drm_drmnet_sample.argtypes = [vp, fp, fp, fp, fp, C.c_uint64, i32, fp, fp, vp, C.POINTER(C.c_int32), i32, i32, i32, vp, C.c_size_t, vp]
     L.drm_sampler_workspace_bytes.argtypes = [vp, i32, i32, i32]
     L.drm_sampler_workspace_bytes.restype = C.c_size_t
-    L.drm_ddim_sample.argtypes = [vp, fp, fp, C.POINTER(C.c_int64), C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, i32, i32, i32, vp, C.c_size_t, vp]
-    L.drm_ddim_sample_logged.argtypes = [vp, fp, fp, C.POINTER(C.c_int64), C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, i32, fp, fp, i32, C.POINTER(C.c_int32),
-                                         i32, i32, i32, vp, C.c_size_t, vp]
-    L.drm_ddpm_sample.argtypes = [vp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, i32, i32, i32, vp, C.c_size_t, vp]
-    L.drm_ddim_sample_ex.argtypes = [vp, fp, fp, C.POINTER(C.c_int64), C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, C.POINTER(SamplerOptions), i32, fp, fp, i32,
-                                     C.POINTER(C.c_int32), i32, i32, i32, vp, C.c_size_t, vp]
-    L.drm_ddpm_sample_ex.argtypes = [vp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, C.POINTER(SamplerOptions), i32, i32, i32, vp, C.c_size_t, vp]
+    L.drm_ddim_sample.argtypes = [vp, fp, fp, C.POINTER(C.c_int64), C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, C.POINTER(SamplerOptions),
+                                  C.POINTER(ChainLog), i32, i32, i32, vp, C.c_size_t, vp]
+    L.drm_ddpm_sample.argtypes = [vp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, fp, C.c_uint64, C.POINTER(SamplerOptions), i32, i32, i32, vp, C.c_size_t, vp]
     L.drm_randn.argtypes = [fp, C.c_size_t, C.c_uint64, C.c_uint64, vp]
     u8p = vp
     L.drm_refmap_workspace_bytes.argtypes = [C.c_int64, i32, C.c_float]
@@ -205,32 +256,22 @@ def lib() -> C.CDLL:
     L.drm_resize.argtypes = [fp, fp, i32, i32, i32, i32, i32, i32, vp]
     L.drm_profile_variants.argtypes = [C.c_char_p, C.c_size_t]
     L.drm_profile_variants.restype = C.c_size_t
-    L.drm_render_refmap.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.drm_render_refmap.argtypes = [C.POINTER(Shading), i32, i32, i32, i32, fp, vp]
     L.drm_brdf_eval.argtypes = [fp, i32, fp, fp, fp, fp, C.c_int64, vp]
-    L.drm_render_refmap_views.argtypes = [fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
-    L.drm_render_refmap_lit.argtypes = [fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
     L.drm_render_light_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.drm_render_light_workspace_bytes.restype = C.c_size_t
     L.drm_render_mesh_workspace_bytes.argtypes = [C.c_int64, i32, i32, i32, i32]
     L.drm_render_mesh_workspace_bytes.restype = C.c_size_t
-    L.drm_render_mesh.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
+    L.drm_render_mesh.argtypes = [C.POINTER(Shading), C.POINTER(MeshRender), vp]
     L.drm_mesh_bvh_bytes.argtypes = [C.c_int64]
     L.drm_mesh_bvh_bytes.restype = C.c_size_t
     L.drm_mesh_bvh_build.argtypes = [fp, vp, C.c_int64, C.c_int64, vp, C.c_size_t]
     L.drm_mesh_occluded.argtypes = [fp, vp, C.c_int64, C.c_int64, vp, fp, fp, vp, vp, C.c_int64, vp]
-    L.drm_render_mesh_shadowed.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t,
-                                           vp, C.c_size_t, vp]
-    L.drm_render_mesh_lit.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t,
-                                      vp, C.c_size_t, i32, vp, C.c_size_t, vp]
     L.drm_mesh_closest_hit.argtypes = [fp, vp, C.c_int64, C.c_int64, vp, fp, fp, vp, vp, fp, C.c_int64, vp]
-    L.drm_render_mesh_bounced.argtypes = [fp, fp, vp, C.c_int64, C.c_int64, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t,
-                                          vp, C.c_size_t, i32, vp]
-    L.drm_render_normals.argtypes = [fp, u8p, i32, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
+    L.drm_render_normals.argtypes = [C.POINTER(Shading), fp, u8p, i32, i32, i32, fp, fp, vp]
     L.drm_image_from_refmap.argtypes = [fp, u8p, i32, i32, fp, u8p, i32, fp, fp, i32, i32, i32, vp]
     L.drm_brdf_to_merl.argtypes = [fp, i32, fp, vp]
     L.drm_merl_eval.argtypes = [fp, i32, vp, fp, fp, fp, fp, C.c_int64, i32, vp]
-    L.drm_render_refmap_table.argtypes = [fp, i32, vp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    L.drm_render_normals_table.argtypes = [fp, u8p, i32, fp, i32, vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.drm_brdf_error_sums.argtypes = [fp, i32, fp, fp, vp, C.c_size_t, vp, vp]
     L.drm_validation_losses.argtypes =[fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]

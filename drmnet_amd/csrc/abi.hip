@@ -79,12 +79,19 @@ size_t unet_ws(UNet& net, int N, int H, int W) {
   return a.peak + 256;
 }
 
-// the tail of the DDIM / DDPM chain entry points: the caller's workspace as the arena, then the chain over it
+// the DDIM / DDPM chain entry points: the options (null: none) checked, the caller's workspace as the arena, then the chain over both
 template <typename Body>
-int run_chain(drm_unet* net, const ChainIO& io, void* workspace, size_t workspace_bytes, Body&& chain) {
+int run_chain(drm_unet* net, const ChainIO& io, const drm_sampler_options* opt, void* workspace, size_t workspace_bytes, Body&& chain) {
+  DRM_REQUIRE(net && io.x && io.cond, "null argument");
+  drm_sampler_options o{};
+  if (opt) {
+    DRM_REQUIRE_SIZE(opt, drm_sampler_options);
+    if (opt->blend) DRM_REQUIRE_SIZE(opt->blend, drm_mask_blend);
+    o = *opt;
+  }
   Arena ar;
   DRM_TRY(make_arena(ar, workspace, workspace_bytes, sampler_workspace_bytes(&net->net, io.N, io.H, io.W)));
-  return chain(ar);
+  return chain(o, ar);
 }
 
 }  // namespace
@@ -369,65 +376,31 @@ size_t drm_sampler_workspace_bytes(const drm_unet* net, int N, int H, int W) {
 }
 
 int drm_ddim_sample(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
-                    const float* noise, uint64_t seed, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+                    const float* noise, uint64_t seed, const drm_sampler_options* opt, const drm_chain_log* log, int N, int H, int W,
+                    void* workspace, size_t workspace_bytes, void* stream) {
   return guarded([&]() -> int {
-    DRM_REQUIRE(net && x && cond, "null argument");
+    drm_chain_log lg{};
+    if (log) {
+      DRM_REQUIRE_SIZE(log, drm_chain_log);
+      DRM_REQUIRE(log->every_t <= 0 || (log->x && log->pred_x0 && log->slots > 0), "ddim intermediates: both log buffers and their slot count");
+      lg = *log;
+      if (lg.every_t <= 0) lg.every_t = 0, lg.x = lg.pred_x0 = nullptr;  // (no intermediates, whatever the buffers)
+    }
     const ChainIO io{x, cond, noise, seed, N, H, W};
-    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
-      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, ChainLog{}, drm_sampler_options{}, ar, static_cast<hipStream_t>(stream));
-    });
-  });
-}
-
-int drm_ddim_sample_logged(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
-                           const float* noise, uint64_t seed, int log_every_t, float* log_x, float* log_pred_x0, int log_slots, int32_t* n_logged, int N,
-                           int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
-  return guarded([&]() -> int {
-    DRM_REQUIRE(net && x && cond, "null argument");
-    DRM_REQUIRE(log_every_t > 0 && log_x && log_pred_x0 && log_slots > 0, "ddim intermediates: log_every_t, both log buffers and their slot count");
-    const ChainIO io{x, cond, noise, seed, N, H, W};
-    const ChainLog log{log_every_t, log_x, log_pred_x0, log_slots, n_logged};
-    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
-      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, log, drm_sampler_options{}, ar, static_cast<hipStream_t>(stream));
+    return run_chain(net, io, opt, workspace, workspace_bytes, [&](const drm_sampler_options& o, Arena& ar) {
+      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, lg, o, ar, static_cast<hipStream_t>(stream));
     });
   });
 }
 
 int drm_ddpm_sample(drm_unet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip_denoised,
-                    const float* noise, uint64_t seed, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+                    const float* noise, uint64_t seed, const drm_sampler_options* opt, int N, int H, int W, void* workspace, size_t workspace_bytes,
+                    void* stream) {
   return guarded([&]() -> int {
-    DRM_REQUIRE(net && x && cond, "null argument");
     const ChainIO io{x, cond, noise, seed, N, H, W};
-    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
-      return ddpm_sample(&net->net, io, pred_x0, coef, T_start, clip_denoised, drm_sampler_options{}, ar, static_cast<hipStream_t>(stream));
-    });
-  });
-}
-
-int drm_ddim_sample_ex(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
-                       const float* noise, uint64_t seed, const drm_sampler_options* opt, int log_every_t, float* log_x, float* log_pred_x0, int log_slots,
-                       int32_t* n_logged, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
-  return guarded([&]() -> int {
-    DRM_REQUIRE(net && x && cond && opt, "null argument");
-    DRM_REQUIRE(log_every_t <= 0 || (log_x && log_pred_x0 && log_slots > 0), "ddim intermediates: both log buffers and their slot count");
-    const ChainIO io{x, cond, noise, seed, N, H, W};
-    ChainLog log{0, nullptr, nullptr, log_slots, n_logged};  // (log_every_t <= 0: no intermediates, whatever the buffers)
-    if (log_every_t > 0) log = ChainLog{log_every_t, log_x, log_pred_x0, log_slots, n_logged};
-    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
-      return ddim_sample(&net->net, io, timesteps, coef, S, num_steps, log, *opt, ar, static_cast<hipStream_t>(stream));
-    });
-  });
-}
-
-int drm_ddpm_sample_ex(drm_unet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip_denoised,
-                       const float* noise, uint64_t seed, const drm_sampler_options* opt, int N, int H, int W, void* workspace, size_t workspace_bytes,
-                       void* stream) {
-  return guarded([&]() -> int {
-    DRM_REQUIRE(net && x && cond && opt, "null argument");
-    DRM_REQUIRE(opt->uncond == nullptr, "drm_ddpm_sample_ex: classifier-free guidance exists on the DDIM chain only (ddim.py:225-232; ddpm.py p_sample has none)");
-    const ChainIO io{x, cond, noise, seed, N, H, W};
-    return run_chain(net, io, workspace, workspace_bytes, [&](Arena& ar) {
-      return ddpm_sample(&net->net, io, pred_x0, coef, T_start, clip_denoised, *opt, ar, static_cast<hipStream_t>(stream));
+    return run_chain(net, io, opt, workspace, workspace_bytes, [&](const drm_sampler_options& o, Arena& ar) {
+      DRM_REQUIRE(o.uncond == nullptr, "drm_ddpm_sample: classifier-free guidance exists on the DDIM chain only (ddim.py:225-232; ddpm.py p_sample has none)");
+      return ddpm_sample(&net->net, io, pred_x0, coef, T_start, clip_denoised, o, ar, static_cast<hipStream_t>(stream));
     });
   });
 }
@@ -558,43 +531,23 @@ int drm_refmap2refimg(const float* refmap, float* out, uint8_t* mask, int B, int
 
 // ------------------------------------------------------------------------------------------------ forward model (render.hip)
 
-int drm_render_refmap(const float* z, const float* envmap, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, void* stream) {
+int drm_render_refmap(const drm_shading* shading, int L, int R, int subpixel, int flip, float* out, void* stream) {
   return guarded([&]() -> int {
-    return launch_render_refmap(z, envmap, out, B, R, EH, EW, quad, subpixel, flip, static_cast<hipStream_t>(stream));
-  });
-}
-
-int drm_render_refmap_views(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
-                            int subpixel, int flip, void* stream) {
-  return guarded([&]() -> int {
-    return launch_render_refmap_views(z, L, envmap, view, out, B, R, EH, EW, quad, subpixel, flip, static_cast<hipStream_t>(stream));
+    DRM_REQUIRE(shading, "drm_render_refmap: shading is null");
+    return launch_render_refmap(*shading, L, R, subpixel, flip, out, static_cast<hipStream_t>(stream));
   });
 }
 
 size_t drm_render_light_workspace_bytes(int B, int EH, int EW, int light_samples) { return render_light_workspace_bytes(B, EH, EW, light_samples); }
 
-int drm_render_refmap_lit(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
-                          int flip, int light_samples, void* workspace, size_t workspace_bytes, void* stream) {
-  return guarded([&]() -> int {
-    return launch_render_refmap_lit(z, L, envmap, view, out, B, R, EH, EW, quad, subpixel, flip, light_samples, workspace, workspace_bytes,
-                                    static_cast<hipStream_t>(stream));
-  });
-}
-
 size_t drm_render_mesh_workspace_bytes(int64_t F, int B, int H, int W, int subpixel) {
   return render_mesh_workspace_bytes((long long)F, B, H, W, subpixel);
 }
 
-int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                    const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
-                    int quad, int subpixel, void* workspace, size_t workspace_bytes, void* stream) {
+int drm_render_mesh(const drm_shading* shading, const drm_mesh_render* mesh, void* stream) {
   return guarded([&]() -> int {
-    MeshRenderArgs a;
-    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
-    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
-    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
-    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
+    DRM_REQUIRE(shading && mesh, "drm_render_mesh: shading or mesh is null");
+    return launch_render_mesh(*shading, *mesh, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -612,20 +565,6 @@ int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64
   });
 }
 
-int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                             const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
-                             int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, void* stream) {
-  return guarded([&]() -> int {
-    MeshRenderArgs a;
-    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
-    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
-    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
-    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-    a.shadowed = true; a.bvh = bvh; a.bvh_bytes = bvh_bytes;
-    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
-  });
-}
-
 int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins,
                          const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, int64_t N, void* stream) {
   return guarded([&]() -> int {
@@ -634,45 +573,11 @@ int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, in
   });
 }
 
-int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                            const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
-                            int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
-                            void* stream) {
+int drm_render_normals(const drm_shading* shading, const float* normals, const uint8_t* mask, int Bn, int H, int W, float* image, float* alpha,
+                       void* stream) {
   return guarded([&]() -> int {
-    DRM_REQUIRE(bounce_quad >= 1 && bounce_quad <= 16, "render_mesh_bounced: bounce_quad in [1, 16]");
-    MeshRenderArgs a;
-    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
-    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
-    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
-    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-    a.shadowed = true; a.bvh = bvh; a.bvh_bytes = bvh_bytes; a.bounce_quad = bounce_quad;
-    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
-  });
-}
-
-int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                        const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
-                        int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
-                        void* light_workspace, size_t light_workspace_bytes, void* stream) {
-  return guarded([&]() -> int {
-    MeshRenderArgs a;
-    a.positions = vertex_positions; a.normals = vertex_normals; a.faces = faces; a.V = (long long)V; a.F = (long long)F;
-    a.z = z; a.env = envmap; a.view = view; a.image = image; a.normal = normal; a.depth = depth; a.alpha = alpha;
-    a.B = B; a.H = H; a.W = W; a.EH = EH; a.EW = EW; a.quad = quad; a.subpixel = subpixel;
-    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-    a.shadowed = bvh != nullptr || bvh_bytes != 0;  // (bvh null with bvh_bytes 0: unshadowed)
-    a.bvh = bvh; a.bvh_bytes = bvh_bytes;
-    a.light_samples = light_samples; a.light_workspace = light_workspace; a.light_workspace_bytes = light_workspace_bytes;
-    return launch_render_mesh(a, static_cast<hipStream_t>(stream));
-  });
-}
-
-int drm_render_normals(const float* normals, const uint8_t* mask, int Bn, const float* z, const float* envmap, const float* view, float* image,
-                       float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
-                       size_t light_workspace_bytes, void* stream) {
-  return guarded([&]() -> int {
-    return launch_render_normals(normals, mask, Bn, z, envmap, view, image, alpha, B, H, W, EH, EW, quad, light_samples, light_workspace,
-                                 light_workspace_bytes, static_cast<hipStream_t>(stream));
+    DRM_REQUIRE(shading, "drm_render_normals: shading is null");
+    return launch_render_normals(*shading, normals, mask, Bn, H, W, image, alpha, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -696,23 +601,6 @@ int drm_brdf_to_merl(const float* z, int rows, float* tables_out, void* stream) 
 int drm_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, int64_t N, int linear,
                   void* stream) {
   return guarded([&]() -> int { return launch_merl_eval(tables, NT, table_of, n, v, l, out, (long long)N, linear, static_cast<hipStream_t>(stream)); });
-}
-
-int drm_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* envmap, const float* view, float* out,
-                            int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, void* stream) {
-  return guarded([&]() -> int {
-    return launch_render_refmap_table(tables, NT, table_of, alpha, envmap, view, out, B, R, EH, EW, quad, subpixel, flip, linear,
-                                      static_cast<hipStream_t>(stream));
-  });
-}
-
-int drm_render_normals_table(const float* normals, const uint8_t* mask, int Bn, const float* tables, int NT, const int32_t* table_of, const float* alpha,
-                             const float* envmap, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH, int EW, int quad,
-                             int linear, void* stream) {
-  return guarded([&]() -> int {
-    return launch_render_normals_table(normals, mask, Bn, tables, NT, table_of, alpha, envmap, view, image, alpha_out, B, H, W, EH, EW, quad, linear,
-                                       static_cast<hipStream_t>(stream));
-  });
 }
 
 int drm_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* workspace, size_t workspace_bytes, double* sums,

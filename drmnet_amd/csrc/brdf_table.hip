@@ -260,31 +260,23 @@ int launch_merl_eval(const float* tables, int NT, const int32_t* table_of, const
   return DRM_OK;
 }
 
-int launch_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* env, const float* view, float* out,
-                               int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, hipStream_t s) {
-  DRM_REQUIRE(out, "render_refmap_table: out is null");
-  DRM_REQUIRE(B >= 1 && B <= 65535 && R > 0 && R <= 8192, "render_refmap_table: 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192");
-  DRM_TRY(check_quadrature("render_refmap_table", quad, subpixel, 16, env, EH, EW));
-  PixelLaunch pl;
-  DRM_TRY(plan_pixel_launch("render_refmap_table", "B R^2", (long long)B * R * R, env, view, EH, EW, pl));
-  DRM_TRY(check_tables("render_refmap_table", tables, NT, table_of, B, alpha, true, s));
-  const TableArgs margs{reinterpret_cast<const float4*>(tables), table_of, alpha, linear ? 1 : 0};
+int launch_refmap_tables(const drm_shading& sh, const PixelLaunch& pl, int R, int subpixel, int flip, float* out, hipStream_t s) {
+  DRM_TRY(check_tables("render_refmap", sh.tables, sh.NT, sh.table_of, sh.B, sh.table_alpha, true, s));
+  const TableArgs margs{reinterpret_cast<const float4*>(sh.tables), sh.table_of, sh.table_alpha, sh.table_linear ? 1 : 0};
   const auto kernel = pl.view ? sphere_pixel_kernel<true, TableMaterial> : sphere_pixel_kernel<false, TableMaterial>;
-  hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, env, pl.view, out, B, B, R, pl.EH, pl.EW, quad, subpixel, flip ? 1 : 0);
+  hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, sh.envmap, pl.view, out, sh.B, sh.B, R, pl.EH, pl.EW, sh.quad, subpixel,
+                     flip ? 1 : 0);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
 
-int launch_render_normals_table(const float* normals, const unsigned char* mask, int Bn, const float* tables, int NT, const int32_t* table_of,
-                                const float* alpha, const float* env, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH,
-                                int EW, int quad, int linear, hipStream_t s) {
-  DRM_REQUIRE(normals && image, "render_normals_table: null pointer");
-  PixelLaunch pl;
-  DRM_TRY(check_normals_launch("render_normals_table", B, H, W, Bn, quad, env, EH, EW, view, pl));
-  DRM_TRY(check_tables("render_normals_table", tables, NT, table_of, B, alpha, true, s));
-  const TableArgs margs{reinterpret_cast<const float4*>(tables), table_of, alpha, linear ? 1 : 0};
+int launch_normals_tables(const drm_shading& sh, const PixelLaunch& pl, const float* normals, const unsigned char* mask, int Bn, int H, int W, float* image,
+                          float* alpha, hipStream_t s) {
+  DRM_TRY(check_tables("render_normals", sh.tables, sh.NT, sh.table_of, sh.B, sh.table_alpha, true, s));
+  const TableArgs margs{reinterpret_cast<const float4*>(sh.tables), sh.table_of, sh.table_alpha, sh.table_linear ? 1 : 0};
   const auto kernel = pl.view ? normals_pixel_kernel<true, TableMaterial> : normals_pixel_kernel<false, TableMaterial>;
-  hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, normals, mask, Bn, env, pl.view, image, alpha_out, B, H, W, pl.EH, pl.EW, quad);
+  hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, normals, mask, Bn, sh.envmap, pl.view, image, alpha, sh.B, H, W, pl.EH,
+                     pl.EW, sh.quad);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }

@@ -1,4 +1,4 @@
-// The bounding-volume hierarchy behind the shadow rays of drm_render_mesh_shadowed: the host builder (drm_mesh_bvh_build: no HIP call, usable
+// The bounding-volume hierarchy behind the shadow rays of drm_render_mesh: the host builder (drm_mesh_bvh_build: no HIP call, usable
 // without a GPU) and the stand-alone ray queries: any-hit (drm_mesh_occluded) and closest-hit (drm_mesh_closest_hit).  The blob layout, the
 // triangle rule, the order of the closest hit and the traversal are in bvh.h.
 //

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <atomic>
 #include <string>
+#include "../../include/drmnet_hip.h"
 #include "conv_forms.h"
 #include "gn_fold.h"
 
@@ -37,6 +38,11 @@ const char* last_error();
       return DRM_ERR_INVALID;                                     \
     }                                                             \
   } while (0)
+
+// a struct the caller filled (include/drmnet_hip.h: struct_bytes) has the size this library was built with
+#define DRM_REQUIRE_SIZE(p, T)                                                                                        \
+  DRM_REQUIRE((p)->struct_bytes == sizeof(T), std::string(#T ": struct_bytes is ") + std::to_string((p)->struct_bytes) + \
+                                                  ", sizeof(" #T ") is " + std::to_string(sizeof(T)))
 
 #define DRM_TRY(expr)          \
   do {                         \
@@ -272,16 +278,9 @@ int launch_mirimg2envmap(const float* img, const float* frames, float* out, int 
                          hipStream_t s);
 int launch_refmap2refimg(const float* refmap, float* out, unsigned char* mask, int B, int C, int H, int W, int radius, int nhwc_in, hipStream_t s);
 
-// reflectance-map forward model (render.hip): z [B][6] canonical principled rows, env [B][EH][EW][3] or null (white), out [B][3][R][R]
-int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s);
-// the same kernel on L stacked sets of rows: z [L][B][6], out [L][B][3][R][R]; row (l, b) under env[b], seen through view[b] ([B][9] row-major
-// rotations, or null: +z)
-int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
-                               int subpixel, int flip, hipStream_t s);
-// the light-sampled form (see drm_render_refmap_lit); light_samples == 0 or env == null is launch_render_refmap_views
+// reflectance-map forward model (render.hip; see drm_render_refmap): every sphere render, principled rows or tables, with or without light samples
 size_t render_light_workspace_bytes(int B, int EH, int EW, int light_samples);
-int launch_render_refmap_lit(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
-                             int flip, int light_samples, void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_render_refmap(const drm_shading& sh, int L, int R, int subpixel, int flip, float* out, hipStream_t s);
 // object images of a triangle mesh (see drm_render_mesh): visibility in mesh.hip, shading in render.hip next to the lobe code it shares.
 // The workspace holds [B][F] face records of kMeshRecordWords 32-bit words, then [B][H S][W S] hits of kMeshHitWords words.
 //   record: words 0-5 the view-space (x, y) of the three vertices, 6-8 their view-space z, 9 the signed 1 / (twice the screen area),
@@ -298,35 +297,10 @@ size_t render_mesh_workspace_bytes(long long F, int B, int H, int W, int subpixe
 // the two visibility launches: records of every (row, face), then the nearest covering face of every film sample.  view [B][9] or null.
 int launch_mesh_visibility(const float* positions, const int32_t* faces, long long V, long long F, const float* view, int B, int H, int W, int subpixel,
                            float* records, float* hits, hipStream_t s);
-// One mesh render (the four drm_render_mesh* entries): what every one takes, then the optional parts, each off by default.
-struct MeshRenderArgs {
-  const float* positions = nullptr;  // [V][3]
-  const float* normals = nullptr;    // [V][3]
-  const int32_t* faces = nullptr;    // [F][3]
-  long long V = 0, F = 0;
-  const float* z = nullptr;     // [B][6]
-  const float* env = nullptr;   // [B][EH][EW][3], or null: white
-  const float* view = nullptr;  // [B][9], or null: +z
-  float *image = nullptr, *normal = nullptr, *depth = nullptr, *alpha = nullptr;
-  int B = 0, H = 0, W = 0, EH = 0, EW = 0, quad = 0, subpixel = 0;
-  void* workspace = nullptr;  // render_mesh_workspace_bytes
-  size_t workspace_bytes = 0;
-  // shadow rays through the blob of drm_mesh_bvh_build (bvh.h): bvh a device pointer to bvh_bytes bytes
-  bool shadowed = false;
-  const void* bvh = nullptr;
-  size_t bvh_bytes = 0;
-  // light samples (see drm_render_mesh_lit): 0, or env == null, renders without them; the workspace is render_light_workspace_bytes
-  int light_samples = 0;
-  void* light_workspace = nullptr;
-  size_t light_workspace_bytes = 0;
-  // one bounce of interreflection (see drm_render_mesh_bounced): with shadowed, without light samples; 0: none
-  int bounce_quad = 0;
-};
-int launch_render_mesh(const MeshRenderArgs& a, hipStream_t s);
+int launch_render_mesh(const drm_shading& sh, const drm_mesh_render& m, hipStream_t s);
 // a normal map shaded B ways (see drm_render_normals): normals [Bn][H][W][3] in the view frame, mask uint8 [Bn][H][W] or null
-int launch_render_normals(const float* normals, const unsigned char* mask, int Bn, const float* z, const float* env, const float* view, float* image,
-                          float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
-                          size_t light_workspace_bytes, hipStream_t s);
+int launch_render_normals(const drm_shading& sh, const float* normals, const unsigned char* mask, int Bn, int H, int W, float* image, float* alpha,
+                          hipStream_t s);
 // validation losses (losses.hip): see drm_validation_losses
 int launch_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,
                              const float* z_K, const int32_t* reversed_k, const float* z0, double gamma, int loss_type, double w_refmap,
@@ -344,11 +318,6 @@ int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v,
 int launch_brdf_to_merl(const float* z, int rows, float* tables_out, hipStream_t s);
 int launch_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, long long N,
                      int linear, hipStream_t s);
-int launch_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* env, const float* view, float* out,
-                               int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, hipStream_t s);
-int launch_render_normals_table(const float* normals, const unsigned char* mask, int Bn, const float* tables, int NT, const int32_t* table_of,
-                                const float* alpha, const float* env, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH,
-                                int EW, int quad, int linear, hipStream_t s);
 // BRDF-space error sums of C principled rows against a packed table or a principled row (brdf_error.hip): see drm_brdf_error_sums
 int launch_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* ws, size_t ws_bytes, double* sums, hipStream_t s);
 

@@ -15,16 +15,16 @@
 // bitwise reproducible (no atomics).
 //
 // Light sampling (opt-in, light_samples = M > 0): the quadrature never consults the map when it places samples, so a light a few texels
-// wide can fall between the strata of a rough lobe.  drm_render_refmap_lit adds a third technique, M directions drawn from the map's own
+// wide can fall between the strata of a rough lobe.  light_samples > 0 adds a third technique, M directions drawn from the map's own
 // light density, and combines the three with lobe-separated multiple importance sampling (power heuristic, beta = 2): see "light density"
 // below.
 //
 // Object images of meshes (drm_render_mesh): mesh.hip finds which face every film sample sees; mesh_shade_kernel here shades the hit with
 // normal_lane_sum, the per-normal body of the sphere's sum, so a mesh point is shaded exactly as the sphere point with the same normal
-// (direct light, no interreflection).  drm_render_mesh_shadowed runs mesh_shade_kernel<VIEW, true, false>, which traces every quadrature
-// direction from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones.  drm_render_mesh_lit runs
+// (direct light, no interreflection).  shadows runs mesh_shade_kernel<VIEW, true, false>, which traces every quadrature
+// direction from the hit point through the mesh's BVH (bvh.h) and drops the occluded ones.  light_samples > 0 runs
 // mesh_shade_kernel<VIEW, SHADOW, true>: the light samples of the sphere's lit render on the mesh, each traced like a lobe direction where
-// there is a BVH.  drm_render_mesh_bounced runs mesh_shade_kernel<VIEW, true, false, true>: an occluded direction reads the radiance its
+// there is a BVH.  bounces = 1 runs mesh_shade_kernel<VIEW, true, false, true>: an occluded direction reads the radiance its
 // closest hit reflects back under direct light (one bounce; see Bounced).
 //
 // Object images of a normal map (drm_render_normals): normals_pixel_kernel (render_shared.h) with Plain, or normals_lit_kernel with
@@ -37,8 +37,8 @@
 //
 // Also stated once: the traced techniques ask the mesh through one Tracer, the only place that builds a Ray; the shading normal
 // (mix_normals, unit_or_zero), the frame about a normal (duff_frame) and the cosine-weighted direction (cosine_direction) serve the film's
-// hit and the bounce's; mesh_technique builds the technique of a mesh pixel; on the host every mesh render is launch_render_mesh over one
-// MeshRenderArgs, and both lit renders share light_workspace_fault and launch_light_tables.
+// hit and the bounce's; mesh_technique builds the technique of a mesh pixel; on the host every render checks its drm_shading through
+// check_shading, every mesh render is launch_render_mesh, and the lit renders share launch_light_tables.
 //
 // Shared with the renders under a measured table (brdf_table.hip), in render_shared.h: the vector, frame, BSDF-term, environment-lookup,
 // sensor, view and butterfly helpers; the sample sets (grid_point, visible_frame, ggx_sample, visible_density, half_vector), so that
@@ -665,140 +665,140 @@ size_t render_light_workspace_bytes(int B, int EH, int EW, int light_samples) {
   return (size_t)B * light_ws_stride(EH, light_samples);
 }
 
-// what is wrong with a light workspace that must hold `need` = render_light_workspace_bytes bytes, `what` naming the entry and its argument;
-// empty where nothing is.  Each entry reports it with its own code.
-static std::string light_workspace_fault(const char* what, const void* ws, size_t bytes, size_t need) {
-  if (need != 0 && ws && bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 7) == 0) return "";
-  return std::string(what) + " must be 8-byte aligned and hold drm_render_light_workspace_bytes = " + std::to_string(need) + " bytes";
-}
 // the light workspace of the B maps, M samples each: three launches (see "building the light workspace")
-static void launch_light_tables(const float* env, char* ws, int B, int EH, int EW, int M, hipStream_t s) {
-  hipLaunchKernelGGL(light_rows_kernel, dim3((unsigned)(EH + 1), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, M);
-  hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)B), dim3(64), 0, s, ws, EH, EW, M);
-  hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(M / 4), (unsigned)B), dim3(256), 0, s, env, ws, EH, EW, M);
+static void launch_light_tables(const drm_shading& sh, hipStream_t s) {
+  char* ws = static_cast<char*>(sh.light_workspace);
+  const int M = sh.light_samples;
+  hipLaunchKernelGGL(light_rows_kernel, dim3((unsigned)(sh.EH + 1), (unsigned)sh.B), dim3(256), 0, s, sh.envmap, ws, sh.EH, sh.EW, M);
+  hipLaunchKernelGGL(light_cdf_kernel, dim3((unsigned)sh.B), dim3(64), 0, s, ws, sh.EH, sh.EW, M);
+  hipLaunchKernelGGL(light_table_kernel, dim3((unsigned)(M / 4), (unsigned)sh.B), dim3(256), 0, s, sh.envmap, ws, sh.EH, sh.EW, M);
+}
+
+int check_shading(const std::string& who, const drm_shading& sh, int subpixel, int subpixel_max, bool* lit, std::string* light_fault) {
+  DRM_REQUIRE_SIZE(&sh, drm_shading);
+  DRM_REQUIRE((sh.z != nullptr) != (sh.tables != nullptr), who + ": exactly one material, z (principled rows) or tables (measured), must be given");
+  DRM_REQUIRE(sh.light_samples >= 0, who + ": light_samples >= 0");
+  DRM_REQUIRE(sh.quad >= 1 && sh.quad <= 1024 && (!subpixel_max || (subpixel >= 1 && subpixel <= subpixel_max)),
+              who + ": quad in [1, 1024]" + (subpixel_max ? ", subpixel in [1, " + std::to_string(subpixel_max) + "]" : ""));
+  DRM_REQUIRE(!sh.envmap || (sh.EH > 0 && sh.EW > 0 && (long long)sh.EH * sh.EW <= (1LL << 28)), who + ": envmap must be EH x EW with EH, EW >= 1");
+  *lit = sh.light_samples > 0 && sh.envmap;
+  light_fault->clear();
+  if (!*lit) return DRM_OK;
+  DRM_REQUIRE(!sh.tables, who + ": light samples under tables are not built");
+  DRM_REQUIRE(light_samples_ok(sh.light_samples), who + ": light_samples must be 0 or a power of two in [64, 65536]");
+  const size_t need = render_light_workspace_bytes(sh.B, sh.EH, sh.EW, sh.light_samples);
+  if (need == 0 || !sh.light_workspace || sh.light_workspace_bytes < need || (reinterpret_cast<uintptr_t>(sh.light_workspace) & 7) != 0)
+    *light_fault = who + ": light_workspace must be 8-byte aligned and hold drm_render_light_workspace_bytes = " + std::to_string(need) + " bytes";
+  return DRM_OK;
 }
 
 // every sphere render: light_samples = 0, or a white environment, is the plain one (no workspace, no light kernels)
-int launch_render_refmap_lit(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad, int subpixel,
-                             int flip, int light_samples, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  DRM_REQUIRE(light_samples >= 0, "render_refmap_lit: light_samples >= 0");
-  const bool lit = light_samples > 0 && env;
-  DRM_REQUIRE(z && out, "render_refmap: null pointer");
-  DRM_REQUIRE(L > 0 && B > 0 && (!lit || B <= 65535) && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
-              lit ? "render_refmap_lit: L >= 1 stacks of 1 <= B <= 65535 rows of R x R pixels, 1 <= R <= 8192"
-                  : "render_refmap: L >= 1 stacks of B >= 1 rows of R x R pixels, 1 <= R <= 8192");
-  DRM_TRY(check_quadrature("render_refmap", quad, subpixel, 16, env, EH, EW));
-  char* ws = lit ? static_cast<char*>(workspace) : nullptr;
-  if (lit) {
-    DRM_REQUIRE(light_samples_ok(light_samples), "render_refmap_lit: light_samples must be 0 or a power of two in [64, 65536]");
-    const std::string fault =
-        light_workspace_fault("render_refmap_lit: workspace", workspace, workspace_bytes, render_light_workspace_bytes(B, EH, EW, light_samples));
-    if (!fault.empty()) {
-      set_error(fault);
-      return DRM_ERR_WORKSPACE;
-    }
+int launch_render_refmap(const drm_shading& sh, int L, int R, int subpixel, int flip, float* out, hipStream_t s) {
+  bool lit;
+  std::string light_fault;
+  DRM_TRY(check_shading("render_refmap", sh, subpixel, 16, &lit, &light_fault));
+  DRM_REQUIRE(out, "render_refmap: out is null");
+  DRM_REQUIRE(!sh.tables || L == 1, "render_refmap: tables render one set of rows (L == 1)");
+  const int B = sh.B;
+  DRM_REQUIRE(L > 0 && B > 0 && ((!lit && !sh.tables) || B <= 65535) && (long long)L * B <= 0x7fffffffLL && R > 0 && R <= 8192,
+              lit || sh.tables ? "render_refmap: L >= 1 stacks of 1 <= B <= 65535 rows (lit, or under tables) of R x R pixels, 1 <= R <= 8192"
+                               : "render_refmap: L >= 1 stacks of B >= 1 rows of R x R pixels, 1 <= R <= 8192");
+  if (!light_fault.empty()) {
+    set_error(light_fault);
+    return DRM_ERR_WORKSPACE;
   }
   PixelLaunch pl;
-  DRM_TRY(plan_pixel_launch("render_refmap", "L B R^2", (long long)L * B * R * R, env, view, EH, EW, pl));
-  if (lit) launch_light_tables(env, ws, B, EH, EW, light_samples, s);
+  DRM_TRY(plan_pixel_launch("render_refmap", "L B R^2", (long long)L * B * R * R, sh.envmap, sh.view, sh.EH, sh.EW, pl));
+  if (sh.tables) return launch_refmap_tables(sh, pl, R, subpixel, flip, out, s);
+  if (lit) launch_light_tables(sh, s);
   const auto launch = [&](auto kernel, auto margs) {
-    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, env, pl.view, out, L * B, B, R, pl.EH, pl.EW, quad, subpixel,
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, margs, sh.envmap, pl.view, out, L * B, B, R, pl.EH, pl.EW, sh.quad, subpixel,
                        flip ? 1 : 0);
   };
-  if (lit) launch(pl.view ? sphere_pixel_kernel<true, RowMaterial<true>> : sphere_pixel_kernel<false, RowMaterial<true>>, LitRowArgs{z, ws, light_samples});
-  else launch(pl.view ? sphere_pixel_kernel<true, RowMaterial<false>> : sphere_pixel_kernel<false, RowMaterial<false>>, RowArgs{z});
+  if (lit)
+    launch(pl.view ? sphere_pixel_kernel<true, RowMaterial<true>> : sphere_pixel_kernel<false, RowMaterial<true>>,
+           LitRowArgs{sh.z, static_cast<char*>(sh.light_workspace), sh.light_samples});
+  else launch(pl.view ? sphere_pixel_kernel<true, RowMaterial<false>> : sphere_pixel_kernel<false, RowMaterial<false>>, RowArgs{sh.z});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
 
-int launch_render_refmap_views(const float* z, int L, const float* env, const float* view, float* out, int B, int R, int EH, int EW, int quad,
-                               int subpixel, int flip, hipStream_t s) {
-  return launch_render_refmap_lit(z, L, env, view, out, B, R, EH, EW, quad, subpixel, flip, 0, nullptr, 0, s);
-}
-
-// Every mesh render: the same checks and visibility launches.  shadowed verifies the blob (nothing is launched before that) and shades with
-// it; light_samples > 0 under a map checks the light workspace, builds the tables as the sphere's lit render does and shades with them;
-// bounce_quad > 0 (the bounced entry's, with shadowed and without light samples) shades with one bounce.
-int launch_render_mesh(const MeshRenderArgs& a, hipStream_t s) {
-  DRM_REQUIRE(a.positions && a.normals && a.faces && a.z && a.image, "render_mesh: null pointer");
-  DRM_REQUIRE(a.light_samples >= 0, "render_mesh_lit: light_samples >= 0");
-  const bool lit = a.light_samples > 0 && a.env;
-  DRM_TRY(check_quadrature("render_mesh", a.quad, a.subpixel, 0, a.env, a.EH, a.EW));
-  const size_t need = render_mesh_workspace_bytes(a.F, a.B, a.H, a.W, a.subpixel);
-  DRM_REQUIRE(need != 0 && a.V >= 1 && a.V <= 0x7fffffffLL,
+// Every mesh render: the same checks and visibility launches.  shadows verifies the blob (nothing is launched before that) and shades with
+// it; light samples build the tables as the sphere's lit render does and shade with them; bounces = 1 (with shadows and without light
+// samples) shades with one bounce.
+int launch_render_mesh(const drm_shading& sh, const drm_mesh_render& m, hipStream_t s) {
+  DRM_REQUIRE_SIZE(&m, drm_mesh_render);
+  bool lit;
+  std::string light_fault;
+  DRM_TRY(check_shading("render_mesh", sh, m.subpixel, 0, &lit, &light_fault));
+  DRM_REQUIRE(!sh.tables, "render_mesh: a mesh is shaded with principled rows z, not tables");
+  DRM_REQUIRE(m.vertex_positions && m.vertex_normals && m.faces && m.image, "render_mesh: null pointer");
+  DRM_REQUIRE(m.bounces == 0 || (m.bounces == 1 && m.shadows && !lit && m.bounce_quad >= 1 && m.bounce_quad <= 16),
+              "render_mesh: bounces is 0, or 1 with shadows, without light samples and with bounce_quad in [1, 16]");
+  const int B = sh.B;
+  const long long V = m.V, F = m.F;
+  const size_t need = render_mesh_workspace_bytes(F, B, m.H, m.W, m.subpixel);
+  DRM_REQUIRE(need != 0 && V >= 1 && V <= 0x7fffffffLL,
               "render_mesh: 1 <= F < 2^24 faces, V >= 1 vertices, 1 <= B <= 65535 rows, H and W in [1, 4096], subpixel in [1, 4]");
-  const long long blocks = pixel_blocks((long long)a.B * a.H * a.W);
+  const long long blocks = pixel_blocks((long long)B * m.H * m.W);
   DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_mesh: B H W too large for one launch");
-  if (!a.workspace || a.workspace_bytes < need || (reinterpret_cast<uintptr_t>(a.workspace) & 15) != 0) {
+  if (!m.workspace || m.workspace_bytes < need || (reinterpret_cast<uintptr_t>(m.workspace) & 15) != 0) {
     set_error("render_mesh: workspace must be 16-byte aligned and hold drm_render_mesh_workspace_bytes = " + std::to_string(need) + " bytes");
     return DRM_ERR_WORKSPACE;
   }
-  char* lws = lit ? static_cast<char*>(a.light_workspace) : nullptr;
-  if (lit) {
-    DRM_REQUIRE(light_samples_ok(a.light_samples), "render_mesh_lit: light_samples must be 0 or a power of two in [64, 65536]");
-    const std::string fault = light_workspace_fault("render_mesh_lit: light_workspace", a.light_workspace, a.light_workspace_bytes,
-                                                    render_light_workspace_bytes(a.B, a.EH, a.EW, a.light_samples));
-    DRM_REQUIRE(fault.empty(), fault);
-  }
-  if (a.shadowed) DRM_TRY(check_device_bvh(a.bvh, a.bvh_bytes, true, a.F, s, "render_mesh_shadowed"));
-  float* records = static_cast<float*>(a.workspace);
-  float* hits = records + (size_t)a.B * a.F * kMeshRecordWords;
-  DRM_TRY(launch_mesh_visibility(a.positions, a.faces, a.V, a.F, a.view, a.B, a.H, a.W, a.subpixel, records, hits, s));
-  if (lit) launch_light_tables(a.env, lws, a.B, a.EH, a.EW, a.light_samples, s);
+  DRM_REQUIRE(light_fault.empty(), light_fault);
+  if (m.shadows) DRM_TRY(check_device_bvh(m.bvh, m.bvh_bytes, true, F, s, "render_mesh"));
+  float* records = static_cast<float*>(m.workspace);
+  float* hits = records + (size_t)B * F * kMeshRecordWords;
+  DRM_TRY(launch_mesh_visibility(m.vertex_positions, m.faces, V, F, sh.view, B, m.H, m.W, m.subpixel, records, hits, s));
+  if (lit) launch_light_tables(sh, s);
   // the instantiation: with or without the view, then the technique
   const auto shade = [&](auto with_view) {
     constexpr bool VIEW = decltype(with_view)::value;
-    const auto launch = [&](auto kernel, auto sh, auto li, auto bo) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, a.z, a.env, a.view, a.normals, records, hits, a.image, a.normal, a.depth,
-                         a.alpha, a.B, a.F, a.H, a.W, a.env ? a.EH : 1, a.env ? a.EW : 1, a.quad, a.subpixel, sh, li, bo);
+    const auto launch = [&](auto kernel, auto shadow, auto li, auto bo) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, sh.z, sh.envmap, sh.view, m.vertex_normals, records, hits, m.image,
+                         m.normal, m.depth, m.alpha, B, F, m.H, m.W, sh.envmap ? sh.EH : 1, sh.envmap ? sh.EW : 1, sh.quad, m.subpixel, shadow, li, bo);
     };
-    const ShadowArgs sh{a.positions, a.faces, a.V, a.bvh};
-    const LightArgs li{lws, a.light_samples};
-    if (a.bounce_quad) launch(mesh_shade_kernel<VIEW, true, false, true>, sh, NoLightArgs{}, BounceArgs{a.bounce_quad});
-    else if (lit && a.shadowed) launch(mesh_shade_kernel<VIEW, true, true>, sh, li, NoBounceArgs{});
+    const ShadowArgs shadow{m.vertex_positions, m.faces, V, m.bvh};
+    const LightArgs li{lit ? static_cast<char*>(sh.light_workspace) : nullptr, sh.light_samples};
+    if (m.bounces) launch(mesh_shade_kernel<VIEW, true, false, true>, shadow, NoLightArgs{}, BounceArgs{m.bounce_quad});
+    else if (lit && m.shadows) launch(mesh_shade_kernel<VIEW, true, true>, shadow, li, NoBounceArgs{});
     else if (lit) launch(mesh_shade_kernel<VIEW, false, true>, NoShadowArgs{}, li, NoBounceArgs{});
-    else if (a.shadowed) launch(mesh_shade_kernel<VIEW, true, false>, sh, NoLightArgs{}, NoBounceArgs{});
+    else if (m.shadows) launch(mesh_shade_kernel<VIEW, true, false>, shadow, NoLightArgs{}, NoBounceArgs{});
     else launch(mesh_shade_kernel<VIEW, false, false>, NoShadowArgs{}, NoLightArgs{}, NoBounceArgs{});
   };
-  if (a.view) shade(std::true_type{});
+  if (sh.view) shade(std::true_type{});
   else shade(std::false_type{});
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
 
-// A normal map shaded B ways (see drm_render_normals): the checks launch_render_mesh makes of what the two share; light_samples > 0 under
-// a map builds the tables as the lit renders do and shades with them.
-int launch_render_normals(const float* normals, const unsigned char* mask, int Bn, const float* z, const float* env, const float* view, float* image,
-                          float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
-                          size_t light_workspace_bytes, hipStream_t s) {
-  DRM_REQUIRE(normals && z && image, "render_normals: null pointer");
-  DRM_REQUIRE(light_samples >= 0, "render_normals: light_samples >= 0");
-  const bool lit = light_samples > 0 && env;
+// A normal map shaded B ways (see drm_render_normals): light samples build the tables as the lit renders do and shade with them.
+int launch_render_normals(const drm_shading& sh, const float* normals, const unsigned char* mask, int Bn, int H, int W, float* image, float* alpha,
+                          hipStream_t s) {
+  bool lit;
+  std::string light_fault;
+  DRM_TRY(check_shading("render_normals", sh, 1, 0, &lit, &light_fault));
+  DRM_REQUIRE(normals && image, "render_normals: null pointer");
+  const int B = sh.B;
+  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
+              "render_normals: 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
   PixelLaunch pl;
-  DRM_TRY(check_normals_launch("render_normals", B, H, W, Bn, quad, env, EH, EW, view, pl));
-  char* lws = lit ? static_cast<char*>(light_workspace) : nullptr;
+  DRM_TRY(plan_pixel_launch("render_normals", "B H W", (long long)B * H * W, sh.envmap, sh.view, sh.EH, sh.EW, pl));
+  DRM_REQUIRE(light_fault.empty(), light_fault);
+  if (sh.tables) return launch_normals_tables(sh, pl, normals, mask, Bn, H, W, image, alpha, s);
   if (lit) {
-    DRM_REQUIRE(light_samples_ok(light_samples), "render_normals: light_samples must be 0 or a power of two in [64, 65536]");
-    const std::string fault = light_workspace_fault("render_normals: light_workspace", light_workspace, light_workspace_bytes,
-                                                    render_light_workspace_bytes(B, EH, EW, light_samples));
-    DRM_REQUIRE(fault.empty(), fault);
-    launch_light_tables(env, lws, B, EH, EW, light_samples, s);
-  }
-  if (lit) {
+    launch_light_tables(sh, s);
     const auto kernel = pl.view ? normals_lit_kernel<true> : normals_lit_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, z, env, pl.view, image, alpha, B, H, W, pl.EH, pl.EW, quad,
-                       lws, light_samples);
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, normals, mask, Bn, sh.z, sh.envmap, pl.view, image, alpha, B, H, W, pl.EH, pl.EW,
+                       sh.quad, static_cast<char*>(sh.light_workspace), sh.light_samples);
   } else {
     const auto kernel = pl.view ? normals_pixel_kernel<true, RowMaterial<false>> : normals_pixel_kernel<false, RowMaterial<false>>;
-    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, RowArgs{z}, normals, mask, Bn, env, pl.view, image, alpha, B, H, W, pl.EH, pl.EW,
-                       quad);
+    hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * kRenderWaves), 0, s, RowArgs{sh.z}, normals, mask, Bn, sh.envmap, pl.view, image, alpha, B, H, W, pl.EH,
+                       pl.EW, sh.quad);
   }
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
-}
-
-int launch_render_refmap(const float* z, const float* env, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, hipStream_t s) {
-  return launch_render_refmap_views(z, 1, env, nullptr, out, B, R, EH, EW, quad, subpixel, flip, s);
 }
 
 int launch_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, long long N, hipStream_t s) {

@@ -375,14 +375,12 @@ __global__ __launch_bounds__(256) void normals_pixel_kernel(typename MAT::Args m
 
 }  // namespace
 
-// What every launch of a pixel kernel checks of its quadrature and environment (`who` names the entry in the message; subpixel_max = 0: the
-// caller bounds subpixel itself), and its grid: one wave per pixel, kRenderWaves to a workgroup.
-static inline int check_quadrature(const std::string& who, int quad, int subpixel, int subpixel_max, const float* env, int EH, int EW) {
-  DRM_REQUIRE(quad >= 1 && quad <= 1024 && (!subpixel_max || (subpixel >= 1 && subpixel <= subpixel_max)),
-              who + ": quad in [1, 1024]" + (subpixel_max ? ", subpixel in [1, " + std::to_string(subpixel_max) + "]" : ""));
-  DRM_REQUIRE(!env || (EH > 0 && EW > 0 && (long long)EH * EW <= (1LL << 28)), who + ": envmap must be EH x EW with EH, EW >= 1");
-  return DRM_OK;
-}
+// What every render checks of its drm_shading (render.hip) before anything is launched: the struct's size, exactly one material, the
+// quadrature (subpixel_max = 0: the caller bounds subpixel itself), the map sizes and light_samples.  `who` names the entry in the messages.
+// *lit: light samples are in play (light_samples > 0 under a map); light_fault: what is wrong with their workspace, empty where nothing is
+// -- handed back, since each surface reports it with its own code.
+int check_shading(const std::string& who, const drm_shading& sh, int subpixel, int subpixel_max, bool* lit, std::string* light_fault);
+// the grid of a pixel kernel: one wave per pixel, kRenderWaves to a workgroup
 static inline long long pixel_blocks(long long pixels) { return (pixels + kRenderWaves - 1) / kRenderWaves; }
 
 // What the launches of a pixel kernel share whatever the material: the grid, and the environment as the kernel sees it (a view only turns
@@ -399,13 +397,10 @@ static inline int plan_pixel_launch(const std::string& who, const char* size, lo
   pl = PixelLaunch{(unsigned)blocks, env ? view : nullptr, env ? EH : 1, env ? EW : 1};
   return DRM_OK;
 }
-// the normal-map kernel's launches (the sphere's two bound their rows differently and say so in their own words: they share plan_pixel_launch)
-static inline int check_normals_launch(const std::string& who, int B, int H, int W, int Bn, int quad, const float* env, int EH, int EW, const float* view,
-                                       PixelLaunch& pl) {
-  DRM_TRY(check_quadrature(who, quad, 1, 0, env, EH, EW));
-  DRM_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096 && (Bn == 1 || Bn == B),
-              who + ": 1 <= B <= 65535 rows, H and W in [1, 4096], Bn = 1 or B normal maps");
-  return plan_pixel_launch(who, "B H W", (long long)B * H * W, env, view, EH, EW, pl);
-}
+// The launches under tables (brdf_table.hip, next to the material they instantiate), after the checks every material shares: check_tables,
+// then sphere_pixel_kernel / normals_pixel_kernel on the planned grid.
+int launch_refmap_tables(const drm_shading& sh, const PixelLaunch& pl, int R, int subpixel, int flip, float* out, hipStream_t s);
+int launch_normals_tables(const drm_shading& sh, const PixelLaunch& pl, const float* normals, const unsigned char* mask, int Bn, int H, int W, float* image,
+                          float* alpha, hipStream_t s);
 
 }  // namespace drm

@@ -62,15 +62,9 @@ struct ChainIO {
   uint64_t seed;
   int N, H, W;
 };
-// the reference's intermediates (ddim.py:198-200): every_t > 0 with x / pred ([slots][N,C,H,W] each), *n_logged = slots written
-struct ChainLog {
-  int every_t;
-  float *x, *pred;
-  int slots;
-  int* n_logged;
-};
+// log: drm_chain_log of the C ABI, the reference's intermediates (ddim.py:198-200): every_t > 0 with x / pred_x0 ([slots][N,C,H,W] each), *n_logged = slots written
 // opt: drm_sampler_options of the C ABI (mask / x0 blending: see mask_blend_kernel; uncond + guidance_scale: DDIM only; noise dropout)
-int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const float* coef, int S, int num_steps, const ChainLog& log,
+int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const float* coef, int S, int num_steps, const drm_chain_log& log,
                 const drm_sampler_options& opt, Arena& ar, hipStream_t s);
 int ddpm_sample(UNet* net, const ChainIO& io, float* pred_x0, const float* coef, int T_start, int clip, const drm_sampler_options& opt, Arena& ar, hipStream_t s);
 

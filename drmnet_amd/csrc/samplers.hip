@@ -612,7 +612,7 @@ static int chain_run(const std::string& name, UNet* net, const ChainIO& io, int 
   });
 }
 
-int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const float* coef, int S, int num_steps, const ChainLog& log,
+int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const float* coef, int S, int num_steps, const drm_chain_log& log,
                 const drm_sampler_options& opt, Arena& ar, hipStream_t caller) {
   DRM_REQUIRE(net && net->desc.kind == 0, "ddim needs a UNetModel");
   DRM_REQUIRE(S >= 1 && timesteps && coef, "ddim schedule");
@@ -620,7 +620,7 @@ int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const fl
   const int steps = (num_steps > 0 && num_steps < S) ? num_steps : S;
   auto fill = [&](float* rows) -> int {
     int logged = 0;
-    DRM_REQUIRE(!log.x || log.pred, "ddim: the intermediates log needs both buffers");
+    DRM_REQUIRE(!log.x || log.pred_x0, "ddim: the intermediates log needs both buffers");
     for (int j = 0; j < steps; ++j) {
       const int index = S - 1 - j;
       rows[(size_t)j * STEP_ROW] = (float)timesteps[index];
@@ -642,7 +642,7 @@ int ddim_sample(UNet* net, const ChainIO& io, const int64_t* timesteps, const fl
       hipLaunchKernelGGL(cfg_combine_kernel, grid, dim3(256), 0, c.s, c.e, c.e_u, opt.guidance_scale, c.n);
       DRM_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(ddim_update_kernel, grid, dim3(256), 0, c.s, io.x, c.e, io.noise, c.n, c.tab, c.counter, io.seed, log.x, log.pred, opt.noise_dropout,
+    hipLaunchKernelGGL(ddim_update_kernel, grid, dim3(256), 0, c.s, io.x, c.e, io.noise, c.n, c.tab, c.counter, io.seed, log.x, log.pred_x0, opt.noise_dropout,
                        opt.dropout_keep);
     DRM_HIP_CHECK(hipGetLastError());
     return DRM_OK;

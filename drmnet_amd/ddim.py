@@ -1,4 +1,4 @@
-"""``DDIMSampler`` -- same surface as ldm/models/diffusion/ddim.py:16-259, loop executed by drm_ddim_sample_ex.
+"""``DDIMSampler`` -- same surface as ldm/models/diffusion/ddim.py:16-259, loop executed by drm_ddim_sample.
 
 Schedule construction restates make_ddim_timesteps / make_ddim_sampling_parameters
 (ldm/modules/diffusionmodules/util.py:46-74) including the reference's mixed fp32/fp64 rounding sequence
@@ -169,9 +169,10 @@ class DDIMSampler(object):
         log_p = torch.empty_like(log_x) if slots else None
         n_logged = C.c_int32(0)
         with torch.cuda.device(dev):
-            _lib.check(L.drm_ddim_sample_ex(h, img.data_ptr(), c.data_ptr(), ts.ctypes.data_as(C.POINTER(C.c_int64)), coef.ctypes.data_as(C.POINTER(C.c_float)), S,
-                                            int(num_steps or 0), _lib.ptr(noise), seed, C.byref(opt), log_every_t if slots else 0, _lib.ptr(log_x), _lib.ptr(log_p),
-                                            slots, C.byref(n_logged), n, hh, ww, ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+            log = _lib.sized(_lib.ChainLog, every_t=log_every_t if slots else 0, x=_lib.ptr(log_x), pred_x0=_lib.ptr(log_p), slots=slots, n_logged=C.pointer(n_logged))
+            _lib.check(L.drm_ddim_sample(h, img.data_ptr(), c.data_ptr(), ts.ctypes.data_as(C.POINTER(C.c_int64)), coef.ctypes.data_as(C.POINTER(C.c_float)), S,
+                                         int(num_steps or 0), _lib.ptr(noise), seed, C.byref(opt), C.byref(log), n, hh, ww, ws.data_ptr(), ws.numel(),
+                                         _lib.stream_ptr(dev)))
             if any(k is not None for k in keep) or noise_dropout > 0.0:
                 torch.cuda.current_stream(dev).synchronize()  # (the options' tensors stay alive until the chain has run)
         inter["x_inter"] += [log_x[k] for k in range(n_logged.value)]

@@ -154,7 +154,7 @@ class DRMNet(nn.Module):
     def rendering_refmaps(self, envmaps, z: torch.Tensor, brdf_param_names=None, transform: bool = True, view_from=None,
                           new_scene: bool = False) -> torch.Tensor:
         """drmnet.py:667-696: envmaps [B, H, W, 3], z [L, B, P], view_from [B, 3] or None (+z) -> reflectance maps [L, B, 3, R, R], every
-        (list, batch) item under envmaps[b] seen from view_from[b] -- one drm_render_refmap_views launch; the L rows of an item read the same
+        (list, batch) item under envmaps[b] seen from view_from[b] -- one drm_render_refmap launch; the L rows of an item read the same
         map (no copies).  Envmap names (a list of str) are read from ``envmap_dir``."""
         assert len(envmaps) == z.size(1)
         if isinstance(envmaps, (list, tuple)):
@@ -519,7 +519,7 @@ class DRMNet(nn.Module):
         refnet_c(, Lr_0)(, envmap)(, envmap_name)(, view_from)].  A reflectance map the batch brings ("LrK", "Lrk", "Lrkm1", "r0") with a
         finite [b, 0, 0, 0] is used as it is; every other one is rendered from its code of the stack (zK, zk, zkm1[, z0]) under
         batch["envmap"][b] (read from envmap_dir/<name>.exr where missing or NaN-marked) seen from batch["view_from"][b], all of them in one
-        drm_render_refmap_views launch (a NaN code, zkm1 where K == 0, gives a NaN map).  Then the exposure scale of LrK (``normalizing_scale``) is applied to every map, then
+        drm_render_refmap launch (a NaN code, zkm1 where K == 0, gives a NaN map).  Then the exposure scale of LrK (``normalizing_scale``) is applied to every map, then
         ``ds.transform``.  Nothing is written to a refmap cache."""
         from . import ops
 

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .render import QUAD, SUBPIXEL, _device, _env_and_view, canonical_rows, check_light_samples, light_samples_error, view_rotation
+from .render import QUAD, SUBPIXEL, _device, _env_and_view, canonical_rows, check_light_samples, view_rotation
 
 Mesh = Dict[str, torch.Tensor]
 _KEYS = ("vertex_positions", "vertex_normals", "faces")
@@ -238,16 +238,16 @@ def check_bounces(bounces, bounce_quad, shadows, light_samples) -> int:
 def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, image_size, view_from=None,
                 quad: int = QUAD, subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None, light_samples: int = 0, bounces: int = 0,
                 bounce_quad: int = 4):
-    """One call of drm_render_mesh (``shadows=True``: of drm_render_mesh_shadowed, where parts of the mesh cut light off from other parts;
+    """One call of drm_render_mesh (``shadows=True``: with shadow rays, where parts of the mesh cut light off from other parts;
     ``bvh`` is then the mesh's ``build_bvh`` blob, built here when None): one mesh, lit and seen B ways.  z [B, P], envmaps [B, EH, EW, 3] (or None: white), view_from [B, 3] (or
     None: +z), image_size H or (H, W) -> (image [B, 3, H, W], normal [B, 3, H, W] in the view frame, depth [B, 1, H, W], alpha [B, H, W]).
-    ``light_samples`` = M > 0 (a power of two in [64, 65536]) renders through drm_render_mesh_lit: M directions drawn from each map's own
+    ``light_samples`` = M > 0 (a power of two in [64, 65536]) adds light samples: M directions drawn from each map's own
     light density join the two lobe quadratures by multiple importance sampling, as in ``render.render``, and with ``shadows`` every light
     sample is traced like a lobe direction, so the cast shadow of a sun is decided by the sun's own samples.  0, or no envmaps, is the
     render without them bit for bit.
-    ``bounces`` = 1 (needs ``shadows``; not combined with ``light_samples``) renders through drm_render_mesh_bounced: a lobe direction the
+    ``bounces`` = 1 (needs ``shadows``; not combined with ``light_samples``) adds one bounce: a lobe direction the
     mesh cuts off reads the radiance its closest hit reflects back under direct light, estimated with ``bounce_quad``^2 traced directions
-    (1 <= bounce_quad <= 16); 0 makes exactly the calls above.  A bad combination is a ValueError before anything touches the GPU.
+    (1 <= bounce_quad <= 16); 0 makes exactly the launches above.  A bad combination is a ValueError before anything touches the GPU.
     GPU only: a ``z`` or ``envmaps`` tensor on the CPU, or a machine without a GPU, is a RuntimeError (the mesh itself and ``view_from`` are
     host data and are brought over)."""
     bounces = check_bounces(bounces, bounce_quad, shadows, light_samples)
@@ -262,7 +262,7 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     H, W = (int(image_size), int(image_size)) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
     rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
     pos, nrm, faces = _mesh_on(obj, dev)
-    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    env, view = _env_and_view(envmaps, view_from, B, dev)
     lib = _lib.lib()
     V, F = int(pos.shape[0]), int(faces.shape[0])
     nbytes = int(lib.drm_render_mesh_workspace_bytes(F, B, H, W, int(subpixel)))
@@ -274,28 +274,14 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
-    light_samples = int(light_samples)
-    if light_samples < 0:
-        raise ValueError(f"light_samples must be >= 0, got {light_samples}")
-    light_ws, light_bytes = None, 0
-    if light_samples and env is not None:
-        light_bytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
-        if light_bytes == 0:
-            raise light_samples_error(light_samples)
-        light_ws = torch.empty(((light_bytes + 7) // 8,), dtype=torch.float64, device=dev)
-    args = (pos.data_ptr(), nrm.data_ptr(), faces.data_ptr(), V, F, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(), normal.data_ptr(),
-            depth.data_ptr(), alpha.data_ptr(), B, H, W, EH, EW, int(quad), int(subpixel), ws.data_ptr(), nbytes)
+    shading, _keep = _lib.make_shading(B, z=rows, env=env, view=view, quad=quad, light_samples=light_samples)
     with torch.cuda.device(dev):
         blob = _bvh_on(build_bvh(obj) if bvh is None else bvh, dev) if shadows else None
-        if light_ws is not None:
-            _lib.check(lib.drm_render_mesh_lit(*args, _lib.ptr(blob), 0 if blob is None else int(blob.numel()), light_samples, light_ws.data_ptr(),
-                                               light_bytes, _lib.stream_ptr(dev)))
-        elif bounces:
-            _lib.check(lib.drm_render_mesh_bounced(*args, blob.data_ptr(), int(blob.numel()), int(bounce_quad), _lib.stream_ptr(dev)))
-        elif shadows:
-            _lib.check(lib.drm_render_mesh_shadowed(*args, blob.data_ptr(), int(blob.numel()), _lib.stream_ptr(dev)))
-        else:
-            _lib.check(lib.drm_render_mesh(*args, _lib.stream_ptr(dev)))
+        m = _lib.sized(_lib.MeshRender, vertex_positions=pos.data_ptr(), vertex_normals=nrm.data_ptr(), faces=faces.data_ptr(), V=V, F=F, H=H, W=W,
+                       subpixel=int(subpixel), image=image.data_ptr(), normal=normal.data_ptr(), depth=depth.data_ptr(), alpha=alpha.data_ptr(),
+                       workspace=ws.data_ptr(), workspace_bytes=nbytes, shadows=int(blob is not None), bvh=_lib.ptr(blob),
+                       bvh_bytes=0 if blob is None else int(blob.numel()), bounces=bounces, bounce_quad=int(bounce_quad) if bounces else 0)
+        _lib.check(lib.drm_render_mesh(shading, m, _lib.stream_ptr(dev)))
     return image, normal, depth, alpha
 
 

@@ -314,7 +314,7 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def _ddpm_loop(self, cond, shape, x_T=None, timesteps=None, start_T=None, noise=None, seed=None, mask=None, x0=None, mask_noise=None, blend_when=1,
                    temperature=1.0, noise_dropout=0.0, dropout_keep=None):
-        """The ancestral chain on the device (drm_ddpm_sample_ex).  mask / x0: the known-region blending of the reference's two loops --
+        """The ancestral chain on the device (drm_ddpm_sample).  mask / x0: the known-region blending of the reference's two loops --
         ``blend_when`` 1 = LatentDiffusion.p_sample_loop (after p_sample, q_sample(x0, t): ddpm.py:1300-1302), 0 = ObsNetDiffusion.p_sample_loop (before
         p_sample, x0 itself at t == 0, else q_sample(x0, t - 1): models/obsnet.py:545-547); ``mask_noise`` [T,N,C,H,W] injects q_sample's draws.
         ``temperature`` scales the step noise (ddpm.py:1157: the exp(0.5 logvar) column); ``noise_dropout`` is p_sample's F.dropout on it (ddpm.py:1158-1159;
@@ -358,9 +358,9 @@ class LatentDiffusion(DDPM):
             blend = _lib.make_mask_blend(mask, x0, q, mask_noise, blend_when, tuple(img.shape))
         opt, keep = _lib.make_sampler_options(tuple(img.shape), T, blend=blend, noise_dropout=noise_dropout, dropout_keep=dropout_keep)
         with torch.cuda.device(dev):
-            _lib.check(L.drm_ddpm_sample_ex(h, img.data_ptr(), pred_x0.data_ptr(), c.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), T,
-                                            int(bool(self.clip_denoised)), _lib.ptr(noise), seed, C.byref(opt), n, hh, ww, ws.data_ptr(), ws.numel(),
-                                            _lib.stream_ptr(dev)))
+            _lib.check(L.drm_ddpm_sample(h, img.data_ptr(), pred_x0.data_ptr(), c.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), T,
+                                         int(bool(self.clip_denoised)), _lib.ptr(noise), seed, C.byref(opt), n, hh, ww, ws.data_ptr(), ws.numel(),
+                                         _lib.stream_ptr(dev)))
         if any(k is not None for k in keep) or noise_dropout > 0.0:
             torch.cuda.current_stream(dev).synchronize()  # (the options' tensors stay alive until the chain has run)
         return img, pred_x0
@@ -458,7 +458,7 @@ class ObsNetDiffusion(LatentDiffusion):
         reference compares against " raw_refmap" with a leading space, and that branch needs the Mitsuba object-image renderer): the first ``bs``
         items of a MaskedRefmapDataset batch -> [LrK_z, c, mask(, LrK, LrK_rec)(, cond)].  Rows whose ``batch[k]`` has a NaN [b, 0, 0, 0], or every
         row when the batch has no ``k``, are rendered from zK under batch["envmap"][b] (read from envmap_dir/<name>.exr where missing or NaN-marked)
-        seen from batch["view_from"][b], all of them in one drm_render_refmap_views launch.  Then ``ds.transform(LrK, dynamic_normalize=True,
+        seen from batch["view_from"][b], all of them in one drm_render_refmap launch.  Then ``ds.transform(LrK, dynamic_normalize=True,
         mask=mask)`` and one drm_obs_forward_process launch: c = mask LrK + noisy_observe e1 + (1 - mask) e2.  The reference's in-place
         ``cond += ...`` also lands in c (IdentityFirstStage.encode returns its argument); restated explicitly: c and cond are the padded tensor.
         The .pt caches are neither read nor written.

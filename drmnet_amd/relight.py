@@ -90,24 +90,18 @@ def render_normals(normals, z, brdf_param_names: Sequence[str], envmaps: Optiona
     rows = canonical_rows(zt.to(dev), brdf_param_names).reshape(-1, 6).contiguous()
     nrm = normals.to(dev, torch.float32).reshape(Bn, H, W, 3).contiguous()
     m8 = _mask_on(mask, Bn, H, W, dev)
-    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    env, view = _env_and_view(envmaps, view_from, B, dev)
     image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    lib = _lib.lib()
-    light_ws, light_bytes = None, 0
-    if light_samples and env is not None:
-        light_bytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
-        light_ws = torch.empty(((light_bytes + 7) // 8,), dtype=torch.float64, device=dev)
+    shading, _keep = _lib.make_shading(B, z=rows, env=env, view=view, quad=quad, light_samples=light_samples)
     with torch.cuda.device(dev):
-        _lib.check(lib.drm_render_normals(nrm.data_ptr(), _lib.ptr(m8), Bn, rows.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(),
-                                          alpha.data_ptr(), B, H, W, EH, EW, int(quad), light_samples if light_ws is not None else 0,
-                                          _lib.ptr(light_ws), light_bytes, _lib.stream_ptr(dev)))
+        _lib.check(_lib.lib().drm_render_normals(shading, nrm.data_ptr(), _lib.ptr(m8), Bn, H, W, image.data_ptr(), alpha.data_ptr(), _lib.stream_ptr(dev)))
     return image, alpha
 
 
 @torch.no_grad()
 def render_normals_measured(normals, bsdfs, envmaps: Optional[torch.Tensor] = None, *, mask=None, view_from=None, quad: int = QUAD, lookup: str = "linear"):
-    """One call of drm_render_normals_table: ``render_normals`` under measured BRDFs.  ``bsdfs`` is one merl.MeasuredBSDF, shared by all rows,
+    """One call of drm_render_normals under tables: ``render_normals`` under measured BRDFs.  ``bsdfs`` is one merl.MeasuredBSDF, shared by all rows,
     or a list of B (equal objects share one device table); B is the number of envmaps [B, EH, EW, 3], or of bsdfs under a white environment
     (None).  normals, mask and view_from as in ``render_normals``; ``lookup`` is "linear" or "nearest" -> (image [B, 3, H, W], alpha [B, H, W]),
     what ``render_normals`` returns.  There are no light samples under a table."""
@@ -132,13 +126,12 @@ def render_normals_measured(normals, bsdfs, envmaps: Optional[torch.Tensor] = No
     tables, table_of, alpha = device_tables(bsdfs, B, dev)
     nrm = normals.to(dev, torch.float32).reshape(Bn, H, W, 3).contiguous()
     m8 = _mask_on(mask, Bn, H, W, dev)
-    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    env, view = _env_and_view(envmaps, view_from, B, dev)
     image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
     drawn = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    shading, _keep = _lib.make_shading(B, tables=(tables, table_of, alpha, linear), env=env, view=view, quad=quad)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().drm_render_normals_table(nrm.data_ptr(), _lib.ptr(m8), Bn, tables.data_ptr(), int(tables.shape[0]), table_of.data_ptr(),
-                                                       alpha.data_ptr(), _lib.ptr(env), _lib.ptr(view), image.data_ptr(), drawn.data_ptr(), B, H, W,
-                                                       EH, EW, int(quad), linear, _lib.stream_ptr(dev)))
+        _lib.check(_lib.lib().drm_render_normals(shading, nrm.data_ptr(), _lib.ptr(m8), Bn, H, W, image.data_ptr(), drawn.data_ptr(), _lib.stream_ptr(dev)))
     return image, drawn
 
 

@@ -58,7 +58,7 @@ def _device(*tensors) -> torch.device:
 
 
 def view_rotation(view_from) -> torch.Tensor:
-    """view_from [B, 3] (or [3]) -> the row-major rotations [B, 3, 3] drm_render_refmap_views reads: the reference's
+    """view_from [B, 3] (or [3]) -> the row-major rotations [B, 3, 3] a drm_shading's view holds: the reference's
     look_at(origin=view_from, target=0, up=+y) (utils/mitsuba3_utils.py:394-396) with columns (right, up', back), back = v / |v|,
     right = normalize(+y x back), up' = back x right.  [0, 0, d > 0] gives the identity exactly; a view along +-y has no right vector and is
     a ValueError.  Built on the host (a [B, 3] input on the GPU is brought over: view positions are per-item metadata)."""
@@ -75,30 +75,27 @@ def view_rotation(view_from) -> torch.Tensor:
 
 def _env_and_view(envmaps, view_from, B: int, dev: torch.device):
     """envmaps [B, H, W, 3] (or None: white) and view_from [B, 3] (or None: +z), checked against B and brought to ``dev`` ->
-    (env, EH, EW, view [B, 3, 3]); None, 0, 0 and None for what is not given."""
-    env, EH, EW, view = None, 0, 0, None
+    (env, view [B, 3, 3]); None for what is not given."""
+    env, view = None, None
     if envmaps is not None:
         env = envmaps.to(dev, torch.float32)
         if env.dim() != 4 or env.shape[0] != B or env.shape[3] != 3:
             raise ValueError(f"envmaps must be [B={B}, H, W, 3], got {tuple(env.shape)}")
         env = env.contiguous()
-        EH, EW = int(env.shape[1]), int(env.shape[2])
     if view_from is not None:
         view = view_rotation(view_from)
         if view.shape[0] != B:
             raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
         view = view.to(dev)
-    return env, EH, EW, view
+    return env, view
 
 
-def light_samples_error(light_samples) -> ValueError:
-    """what a ``light_samples`` that is neither 0 nor a power of two in [64, 65536] raises, wherever it is found out"""
-    return ValueError(f"light_samples must be 0 or a power of two in [64, 65536], got {light_samples}")
+light_samples_error = _lib.light_samples_error
 
 
 def check_light_samples(light_samples) -> int:
     """``light_samples`` as an int: 0 (none) or a power of two in [64, 65536]; anything else is a ValueError (a renderer's constructor asks this;
-    ``render`` and ``render_mesh`` learn the same from drm_render_light_workspace_bytes, which answers 0 for what the library will not take)"""
+    ``_lib.make_shading`` learns the same from drm_render_light_workspace_bytes, which answers 0 for what the library will not take)"""
     m = int(light_samples)
     if m and (m < 64 or m > 65536 or m & (m - 1)):
         raise light_samples_error(light_samples)
@@ -108,9 +105,9 @@ def check_light_samples(light_samples) -> int:
 @torch.no_grad()
 def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD,
            subpixel: int = SUBPIXEL, flip: bool = False, view_from=None, light_samples: int = 0) -> torch.Tensor:
-    """One launch of drm_render_refmap_views: z [B, P] or [L, B, P], envmaps [B, H, W, 3] (or None: white), view_from [B, 3] (or None: +z)
+    """One launch of drm_render_refmap: z [B, P] or [L, B, P], envmaps [B, H, W, 3] (or None: white), view_from [B, 3] (or None: +z)
     -> reflectance maps [B, 3, res, res] or [L, B, 3, res, res].  The L rows of a batch item read the same map: nothing is expanded.
-    ``light_samples`` = M > 0 (a power of two in [64, 65536]) renders through drm_render_refmap_lit: M directions drawn from each map's own
+    ``light_samples`` = M > 0 (a power of two in [64, 65536]) adds light samples: M directions drawn from each map's own
     light density join the two lobe quadratures by multiple importance sampling, which is what a map with a sun or a lamp a few texels wide
     needs (the plain quadrature can be 10 % off there).  0, or no envmaps, is the plain render bit for bit."""
     dev = _device(z, envmaps)
@@ -120,22 +117,11 @@ def render(z, brdf_param_names: Sequence[str], envmaps: Optional[torch.Tensor] =
     stacked = z.dim() == 3
     L, B = (z.shape[0], z.shape[1]) if stacked else (1, z.shape[0])
     rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
-    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    env, view = _env_and_view(envmaps, view_from, B, dev)
     out = torch.empty((L * B, 3, res, res), dtype=torch.float32, device=dev)
-    light_samples = int(light_samples)
-    if light_samples < 0:
-        raise ValueError(f"light_samples must be >= 0, got {light_samples}")
-    lib = _lib.lib()
-    entry, light_args = lib.drm_render_refmap_views, ()
-    if light_samples and env is not None:
-        nbytes = int(lib.drm_render_light_workspace_bytes(B, EH, EW, light_samples))
-        if nbytes == 0:
-            raise light_samples_error(light_samples)
-        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
-        entry, light_args = lib.drm_render_refmap_lit, (light_samples, ws.data_ptr(), nbytes)
+    shading, _keep = _lib.make_shading(B, z=rows, env=env, view=view, quad=quad, light_samples=light_samples)
     with torch.cuda.device(dev):
-        _lib.check(entry(rows.data_ptr(), L, _lib.ptr(env), _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad), int(subpixel),
-                         int(bool(flip)), *light_args, _lib.stream_ptr(dev)))
+        _lib.check(_lib.lib().drm_render_refmap(shading, L, int(res), int(subpixel), int(bool(flip)), out.data_ptr(), _lib.stream_ptr(dev)))
     return out.reshape(L, B, 3, res, res) if stacked else out
 
 
@@ -257,7 +243,7 @@ def eval_bsdf(bsdf, normal, wo, wi, *, lookup: str = "nearest") -> np.ndarray:
 @torch.no_grad()
 def render_table(bsdfs, envmaps: Optional[torch.Tensor] = None, *, res: int = 128, quad: int = QUAD, subpixel: int = SUBPIXEL, flip: bool = False,
                  view_from=None, lookup: str = "linear") -> torch.Tensor:
-    """One launch of drm_render_refmap_table: the sphere of ``render`` under measured BRDFs.  ``bsdfs`` is one merl.MeasuredBSDF, shared by
+    """One launch of drm_render_refmap under tables: the sphere of ``render`` under measured BRDFs.  ``bsdfs`` is one merl.MeasuredBSDF, shared by
     all rows, or a list of B (equal objects share one device table); envmaps [B, H, W, 3] (or None: white, and then B = len(bsdfs), 1 for a
     single one); view_from [B, 3] (or None: +z) -> reflectance maps [B, 3, res, res].  Each table is sampled with its own proxy roughness
     (``MeasuredBSDF.alpha``) and read as ``lookup`` says ("linear" or "nearest")."""
@@ -272,12 +258,11 @@ def render_table(bsdfs, envmaps: Optional[torch.Tensor] = None, *, res: int = 12
     if not 1 <= B <= 65535:
         raise ValueError(f"render_table: B = {B} rows in [1, 65535]")
     tables, table_of, alpha = device_tables(bsdfs, B, dev)
-    env, EH, EW, view = _env_and_view(envmaps, view_from, B, dev)
+    env, view = _env_and_view(envmaps, view_from, B, dev)
     out = torch.empty((B, 3, res, res), dtype=torch.float32, device=dev)
+    shading, _keep = _lib.make_shading(B, tables=(tables, table_of, alpha, linear), env=env, view=view, quad=quad)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().drm_render_refmap_table(tables.data_ptr(), int(tables.shape[0]), table_of.data_ptr(), alpha.data_ptr(), _lib.ptr(env),
-                                                      _lib.ptr(view), out.data_ptr(), B, int(res), EH, EW, int(quad), int(subpixel), int(bool(flip)),
-                                                      linear, _lib.stream_ptr(dev)))
+        _lib.check(_lib.lib().drm_render_refmap(shading, 1, int(res), int(subpixel), int(bool(flip)), out.data_ptr(), _lib.stream_ptr(dev)))
     return out
 
 

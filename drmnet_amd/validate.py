@@ -37,7 +37,7 @@ QUADRATURE_NOTE = ("the reflectance maps are rendered with a fixed 32 x 32 quadr
 def light_note(light_samples: int) -> str:
     """The caveat's replacement once the renders are light-sampled"""
     return (f"the reflectance maps are rendered with a 32 x 32 quadrature per lobe combined by multiple importance sampling with M = {light_samples} "
-            "light samples drawn from each environment map (drm_render_refmap_lit)")
+            "light samples drawn from each environment map (drm_shading's light_samples)")
 
 
 def set_light_samples(model, light_samples: int) -> None:

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define DRM_ABI_VERSION 3
+#define DRM_ABI_VERSION 4
 #define DRM_MAX_LEVELS 8
 
 int drm_abi_version(void);
@@ -185,28 +185,6 @@ int drm_drmnet_sample(drm_drmnet* s, const float* LrK, const float* cond, const 
                       float* Lr0, float* zK, int32_t* K, int32_t* steps_done, int B, int H, int W, void* workspace, size_t workspace_bytes,
                       void* stream);
 
-/* DDIM sampling (DDIMSampler.ddim_sampling + p_sample_ddim, ldm/models/diffusion/ddim.py:128-259).
- *   timesteps: int64[S] (host) ddim_timesteps; coef: float[S][5] (host) = sqrt(a_t), sqrt(1-a_t), sqrt(a_prev),
- *   sqrt(1-a_prev-sigma^2), sigma per index; runs index S-1 .. 0 (or the first num_steps of them).  Synchronises the stream once
- *   at entry (upload of the per-step table).
- *   x: [N,3,H,W] in = x_T, out = final x;  cond: [N,3,H,W];  noise: [steps,N,3,H,W] or NULL (Philox). */
-int drm_ddim_sample(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
-                    const float* noise, uint64_t seed, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The same chain with the reference's `intermediates` (ddim.py:171-204: after the step of `index`, (img, pred_x0) are appended when
- * index % log_every_t == 0 or at the first step): slot k of log_x / log_pred_x0 ([log_slots][N,3,H,W] each, device) receives the k-th appended
- * pair, *n_logged (host) the number of pairs.  The steps that log are marked in the device step table, so graph replay applies unchanged. */
-int drm_ddim_sample_logged(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
-                           const float* noise, uint64_t seed, int log_every_t, float* log_x, float* log_pred_x0, int log_slots, int32_t* n_logged, int N,
-                           int H, int W, void* workspace, size_t workspace_bytes, void* stream);
-
-/* Ancestral DDPM (LatentDiffusion.p_sample via ObsNetDiffusion.p_sample_loop, ldm/models/diffusion/ddpm.py:1079-1167,
- * models/obsnet.py:500-564).  coef: float[T][5] (host) = sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
- * posterior_mean_coef1, posterior_mean_coef2, exp(0.5*posterior_log_variance_clipped) for t = 0..T-1; runs t = T_start-1 .. 0.
- * x: in = x_T, out = last img; pred_x0: [N,3,H,W] out (what ObsNetDiffusion.p_sample_loop returns). */
-int drm_ddpm_sample(drm_unet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip_denoised,
-                    const float* noise, uint64_t seed, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
-
 /* The samplers' `mask` / `x0` arguments (known-region blending): img = q_sample(x0, t) * mask + (1 - mask) * img with
  * q_sample(x0, t) = sqrt(a_bar_t) x0 + sqrt(1 - a_bar_t) noise (ddpm.py:1052-1058).  Where and at which t it is applied differs between the three
  * reference loops, so the caller supplies the (a, b) pair of every chain step and the side of the step:
@@ -214,8 +192,11 @@ int drm_ddpm_sample(drm_unet* net, float* x, float* pred_x0, const float* cond, 
  *   ObsNetDiffusion.p_sample_loop  models/obsnet.py:545-547               before p_sample: x0 itself at t == 0, else t - 1       -> when = 0
  *   LatentDiffusion.p_sample_loop  ldm/models/diffusion/ddpm.py:1300-1302 after p_sample, at the step's t                       -> when = 1
  * (`temperature` of p_sample_ddim / p_sample, ddim.py:255 / ddpm.py:1157, needs no entry point: it scales the sigma column of `coef`.)  Passed through
- * drm_sampler_options below. */
+ * drm_sampler_options below.
+ * struct_bytes, here and in every struct a caller fills: the caller sets it to the struct's sizeof; a library that was built with another
+ * size returns DRM_ERR_INVALID, naming the struct and both sizes, before it reads any other member. */
 typedef struct drm_mask_blend {
+  uint32_t struct_bytes;
   const float* mask;   /* [N, mask_channels, H, W], device */
   int mask_channels;   /* 1 (broadcast over the channels) or 3 */
   const float* x0;     /* [N,3,H,W], device */
@@ -224,7 +205,7 @@ typedef struct drm_mask_blend {
   int when;            /* 0 = before the step's network forward, 1 = after its update */
 } drm_mask_blend;
 
-/* The remaining per-step options of the reference's samplers, in one struct (zero-initialise; every member optional):
+/* The remaining per-step options of the reference's samplers, in one struct (zero-initialise, then struct_bytes; every other member optional):
  *   blend          mask / x0 (above)
  *   uncond         DDIM only -- classifier-free guidance (p_sample_ddim, ldm/models/diffusion/ddim.py:225-232): the unconditional conditioning
  *                  [N,3,H,W]; every step evaluates the network on it as well and uses e = e_uncond + guidance_scale * (e_cond - e_uncond).  (The
@@ -234,6 +215,7 @@ typedef struct drm_mask_blend {
  *                  its own.
  * Not offered: score correctors, quantize_denoised, callbacks (host hooks of the reference with no device meaning here). */
 typedef struct drm_sampler_options {
+  uint32_t struct_bytes;
   const drm_mask_blend* blend;
   const float* uncond;
   float guidance_scale;
@@ -241,14 +223,38 @@ typedef struct drm_sampler_options {
   const float* dropout_keep;
 } drm_sampler_options;
 
-/* drm_ddim_sample_logged / drm_ddpm_sample with the options above (log_every_t <= 0: no intermediates).  Graph replay applies unchanged (every
- * per-step quantity lives in a device table read through the step counter). */
-int drm_ddim_sample_ex(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
-                       const float* noise, uint64_t seed, const drm_sampler_options* opt, int log_every_t, float* log_x, float* log_pred_x0, int log_slots,
-                       int32_t* n_logged, int N, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
-int drm_ddpm_sample_ex(drm_unet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip_denoised,
-                       const float* noise, uint64_t seed, const drm_sampler_options* opt, int N, int H, int W, void* workspace, size_t workspace_bytes,
-                       void* stream);
+/* The reference's `intermediates` of the DDIM chain (ddim.py:171-204: after the step of `index`, (img, pred_x0) are appended when
+ * index % every_t == 0 or at the first step): slot k of x / pred_x0 ([slots][N,3,H,W] each, device) receives the k-th appended pair,
+ * *n_logged (host, may be NULL) the number of pairs.  The steps that log are marked in the device step table, so graph replay applies unchanged.
+ * every_t <= 0: no intermediates, whatever the buffers.  every_t > 0 without both buffers and slots > 0 is DRM_ERR_INVALID. */
+typedef struct drm_chain_log {
+  uint32_t struct_bytes;
+  int32_t every_t;
+  float* x;
+  float* pred_x0;
+  int32_t slots;
+  int32_t* n_logged;
+} drm_chain_log;
+
+/* DDIM sampling (DDIMSampler.ddim_sampling + p_sample_ddim, ldm/models/diffusion/ddim.py:128-259).
+ *   timesteps: int64[S] (host) ddim_timesteps; coef: float[S][5] (host) = sqrt(a_t), sqrt(1-a_t), sqrt(a_prev),
+ *   sqrt(1-a_prev-sigma^2), sigma per index; runs index S-1 .. 0 (or the first num_steps of them).  Synchronises the stream once
+ *   at entry (upload of the per-step table).
+ *   x: [N,3,H,W] in = x_T, out = final x;  cond: [N,3,H,W];  noise: [steps,N,3,H,W] or NULL (Philox).
+ *   opt: NULL means zero options;  log: NULL means no intermediates.  Graph replay applies whatever they hold (every per-step quantity lives
+ *   in a device table read through the step counter). */
+int drm_ddim_sample(drm_unet* net, float* x, const float* cond, const int64_t* timesteps, const float* coef, int S, int num_steps,
+                    const float* noise, uint64_t seed, const drm_sampler_options* opt, const drm_chain_log* log, int N, int H, int W,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* Ancestral DDPM (LatentDiffusion.p_sample via ObsNetDiffusion.p_sample_loop, ldm/models/diffusion/ddpm.py:1079-1167,
+ * models/obsnet.py:500-564).  coef: float[T][5] (host) = sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
+ * posterior_mean_coef1, posterior_mean_coef2, exp(0.5*posterior_log_variance_clipped) for t = 0..T-1; runs t = T_start-1 .. 0.
+ * x: in = x_T, out = last img; pred_x0: [N,3,H,W] out (what ObsNetDiffusion.p_sample_loop returns).
+ * opt: NULL means zero options; opt->uncond must be NULL (guidance exists on the DDIM chain only). */
+int drm_ddpm_sample(drm_unet* net, float* x, float* pred_x0, const float* cond, const float* coef, int T_start, int clip_denoised,
+                    const float* noise, uint64_t seed, const drm_sampler_options* opt, int N, int H, int W, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 size_t drm_sampler_workspace_bytes(const drm_unet* net, int N, int H, int W);
 
@@ -386,86 +392,121 @@ int drm_refmap2refimg(const float* refmap, float* out, uint8_t* mask, int B, int
 /* ---------------------------------------------------------------------------------------------
  * The forward model DRMNet inverts: reflectance maps of a sphere lit by an environment map (csrc/render.hip).
  * ------------------------------------------------------------------------------------------- */
-/* A BSDF row is canonical: z[6] = (metallic, base colour R, G, B, roughness, specular), each clipped to [0, 1] by the kernels.  The BSDF is
- * Mitsuba 3's "principled" with every other parameter 0 (GGX alpha = max(0.001, roughness^2), eta = 2 / (1 - sqrt(0.08 specular)) - 1).
- *
- * Replaces MitsubaRefMapRenderer.rendering (utils/mitsuba3_utils.py:324-430: sphere, "envmap" emitter, "direct" integrator, RefMapSensor
- * :14-89 at +z looking at -z, box filter) and the basis_r0 render of DRMNet.instantiate_brdf_model (models/drmnet.py:328-347).
- *   z [B][6]; envmap [B][EH][EW][3] channels-last lat-long maps (texel (i, j) looks along theta = (i + 1/2) pi / EH, psi = (j + 1/2) 2 pi / EW,
- *   (sin theta sin psi, cos theta, -sin theta cos psi); bilinear, wraps in psi, clamps in theta), or NULL for a white environment (L = 1).
- *   out [B][3][R][R]: pixel (i, j) is the mean over its footprint of the radiance the sphere reflects toward +z at the normal
- *   n = (cos b sin a, sin b, cos b cos a), a = (2 px - 1) pi / 2, b = (1 - 2 py) pi / 2 (flip != 0 negates n.x).
- *   The integral is a deterministic quadrature: subpixel x subpixel normals per pixel, a quad x quad stratified grid per lobe
- *   (GGX-sampled half vectors for the specular lobe, cosine-weighted directions for the diffuse one); bitwise reproducible.
- *   quad in [1, 1024] (32 by default in the Python layer), subpixel in [1, 16] (2). */
-int drm_render_refmap(const float* z, const float* envmap, float* out, int B, int R, int EH, int EW, int quad, int subpixel, int flip, void* stream);
-/* The same kernel on L stacked sets of B rows, each batch item under its own view: what DRMNet.get_input / rendering_refmaps ask of the
- * renderer (models/drmnet.py:559-569, 667-705: a Python loop of MitsubaRefMapRenderer.rendering(z, envmap, view_from) calls, one scene
- * update and one render per (stack, batch) item) in one launch.  drm_render_refmap is this entry with L = 1 and view = NULL.
- *   z [L][B][6]; out [L][B][3][R][R]; row (l, b) is lit by envmap[b] and seen through view[b]: the L rows of a batch item index the same map,
- *   nothing is expanded.  envmap [B][EH][EW][3] or NULL (white; the view is then not read).
+/* What the B rows of any render share: a material, an environment, a view, a quadrature and optional light samples.  Zero-initialise, set
+ * struct_bytes = sizeof(drm_shading), then the members in use.  All pointers are device pointers.
+ *   Material: exactly one of z and tables (both, or neither, is DRM_ERR_INVALID).
+ *     z: principled rows, [B][6], or [L][B][6] for the sphere.  A row is canonical: z[6] = (metallic, base colour R, G, B, roughness, specular),
+ *     each clipped to [0, 1] by the kernels.  The BSDF is Mitsuba 3's "principled" with every other parameter 0 (GGX alpha =
+ *     max(0.001, roughness^2), eta = 2 / (1 - sqrt(0.08 specular)) - 1).
+ *     tables, NT, table_of, table_alpha, table_linear: measured BRDFs ("Measured BRDFs" below states the packed layout, the lookup and the
+ *     checks made of them).  Row b is under table table_of[b] (NULL: table 0 for all); table_alpha [NT]: the proxy roughness of each table,
+ *     in [0.005, 1]; table_linear: the lookup.  Under tables there are no stacks (L == 1), no light samples under a map and no mesh:
+ *     otherwise DRM_ERR_INVALID.  1 <= B <= 65535.
+ *   envmap [B][EH][EW][3]: channels-last lat-long maps (texel (i, j) looks along theta = (i + 1/2) pi / EH, psi = (j + 1/2) 2 pi / EW,
+ *     (sin theta sin psi, cos theta, -sin theta cos psi); bilinear, wraps in psi, clamps in theta), or NULL for a white environment (L = 1;
+ *     EH, EW and the view are then not read).
  *   view [B][9] or NULL: row-major rotations Rot.  Every light direction l of the quadrature (in the frame whose viewer is +z) is looked up
- *   in the environment at Rot l.  For the reference's look_at(origin = v, target = 0, up = +y) (utils/mitsuba3_utils.py:394-396) the columns
- *   of Rot are (right, up', back): back = v / |v|, right = normalize(+y x back), up' = back x right.  NULL and an exact identity skip the
- *   rotation (they are not multiplied by it), so the view from +z is the drm_render_refmap result bit for bit.
- *   Every row is summed in the per-lane order of drm_render_refmap whatever L is: a stacked render equals its rows rendered one by one. */
-int drm_render_refmap_views(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
-                            int subpixel, int flip, void* stream);
-/* drm_render_refmap_views with light sampling, for maps with small bright lights (a sun, a lamp) that fall between the strata of a rough
- * lobe's quadrature.  light_samples = M directions are drawn from each map's own light density and combined with the two lobe quadratures by
- * lobe-separated multiple importance sampling, power heuristic (beta = 2).  Additive: the ABI version is unchanged.
- *   Light density.  On the dual grid of the bilinear lookup: cell (c, j), c = 0 .. EH, j = 0 .. EW - 1, spans theta in
- *   [(c - 1/2), (c + 1/2)] pi / EH clipped to [0, pi] and psi in [(j + 1/2), (j + 3/2)] 2 pi / EW; its corners are the texels
- *   (clamp(c - 1), clamp(c)) x (j, j + 1 mod EW), valued at their Rec. 709 luminance clamped at 0.  Density with respect to (theta, psi):
- *   val sc_c / (tot dpsi), val the bilinear interpolant of the corners, sc_c the sine of the row's mid colatitude, tot the sum over cells of
- *   mean4(corners) sc_c (hi_c - lo_c); p_L(w) = density / max(sin theta, 1e-6).
- *   Samples.  Sample k is the Hammersley point ((k + 1/2) / M, bitreverse32(k) 2^-32 + 1 / (2 M)) taken through the marginal CDF over rows, the
- *   row's conditional CDF over columns and the inverse of the bilinear density inside the cell.  fp64, fixed order, no atomics.
- *   Estimator.  With n_s = n_d = quad^2 (n_d = 0 for a metal) and n_L = M: each lobe sample is weighted by (n p)^2 / ((n p)^2 + (n_L p_L)^2),
- *   p = G1(v) D(h) / (4 n.v) for the specular lobe and n.l / pi for the diffuse one; light sample k with n.l_k > 0 adds
- *   L_k [f_s cos n_L p_L / ((n_s p_s)^2 + (n_L p_L)^2) + f_d cos n_L p_L / ((n_d p_d)^2 + (n_L p_L)^2)] / subpixel^2.
- *   light_samples: 0, or a power of two in [64, 65536].  0, or envmap == NULL, is drm_render_refmap_views exactly (workspace not read).
- *   workspace: at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device memory, 8-byte aligned; it is rebuilt by
- *   every call (three small launches before the render) and holds nothing the caller needs.  A map whose tot is 0 (black, or all
- *   non-positive) has no light technique: its rows are the plain quadrature.  Bitwise reproducible; a stacked render equals its rows alone.
- *   DRM_ERR_INVALID for a bad light_samples, DRM_ERR_WORKSPACE for a missing, misaligned or short workspace: nothing is launched. */
-size_t drm_render_light_workspace_bytes(int B, int EH, int EW, int light_samples); /* 0 for arguments drm_render_refmap_lit rejects */
-int drm_render_refmap_lit(const float* z, int L, const float* envmap, const float* view, float* out, int B, int R, int EH, int EW, int quad,
-                          int subpixel, int flip, int light_samples, void* workspace, size_t workspace_bytes, void* stream);
-/* Object images of a triangle mesh: the input side of the chain (csrc/mesh.hip for visibility, csrc/render.hip for shading).  Replaces
- * MitsubaOrthoRenderer.rendering (utils/mitsuba3_utils.py:433-564: an orthographic camera on a smooth-shaded mesh with image, shading-normal
- * and depth AOVs).  Every visible point is shaded exactly as drm_render_refmap_views shades the sphere point with the same normal: direct
- * light from the environment map, NO interreflection (Mitsuba's path integrator has it), and the background is black, not the environment.
- * drm_render_mesh has NO self-shadowing either: it is the model the reflectance map itself assumes.  drm_render_mesh_shadowed (below) adds
- * shadow rays, drm_render_mesh_lit the light samples of drm_render_refmap_lit, with or without them, drm_render_mesh_bounced one bounce of
- * interreflection on top of the shadow rays.  Additive: the ABI version is unchanged.
- *   One mesh per call, lit and seen B ways: vertex_positions, vertex_normals [V][3], faces [F][3] int32 (smooth shading, no back-face
- *   culling), z [B][6], envmap [B][EH][EW][3] or NULL (white), view [B][9] or NULL (+z).
- *   View frame.  right, up, back are the columns of the row-major Rot = view[b] (the rotation drm_render_refmap_views takes).  Mesh points
- *   and normals enter the view frame as Rot^T p and Rot^T n; the environment is looked up at Rot l.  NULL or an exact identity multiplies
- *   nothing.
- *   Film samples.  H x W pixels, S x S = subpixel^2 samples per pixel, box filter.  Sample (i, sy, j, sx) is at
- *   x = (2 (j S + sx) + 1) / (W S) - 1, y = (H / W) (1 - (2 (i S + sy) + 1) / (H S)); the ray runs along -z, and of the faces covering a
- *   sample the one with the largest view-space z is seen.  The film spans x in [-1, 1] (a mesh normalised to radius 0.9 fits).
- *   Coverage.  All three edge functions, oriented by the sign of the face's screen area, are >= 0 (edges inclusive).  Ties: larger z, then
- *   the lower face index, so the result does not depend on the order faces are visited in.  Faces of zero screen area are skipped, and so is
- *   a face with a vertex index outside [0, V), whose index is never dereferenced.
- *   Shading normal.  The barycentric mix of the three vertex normals, in the view frame, normalised (a zero mix stays zero).  A sample with
- *   no hit, or with n.z <= 0, contributes zero radiance.
- *   Outputs per row b: image [3][H][W] the mean over the S^2 samples of the radiance; normal [3][H][W] the mean of the samples' unit shading
- *   normals, zero for a miss (|normal| > 0.5 is "more than half covered", the mask the reference derives); depth [1][H][W] the mean of
- *   1.1 - z_view over the hit samples, 0 where there are none; alpha [H][W] the hit fraction.  normal, depth and alpha may each be NULL.
- *   Limits: quad in [1, 1024], subpixel in [1, 4], H, W in [1, 4096], 1 <= F < 2^24, V >= 1, 1 <= B <= 65535.  Light samples: drm_render_mesh_lit (below).
- *   workspace: at least drm_render_mesh_workspace_bytes = 80 B F + 16 B (H S) (W S) bytes of device memory, 16-byte aligned: one record per
- *   (row, face) and one hit per film sample, rebuilt by every call.  Three launches (mesh_setup_kernel, mesh_visibility_kernel,
- *   mesh_shade_kernel), no atomics: bitwise reproducible, and a call of B rows equals its rows rendered one by one.
- *   DRM_ERR_INVALID for an argument outside the limits, DRM_ERR_WORKSPACE for a missing, misaligned or short workspace: nothing is launched. */
-size_t drm_render_mesh_workspace_bytes(int64_t F, int B, int H, int W, int subpixel); /* 0 for arguments drm_render_mesh rejects */
-int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                    const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
-                    int quad, int subpixel, void* workspace, size_t workspace_bytes, void* stream);
-/* Self-shadowing for the object images: any-hit ray queries against the mesh through a bounding-volume hierarchy (csrc/bvh.h, csrc/bvh.hip).
- * Additive: the ABI version is unchanged.
+ *     in the environment at Rot l.  For the reference's look_at(origin = v, target = 0, up = +y) (utils/mitsuba3_utils.py:394-396) the columns
+ *     of Rot are (right, up', back): back = v / |v|, right = normalize(+y x back), up' = back x right.  NULL and an exact identity skip the
+ *     rotation (they are not multiplied by it), so the view from +z is the render without a view bit for bit.
+ *   quad in [1, 1024] (32 by default in the Python layer): the integral is a deterministic quadrature, a quad x quad stratified grid per lobe
+ *     (GGX-sampled half vectors for the specular lobe, cosine-weighted directions for the diffuse one); bitwise reproducible.
+ *   light_samples = M: light sampling, for maps with small bright lights (a sun, a lamp) that fall between the strata of a rough lobe's
+ *     quadrature.  M directions are drawn from each map's own light density and combined with the two lobe quadratures by lobe-separated
+ *     multiple importance sampling, power heuristic (beta = 2).
+ *     Light density.  On the dual grid of the bilinear lookup: cell (c, j), c = 0 .. EH, j = 0 .. EW - 1, spans theta in
+ *     [(c - 1/2), (c + 1/2)] pi / EH clipped to [0, pi] and psi in [(j + 1/2), (j + 3/2)] 2 pi / EW; its corners are the texels
+ *     (clamp(c - 1), clamp(c)) x (j, j + 1 mod EW), valued at their Rec. 709 luminance clamped at 0.  Density with respect to (theta, psi):
+ *     val sc_c / (tot dpsi), val the bilinear interpolant of the corners, sc_c the sine of the row's mid colatitude, tot the sum over cells of
+ *     mean4(corners) sc_c (hi_c - lo_c); p_L(w) = density / max(sin theta, 1e-6).
+ *     Samples.  Sample k is the Hammersley point ((k + 1/2) / M, bitreverse32(k) 2^-32 + 1 / (2 M)) taken through the marginal CDF over rows, the
+ *     row's conditional CDF over columns and the inverse of the bilinear density inside the cell.  fp64, fixed order, no atomics.
+ *     Estimator.  With n_s = n_d = quad^2 (n_d = 0 for a metal) and n_L = M: each lobe sample is weighted by (n p)^2 / ((n p)^2 + (n_L p_L)^2),
+ *     p = G1(v) D(h) / (4 n.v) for the specular lobe and n.l / pi for the diffuse one; light sample k with n.l_k > 0 adds
+ *     L_k [f_s cos n_L p_L / ((n_s p_s)^2 + (n_L p_L)^2) + f_d cos n_L p_L / ((n_d p_d)^2 + (n_L p_L)^2)] / subpixel^2.
+ *     M is 0, or a power of two in [64, 65536] (anything else is DRM_ERR_INVALID).  0, or envmap == NULL, makes exactly the launches of the
+ *     render without light samples -- the same bytes -- and the light workspace is neither read nor written.  With light samples
+ *     1 <= B <= 65535.  A map whose tot is 0 (black, or all non-positive) has no light technique: its rows are the plain quadrature.
+ *   light_workspace: at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device memory, 8-byte aligned; one table per
+ *     map b, rebuilt by every call (three small launches before the shading launch) and holding nothing the caller needs.  A missing,
+ *     misaligned or short one is DRM_ERR_WORKSPACE on the sphere and DRM_ERR_INVALID for normal maps and meshes: nothing is launched. */
+typedef struct drm_shading {
+  uint32_t struct_bytes;
+  int32_t B;
+  const float* z;
+  const float* tables;
+  int32_t NT;
+  const int32_t* table_of;
+  const float* table_alpha;
+  int32_t table_linear;
+  const float* envmap;
+  int32_t EH, EW;
+  const float* view;
+  int32_t quad;
+  int32_t light_samples;
+  void* light_workspace;
+  size_t light_workspace_bytes;
+} drm_shading;
+size_t drm_render_light_workspace_bytes(int B, int EH, int EW, int light_samples); /* 0 for arguments the renders reject */
+
+/* Reflectance maps of a sphere: L stacked sets of B rows, each batch item under its own map and view, in one launch.  Replaces
+ * MitsubaRefMapRenderer.rendering (utils/mitsuba3_utils.py:324-430: sphere, "envmap" emitter, "direct" integrator, RefMapSensor :14-89 at +z
+ * looking at -z, box filter), the basis_r0 render of DRMNet.instantiate_brdf_model (models/drmnet.py:328-347) and what DRMNet.get_input /
+ * rendering_refmaps ask of the renderer (models/drmnet.py:559-569, 667-705: a Python loop of rendering(z, envmap, view_from) calls, one scene
+ * update and one render per (stack, batch) item).
+ *   out [L][B][3][R][R]: row (l, b) is lit by envmap[b] and seen through view[b]: the L rows of a batch item index the same map, nothing is
+ *   expanded.  Pixel (i, j) is the mean over its footprint of the radiance the sphere reflects toward +z at the normal
+ *   n = (cos b sin a, sin b, cos b cos a), a = (2 px - 1) pi / 2, b = (1 - 2 py) pi / 2 (flip != 0 negates n.x): subpixel x subpixel normals
+ *   per pixel, each with the quadrature of the shading.  subpixel in [1, 16] (2 by default in the Python layer); L >= 1, B >= 1, L B < 2^31,
+ *   1 <= R <= 8192.  One wave per pixel, fixed per-lane order and butterfly, no atomics: every row is summed in the same per-lane order
+ *   whatever L is, so a stacked render equals its rows rendered one by one, and a batch its rows alone.
+ *   Under tables (MitsubaRefMapRenderer.rendering with a measured BSDF): the same sensor and sub-pixel normals.  The quadrature per normal n
+ *   (v = +z): the quad x quad midpoint grid mapped to the GGX visible normals of roughness alpha seen from v with l = reflect(v, h), and the
+ *   same grid mapped to cosine-weighted directions (the two constructions of the principled render); a sample l of either set with n.l > 0
+ *   (a GGX sample also v.h > 0 and D > 0) adds
+ *     L(Rot l) f_table(n, v, l) (n.l) / (quad^2 (p_s(l) + p_d(l))),  p_s = G1(v) D(h) / (4 n.v) at h = normalize(v + l),  p_d = (n.l) / pi
+ *   (the balance heuristic over both sets: consistent for any alpha, which only decides where the accuracy goes); the pixel is the sum
+ *   over both sets and the subpixel^2 normals, divided by subpixel^2.  All in fp32.
+ *   DRM_ERR_INVALID for a bad size, quadrature, material or light_samples, DRM_ERR_WORKSPACE for the light workspace: nothing is launched. */
+int drm_render_refmap(const drm_shading* shading, int L, int R, int subpixel, int flip, float* out, void* stream);
+
+/* Object images from a normal map: the forward model pointed at the inputs of the estimate (an object image, its normal map, a mask), with
+ * no mesh behind it.  The two entries complement MitsubaOrthoRenderer (utils/mitsuba3_utils.py:433-564), which needs the mesh, and
+ * DRMNet.reconstruct (models/drmnet.py:943-953), which renders the estimate back onto the sphere only.
+ *   normals [Bn][H][W][3]: channel-last, as normal.npy holds them, in the view frame (right, up, back); mask [Bn][H][W] uint8 or NULL;
+ *   Bn = 1 (one normal map for all B rows: one object relit B ways) or B.  n = the normal divided by its length (any length is taken).
+ *   A pixel is not drawn -- image 0, alpha 0 -- where the mask is 0, where the normal is zero or has a NaN or infinite component, and
+ *   where n.z <= 0 (it does not face the viewer at +z).  image [B][3][H][W]; alpha [B][H][W], 1.0 where drawn, may be NULL.
+ *   Limits: 1 <= B <= 65535, H and W in [1, 4096].
+ * drm_render_normals (csrc/render_shared.h, normals_pixel_kernel): every drawn pixel is the radiance its normal reflects toward +z under row b
+ *   of the shading, exactly as drm_render_refmap shades the sphere point and drm_render_mesh the mesh hit with that normal: one wave per pixel,
+ *   the same quad x quad grids, per-lane order and butterfly, subpixel = 1 (under tables: the per-normal sum of the sphere's table render, so a
+ *   pixel whose normal is a sphere normal equals that render's pixel bit for bit).  The view turns the environment lookups only (a lobe
+ *   direction l is looked up at Rot l); the normals are already in the view frame.  Light samples: the same tables, built by the same three
+ *   launches, the same estimator with subpixel = 1.
+ *   Bitwise reproducible; a call of B rows equals its rows alone, and Bn = 1 equals the normal map repeated B times.
+ *   DRM_ERR_INVALID for Bn outside {1, B}, sizes outside the limits, a bad quadrature, material or light_samples, or a missing, misaligned
+ *   or short light workspace: nothing is launched.
+ * drm_image_from_refmap (csrc/refmap.hip, image_from_refmap_kernel): every drawn pixel reads a given reflectance map at its normal -- what
+ *   the image would be if the reflectance-map model held exactly; the inverse of drm_refmap_mask_make's gather.  One thread per pixel.
+ *   refmap [Br][3][R][R] channel-first, as drm_render_refmap writes it and the networks return it; refmask [Br][R][R] uint8 or NULL;
+ *   Br = 1 or B; 1 <= R <= 8192.
+ *   Texel coordinates: the inverse of the sensor's n = (cos b sin a, sin b, cos b cos a) (drm_render_refmap, flip = 0), which is also the
+ *   parametrisation of drm_refmap_mask_make (theta from +y, phi = atan2(n.z, -n.x)):  a = atan2f(n.x, n.z), b = asinf(n.y) (n.y clamped to
+ *   [-1, 1]);  tj = (a / pi + 0.5) R - 0.5, ti = (0.5 - b / pi) R - 0.5: texel (i, j)'s centre maps to (ti, tj) = (i, j).
+ *   Bilinear over the taps (i0, i1) x (j0, j1) = (floor ti, floor ti + 1) x (floor tj, floor tj + 1), every index clamped to [0, R - 1], with
+ *   fy = ti - floor ti, fx = tj - floor tj, added in this order (fp32, no contraction):
+ *     top = (1 - fx) v[i0][j0] + fx v[i0][j1];  bot = (1 - fx) v[i1][j0] + fx v[i1][j1];  value = (1 - fy) top + fy bot.
+ *   With a refmask a pixel is drawn only if all four clamped taps are observed (non-zero), whatever their weights: the rule depends on
+ *   floor ti and floor tj alone, so it changes only where a coordinate crosses an integer.
+ *   DRM_ERR_INVALID for Bn or Br outside {1, B} or sizes outside the limits: nothing is launched. */
+int drm_render_normals(const drm_shading* shading, const float* normals, const uint8_t* mask, int Bn, int H, int W, float* image, float* alpha,
+                       void* stream);
+int drm_image_from_refmap(const float* refmap, const uint8_t* refmask, int Br, int R, const float* normals, const uint8_t* mask, int Bn, float* image,
+                          float* alpha, int B, int H, int W, void* stream);
+
+/* Ray queries against a triangle mesh through a bounding-volume hierarchy (csrc/bvh.h, csrc/bvh.hip): what the shadows and the bounce of
+ * drm_render_mesh are made of, offered on their own.
  *   The intersection rule.  A ray (o, d) is given in OBJECT space; d need not be unit length.  It is occluded iff some face g satisfies all of:
  *   g != exclude; its three vertex indices are in [0, V); and with e1 = p1 - p0, e2 = p2 - p0, pv = d x e2, det = e1.pv, tv = o - p0,
  *   qv = tv x e1, U = tv.pv, V = d.qv, T = e2.qv and s = sign(det):  det != 0 and det is finite;  s U >= 0;  s V >= 0;  s (U + V) <= |det|;
@@ -491,53 +532,8 @@ int drm_render_mesh(const float* vertex_positions, const float* vertex_normals, 
  *   drm_mesh_occluded: one thread per ray.  All pointers are device pointers: origins, dirs [N][3], exclude [N] int32 (a face index, or any
  *   value outside [0, F) for none) or NULL, out [N] int32 0 / 1.  bvh == NULL tests all F faces per ray with the same triangle routine (the
  *   diagnostic path that shows the BVH changes nothing).  The caller vouches for the blob's length as for every other array's.
- *   drm_render_mesh_shadowed: drm_render_mesh (same arguments, same workspace, same setup and visibility launches) with shadow rays; bvh is a
- *   device copy of the blob, 16-byte aligned, required, bvh_bytes its length (a length shorter than the header implies is DRM_ERR_INVALID).
- *   For every hit sample the ray origin is the view-space hit point (x_sample, y_sample, z_hit) taken to object space with Rot (no view:
- *   nothing is multiplied), exclude is the hit face, and every quadrature direction l with a non-zero weight is traced along Rot l, the vector
- *   the environment lookup forms: the specular direction inside its (v.h > 0, n.l > 0, D > 0) branch, the diffuse direction always.  An
- *   occluded direction contributes nothing, an open one exactly what it contributes in drm_render_mesh, so a shadowed image is <= the plain
- *   one in every pixel and channel under a non-negative map.  Interreflection stays out of this entry (one bounce: drm_render_mesh_bounced,
- *   below).  Bitwise reproducible; rows are independent. */
-size_t drm_mesh_bvh_bytes(int64_t F);
-int drm_mesh_bvh_build(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, void* bvh, size_t bytes);
-int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins, const float* dirs,
-                      const int32_t* exclude, int32_t* out, int64_t N, void* stream);
-int drm_render_mesh_shadowed(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                             const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
-                             int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, void* stream);
-/* Light sampling on the object images, for maps with small bright lights: drm_render_mesh / drm_render_mesh_shadowed with the light samples of
- * drm_render_refmap_lit.  Additive: the ABI version is unchanged.
- *   Arguments: those of drm_render_mesh_shadowed, where bvh == NULL with bvh_bytes == 0 means unshadowed (any other bvh is checked as
- *   drm_render_mesh_shadowed checks it); then light_samples, light_workspace, light_workspace_bytes; then stream.
- *   Estimator (the contract).  For a hit sample with shading normal n (n.z > 0), origin o (the view-space hit point taken to object space with
- *   Rot) and hit face g the integrand is L(w) V(w) f(w) cos: V(w) = 0 iff the ray (o, w) is occluded by the intersection rule above with
- *   exclude = g; without a BVH V = 1 everywhere.  Both techniques of drm_render_refmap_lit estimate this one integrand with the SAME weights
- *   as there (n_s = n_d = quad^2, n_d = 0 for a metal, n_L = light_samples):
- *     each lobe sample keeps its power-heuristic weight (n p)^2 / ((n p)^2 + (n_L p_L)^2) and contributes only if the ray along Rot l is open;
- *     it is traced where drm_render_mesh_shadowed traces it, before any texel fetch;
- *     each light-table entry k keeps its term L_k [f_s cos n_L p_L / ((n_s p_s)^2 + (n_L p_L)^2) + f_d cos n_L p_L / ((n_d p_d)^2 + (n_L p_L)^2)]
- *     / subpixel^2 and contributes only if the ray along its table direction is open.  The table holds world (environment-frame)
- *     directions, which in the mesh convention are also the object-space ray directions (as Rot l is for a lobe sample); it enters the
- *     view frame as Rot^T w_k for the BSDF.  It is traced only after its cheap rejections (n.l_k > 0, p_L > 0).
- *   p_L knows nothing of occlusion; the weights of a direction still sum to one, so the estimator is consistent for the shadowed integral.
- *   With a BVH the image is <= the one without in every pixel and channel under a non-negative map.  A map whose tot is 0 renders as
- *   drm_render_mesh / drm_render_mesh_shadowed render it.
- *   light_samples: 0, or a power of two in [64, 65536].  0, or envmap == NULL, makes exactly the launches of drm_render_mesh /
- *   drm_render_mesh_shadowed (the light workspace is not read): the same bytes.
- *   light_workspace: at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device memory, 8-byte aligned, one table per
- *   map b, rebuilt by every call (the three light launches of drm_render_refmap_lit, after the visibility launches).
- *   The lanes keep the per-lane order of the sphere's lit kernel over the pixel's hit samples and meet in its two butterflies: bitwise
- *   reproducible, and a call of B rows equals its rows rendered one by one.
- *   DRM_ERR_INVALID for a bad light_samples, a missing, misaligned or short light workspace, a short or damaged blob or bad sizes;
- *   DRM_ERR_WORKSPACE for the mesh workspace, as in drm_render_mesh: nothing is launched. */
-int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                        const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH, int EW,
-                        int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int light_samples,
-                        void* light_workspace, size_t light_workspace_bytes, void* stream);
-/* One bounce of interreflection for the object images, on a closest-hit ray query of its own.  Additive: the ABI version is unchanged.
- *   The closest hit.  For a ray (o, d) and an exclude, a face g is a CANDIDATE iff the intersection rule above (drm_mesh_occluded) accepts it:
- *   its conditions are unchanged, the clause about a zero fp32 cross product included.  A candidate has, in fp32, t = T / det, u = U / det,
+ *   The closest hit.  For a ray (o, d) and an exclude, a face g is a CANDIDATE iff the intersection rule above accepts it: its conditions are
+ *   unchanged, the clause about a zero fp32 cross product included.  A candidate has, in fp32, t = T / det, u = U / det,
  *   v = V / det, each the correctly rounded quotient (the library is built without any flag that relaxes fp32 division; denormals are kept).
  *   s T > 0 and a finite non-zero det make t one of +0 .. +inf, never NaN.  The hit is the candidate that is least under the lexicographic
  *   order (t, g), t compared as an fp32 value: a total order, so the order faces are visited in cannot matter.  Cross-multiplied products are
@@ -547,13 +543,69 @@ int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_norma
  *   end of the slab test, under the same 2^-20 of slack.  A ray is occluded iff it has a closest hit.
  *   drm_mesh_closest_hit: one launch, one thread per ray; the arguments of drm_mesh_occluded with two outputs: out_face [N] int32 (-1: no
  *   hit) and out_tuv [N][3] float (t, u, v; zeros where there is no hit).  bvh == NULL tests all F faces per ray (the diagnostic path).  The
- *   header check and the error codes are those of drm_mesh_occluded; nothing is launched on an error.
- *   drm_render_mesh_bounced: the arguments of drm_render_mesh_shadowed up to bvh_bytes, then bounce_quad in [1, 16], then stream; the
- *   launches of drm_render_mesh_shadowed with the shading kernel's bounced instantiation in place of the shadowed one.
+ *   header check and the error codes are those of drm_mesh_occluded; nothing is launched on an error. */
+size_t drm_mesh_bvh_bytes(int64_t F);
+int drm_mesh_bvh_build(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, void* bvh, size_t bytes);
+int drm_mesh_occluded(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins, const float* dirs,
+                      const int32_t* exclude, int32_t* out, int64_t N, void* stream);
+int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins,
+                         const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, int64_t N, void* stream);
+
+/* Object images of a triangle mesh: the input side of the chain (csrc/mesh.hip for visibility, csrc/render.hip for shading).  Replaces
+ * MitsubaOrthoRenderer.rendering (utils/mitsuba3_utils.py:433-564: an orthographic camera on a smooth-shaded mesh with image, shading-normal
+ * and depth AOVs).  One mesh per call, lit and seen B ways under a drm_shading with principled rows z [B][6] (tables are DRM_ERR_INVALID).
+ * Every visible point is shaded exactly as drm_render_refmap shades the sphere point with the same normal: direct light from the
+ * environment map, and the background is black, not the environment.  Without shadows there is no self-shadowing: it is the model the
+ * reflectance map itself assumes.  Zero-initialise drm_mesh_render, set struct_bytes = sizeof(drm_mesh_render), then the members in use.
+ *   The mesh: vertex_positions, vertex_normals [V][3], faces [F][3] int32 (smooth shading, no back-face culling).  1 <= F < 2^24, V >= 1.
+ *   View frame.  right, up, back are the columns of the row-major Rot = view[b] of the shading.  Mesh points and normals enter the view frame
+ *   as Rot^T p and Rot^T n; the environment is looked up at Rot l.  NULL or an exact identity multiplies nothing.
+ *   The film: H x W pixels, S x S = subpixel^2 samples per pixel, box filter.  Sample (i, sy, j, sx) is at
+ *   x = (2 (j S + sx) + 1) / (W S) - 1, y = (H / W) (1 - (2 (i S + sy) + 1) / (H S)); the ray runs along -z, and of the faces covering a
+ *   sample the one with the largest view-space z is seen.  The film spans x in [-1, 1] (a mesh normalised to radius 0.9 fits).
+ *   H, W in [1, 4096], subpixel in [1, 4], 1 <= B <= 65535.
+ *   Coverage.  All three edge functions, oriented by the sign of the face's screen area, are >= 0 (edges inclusive).  Ties: larger z, then
+ *   the lower face index, so the result does not depend on the order faces are visited in.  Faces of zero screen area are skipped, and so is
+ *   a face with a vertex index outside [0, V), whose index is never dereferenced.
+ *   Shading normal.  The barycentric mix of the three vertex normals, in the view frame, normalised (a zero mix stays zero).  A sample with
+ *   no hit, or with n.z <= 0, contributes zero radiance.
+ *   The four outputs, per row b: image [3][H][W] the mean over the S^2 samples of the radiance; normal [3][H][W] the mean of the samples' unit
+ *   shading normals, zero for a miss (|normal| > 0.5 is "more than half covered", the mask the reference derives); depth [1][H][W] the mean of
+ *   1.1 - z_view over the hit samples, 0 where there are none; alpha [H][W] the hit fraction.  normal, depth and alpha may each be NULL.
+ *   workspace: at least drm_render_mesh_workspace_bytes = 80 B F + 16 B (H S) (W S) bytes of device memory, 16-byte aligned: one record per
+ *   (row, face) and one hit per film sample, rebuilt by every call.  Three launches (mesh_setup_kernel, mesh_visibility_kernel,
+ *   mesh_shade_kernel), no atomics: bitwise reproducible, and a call of B rows equals its rows rendered one by one.
+ *   shadows != 0: shadow rays, any-hit queries by the intersection rule above (the same workspace, the same setup and visibility launches).
+ *   bvh is a device copy of the blob, 16-byte aligned, required, bvh_bytes its length (a length shorter than the header implies is
+ *   DRM_ERR_INVALID).  shadows == 0: bvh and bvh_bytes are not read.
+ *   For every hit sample the ray origin is the view-space hit point (x_sample, y_sample, z_hit) taken to object space with Rot (no view:
+ *   nothing is multiplied), exclude is the hit face, and every quadrature direction l with a non-zero weight is traced along Rot l, the vector
+ *   the environment lookup forms: the specular direction inside its (v.h > 0, n.l > 0, D > 0) branch, the diffuse direction always.  An
+ *   occluded direction contributes nothing, an open one exactly what it contributes without shadows, so a shadowed image is <= the plain
+ *   one in every pixel and channel under a non-negative map.  Bitwise reproducible; rows are independent.
+ *   Light samples on a mesh (light_samples > 0 of the shading, under a map), with or without shadows.
+ *   Estimator (the contract).  For a hit sample with shading normal n (n.z > 0), origin o (the view-space hit point taken to object space with
+ *   Rot) and hit face g the integrand is L(w) V(w) f(w) cos: V(w) = 0 iff the ray (o, w) is occluded by the intersection rule above with
+ *   exclude = g; without shadows V = 1 everywhere.  Both techniques of the shading's light sampling estimate this one integrand with the SAME
+ *   weights as on the sphere (n_s = n_d = quad^2, n_d = 0 for a metal, n_L = light_samples):
+ *     each lobe sample keeps its power-heuristic weight (n p)^2 / ((n p)^2 + (n_L p_L)^2) and contributes only if the ray along Rot l is open;
+ *     it is traced where the shadowed render traces it, before any texel fetch;
+ *     each light-table entry k keeps its term L_k [f_s cos n_L p_L / ((n_s p_s)^2 + (n_L p_L)^2) + f_d cos n_L p_L / ((n_d p_d)^2 + (n_L p_L)^2)]
+ *     / subpixel^2 and contributes only if the ray along its table direction is open.  The table holds world (environment-frame)
+ *     directions, which in the mesh convention are also the object-space ray directions (as Rot l is for a lobe sample); it enters the
+ *     view frame as Rot^T w_k for the BSDF.  It is traced only after its cheap rejections (n.l_k > 0, p_L > 0).
+ *   p_L knows nothing of occlusion; the weights of a direction still sum to one, so the estimator is consistent for the shadowed integral.
+ *   With shadows the image is <= the one without in every pixel and channel under a non-negative map.  A map whose tot is 0 renders as
+ *   without light samples.  The tables are built by the three light launches of the sphere, after the visibility launches.
+ *   The lanes keep the per-lane order of the sphere's lit kernel over the pixel's hit samples and meet in its two butterflies: bitwise
+ *   reproducible, and a call of B rows equals its rows rendered one by one.
+ *   bounces: 0, or 1 for one bounce of interreflection on the closest-hit query above; 1 needs shadows != 0, no light samples under a map
+ *   and bounce_quad in [1, 16]; anything else is DRM_ERR_INVALID.  The launches of the shadowed render with the shading kernel's bounced
+ *   instantiation in place of the shadowed one.  bounces == 0: bounce_quad is not read.
  *   Estimator (the contract).  The shadowed render, except for a lobe direction w (object space, non-zero weight) whose ray from the hit
  *   sample (origin o, exclude = the hit face g) is occluded.  It no longer drops out: in place of the map's radiance it reads
  *   L_b = the radiance its closest hit reflects toward -w under direct light, traced.  The lobe's weight and everything else about the
- *   sample are unchanged, and an open direction contributes exactly what it contributes in drm_render_mesh_shadowed, bit for bit.  With
+ *   sample are unchanged, and an open direction contributes exactly what it contributes in the shadowed render, bit for bit.  With
  *   (g', t, u, v) the closest hit of (o, w) excluding g:
  *     y = o + t w;  n_y = the normalised barycentric mix (1 - u - v, u, v) of the vertex normals of g', in object space (a zero or NaN mix:
  *     L_b = 0);  w_o = -w / |w|;  n_y.w_o <= 0: L_b = 0.
@@ -567,60 +619,34 @@ int drm_render_mesh_lit(const float* vertex_positions, const float* vertex_norma
  *     |n x .|^2 (0 unless n.w_o > 0 and n.w_k > 0).  V_k = 0 iff the ray (y, w_k) with exclude = g' is occluded (the any-hit rule; a
  *     direction with E = 0 is not traced).  L(w_k) = the map's bilinear radiance along w_k -- an object-space direction is the world
  *     direction, as for lobe rays -- or 1 under a NULL map.
- *   One bounce only; shadows are required (bvh is checked as drm_render_mesh_shadowed checks it); light samples are not combined with it.
  *   Weights and radiances are non-negative under a non-negative map: a bounced image is >= the shadowed one in every pixel and channel.
  *   Each lane runs the K directions of its own bounce serially, in k order: bitwise reproducible, and a call of B rows equals its rows alone.
- *   DRM_ERR_INVALID for a bounce_quad outside [1, 16], a NULL, short or damaged blob or bad sizes, DRM_ERR_WORKSPACE for the mesh workspace,
- *   as in drm_render_mesh_shadowed: nothing is launched. */
-int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, const void* bvh, const float* origins,
-                         const float* dirs, const int32_t* exclude, int32_t* out_face, float* out_tuv, int64_t N, void* stream);
-int drm_render_mesh_bounced(const float* vertex_positions, const float* vertex_normals, const int32_t* faces, int64_t V, int64_t F, const float* z,
-                            const float* envmap, const float* view, float* image, float* normal, float* depth, float* alpha, int B, int H, int W, int EH,
-                            int EW, int quad, int subpixel, void* workspace, size_t workspace_bytes, const void* bvh, size_t bvh_bytes, int bounce_quad,
-                            void* stream);
-/* Object images from a normal map: the forward model pointed at the inputs of the estimate (an object image, its normal map, a mask), with
- * no mesh behind it.  The two entries complement MitsubaOrthoRenderer (utils/mitsuba3_utils.py:433-564), which needs the mesh, and
- * DRMNet.reconstruct (models/drmnet.py:943-953), which renders the estimate back onto the sphere only.  Additive: the ABI version is unchanged.
- *   normals [Bn][H][W][3]: channel-last, as normal.npy holds them, in the view frame (right, up, back); mask [Bn][H][W] uint8 or NULL;
- *   Bn = 1 (one normal map for all B rows: one object relit B ways) or B.  n = the normal divided by its length (any length is taken).
- *   A pixel is not drawn -- image 0, alpha 0 -- where the mask is 0, where the normal is zero or has a NaN or infinite component, and
- *   where n.z <= 0 (it does not face the viewer at +z).  image [B][3][H][W]; alpha [B][H][W], 1.0 where drawn, may be NULL.
- *   Limits: 1 <= B <= 65535, H and W in [1, 4096].
- * drm_render_normals (csrc/render_shared.h, normals_pixel_kernel): every drawn pixel is the radiance its normal reflects toward +z under row b's
- *   BSDF z[b] (z [B][6]) and envmap[b] ([B][EH][EW][3] or NULL: white), exactly as drm_render_refmap_views shades the sphere point and
- *   drm_render_mesh the mesh hit with that normal: one wave per pixel, the same quad x quad grids, per-lane order and butterfly, subpixel = 1.
- *   view [B][9] or NULL: the rotations of drm_render_refmap_views.  They turn the environment lookups only (a lobe direction l is looked up
- *   at Rot l); the normals are already in the view frame.  Under a NULL map the view is not read.
- *   light_samples > 0 with a map: the light samples of drm_render_refmap_lit (the same tables, built by the same three launches, the same
- *   estimator with subpixel = 1) on light_workspace, at least drm_render_light_workspace_bytes(B, EH, EW, light_samples) bytes of device
- *   memory, 8-byte aligned.  light_samples = 0, or envmap == NULL, makes exactly the launch without them (the workspace is not read).
- *   Bitwise reproducible; a call of B rows equals its rows alone, and Bn = 1 equals the normal map repeated B times.
- *   DRM_ERR_INVALID for Bn outside {1, B}, sizes outside the limits, quad outside [1, 1024], a bad light_samples, or a missing, misaligned
- *   or short light workspace: nothing is launched.
- * drm_image_from_refmap (csrc/refmap.hip, image_from_refmap_kernel): every drawn pixel reads a given reflectance map at its normal -- what
- *   the image would be if the reflectance-map model held exactly; the inverse of drm_refmap_mask_make's gather.  One thread per pixel.
- *   refmap [Br][3][R][R] channel-first, as drm_render_refmap writes it and the networks return it; refmask [Br][R][R] uint8 or NULL;
- *   Br = 1 or B; 1 <= R <= 8192.
- *   Texel coordinates: the inverse of the sensor's n = (cos b sin a, sin b, cos b cos a) (drm_render_refmap, flip = 0), which is also the
- *   parametrisation of drm_refmap_mask_make (theta from +y, phi = atan2(n.z, -n.x)):  a = atan2f(n.x, n.z), b = asinf(n.y) (n.y clamped to
- *   [-1, 1]);  tj = (a / pi + 0.5) R - 0.5, ti = (0.5 - b / pi) R - 0.5: texel (i, j)'s centre maps to (ti, tj) = (i, j).
- *   Bilinear over the taps (i0, i1) x (j0, j1) = (floor ti, floor ti + 1) x (floor tj, floor tj + 1), every index clamped to [0, R - 1], with
- *   fy = ti - floor ti, fx = tj - floor tj, added in this order (fp32, no contraction):
- *     top = (1 - fx) v[i0][j0] + fx v[i0][j1];  bot = (1 - fx) v[i1][j0] + fx v[i1][j1];  value = (1 - fy) top + fy bot.
- *   With a refmask a pixel is drawn only if all four clamped taps are observed (non-zero), whatever their weights: the rule depends on
- *   floor ti and floor tj alone, so it changes only where a coordinate crosses an integer.
- *   DRM_ERR_INVALID for Bn or Br outside {1, B} or sizes outside the limits: nothing is launched. */
-int drm_render_normals(const float* normals, const uint8_t* mask, int Bn, const float* z, const float* envmap, const float* view, float* image,
-                       float* alpha, int B, int H, int W, int EH, int EW, int quad, int light_samples, void* light_workspace,
-                       size_t light_workspace_bytes, void* stream);
-int drm_image_from_refmap(const float* refmap, const uint8_t* refmask, int Br, int R, const float* normals, const uint8_t* mask, int Bn, float* image,
-                          float* alpha, int B, int H, int W, void* stream);
+ *   DRM_ERR_INVALID for an argument outside the limits, a bad quadrature, material, light_samples or bounce setting, a missing, misaligned or
+ *   short light workspace, a NULL, short or damaged blob under shadows; DRM_ERR_WORKSPACE for a missing, misaligned or short mesh workspace:
+ *   nothing is launched. */
+typedef struct drm_mesh_render {
+  uint32_t struct_bytes;
+  const float* vertex_positions;
+  const float* vertex_normals;
+  const int32_t* faces;
+  int64_t V, F;
+  int32_t H, W, subpixel;
+  float *image, *normal, *depth, *alpha;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t shadows;
+  const void* bvh;
+  size_t bvh_bytes;
+  int32_t bounces, bounce_quad;
+} drm_mesh_render;
+size_t drm_render_mesh_workspace_bytes(int64_t F, int B, int H, int W, int subpixel); /* 0 for arguments drm_render_mesh rejects */
+int drm_render_mesh(const drm_shading* shading, const drm_mesh_render* mesh, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */
 int drm_brdf_eval(const float* z, int z_rows, const float* n, const float* v, const float* l, float* out, int64_t N, void* stream);
 
-/* Measured BRDFs (csrc/brdf_table.hip): a material given as a MERL table instead of a principled row.  Additive: the ABI version is unchanged.
+/* Measured BRDFs (csrc/brdf_table.hip): a material given as a MERL table instead of a principled row (the tables of a drm_shading).
  * Layout "packed table": one table is [90][90][180][4] fp32 = (theta_h, theta_d, phi_d, (r, g, b, 0)), 23 328 000 bytes, 16-byte aligned, so
  *   a lookup corner is one 16-byte load; `tables` is [NT] such blocks back to back.  Node (i, j, k) stands for theta_h = (i / 90)^2 pi / 2,
  *   theta_d = j pi / 180, phi_d = k pi / 180.  An entry without a measurement (below the horizon) has r = g = b = -1.  The values are
@@ -648,26 +674,8 @@ int drm_brdf_to_merl(const float* z, int rows, float* tables_out, void* stream);
  *   -- Mitsuba's eval convention, as drm_brdf_eval -- for N triples n, v, l [N][3]; coordinates and interpolation in fp64. */
 int drm_merl_eval(const float* tables, int NT, const int32_t* table_of, const float* n, const float* v, const float* l, float* out, int64_t N, int linear,
                   void* stream);
-/* drm_render_refmap_table (MitsubaRefMapRenderer.rendering with a measured BSDF, utils/mitsuba3_utils.py:324-430): the sphere of
- *   drm_render_refmap_views under tables: the same sensor, sub-pixel normals, one wave per pixel, fixed per-lane order and butterfly, no
- *   atomics: bitwise reproducible, and a batch equals its rows rendered alone.  Row b is lit by envmap[b] ([B][EH][EW][3] or NULL: white),
- *   seen through view[b] ([B][9] or NULL: +z), under table table_of[b].  out [B][3][R][R].  1 <= B <= 65535, 1 <= R <= 8192.
- *   alpha [NT] (device): the proxy roughness of each table, in [0.005, 1].  The quadrature per normal n (v = +z): the quad x quad midpoint
- *   grid mapped to the GGX visible normals of roughness alpha seen from v with l = reflect(v, h), and the same grid mapped to cosine-weighted
- *   directions (the two constructions of drm_render_refmap); a sample l of either set with n.l > 0 (a GGX sample also v.h > 0 and D > 0) adds
- *     L(Rot l) f_table(n, v, l) (n.l) / (quad^2 (p_s(l) + p_d(l))),  p_s = G1(v) D(h) / (4 n.v) at h = normalize(v + l),  p_d = (n.l) / pi
- *   (the balance heuristic over both sets: consistent for any alpha, which only decides where the accuracy goes); the pixel is the sum
- *   over both sets and the subpixel^2 normals, divided by subpixel^2.  All in fp32. */
-int drm_render_refmap_table(const float* tables, int NT, const int32_t* table_of, const float* alpha, const float* envmap, const float* view, float* out,
-                            int B, int R, int EH, int EW, int quad, int subpixel, int flip, int linear, void* stream);
-/* drm_render_normals_table: drm_render_normals with (tables, NT, table_of, alpha, linear) in place of z and without light samples: the same
- *   reading of the normal map and drawn mask, and the per-normal sum of drm_render_refmap_table with subpixel = 1 (a pixel whose normal is a
- *   sphere normal equals that render's pixel bit for bit).  image [B][3][H][W]; alpha_out [B][H][W] or NULL. */
-int drm_render_normals_table(const float* normals, const uint8_t* mask, int Bn, const float* tables, int NT, const int32_t* table_of, const float* alpha,
-                             const float* envmap, const float* view, float* image, float* alpha_out, int B, int H, int W, int EH, int EW, int quad,
-                             int linear, void* stream);
 /* drm_brdf_error_sums (csrc/brdf_error.hip; serves drmnet_amd/reflectance.py: brdf_errors, fit_principled, estimate --gt_z / --gt_merl and
- *   merl --fit / --compare.  Additive: the ABI version is unchanged): C candidate rows z [C][6], 1 <= C <= 4096, scored against ONE target on
+ *   merl --fit / --compare): C candidate rows z [C][6], 1 <= C <= 4096, scored against ONE target on
  *   the MERL grid in one pass.  The target is `table` (one packed table, 16-byte aligned) or `z_target` (one principled row [6]); exactly one
  *   of the two is non-NULL.  At a node, a = the candidate's value there = the entry drm_brdf_to_merl stores (the same device function), b =
  *   the target's entry (a principled target's formed the same way), ci = n.wi.  A node counts where drm_brdf_to_merl stores a BRDF value

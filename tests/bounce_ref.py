@@ -1,5 +1,5 @@
 """float64 numpy restatement of the closest-hit query and of the one-bounce render of the mesh object images (drm_mesh_closest_hit,
-drm_render_mesh_bounced: csrc/bvh.h, csrc/bvh.hip and mesh_shade_kernel<VIEW, true, false, true> in csrc/render.hip), written from the contract in
+drm_render_mesh with bounces = 1: csrc/bvh.h, csrc/bvh.hip and mesh_shade_kernel<VIEW, true, false, true> in csrc/render.hip), written from the contract in
 include/drmnet_hip.h on top of tests/shadow_ref.py: brute force over faces, no BVH.  Used by tests/test_bounce_cpu.py and
 tests/test_gpu_bounce.py; nothing here touches a GPU.
 
@@ -172,7 +172,7 @@ def shade(tr, env):
 
 
 def render(positions, normals, faces, z, env, Rot, H, W, S, Q, bounces=1, bounce_quad=4):
-    """drm_render_mesh_bounced for one row (bounces=0: shadow_ref.render, the shadowed image), with the trace added under "trace" """
+    """drm_render_mesh with bounces = 1 for one row (bounces=0: shadow_ref.render, the shadowed image), with the trace added under "trace" """
     if not bounces:
         return sr.render(positions, normals, faces, z, env, Rot, H, W, S, Q)
     tr = trace(positions, normals, faces, z, Rot, H, W, S, Q, bounce_quad)

@@ -150,7 +150,7 @@ def sample_radiance(table, alpha, env, n, Q, rot=None, mode="linear"):
 
 
 def render_table(table, alpha, env, R, Q=32, S=2, flip=False, rot=None, mode="linear"):
-    """drm_render_refmap_table for one row in float64: [3, R, R]"""
+    """drm_render_refmap under a table for one row in float64: [3, R, R]"""
     n = rr.sensor_normals(R, S, flip)
     rows = max(1, (1 << 18) // (R * S * S * Q * Q))
     out = [sample_radiance(table, alpha, env, n[i:i + rows], Q, rot, mode).mean(axis=2) for i in range(0, R, rows)]
@@ -158,7 +158,7 @@ def render_table(table, alpha, env, R, Q=32, S=2, flip=False, rot=None, mode="li
 
 
 def shade(table, alpha, env, normals, mask, Q, rot=None, mode="linear"):
-    """drm_render_normals_table for one row -> (image [3, H, W], drawn [H, W]); normals as relight_ref.unit_normals takes them"""
+    """drm_render_normals under a table for one row -> (image [3, H, W], drawn [H, W]); normals as relight_ref.unit_normals takes them"""
     import relight_ref as rl
 
     n, drawn = rl.unit_normals(normals, mask)

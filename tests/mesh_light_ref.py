@@ -1,4 +1,4 @@
-"""float64 numpy restatement of light sampling on the mesh object images (drm_render_mesh_lit: mesh_shade_kernel<VIEW, SHADOW, true> in
+"""float64 numpy restatement of light sampling on the mesh object images (drm_render_mesh with light samples: mesh_shade_kernel<VIEW, SHADOW, true> in
 csrc/render.hip), written from the estimator in include/drmnet_hip.h.  It composes the three restatements it stands on and adds nothing of
 its own but the composition: light_ref (Density, light_table, light_pdf, _power), shadow_ref (trace, occluded(..., marginal=True)) and
 render_ref.lobes.  Used by tests/test_mesh_light_cpu.py and tests/test_gpu_mesh_light.py; nothing here touches a GPU.
@@ -141,7 +141,7 @@ def trace(positions, normals, faces, z, Rot, H, W, S, Q, shadows=True):
 
 
 def render(positions, normals, faces, z, env, Rot, H, W, S, Q, M, shadows=True):
-    """drm_render_mesh_lit for one row (shadows=False: bvh == NULL): shade(trace(...)) with the trace added under "trace" """
+    """drm_render_mesh with light samples for one row (shadows=False: bvh == NULL): shade(trace(...)) with the trace added under "trace" """
     tr = trace(positions, normals, faces, z, Rot, H, W, S, Q, shadows)
     out = shade(tr, env, M, positions, faces)
     out["trace"] = tr

@@ -1,4 +1,4 @@
-"""float64 numpy restatement of the shadow rays of the mesh object-image renderer (drm_mesh_occluded, drm_render_mesh_shadowed: csrc/bvh.h,
+"""float64 numpy restatement of the shadow rays of the mesh object-image renderer (drm_mesh_occluded, drm_render_mesh with shadows: csrc/bvh.h,
 csrc/bvh.hip and mesh_shade_kernel<VIEW, true> in csrc/render.hip), written from the rule in include/drmnet_hip.h: brute force over faces, no
 BVH.  Used by tests/test_shadow_cpu.py and tests/test_gpu_shadow.py; nothing here touches a GPU.
 
@@ -149,7 +149,7 @@ def shade(tr, env):
 
 
 def render(positions, normals, faces, z, env, Rot, H, W, S, Q, shadows=True):
-    """drm_render_mesh_shadowed (or, shadows=False, drm_render_mesh) for one row: shade(trace(...)) with the trace added under "trace" """
+    """drm_render_mesh with shadows (or, shadows=False, drm_render_mesh) for one row: shade(trace(...)) with the trace added under "trace" """
     tr = trace(positions, normals, faces, z, Rot, H, W, S, Q, shadows)
     out = shade(tr, env)
     out["trace"] = tr

@@ -1,6 +1,6 @@
 """One-bounce interreflection without a GPU: the float64 restatement in tests/bounce_ref.py checked against itself and against
 tests/shadow_ref.py, the new symbols, and the argument errors of the Python surface and of the two entries (drm_mesh_closest_hit,
-drm_render_mesh_bounced) that return before anything touches a GPU.
+drm_render_mesh with bounces = 1) that return before anything touches a GPU.
 
 The contract, restated (include/drmnet_hip.h): a lobe direction w of a hit sample whose ray is occluded reads, instead of the map,
 L_b = (pi / K) sum_k V_k L(w_k) E(n_y, w_o, w_k) / cos_k at its closest hit y -- the candidate of shadow_ref's rule least under (t, face index),
@@ -121,9 +121,10 @@ def test_header_and_symbol_list_carry_the_new_entry_points():
     from drmnet_amd.mesh import MeshRenderer, closest_hit, render_mesh
 
     header = open(os.path.join(ROOT, "include", "drmnet_hip.h")).read()
-    for name in ("drm_mesh_closest_hit", "drm_render_mesh_bounced"):
+    for name in ("drm_mesh_closest_hit", "drm_render_mesh"):
         assert name + "(" in header and name in _lib.SYMBOLS and hasattr(_lib.lib(), name)
-    assert _lib.lib().drm_abi_version() == 3
+    assert {"bounces", "bounce_quad"} <= {n for n, _ in _lib.MeshRender._fields_} and "int32_t bounces, bounce_quad;" in header
+    assert _lib.lib().drm_abi_version() == 4
     sig = inspect.signature(render_mesh).parameters
     assert sig["bounces"].default == 0 and sig["bounce_quad"].default == 4
     assert inspect.signature(closest_hit).parameters["bvh"].default == "auto"
@@ -168,6 +169,7 @@ def test_python_argument_errors_raise_before_anything_touches_a_gpu(tmp_path):
 
 def test_entry_argument_errors_return_before_any_hip_call():
     """host buffers stand in for device memory: every case returns from the checks, which dereference nothing"""
+    import abi_call
     from drmnet_amd import _lib
 
     lib = _lib.lib()
@@ -183,8 +185,9 @@ def test_entry_argument_errors_return_before_any_hip_call():
     INVALID, WORKSPACE = 1, 3
 
     def render(bounce_quad=4, bvh=None, bvh_bytes=0, ws_bytes=need, quad=8, pos_ptr=pos.ctypes.data, Fn=F):
-        return lib.drm_render_mesh_bounced(pos_ptr, nrm.ctypes.data, faces.ctypes.data, V, Fn, z.ctypes.data, env.ctypes.data, None,
-                                           *[o.ctypes.data for o in outs], B, HH, W, EH, EW, quad, 2, ws_ptr, ws_bytes, bvh, bvh_bytes, bounce_quad, None)
+        sh = abi_call.shading(B, z=z.ctypes.data, env=env.ctypes.data, EH=EH, EW=EW, quad=quad)
+        return abi_call.render_mesh(sh, abi_call.mesh_render(pos_ptr, nrm.ctypes.data, faces.ctypes.data, V, Fn, [o.ctypes.data for o in outs], HH, W, 2, ws_ptr,
+                                                             ws_bytes, shadows=1, bvh=bvh, bvh_bytes=bvh_bytes, bounces=1, bounce_quad=bounce_quad))
 
     for want, over in [(INVALID, dict(bounce_quad=0)), (INVALID, dict(bounce_quad=17)), (INVALID, dict(bounce_quad=-4)), (INVALID, dict(quad=0)),
                        (INVALID, dict(pos_ptr=None)), (INVALID, dict(Fn=0)), (INVALID, dict(bvh=None, bvh_bytes=0)),   # shadows are required

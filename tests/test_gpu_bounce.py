@@ -1,4 +1,4 @@
-"""One-bounce interreflection on the GPU (drm_mesh_closest_hit, drm_render_mesh_bounced: csrc/bvh.h, csrc/bvh.hip,
+"""One-bounce interreflection on the GPU (drm_mesh_closest_hit, drm_render_mesh with bounces = 1: csrc/bvh.h, csrc/bvh.hip,
 mesh_shade_kernel<VIEW, true, false, true> in csrc/render.hip, through drmnet_amd.mesh and drmnet_amd.synthesize) against the float64 restatement in
 tests/bounce_ref.py.
 
@@ -203,7 +203,8 @@ def test_bounced_renders_are_reproducible_and_rows_are_independent():
 
 # ---------------------------------------------------------------------------------------------- 5. arguments and surface
 def raw_bounced(mesh, bounce_quad=BQ, blob="build", blob_bytes=None, ws_bytes=None, H=FILM, W=FILM):
-    """drm_render_mesh_bounced through ctypes on sentinel-filled outputs: (status, outputs)"""
+    """drm_render_mesh with bounces = 1 through ctypes on sentinel-filled outputs: (status, outputs)"""
+    import abi_call
     from drmnet_amd import _lib
     from drmnet_amd.mesh import build_bvh
 
@@ -219,9 +220,11 @@ def raw_bounced(mesh, bounce_quad=BQ, blob="build", blob_bytes=None, ws_bytes=No
         blob = build_bvh(as_obj(*mesh))
     dev_blob = None if blob is None else blob.to(DEV)
     nbytes = (0 if blob is None else blob.numel()) if blob_bytes is None else blob_bytes
-    status = lib.drm_render_mesh_bounced(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), V, F, z.data_ptr(),
-                                         env.data_ptr(), None, *[o.data_ptr() for o in outs], 1, H, W, env.shape[1], env.shape[2], Q, S, ws.data_ptr(),
-                                         need if ws_bytes is None else ws_bytes, _lib.ptr(dev_blob), nbytes, bounce_quad, _lib.stream_ptr(DEV))
+    sh = abi_call.shading(1, z=z.data_ptr(), env=env.data_ptr(), EH=env.shape[1], EW=env.shape[2], quad=Q)
+    m = abi_call.mesh_render(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), V, F,
+                             [o.data_ptr() for o in outs], H, W, S, ws.data_ptr(), need if ws_bytes is None else ws_bytes, shadows=1,
+                             bvh=_lib.ptr(dev_blob), bvh_bytes=nbytes, bounces=1, bounce_quad=bounce_quad)
+    status = abi_call.render_mesh(sh, m, _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return status, [o.cpu().numpy() for o in outs]
 

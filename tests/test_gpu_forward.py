@@ -68,6 +68,7 @@ def test_view_off_the_horizontal_circle_is_no_roll():
 
 
 def test_stacked_rows_equal_single_rows_bit_for_bit():
+    import abi_call
     from drmnet_amd import _lib
     from drmnet_amd.render import RefMapRenderer, render, view_rotation
 
@@ -82,18 +83,19 @@ def test_stacked_rows_equal_single_rows_bit_for_bit():
         for b in range(B):
             one = render(z[l, b][None], NAMES6, env[b][None], res=R, view_from=views[b][None])
             assert torch.equal(stacked[l, b], one[0]), (l, b)
-    # no view == the view from +z == identity matrices handed to the kernel, bit for bit; and the L = 1 entry point
+    # no view == the view from +z == identity matrices handed to the kernel, bit for bit; and L = 1 without a view
     plain = render(z, NAMES6, env, res=R)
     assert torch.equal(plain, render(z, NAMES6, env, res=R, view_from=torch.tensor([[0.0, 0.0, 1.1]] * B)))
     assert torch.equal(plain[1], render(z[1], NAMES6, env, res=R))
     eye = torch.eye(3, device=DEV)[None].expand(B, 3, 3).contiguous()
     rows = z.reshape(-1, 6).to(DEV).contiguous()
     out = torch.empty((L, B, 3, R, R), device=DEV)
-    _lib.check(_lib.lib().drm_render_refmap_views(rows.data_ptr(), L, env.data_ptr(), eye.data_ptr(), out.data_ptr(), B, R, 16, 32, 32, 2, 0,
-                                                  _lib.stream_ptr(DEV)))
+    sh = abi_call.shading(B, z=rows.data_ptr(), env=env.data_ptr(), EH=16, EW=32, view=eye.data_ptr(), quad=32)
+    _lib.check(abi_call.render_refmap(sh, L, R, 2, 0, out.data_ptr(), _lib.stream_ptr(DEV)))
     assert torch.equal(out, plain)
     old = torch.empty((B, 3, R, R), device=DEV)
-    _lib.check(_lib.lib().drm_render_refmap(rows.data_ptr(), env.data_ptr(), old.data_ptr(), B, R, 16, 32, 32, 2, 0, _lib.stream_ptr(DEV)))
+    sh = abi_call.shading(B, z=rows.data_ptr(), env=env.data_ptr(), EH=16, EW=32, quad=32)  # (one set of rows, no view)
+    _lib.check(abi_call.render_refmap(sh, 1, R, 2, 0, old.data_ptr(), _lib.stream_ptr(DEV)))
     assert torch.equal(old, plain[0])
     assert not torch.equal(stacked[:, 0], plain[:, 0]) and torch.equal(stacked[:, 1], plain[:, 1])  # (views[1] is +z)
     # the scene object keeps the view it was given, like the map

@@ -435,7 +435,8 @@ def test_estimate_save_merl_writes_a_loadable_table(tmp_path):
 
 # ---------------------------------------------------------------------------------------------- 6. arguments
 def raw_render(entry, tables="ok", NT=2, table_of=(0, 1, 0), alpha=(0.3, 0.5), quad=8, subpixel=1, EH=16, EW=32, out="ok"):
-    """drm_render_refmap_table / drm_render_normals_table through ctypes on sentinel-filled outputs: (status, message, outputs)"""
+    """drm_render_refmap / drm_render_normals under tables through ctypes on sentinel-filled outputs: (status, message, outputs)"""
+    import abi_call
     from drmnet_amd import _lib
 
     lib = _lib.lib()
@@ -444,15 +445,14 @@ def raw_render(entry, tables="ok", NT=2, table_of=(0, 1, 0), alpha=(0.3, 0.5), q
     al = None if alpha is None else torch.tensor(alpha, dtype=torch.float32, device=DEV)
     env = torch.tensor(envs3(), device=DEV)
     tp = {"ok": t.data_ptr(), None: None, "misaligned": t.data_ptr() + 4}[tables]
+    sh = abi_call.shading(3, tables=tp, NT=NT, table_of=_lib.ptr(of), alpha=_lib.ptr(al), linear=1, env=env.data_ptr(), EH=EH, EW=EW, quad=quad)
     if entry == "refmap":
         outs = [torch.full((3, 3, 8, 8), -7.0, device=DEV)]
-        status = lib.drm_render_refmap_table(tp, NT, _lib.ptr(of), _lib.ptr(al), env.data_ptr(), None, outs[0].data_ptr() if out else None, 3, 8, EH, EW, quad,
-                                             subpixel, 0, 1, _lib.stream_ptr(DEV))
+        status = abi_call.render_refmap(sh, 1, 8, subpixel, 0, outs[0].data_ptr() if out else None, _lib.stream_ptr(DEV))
     else:
         nrm = torch.tensor(rl.normal_map(5)[0], device=DEV)
         outs = [torch.full((3, 3, 12, 12), -7.0, device=DEV), torch.full((3, 12, 12), -7.0, device=DEV)]
-        status = lib.drm_render_normals_table(nrm.data_ptr(), None, 1, tp, NT, _lib.ptr(of), _lib.ptr(al), env.data_ptr(), None,
-                                              outs[0].data_ptr() if out else None, outs[1].data_ptr(), 3, 12, 12, EH, EW, quad, 1, _lib.stream_ptr(DEV))
+        status = abi_call.render_normals(sh, nrm.data_ptr(), None, 1, 12, 12, outs[0].data_ptr() if out else None, outs[1].data_ptr(), _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return status, (lib.drm_last_error() or b"").decode(), [o.cpu().numpy() for o in outs]
 

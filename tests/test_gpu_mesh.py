@@ -220,9 +220,9 @@ def test_degenerate_input_matches_the_restatement():
 
 def raw_call(mesh, **over):
     """drm_render_mesh through ctypes on sentinel-filled outputs: (status, outputs)"""
+    import abi_call
     from drmnet_amd import _lib
 
-    lib = _lib.lib()
     obj = {k: v.to(DEV) for k, v in as_obj(*mesh).items()}
     a = dict(V=obj["vertex_positions"].shape[0], F=obj["faces"].shape[0], B=1, H=8, W=8, EH=16, EW=32, quad=Q, subpixel=2)
     a.update({k: v for k, v in over.items() if k in a})
@@ -233,9 +233,10 @@ def raw_call(mesh, **over):
     outs = [torch.full(s, -7.0, device=DEV) for s in ((1, 3, 8, 8), (1, 3, 8, 8), (1, 1, 8, 8), (1, 8, 8))]
     ptrs = [None if over.get("drop_aovs") and k else o.data_ptr() for k, o in enumerate(outs)]
     base = ws.data_ptr() + (-ws.data_ptr()) % 16
-    status = lib.drm_render_mesh(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), a["V"], a["F"],
-                                 zrow.data_ptr(), env.data_ptr(), None, *ptrs, a["B"], a["H"], a["W"], a["EH"], a["EW"], a["quad"], a["subpixel"],
-                                 over.get("ws", base + over.get("ws_offset", 0)), over.get("ws_bytes", need), _lib.stream_ptr(DEV))
+    sh = abi_call.shading(a["B"], z=zrow.data_ptr(), env=env.data_ptr(), EH=a["EH"], EW=a["EW"], quad=a["quad"])
+    m = abi_call.mesh_render(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), a["V"], a["F"], ptrs, a["H"],
+                             a["W"], a["subpixel"], over.get("ws", base + over.get("ws_offset", 0)), over.get("ws_bytes", need))
+    status = abi_call.render_mesh(sh, m, _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return status, [o.cpu().numpy() for o in outs]
 

@@ -1,4 +1,4 @@
-"""Light sampling on mesh object images on the GPU (drm_render_mesh_lit: mesh_shade_kernel<VIEW, SHADOW, true> in csrc/render.hip, through
+"""Light sampling on mesh object images on the GPU (drm_render_mesh with light samples: mesh_shade_kernel<VIEW, SHADOW, true> in csrc/render.hip, through
 drmnet_amd.mesh and drmnet_amd.synthesize) against the float64 restatement tests/mesh_light_ref.py.
 
 The scene is the two-sphere scene of tests/test_gpu_shadow.py (a ball over a body) on its 16 x 16 film, S = 2, Q = 8, with M = 64 light
@@ -99,7 +99,8 @@ def test_lit_mesh_images_match_the_restatement(v, r):
 # ---------------------------------------------------------------------------------------------- 2. neutral and monotonic
 def raw_lit(mesh, shadowed=True, rows=(ROUGH,), envs=(ENV,), views=None, light_samples=M, blob="build", blob_bytes=None, ws_bytes=None, lws_bytes=None,
             lws_offset=0, H=FILM, W=FILM):
-    """drm_render_mesh_lit through ctypes on sentinel-filled outputs: (status, outputs)"""
+    """drm_render_mesh with light samples through ctypes on sentinel-filled outputs: (status, outputs)"""
+    import abi_call
     from drmnet_amd import _lib
     from drmnet_amd.mesh import build_bvh
     from drmnet_amd.render import view_rotation
@@ -120,10 +121,13 @@ def raw_lit(mesh, shadowed=True, rows=(ROUGH,), envs=(ENV,), views=None, light_s
         blob = build_bvh(as_obj(*mesh))
     dev_blob = None if (blob is None or not shadowed) else blob.to(DEV)
     nbytes = (0 if dev_blob is None else dev_blob.numel()) if blob_bytes is None else blob_bytes
-    status = lib.drm_render_mesh_lit(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), V, F, z.data_ptr(),
-                                     _lib.ptr(env), _lib.ptr(view), *[o.data_ptr() for o in outs], B, H, W, EH, EW, Q, S, ws.data_ptr(),
-                                     need if ws_bytes is None else ws_bytes, _lib.ptr(dev_blob), nbytes, light_samples, lws.data_ptr() + lws_offset,
-                                     light_need if lws_bytes is None else lws_bytes, _lib.stream_ptr(DEV))
+    sh = abi_call.shading(B, z=z.data_ptr(), env=_lib.ptr(env), EH=EH, EW=EW, view=_lib.ptr(view), quad=Q, light_samples=light_samples,
+                          lws=lws.data_ptr() + lws_offset, lws_bytes=light_need if lws_bytes is None else lws_bytes)
+    # shadows: what the blob and its length say together (a blob without a length, or a length without a blob, asks for shadows)
+    m = abi_call.mesh_render(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), V, F,
+                             [o.data_ptr() for o in outs], H, W, S, ws.data_ptr(), need if ws_bytes is None else ws_bytes,
+                             shadows=int(dev_blob is not None or nbytes != 0), bvh=_lib.ptr(dev_blob), bvh_bytes=nbytes)
+    status = abi_call.render_mesh(sh, m, _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return status, [o.cpu().numpy() for o in outs]
 
@@ -186,7 +190,7 @@ def test_lit_mesh_renders_are_reproducible_and_rows_are_independent():
             for a, b in zip(stacked, one):
                 assert np.array_equal(a[r], b[0]), (shadowed, r)
         assert not np.array_equal(stacked[0][0], stacked[0][1])
-        # render_mesh(light_samples = M) is drm_render_mesh_lit itself
+        # render_mesh(light_samples = M) is drm_render_mesh with light samples itself
         status, direct = raw_lit(SCENE, shadowed=shadowed, rows=ROWS, envs=envs, views=views)
         assert status == 0
         for a, b in zip(stacked, direct):

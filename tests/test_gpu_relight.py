@@ -191,6 +191,7 @@ def test_the_lookup_at_the_texel_centres_returns_the_map():
 # ---------------------------------------------------------------------------------------------- 6. arguments
 def raw_normals(B=3, Bn=1, H=12, W=12, EH=16, EW=32, quad=Q, light_samples=0, env=True, lws="ok", lws_bytes=None, lws_offset=0):
     """drm_render_normals through ctypes on sentinel-filled outputs of the good sizes: (status, outputs)"""
+    import abi_call
     from drmnet_amd import _lib
 
     lib = _lib.lib()
@@ -200,9 +201,9 @@ def raw_normals(B=3, Bn=1, H=12, W=12, EH=16, EW=32, quad=Q, light_samples=0, en
     outs = [torch.full((3, 3, 12, 12), -7.0, device=DEV), torch.full((3, 12, 12), -7.0, device=DEV)]
     need = int(lib.drm_render_light_workspace_bytes(3, 16, 32, M))
     ws = torch.zeros(need // 8 + 2, dtype=torch.float64, device=DEV)
-    status = lib.drm_render_normals(nrm.data_ptr(), None, Bn, z.data_ptr(), e.data_ptr() if env else None, None, outs[0].data_ptr(), outs[1].data_ptr(), B, H, W,
-                                    EH, EW, quad, light_samples, None if lws is None else ws.data_ptr() + lws_offset,
-                                    need if lws_bytes is None else lws_bytes, _lib.stream_ptr(DEV))
+    sh = abi_call.shading(B, z=z.data_ptr(), env=e.data_ptr() if env else None, EH=EH, EW=EW, quad=quad, light_samples=light_samples,
+                          lws=None if lws is None else ws.data_ptr() + lws_offset, lws_bytes=need if lws_bytes is None else lws_bytes)
+    status = abi_call.render_normals(sh, nrm.data_ptr(), None, Bn, H, W, outs[0].data_ptr(), outs[1].data_ptr(), _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return status, [o.cpu().numpy() for o in outs]
 

@@ -1,4 +1,4 @@
-"""The light-sampled render on the GPU (drm_render_refmap_lit through drmnet_amd.render, DRMNet and validate) against its float64
+"""The light-sampled render on the GPU (drm_render_refmap with light samples through drmnet_amd.render, DRMNet and validate) against its float64
 restatement tests/light_ref.py and, on the sun scene of tests/golden/render_light_sun.npz, against the texel-sum integral.
 
 Not yet run on an MI355X: the bar against the restatement is the 1e-5 the plain render is held to; each test prints its
@@ -39,18 +39,22 @@ def hot_envs():
 
 
 def raw_lit(z, L, env, view, B, R, M, ws=None, ws_bytes=None, out=None, quad=32, flip=0):
-    """drm_render_refmap_lit itself: (status, out)"""
+    """drm_render_refmap itself with light_samples = M: (status, out).  ws = False: no light workspace at all (NULL, 0 bytes)"""
+    import abi_call
     from drmnet_amd import _lib
 
     lib = _lib.lib()
     EH, EW = (int(env.shape[1]), int(env.shape[2])) if env is not None else (0, 0)
-    if ws is None:
+    if ws is False:
+        ws_bytes = 0
+    elif ws is None:
         n = int(lib.drm_render_light_workspace_bytes(B, EH, EW, M))
         ws = torch.empty((max(n, 8) // 8,), dtype=torch.float64, device=DEV)
         ws_bytes = n if ws_bytes is None else ws_bytes
     out = torch.empty((L * B, 3, R, R), device=DEV) if out is None else out
-    st = lib.drm_render_refmap_lit(z.data_ptr(), L, _lib.ptr(env), _lib.ptr(view), out.data_ptr(), B, R, EH, EW, quad, 2, flip, M, ws.data_ptr(), ws_bytes,
-                                   _lib.stream_ptr(DEV))
+    sh = abi_call.shading(B, z=z.data_ptr(), env=_lib.ptr(env), EH=EH, EW=EW, view=_lib.ptr(view), quad=quad, light_samples=M,
+                          lws=None if ws is False else ws.data_ptr(), lws_bytes=ws_bytes)
+    st = abi_call.render_refmap(sh, L, R, 2, flip, out.data_ptr(), _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return st, out
 
@@ -100,14 +104,13 @@ def test_without_light_samples_it_is_the_old_path_bit_for_bit():
     env_d, view_d = envs.to(DEV), view_rotation(view_from).to(DEV)
     old = torch.empty((4, 3, 8, 8), device=DEV)
     for view in (None, view_d):
-        _lib.check(_lib.lib().drm_render_refmap_views(rows.data_ptr(), 2, env_d.data_ptr(), _lib.ptr(view), old.data_ptr(), 2, 8, 32, 64, 32, 2, 0,
-                                                      _lib.stream_ptr(DEV)))
+        assert raw_lit(rows, 2, env_d, view, 2, 8, 0, ws=False, out=old)[0] == 0  # the plain render: no light samples, no workspace
         got = render(z, NAMES6, envs, res=8, light_samples=0, view_from=None if view is None else view_from)
         assert torch.equal(got.reshape(4, 3, 8, 8), old)
         st, raw = raw_lit(rows, 2, env_d, view, 2, 8, 0, ws=torch.empty(1, dtype=torch.float64, device=DEV), ws_bytes=0)
         assert st == 0 and torch.equal(raw, old)
     # no map: the white environment, whatever light_samples says (no workspace is asked for)
-    _lib.check(_lib.lib().drm_render_refmap_views(rows.data_ptr(), 2, None, None, old.data_ptr(), 2, 8, 0, 0, 32, 2, 0, _lib.stream_ptr(DEV)))
+    assert raw_lit(rows, 2, None, None, 2, 8, 0, ws=False, out=old)[0] == 0
     assert torch.equal(render(z, NAMES6, None, res=8, light_samples=1024).reshape(4, 3, 8, 8), old)
     st, raw = raw_lit(rows, 2, None, None, 2, 8, 1024, ws=torch.empty(1, dtype=torch.float64, device=DEV), ws_bytes=0)
     assert st == 0 and torch.equal(raw, old)

@@ -346,8 +346,8 @@ def test_graph_replayed_chain_equals_eager_chain(dev, precision):
 
 
 def test_plain_chain_entry_points_equal_the_host_classes(dev):
-    """drm_ddim_sample / drm_ddim_sample_logged / drm_ddpm_sample (the entry points without drm_sampler_options; the host classes go through the _ex
-    ones) called as INTEGRATION.md binds them: bit for bit what DDIMSampler / p_sample_loop return for the same inputs -- the final state, pred_x0,
+    """drm_ddim_sample (with and without a drm_chain_log) and drm_ddpm_sample with opt = NULL (the host classes always pass a drm_sampler_options)
+    called as INTEGRATION.md binds them: bit for bit what DDIMSampler / p_sample_loop return for the same inputs -- the final state, pred_x0,
     and every logged slot and their count."""
     import ctypes as C
 
@@ -373,13 +373,14 @@ def test_plain_chain_entry_points_equal_the_host_classes(dev):
     sched = (ts.ctypes.data_as(C.POINTER(C.c_int64)), s.ddim_coef.ctypes.data_as(C.POINTER(C.c_float)), 50, 0, noise.data_ptr(), 0)
     with torch.cuda.device(dev):
         x = x_T.clone()
-        _lib.check(L.drm_ddim_sample(h, x.data_ptr(), cond.data_ptr(), *sched, *tail(x)))
+        _lib.check(L.drm_ddim_sample(h, x.data_ptr(), cond.data_ptr(), *sched, None, None, *tail(x)))
         assert torch.equal(x, want_x)
         x = x_T.clone()
         log_x = torch.empty((slots,) + tuple(x.shape), dtype=torch.float32, device=dev)
         log_p = torch.empty_like(log_x)
         n_logged = C.c_int32(0)
-        _lib.check(L.drm_ddim_sample_logged(h, x.data_ptr(), cond.data_ptr(), *sched, 10, log_x.data_ptr(), log_p.data_ptr(), slots, C.byref(n_logged), *tail(x)))
+        log = _lib.sized(_lib.ChainLog, every_t=10, x=log_x.data_ptr(), pred_x0=log_p.data_ptr(), slots=slots, n_logged=C.pointer(n_logged))
+        _lib.check(L.drm_ddim_sample(h, x.data_ptr(), cond.data_ptr(), *sched, None, C.byref(log), *tail(x)))
         assert n_logged.value == slots and torch.equal(x, want_x)
         for k in range(slots):
             assert torch.equal(log_x[k], want["x_inter"][1 + k]) and torch.equal(log_p[k], want["pred_x0"][1 + k]), k
@@ -390,5 +391,5 @@ def test_plain_chain_entry_points_equal_the_host_classes(dev):
         coef = m.ddpm_coef_table()
         x, pred = x_T.clone(), torch.empty_like(x_T)
         _lib.check(L.drm_ddpm_sample(h, x.data_ptr(), pred.data_ptr(), cond.data_ptr(), coef.ctypes.data_as(C.POINTER(C.c_float)), 6, int(bool(m.clip_denoised)),
-                                     noise.data_ptr(), 0, *tail(x)))
+                                     noise.data_ptr(), 0, None, *tail(x)))
         assert torch.equal(x, want["x_inter"][-1]) and torch.equal(pred, want_p)

@@ -1,4 +1,4 @@
-"""Self-shadowing on the GPU (drm_mesh_occluded, drm_render_mesh_shadowed: csrc/bvh.h, csrc/bvh.hip, mesh_shade_kernel<VIEW, true> in
+"""Self-shadowing on the GPU (drm_mesh_occluded, drm_render_mesh with shadows: csrc/bvh.h, csrc/bvh.hip, mesh_shade_kernel<VIEW, true> in
 csrc/render.hip, through drmnet_amd.mesh and drmnet_amd.synthesize) against the float64 restatement in tests/shadow_ref.py.
 
 The rule, restated (include/drmnet_hip.h): a ray (o, d) in object space, d of any length, is occluded iff some face g != exclude with its
@@ -306,7 +306,8 @@ def test_shadowed_renders_are_reproducible_and_rows_are_independent():
 
 # ---------------------------------------------------------------------------------------------- 6. arguments
 def raw_call(mesh, shadowed=True, rows=(ROUGH,), envs=(ENV,), views=None, blob="build", blob_bytes=None, ws_bytes=None, H=FILM, W=FILM):
-    """drm_render_mesh_shadowed (or drm_render_mesh) through ctypes on sentinel-filled outputs: (status, outputs)"""
+    """drm_render_mesh with shadows = 1 (or 0) through ctypes on sentinel-filled outputs: (status, outputs)"""
+    import abi_call
     from drmnet_amd import _lib
     from drmnet_amd.mesh import build_bvh
     from drmnet_amd.render import view_rotation
@@ -320,16 +321,17 @@ def raw_call(mesh, shadowed=True, rows=(ROUGH,), envs=(ENV,), views=None, blob="
     env = torch.tensor(np.asarray(envs), dtype=torch.float32, device=DEV).contiguous()
     view = None if views is None else view_rotation(torch.tensor(views, dtype=torch.float32)).to(DEV).contiguous()
     outs = [torch.full(s, -7.0, device=DEV) for s in ((B, 3, H, W), (B, 3, H, W), (B, 1, H, W), (B, H, W))]
-    args = [obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), V, F, z.data_ptr(), env.data_ptr(),
-            _lib.ptr(view), *[o.data_ptr() for o in outs], B, H, W, env.shape[1], env.shape[2], Q, S, ws.data_ptr(), need if ws_bytes is None else ws_bytes]
+    sh = abi_call.shading(B, z=z.data_ptr(), env=env.data_ptr(), EH=env.shape[1], EW=env.shape[2], view=_lib.ptr(view), quad=Q)
+    dev_blob, nbytes = None, 0
     if shadowed:
         if isinstance(blob, str):
             blob = build_bvh(as_obj(*mesh))
         dev_blob = None if blob is None else blob.to(DEV)
         nbytes = (0 if blob is None else blob.numel()) if blob_bytes is None else blob_bytes
-        status = lib.drm_render_mesh_shadowed(*args, _lib.ptr(dev_blob), nbytes, _lib.stream_ptr(DEV))
-    else:
-        status = lib.drm_render_mesh(*args, _lib.stream_ptr(DEV))
+    m = abi_call.mesh_render(obj["vertex_positions"].data_ptr(), obj["vertex_normals"].data_ptr(), obj["faces"].data_ptr(), V, F,
+                             [o.data_ptr() for o in outs], H, W, S, ws.data_ptr(), need if ws_bytes is None else ws_bytes, shadows=int(shadowed),
+                             bvh=_lib.ptr(dev_blob), bvh_bytes=nbytes)
+    status = abi_call.render_mesh(sh, m, _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     return status, [o.cpu().numpy() for o in outs]
 

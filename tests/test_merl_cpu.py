@@ -145,10 +145,11 @@ def test_symbols_are_declared_listed_and_typed():
 
     header = open(os.path.join(ROOT, "include", "drmnet_hip.h")).read()
     L = _lib.lib()
-    for name in ("drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap_table", "drm_render_normals_table"):
+    for name in ("drm_brdf_to_merl", "drm_merl_eval", "drm_render_refmap", "drm_render_normals"):
         assert name + "(" in header and name in _lib.SYMBOLS and hasattr(L, name)
         assert getattr(L, name).argtypes is not None, name
-    assert L.drm_abi_version() == 3 and "packed table" in header
+    assert {"tables", "NT", "table_of", "table_alpha", "table_linear"} <= {n for n, _ in _lib.Shading._fields_}
+    assert L.drm_abi_version() == 4 and "packed table" in header
     from drmnet_amd import build
 
     assert "brdf_table.hip" in build.SOURCES and "render_shared.h" in build.HEADERS

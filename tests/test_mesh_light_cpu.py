@@ -1,5 +1,5 @@
 """Light sampling on mesh object images without a GPU: the float64 restatement tests/mesh_light_ref.py (the composition of light_ref,
-shadow_ref and render_ref.lobes that drm_render_mesh_lit is held to), the interfaces that carry `light_samples`, and the entry's argument
+shadow_ref and render_ref.lobes that drm_render_mesh with light samples is held to), the interfaces that carry `light_samples`, and the entry's argument
 checks that return before anything touches a GPU.
 
 Convergence.  The sun scene of tests/golden/mesh_light_sun.npz (tools/make_golden_mesh_light.py): shadow_ref.two_spheres() from +z on a
@@ -133,8 +133,9 @@ def test_the_interfaces_carry_light_samples():
     from drmnet_amd.mesh import MeshRenderer, render_mesh
 
     header = open(os.path.join(ROOT, "include", "drmnet_hip.h")).read()
-    assert "drm_render_mesh_lit(" in header and "drm_render_mesh_lit" in _lib.SYMBOLS and hasattr(_lib.lib(), "drm_render_mesh_lit")
-    assert "light_samples is not offered" not in header and _lib.lib().drm_abi_version() == 3
+    assert "drm_render_mesh(const drm_shading*" in header and "drm_render_mesh" in _lib.SYMBOLS and hasattr(_lib.lib(), "drm_render_mesh")
+    assert "int32_t light_samples;" in header and "light_samples" in {n for n, _ in _lib.Shading._fields_}
+    assert "light_samples is not offered" not in header and _lib.lib().drm_abi_version() == 4
     assert inspect.signature(render_mesh).parameters["light_samples"].default == 0
     assert MeshRenderer(16).light_samples == 0 and MeshRenderer(16, light_samples=256, shadows=True).light_samples == 256
     for bad in (100, 32, 1 << 17, -64):
@@ -151,6 +152,7 @@ def test_the_interfaces_carry_light_samples():
 
 def test_argument_errors_return_before_anything_touches_a_gpu():
     """host buffers stand in for device memory: every case returns from the checks, which dereference nothing"""
+    import abi_call
     from drmnet_amd import _lib
 
     lib = _lib.lib()
@@ -166,9 +168,10 @@ def test_argument_errors_return_before_anything_touches_a_gpu():
     ws_ptr = (ws.ctypes.data + 15) & ~15
 
     def call(light_samples=M, lws_ptr=lws.ctypes.data, lws_bytes=light_need, bvh=None, bvh_bytes=0, ws_bytes=need, env_ptr=env.ctypes.data):
-        return lib.drm_render_mesh_lit(pos.ctypes.data, nrm.ctypes.data, faces.ctypes.data, V, F, z.ctypes.data, env_ptr, None,
-                                       *[o.ctypes.data for o in outs], B, H, W, EH, EW, 8, 2, ws_ptr, ws_bytes, bvh, bvh_bytes, light_samples, lws_ptr,
-                                       lws_bytes, None)
+        sh = abi_call.shading(B, z=z.ctypes.data, env=env_ptr, EH=EH, EW=EW, quad=8, light_samples=light_samples, lws=lws_ptr, lws_bytes=lws_bytes)
+        # shadows: what the blob and its length say together
+        return abi_call.render_mesh(sh, abi_call.mesh_render(pos.ctypes.data, nrm.ctypes.data, faces.ctypes.data, V, F, [o.ctypes.data for o in outs], H, W, 2,
+                                                             ws_ptr, ws_bytes, shadows=int(bvh is not None or bvh_bytes != 0), bvh=bvh, bvh_bytes=bvh_bytes))
 
     INVALID, WORKSPACE = 1, 3
     for want, over in [(INVALID, dict(light_samples=-64)), (INVALID, dict(light_samples=100)), (INVALID, dict(light_samples=32)),

@@ -21,8 +21,8 @@ def test_both_entries_are_declared_and_exported():
     L = _lib.lib()
     for name in ("drm_render_normals", "drm_image_from_refmap"):
         assert name + "(" in header and name in _lib.SYMBOLS and hasattr(L, name)
-    assert len(L.drm_render_normals.argtypes) == 18 and len(L.drm_image_from_refmap.argtypes) == 13
-    assert L.drm_abi_version() == 3
+    assert L.drm_render_normals.argtypes[0]._type_ is _lib.Shading and len(L.drm_image_from_refmap.argtypes) == 13
+    assert L.drm_abi_version() == 4
 
 
 @pytest.mark.parametrize("R", [1, 7, 16, 128])

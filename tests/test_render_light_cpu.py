@@ -123,7 +123,7 @@ def test_the_interfaces_carry_light_samples():
     for bad in (100, 32, 1 << 17, -64):
         with pytest.raises(ValueError):
             RefMapRenderer(16, light_samples=bad)
-    assert "drm_render_refmap_lit" in _lib.SYMBOLS and "drm_render_light_workspace_bytes" in _lib.SYMBOLS
+    assert "light_samples" in {n for n, _ in _lib.Shading._fields_} and "drm_render_refmap" in _lib.SYMBOLS and "drm_render_light_workspace_bytes" in _lib.SYMBOLS
     plain, lit = V.make_parser().description, V.make_parser(1024).description
     assert V.QUADRATURE_NOTE in plain and V.make_parser(0).description == plain
     assert V.QUADRATURE_NOTE not in lit and "M = 1024" in lit

@@ -45,9 +45,9 @@ def test_header_and_symbol_list_carry_the_shadow_entry_points():
     import os
 
     header = open(os.path.join(ROOT, "include", "drmnet_hip.h")).read()
-    for name in ("drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh_shadowed"):
+    for name in ("drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_render_mesh"):
         assert name + "(" in header and name in _lib.SYMBOLS and hasattr(_lib.lib(), name)
-    assert _lib.lib().drm_abi_version() == 3
+    assert {"shadows", "bvh", "bvh_bytes"} <= {n for n, _ in _lib.MeshRender._fields_} and _lib.lib().drm_abi_version() == 4
 
 
 @pytest.mark.parametrize("name", sorted(MESHES))

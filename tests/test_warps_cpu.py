@@ -84,7 +84,7 @@ def test_the_entries_are_declared_and_the_abi_version_stays():
     for name in NEW_SYMBOLS:
         assert re.search(rf"\bint {name}\(", header), name
         assert name in _lib.SYMBOLS
-    assert _lib.ABI_VERSION == 3 and re.search(r"#define DRM_ABI_VERSION 3\b", header)
+    assert _lib.ABI_VERSION == 4 and re.search(r"#define DRM_ABI_VERSION 4\b", header)
     assert "sphere_warp.hip" in __import__("drmnet_amd.build", fromlist=["SOURCES"]).SOURCES
 
 

@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
 """Timings behind DESIGN.md's forward-process paragraph (one MI355X).
 
-    python tools/forward_bench.py render [--libs - drmnet_amd/csrc/_ab/libdrmnet_hip_parent.so]
-        L x B stacked rows at R = 128 through drm_render_refmap_views (maps indexed per row) against the same L B rows through
-        drm_render_refmap with the maps expanded L times, per library, alternating ("-" = the product library; a library without the
-        stacked entry point, e.g. the parent commit's built with tools/build_variant.sh, runs the expanded form only).
-        --light_samples M also times the same stacked rows through drm_render_refmap_lit (the density and table launches included; under
+    python tools/forward_bench.py render [--libs - drmnet_amd/csrc/_ab/libdrmnet_hip_copy.so]
+        L x B stacked rows at R = 128 through one drm_render_refmap call (maps indexed per row) against the same L B rows as one set
+        (L = 1) with the maps expanded L times, per library, alternating ("-" = the product library).
+        --light_samples M also times the same stacked rows with light samples (the density and table launches included; under
         `rocprofv3 --kernel-trace --stats` the three light kernels and the render show on their own).
     python tools/forward_bench.py render --entries --libs - A.so B.so [--reps 10 --rounds 2] [--mesh_batch 4] [--match table normals]
-        one call each of drm_render_refmap_views / _lit / _table, drm_render_normals (plain and lit) / _table and the four mesh entries at
-        B rows, 128 x 128, maps 128 x 256, quad 32, subpixel 2, M = 1024, a mesh of 20 480 faces; device events, the libraries alternating
-        in every round, and whether every library wrote the same bits.  Two copies of one library under two names give the spread that a
-        difference between two libraries has to exceed.
+        one call each of drm_render_refmap (plain, lit, under tables), drm_render_normals (plain, lit, under tables) and drm_render_mesh
+        (plain, shadowed, lit, bounced) at B rows, 128 x 128, maps 128 x 256, quad 32, subpixel 2, M = 1024, a mesh of 20 480 faces; device
+        events, the libraries alternating in every round, and whether every library wrote the same bits.  The case labels are those of the
+        logs recorded before the entries were merged (DESIGN.md maps them), so old and new logs line up.  Two copies of one library under
+        two names give the spread that a difference between two libraries has to exceed.
     python tools/forward_bench.py step [--batch 20]
         one DRMNet.validation_step at full width (synthetic weights, 128 x 128, 128 x 256 maps) split into forward process (renders +
         transforms), networks and loss by device events.  Run it under `rocprofv3 --kernel-trace --stats -- python ...` for the kernel table.
@@ -53,10 +53,7 @@ def bench_render(args):
         return bench_entries(args)
     dev = torch.device("cuda:0")
     L, B, R = args.stack, args.batch, 128
-    libs = []
-    for path in args.libs:
-        lib = C.CDLL(_lib.LIB_PATH if path == "-" else os.path.join(ROOT, path))
-        libs.append((path, lib, hasattr(lib, "drm_render_refmap_views")))
+    libs = [(path, C.CDLL(_lib.LIB_PATH if path == "-" else os.path.join(ROOT, path))) for path in args.libs]
     g = torch.Generator().manual_seed(1)
     z = torch.rand((L, B, 6), generator=g).to(dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -64,43 +61,33 @@ def bench_render(args):
     for EH, EW in ((128, 256), (1000, 2000)):
         env = (torch.rand((B, EH, EW, 3), generator=g) + 0.05).to(dev)
         out = torch.empty((L, B, 3, R, R), device=dev)
+        stacked_sh = _lib.sized(_lib.Shading, B=B, z=z.data_ptr(), envmap=env.data_ptr(), EH=EH, EW=EW, quad=32)
+
+        def expanded(lib):
+            e = env[None].expand(L, *env.shape).reshape(L * B, *env.shape[1:])  # (the copy is part of what is timed)
+            sh = _lib.sized(_lib.Shading, B=L * B, z=z.data_ptr(), envmap=e.data_ptr(), EH=EH, EW=EW, quad=32)
+            assert lib.drm_render_refmap(C.byref(sh), 1, R, 2, 0, vp(out.data_ptr()), stream) == 0
+
+        def stacked(lib, sh=stacked_sh):
+            assert lib.drm_render_refmap(C.byref(sh), L, R, 2, 0, vp(out.data_ptr()), stream) == 0
+
         results = {}
         for rep in range(args.rounds):
-            for name, lib, has_views in libs:
-                def expanded():
-                    e = env[None].expand(L, *env.shape).reshape(L * B, *env.shape[1:])  # (the copy is part of what is timed)
-                    assert lib.drm_render_refmap(vp(z.data_ptr()), vp(e.data_ptr()), vp(out.data_ptr()), L * B, R, EH, EW, 32, 2, 0, stream) == 0
-
-                def stacked():
-                    assert lib.drm_render_refmap_views(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0, stream) == 0
-
-                def lit():
-                    assert lib.drm_render_refmap_lit(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0,
-                                                     args.light_samples, vp(ws.data_ptr()), C.c_size_t(ws.numel() * 8), stream) == 0
-
-                if args.light_samples and hasattr(lib, "drm_render_refmap_lit"):
-                    lib.drm_render_light_workspace_bytes.restype = C.c_size_t
-                    nbytes = lib.drm_render_light_workspace_bytes(B, EH, EW, args.light_samples)
-                    assert nbytes > 0, "--light_samples: a power of two in [64, 65536]"
-                    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
-                    results.setdefault((name, f"drm_render_refmap_lit M={args.light_samples}"), []).extend(timed(lit, args.reps))
-                results.setdefault((name, "expanded + drm_render_refmap"), []).extend(timed(expanded, args.reps))
-                if has_views:
-                    results.setdefault((name, "drm_render_refmap_views"), []).extend(timed(stacked, args.reps))
+            for name, lib in libs:
+                if args.light_samples:
+                    lit_sh, _keep = _lib.make_shading(B, z=z, env=env, quad=32, light_samples=args.light_samples)
+                    results.setdefault((name, f"drm_render_refmap_lit M={args.light_samples}"), []).extend(timed(lambda: stacked(lib, lit_sh), args.reps))
+                results.setdefault((name, "expanded + drm_render_refmap"), []).extend(timed(lambda: expanded(lib), args.reps))
+                results.setdefault((name, "drm_render_refmap_views"), []).extend(timed(lambda: stacked(lib), args.reps))
         # every form of every library renders the same bits
         ref = None
-        for name, lib, has_views in libs:
-            e = env[None].expand(L, *env.shape).reshape(L * B, *env.shape[1:])
-            forms = [("expanded", lambda: lib.drm_render_refmap(vp(z.data_ptr()), vp(e.data_ptr()), vp(out.data_ptr()), L * B, R, EH, EW, 32, 2, 0, stream))]
-            if has_views:
-                forms.append(("stacked", lambda: lib.drm_render_refmap_views(vp(z.data_ptr()), L, vp(env.data_ptr()), None, vp(out.data_ptr()), B, R, EH, EW, 32, 2, 0, stream)))
-            for form, call in forms:
+        for name, lib in libs:
+            for form, call in (("expanded", expanded), ("stacked", stacked)):
                 out.zero_()
-                assert call() == 0
+                call(lib)
                 torch.cuda.synchronize()
                 ref = out.clone() if ref is None else ref
                 print(f"maps {EH}x{EW}  [{name}] {form}: bitwise equal to the first form: {torch.equal(out, ref)}", flush=True)
-            del e
         for (name, form), ms in results.items():
             ms = sorted(ms)
             print(f"maps {EH}x{EW} L={L} B={B} R={R}  [{name}] {form}: median {ms[len(ms) // 2]:.2f} ms  min {ms[0]:.2f}  max {ms[-1]:.2f}  (n={len(ms)})", flush=True)
@@ -141,12 +128,9 @@ def bench_entries(args):
            "faces": torch.tensor(np.concatenate([f + k * len(d) for k in range(4)]), dtype=torch.int32)}
     pos, vn, faces = (obj[k].to(dev).contiguous() for k in ("vertex_positions", "vertex_normals", "faces"))
     blob = build_bvh(obj).to(dev)
-    V, F = C.c_int64(pos.shape[0]), C.c_int64(faces.shape[0])
-    first = libs[0][1]
-    for fn in ("drm_render_light_workspace_bytes", "drm_render_mesh_workspace_bytes"):
-        getattr(first, fn).restype = C.c_size_t
-    lbytes = first.drm_render_light_workspace_bytes(B, EH, EW, M)
-    mbytes = first.drm_render_mesh_workspace_bytes(F, Bm, R, R, S)
+    V, F = int(pos.shape[0]), int(faces.shape[0])
+    lbytes = int(_lib.lib().drm_render_light_workspace_bytes(B, EH, EW, M))
+    mbytes = int(_lib.lib().drm_render_mesh_workspace_bytes(F, Bm, R, R, S))
     assert lbytes > 0 and mbytes > 0
     lws = torch.empty(((lbytes + 7) // 8,), dtype=torch.float64, device=dev)
     mws = torch.empty(((mbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
@@ -154,28 +138,47 @@ def bench_entries(args):
     drawn = torch.empty((B, R, R), device=dev)
     mesh_out = [torch.empty((Bm, c, R, R), device=dev) for c in (3, 3, 1, 1)]
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    vp, sz = (lambda t: C.c_void_p(t.data_ptr())), C.c_size_t
+    vp = lambda t: C.c_void_p(t.data_ptr())
+
+    # the shadings: B rows (Bm for the mesh) of principled rows or tables under the maps and views, plain or with M light samples
+    def shading(rows, lit=False, measured=False):
+        sh = _lib.sized(_lib.Shading, B=rows, envmap=env.data_ptr(), EH=EH, EW=EW, view=view.data_ptr(), quad=Q)
+        if measured:
+            sh.tables, sh.NT, sh.table_of, sh.table_alpha, sh.table_linear = tables.data_ptr(), int(tables.shape[0]), table_of.data_ptr(), alpha.data_ptr(), 1
+        else:
+            sh.z = z.data_ptr()
+        if lit:
+            sh.light_samples, sh.light_workspace, sh.light_workspace_bytes = M, lws.data_ptr(), lbytes
+        return sh
+
+    def mesh(**technique):
+        return _lib.sized(_lib.MeshRender, vertex_positions=pos.data_ptr(), vertex_normals=vn.data_ptr(), faces=faces.data_ptr(), V=V, F=F, H=R, W=R,
+                          subpixel=S, image=mesh_out[0].data_ptr(), normal=mesh_out[1].data_ptr(), depth=mesh_out[2].data_ptr(),
+                          alpha=mesh_out[3].data_ptr(), workspace=mws.data_ptr(), workspace_bytes=mbytes, **technique)
+
+    shadowed = dict(shadows=1, bvh=blob.data_ptr(), bvh_bytes=int(blob.numel()))
 
     def entries(lib):
-        mesh_args = (vp(pos), vp(vn), vp(faces), V, F, vp(z), vp(env), vp(view), *(vp(t) for t in mesh_out), Bm, R, R, EH, EW, Q, S, vp(mws), sz(mbytes))
-        bvh = (vp(blob), sz(blob.numel()))
+        def refmap(sh):
+            return [out], lambda: lib.drm_render_refmap(C.byref(sh), 1, R, S, 0, vp(out), stream)
+
+        def normals(sh):
+            return [out, drawn], lambda: lib.drm_render_normals(C.byref(sh), vp(nrm), None, B, R, R, vp(out), vp(drawn), stream)
+
+        def meshes(sh, m):
+            return mesh_out, lambda: lib.drm_render_mesh(C.byref(sh), C.byref(m), stream)
+
         return {
-            "drm_render_refmap_views": ([out], lambda: lib.drm_render_refmap_views(vp(z), 1, vp(env), vp(view), vp(out), B, R, EH, EW, Q, S, 0, stream)),
-            f"drm_render_refmap_lit M={M}": ([out], lambda: lib.drm_render_refmap_lit(vp(z), 1, vp(env), vp(view), vp(out), B, R, EH, EW, Q, S, 0, M, vp(lws),
-                                                                                      sz(lbytes), stream)),
-            "drm_render_refmap_table": ([out], lambda: lib.drm_render_refmap_table(vp(tables), int(tables.shape[0]), vp(table_of), vp(alpha), vp(env), vp(view),
-                                                                                  vp(out), B, R, EH, EW, Q, S, 0, 1, stream)),
-            "drm_render_normals": ([out, drawn], lambda: lib.drm_render_normals(vp(nrm), None, B, vp(z), vp(env), vp(view), vp(out), vp(drawn), B, R, R, EH, EW, Q,
-                                                                               0, None, sz(0), stream)),
-            f"drm_render_normals M={M}": ([out, drawn], lambda: lib.drm_render_normals(vp(nrm), None, B, vp(z), vp(env), vp(view), vp(out), vp(drawn), B, R, R, EH,
-                                                                                     EW, Q, M, vp(lws), sz(lbytes), stream)),
-            "drm_render_normals_table": ([out, drawn], lambda: lib.drm_render_normals_table(vp(nrm), None, B, vp(tables), int(tables.shape[0]), vp(table_of),
-                                                                                           vp(alpha), vp(env), vp(view), vp(out), vp(drawn), B, R, R, EH, EW, Q, 1,
-                                                                                           stream)),
-            f"drm_render_mesh B={Bm}": (mesh_out, lambda: lib.drm_render_mesh(*mesh_args, stream)),
-            f"drm_render_mesh_shadowed B={Bm}": (mesh_out, lambda: lib.drm_render_mesh_shadowed(*mesh_args, *bvh, stream)),
-            f"drm_render_mesh_lit B={Bm} M={M}": (mesh_out, lambda: lib.drm_render_mesh_lit(*mesh_args, None, sz(0), M, vp(lws), sz(lbytes), stream)),
-            f"drm_render_mesh_bounced B={Bm}": (mesh_out, lambda: lib.drm_render_mesh_bounced(*mesh_args, *bvh, 4, stream)),
+            "drm_render_refmap_views": refmap(shading(B)),
+            f"drm_render_refmap_lit M={M}": refmap(shading(B, lit=True)),
+            "drm_render_refmap_table": refmap(shading(B, measured=True)),
+            "drm_render_normals": normals(shading(B)),
+            f"drm_render_normals M={M}": normals(shading(B, lit=True)),
+            "drm_render_normals_table": normals(shading(B, measured=True)),
+            f"drm_render_mesh B={Bm}": meshes(shading(Bm), mesh()),
+            f"drm_render_mesh_shadowed B={Bm}": meshes(shading(Bm), mesh(**shadowed)),
+            f"drm_render_mesh_lit B={Bm} M={M}": meshes(shading(Bm, lit=True), mesh()),
+            f"drm_render_mesh_bounced B={Bm}": meshes(shading(Bm), mesh(bounces=1, bounce_quad=4, **shadowed)),
         }
 
     results, bits = {}, {}
@@ -316,7 +319,7 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="f16mx")
-    ap.add_argument("--light_samples", type=int, default=0, help="render: also time drm_render_refmap_lit with this many light samples per map")
+    ap.add_argument("--light_samples", type=int, default=0, help="render: also time the stacked render with this many light samples per map")
     ap.add_argument("--entries", action="store_true", help="render: time the sphere, table, normal-map and mesh entries per library instead")
     ap.add_argument("--mesh_batch", type=int, default=0, help="render --entries: rows of the mesh entries (default: --batch)")
     ap.add_argument("--match", nargs="*", default=[], help="render --entries: only the entries whose name contains one of these")
