@@ -52,6 +52,7 @@ SYMBOLS = [
     "drm_brdf_to_merl", "drm_merl_eval", "drm_brdf_error_sums",
     "drm_obs_forward_process", "drm_diffusion_losses",
     "drm_envmap2mirmap", "drm_rotate_envmap", "drm_mirimg2envmap", "drm_refmap2refimg",
+    "drm_op_stem_conv", "drm_op_avgpool2", "drm_op_encoder_head",
 ]
 
 
@@ -217,6 +218,9 @@ def lib() -> C.CDLL:
     L.drm_op_norm_act_conv.argtypes = [fp, fp, fp, i32, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, vp]
     L.drm_op_resblock.argtypes = [fp, i32, i32, fp, i32, fp, i32, C.POINTER(vp), i32, fp, i32, i32, i32, i32, vp]
     L.drm_op_attention_block.argtypes = [fp, C.POINTER(vp), fp, i32, i32, i32, i32, vp]
+    L.drm_op_stem_conv.argtypes = [fp, i32, fp, i32, vp, fp, fp, fp, vp, i32, i32, i32, i32, vp]
+    L.drm_op_avgpool2.argtypes = [fp, fp, vp, i32, i32, i32, i32, vp]
+    L.drm_op_encoder_head.argtypes = [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
     L.drm_drmnet_create.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(DrmnetCfg), C.POINTER(vp)]
     L.drm_drmnet_destroy.argtypes = [vp]
     L.drm_drmnet_destroy.restype = None

@@ -302,6 +302,64 @@ int drm_op_attention_block(const float* x, const float* const* params, float* ou
   });
 }
 
+int drm_op_stem_conv(const float* x, int Cx, const float* cond, int Cc, const int32_t* rows, const float* w, const float* b, float* out, double* stat,
+                     int N, int Cout, int H, int W, void* stream) {
+  return guarded([&]() -> int {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DRM_REQUIRE(x && w && out, "stem conv: x, w and out must not be null");
+    DRM_REQUIRE(Cx >= 1 && Cc >= 0 && (Cc == 0 || cond), "stem conv: cond is null but Cc > 0");
+    DRM_REQUIRE(stem_direct_applicable(Cx + Cc, Cout), "stem conv: Cx + Cc must be 4 or 6 and Cout must be 128 (got Cx + Cc = " + std::to_string(Cx + Cc) +
+                                                           ", Cout = " + std::to_string(Cout) + ")");
+    DRM_REQUIRE(N >= 1 && H >= 1 && W >= 1, "stem conv: N, H, W");
+    return with_scratch(s, [&](Arena& ar) -> int {
+      const bool exact = g_op_precision.load(std::memory_order_relaxed) == PREC_FP32;  // (read once: the whole call runs in this form)
+      float* wimg = ar.alloc<float>(stem_weight_floats());
+      float* bz = ar.alloc<float>(Cout);  // (the scratch is zeroed: the bias of a call without one)
+      float* nhwc = ar.alloc<float>((size_t)N * H * W * Cout);
+      if (ar.dry) return DRM_OK;
+      if (stat) DRM_HIP_CHECK(hipMemsetAsync(stat, 0, (size_t)N * Cout * sizeof(double2), s));
+      DRM_TRY(launch_pack_stem_weight(w, wimg, Cout, Cx + Cc, exact, s));
+      DRM_TRY(launch_stem_conv(x, Cx, cond, Cc, rows, wimg, b ? b : bz, nhwc, reinterpret_cast<double2*>(stat), N, H, W, Cout, exact, s));
+      return launch_nhwc_to_nchw(nhwc, out, N, H, W, Cout, s);
+    });
+  });
+}
+
+int drm_op_avgpool2(const float* x, float* out, double* stat, int N, int C, int H, int W, void* stream) {
+  return guarded([&]() -> int {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DRM_REQUIRE(x && out, "avgpool2: x and out must not be null");
+    DRM_REQUIRE(C >= 4 && C % 4 == 0, "avgpool2: C must be a multiple of 4 (got C = " + std::to_string(C) + ")");
+    DRM_REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "avgpool2: H and W must be even (got H = " + std::to_string(H) + ", W = " + std::to_string(W) + ")");
+    DRM_REQUIRE(N >= 1, "avgpool2: N");
+    return with_scratch(s, [&](Arena& ar) -> int {
+      float* xin = ar.alloc<float>((size_t)N * H * W * C);
+      float* pooled = ar.alloc<float>((size_t)N * (H / 2) * (W / 2) * C);
+      if (ar.dry) return DRM_OK;
+      if (stat) DRM_HIP_CHECK(hipMemsetAsync(stat, 0, (size_t)N * C * sizeof(double2), s));
+      DRM_TRY(launch_nchw_to_nhwc(x, xin, N, H, W, C, s));
+      DRM_TRY(launch_avgpool2(xin, pooled, N, H, W, C, s, reinterpret_cast<double2*>(stat)));
+      return launch_nhwc_to_nchw(pooled, out, N, H / 2, W / 2, C, s);
+    });
+  });
+}
+
+int drm_op_encoder_head(const float* x, const float* scale, const float* shift, const float* w, const float* b, float* out, int N, int C, int H, int W,
+                        int O, void* stream) {
+  return guarded([&]() -> int {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DRM_REQUIRE(x && scale && shift && w && b && out, "encoder head: null argument");
+    DRM_REQUIRE(C >= 4 && C % 4 == 0, "encoder head: C must be a multiple of 4 (got C = " + std::to_string(C) + ")");
+    DRM_REQUIRE(N >= 1 && H >= 1 && W >= 1 && O >= 1, "encoder head: N, H, W, O");
+    return with_scratch(s, [&](Arena& ar) -> int {
+      float* xin = ar.alloc<float>((size_t)N * H * W * C);
+      if (ar.dry) return DRM_OK;
+      DRM_TRY(launch_nchw_to_nhwc(x, xin, N, H, W, C, s));
+      return launch_encoder_head(xin, scale, shift, w, b, out, N, H * W, C, O, s);
+    });
+  });
+}
+
 // ------------------------------------------------------------------------------------------------ samplers
 
 int drm_drmnet_create(drm_unet* illnet, drm_unet* refnet, const float* const* zemb, const drm_drmnet_cfg* cfg, drm_drmnet** out) {

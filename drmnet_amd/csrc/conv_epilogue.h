@@ -14,6 +14,18 @@ __device__ __forceinline__ float epi_scale(const ConvArgs& a, int n, float inv_s
 }
 __device__ __forceinline__ float epi_value(float scaled, float bias, float emb, float res) { return scaled + bias + emb + res; }
 
+// ---- the fused GroupNorm statistics of a producer (conv_split2.hip, stemhead.hip, misc.hip avgpool2_kernel)
+// Output statistics of a lane, about a pivot.  E[x^2] - E[x]^2 cancels badly when |mean| >> std (gn.hip squares in double for that reason), and an
+// output channel does carry an offset: bias and emb are added right here.  Sums of x and x * x in fp32 lose the variance's low bits to the
+// offset's square (2^6 on unit noise: eleven bits); sums of d = x - p and d * d about one of the lane's own values p are the size of the
+// spread whatever the offset, so fp32 keeps them, and the pivot is put back exactly, in double, once per lane and row half:
+//   sum x = sum d + n p,   sum x^2 = sum d^2 + p (2 sum d + n p).
+__device__ __forceinline__ void stat_unpivot(float s, float q, float p, int n, double& S, double& Q) {
+  const double pd = (double)p, sd = (double)s, np = (double)n * pd;
+  S = sd + np;
+  Q = (double)q + pd * (2.0 * sd + np);
+}
+
 // ---- the accesses and the lane exchange of the NHWC stores (conv_split2.hip, stemhead.hip)
 // Agent-scope accesses of the fused split-K hand-off (sc1: coherent across the 8 XCD-private L2s by themselves, the way relaxed agent-scope atomics
 // are -- LLVM AMDGPU memory model, gfx942 rows "load / store atomic monotonic agent").  The slabs move only through these, so the hand-off needs

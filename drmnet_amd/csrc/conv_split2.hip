@@ -150,16 +150,6 @@ struct S2Cfg {
 // v * sigmoid(v) with v_rcp_f32 (1 ulp) in place of the IEEE division sequence (11 VALU instructions per value inside the
 // activation staging, which runs on the same SIMDs as the MFMAs); the hi/lo fp16 split that follows keeps 22 bits anyway.
 __device__ __forceinline__ float silu2(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-// Output statistics of a lane, about a pivot.  E[x^2] - E[x]^2 cancels badly when |mean| >> std (gn.hip squares in double for that reason), and an
-// output channel does carry an offset: bias and emb are added right here.  Sums of x and x * x in fp32 lose the variance's low bits to the
-// offset's square (2^6 on unit noise: eleven bits); sums of d = x - p and d * d about one of the lane's own values p are the size of the
-// spread whatever the offset, so fp32 keeps them, and the pivot is put back exactly, in double, once per lane and row half:
-//   sum x = sum d + n p,   sum x^2 = sum d^2 + p (2 sum d + n p).
-__device__ __forceinline__ void stat_unpivot(float s, float q, float p, int n, double& S, double& Q) {
-  const double pd = (double)p, sd = (double)s, np = (double)n * pd;
-  S = sd + np;
-  Q = (double)q + pd * (2.0 * sd + np);
-}
 __device__ __forceinline__ void split2(float v, _Float16& hi, _Float16& lo) {
   const float c = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
   hi = (_Float16)c;

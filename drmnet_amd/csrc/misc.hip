@@ -1,6 +1,8 @@
 // Small HBM-bound kernels around the convolutions: boundary layout conversion, 2x2 average pool,
 // embedding MLPs, sinusoidal timestep embedding, RefNet pooled head.
 #include "common.h"
+#include "conv_epilogue.h"
+#include "profiler.h"
 
 namespace drm {
 
@@ -93,11 +95,12 @@ int launch_pack_input(const float* x, const float* cond, const int* idx, float* 
 
 // Downsample without conv = AvgPool2d(2,2) (openaimodel.py:154-160), NHWC, fused with the per-(image, channel) sums / sums of
 // squares of its OUTPUT (the next block's GroupNorm statistics: no stand-alone moments pass over the pooled tensor).
-// grid (pixel blocks, N), block 256 = QL channel-quad lanes x PL pixel lanes; a thread walks its pixels with fp32 partial sums and
-// ends with one fp64 atomic per (channel, moment).
+// grid (pixel blocks, N), block 256 = QL channel-quad lanes x PL pixel lanes; a thread walks its pixels with fp32 partial sums about
+// its first pooled value (conv_epilogue.h stat_unpivot: the channel's offset stays out of the squares; up to 64 pixels per thread),
+// restores the pivot in double, and a channel ends with one fp64 atomic per moment.
 __global__ __launch_bounds__(256) void avgpool2_kernel(const float4* __restrict__ x, float4* __restrict__ out, double2* __restrict__ stat, int Ho, int Wo,
                                                        int q4, int QL, int px_per_block) {
-  __shared__ float red[256][8];  // per-thread partial (4 sums, 4 sums of squares): the pixel lanes of a channel quad are folded here
+  __shared__ double red[256][8];  // per-thread partial (4 sums, 4 sums of squares): the pixel lanes of a channel quad are folded here
   const int n = blockIdx.y;
   const int ql = threadIdx.x % QL, pl = threadIdx.x / QL, PL = 256 / QL;
   const int HWo = Ho * Wo, W = Wo * 2;
@@ -105,7 +108,8 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float4* __restrict_
   // (every thread runs every pass: the statistics fold has barriers; blockIdx.z strides the channel passes when the launch is sparse)
   for (int q0 = blockIdx.z * QL; q0 < q4; q0 += QL * gridDim.z) {
     const int q = q0 + ql;
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+    float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
+    int cnt = 0;  // pixels this thread pooled: the pivot is the first of them (a thread without pixels adds exact zeros)
     for (int p = p0 + pl; p < p1 && q < q4; p += PL) {
       const int yo = p / Wo, xo = p % Wo;
       const size_t base = (((size_t)n * Ho * 2 + yo * 2) * W + xo * 2) * q4 + q;
@@ -116,23 +120,22 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float4* __restrict_
       r.z = (a.z + b.z + c.z + d.z) * 0.25f;
       r.w = (a.w + b.w + c.w + d.w) * 0.25f;
       out[((size_t)n * HWo + p) * q4 + q] = r;
-      s[0] += r.x; s[1] += r.y; s[2] += r.z; s[3] += r.w;
-      ss[0] += r.x * r.x; ss[1] += r.y * r.y; ss[2] += r.z * r.z; ss[3] += r.w * r.w;
+      if (cnt++ == 0) { pv[0] = r.x; pv[1] = r.y; pv[2] = r.z; pv[3] = r.w; }
+      const float d0 = r.x - pv[0], d1 = r.y - pv[1], d2 = r.z - pv[2], d3 = r.w - pv[3];
+      s[0] += d0; s[1] += d1; s[2] += d2; s[3] += d3;
+      ss[0] += d0 * d0; ss[1] += d1 * d1; ss[2] += d2 * d2; ss[3] += d3 * d3;
     }
     if (stat) {  // (uniform per block: every thread reaches the barriers)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        red[threadIdx.x][k] = s[k];
-        red[threadIdx.x][4 + k] = ss[k];
-      }
+      for (int k = 0; k < 4; ++k) stat_unpivot(s[k], ss[k], pv[k], cnt, red[threadIdx.x][k], red[threadIdx.x][4 + k]);
       __syncthreads();
       if (pl == 0 && q < q4) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           double a = 0.0, b = 0.0;
           for (int j = 0; j < PL; ++j) {  // fixed order
-            a += (double)red[j * QL + ql][k];
-            b += (double)red[j * QL + ql][4 + k];
+            a += red[j * QL + ql][k];
+            b += red[j * QL + ql][4 + k];
           }
           double* dd = reinterpret_cast<double*>(stat + (size_t)n * q4 * 4 + 4 * q + k);
           atomicAdd(dd, a);
@@ -157,6 +160,8 @@ int launch_avgpool2(const float* x, float* out, int N, int H, int W, int C, hipS
   while (blocks() < 256 && QL > 8) QL >>= 1;
   while (blocks() < 256 && (HWo + ppb - 1) / ppb < 16 && ppb > 256 / QL) ppb >>= 1;
   const int passes = (q4 + QL - 1) / QL;
+  if (prof_enabled()) prof_variant("drm::avgpool2_kernel");
+  ProfScope ps(PROF_MISC, 4.0 * N * HWo * C, 4.0 * 5.0 * N * HWo * C, s);
   hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)((HWo + ppb - 1) / ppb), (unsigned)N, (unsigned)passes), dim3(256), 0, s, reinterpret_cast<const float4*>(x),
                      reinterpret_cast<float4*>(out), stat, H / 2, W / 2, q4, QL, ppb);
   DRM_HIP_CHECK(hipGetLastError());
@@ -374,6 +379,8 @@ __global__ __launch_bounds__(256) void encoder_head_kernel(const float* __restri
 int launch_encoder_head(const float* x, const float* scale, const float* shift, const float* w, const float* b, float* out, int N, int HW,
                         int C, int O, hipStream_t s) {
   DRM_REQUIRE(C % 4 == 0, "encoder head: C % 4");
+  if (prof_enabled()) prof_variant("drm::encoder_head_kernel");
+  ProfScope ps(PROF_MISC, (double)N * C * (8.0 * HW + 2.0 * O), 4.0 * ((double)N * HW * C + (double)O * C), s);
   hipLaunchKernelGGL(encoder_head_kernel, dim3(N), dim3(256), (size_t)5 * C * sizeof(float), s, x, scale, shift, w, b, out, HW, C, O);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;

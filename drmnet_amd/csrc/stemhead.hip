@@ -254,6 +254,13 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
     for (int c = 0; c < 2; ++c) {
       const int col = (wn * 2 + c) * 32 + r;
       const float bv = bias[col];
+      // statistics about a pivot (stat_unpivot: the bias is an offset on every output of the channel).  A lane's live pixels are the top-left
+      // ny x nx corner of each of its two 4 x 4 blocks, and block 0 lies left of block 1 in the same rows: element 0 of block 0 is live whenever
+      // anything of the lane is -- the first LIVE value, never a masked pixel of a ragged tile (a lane with nothing live adds exact zeros).
+      const int ny = min(max(H - (ty0 + wm * 4), 0), 4);
+      const int nx0 = min(max(W - (tx0 + 4 * h), 0), 4), nx1 = min(max(W - (tx0 + 8 + 4 * h), 0), 4);
+      const int live_n = ny * (nx0 + nx1);
+      const float pv = live_n > 0 ? (EXACT ? acc[0][c][0] + bv : acc[0][c][0] * un + bv) : 0.f;
       float s = 0.f, q = 0.f;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -265,8 +272,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
           v[e] = EXACT ? acc[i][c][e] + bv : acc[i][c][e] * un + bv;
           const int y = ty0 + py0 + (e >> 2), xx = tx0 + px0 + (e & 3);
           if (y < H && xx < W) {
-            s += v[e];
-            q += v[e] * v[e];
+            const float d = v[e] - pv;
+            s += d;
+            q += d * d;
           }
         }
         const int cq = (wn * 2 + c) * 32 + (r & ~3);
@@ -278,8 +286,10 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
             *reinterpret_cast<float4*>(out + (((size_t)n * H + y) * W + xx) * STEM_COUT + cq) = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
         }
       }
-      atomicAdd(lst + 2 * col, (double)s);
-      atomicAdd(lst + 2 * col + 1, (double)q);
+      double S, Q;
+      stat_unpivot(s, q, pv, live_n, S, Q);
+      atomicAdd(lst + 2 * col, S);
+      atomicAdd(lst + 2 * col + 1, Q);
     }
   }
   __syncthreads();
@@ -366,6 +376,9 @@ int launch_stem_conv(const float* x, int Cx, const float* cond, int Cc, const in
   const long long tiles = (long long)N * ((H + STEM_TH - 1) / STEM_TH) * ((W + STEM_TW - 1) / STEM_TW);
   const int grid = (int)std::min<long long>(tiles, 2ll * di->cus);
   prof_tag(N, H, W, Cin, Cout);
+  if (prof_enabled())  // (the instantiation's name for the per-variant totals: tests assert through it which of the four ran)
+    prof_variant(Cin == 4 ? (exact ? "drm::stem_conv_kernel<4, true>" : "drm::stem_conv_kernel<4, false>")
+                          : (exact ? "drm::stem_conv_kernel<6, true>" : "drm::stem_conv_kernel<6, false>"));
   ProfScope ps(PROF_CONV3, 2.0 * N * H * W * 9.0 * Cin * Cout, 4.0 * ((double)N * H * W * (Cin + Cout) + 9.0 * Cin * Cout), s);
   auto go = [&](auto tag) -> int {  // (one opt-in state per kernel variant, though all four share a function type: opt_in_lds)
     constexpr auto kern = decltype(tag)::kernel;

@@ -136,6 +136,79 @@ def attention_block(params: Sequence[torch.Tensor], x):
 
 
 @torch.no_grad()
+def stem_conv(x, cond, weight, bias=None, rows=None, want_stats=False):
+    """input_blocks.0.0 on the stem kernel of its own (csrc/stemhead.hip; drm_op_stem_conv): conv3x3(cat([x, cond], 1)[rows]) with x [B, Cx, H, W],
+    cond [B, Cc, H, W] or None, weight [128, Cx + Cc, 3, 3], rows int32 [N] or None -> out [N, 128, H, W]; with ``want_stats`` also the fused
+    GroupNorm table [N, 128, 2] fp64 = (sum, sum of squares) of each output channel.  ops.set_precision("fp32") runs the exact fp32 form, every
+    other mode the fp16 hi / lo split."""
+    x = _lib.require_gpu_tensor(x, "x")
+    weight = _lib.require_gpu_tensor(weight, "weight")
+    cond = None if cond is None else _lib.require_gpu_tensor(cond, "cond")
+    bias = None if bias is None else _lib.require_gpu_tensor(bias, "bias")
+    if x.ndim != 4 or weight.ndim != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise RuntimeError(f"stem_conv expects x [B, Cx, H, W] and weight [Cout, Cin, 3, 3], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    b, cx, h, w = x.shape
+    cc = 0 if cond is None else cond.shape[1]
+    if cond is not None and (cond.ndim != 4 or cond.shape[0] != b or tuple(cond.shape[2:]) != (h, w)):
+        raise RuntimeError(f"cond must be [B={b}, Cc, {h}, {w}], got {tuple(cond.shape)}")
+    cout = weight.shape[0]
+    if weight.shape[1] != cx + cc:
+        raise RuntimeError(f"weight must have Cx + Cc = {cx + cc} input channels, got {weight.shape[1]}")
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise RuntimeError(f"bias must be [{cout}], got {tuple(bias.shape)}")
+    n = b
+    if rows is not None:
+        rows = _lib.require_gpu_tensor(rows.to(torch.int32), "rows", torch.int32)
+        n = rows.numel()
+        if rows.ndim != 1 or n < 1 or int(rows.min()) < 0 or int(rows.max()) >= b:
+            raise RuntimeError(f"rows must be a non-empty int32 vector of indices into the {b} rows of x")
+    out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
+    stat = torch.empty((n, cout, 2), dtype=torch.float64, device=x.device) if want_stats else None
+    with _dev(x):
+        _lib.check(_lib.lib().drm_op_stem_conv(x.data_ptr(), cx, _lib.ptr(cond), cc, _lib.ptr(rows), weight.data_ptr(), _lib.ptr(bias), out.data_ptr(),
+                                                _lib.ptr(stat), n, cout, h, w, _lib.stream_ptr(x.device)))
+    return (out, stat) if want_stats else out
+
+
+@torch.no_grad()
+def avgpool2(x, want_stats=False):
+    """Downsample without conv = AvgPool2d(2, 2) (openaimodel.py:154-160; csrc/misc.hip avgpool2_kernel, drm_op_avgpool2): x [N, C, H, W] ->
+    out [N, C, H/2, W/2]; with ``want_stats`` also the fused GroupNorm table [N, C, 2] fp64 = (sum, sum of squares) of each output channel."""
+    x = _lib.require_gpu_tensor(x, "x")
+    if x.ndim != 4:
+        raise RuntimeError(f"avgpool2 expects x [N, C, H, W], got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    stat = torch.empty((n, c, 2), dtype=torch.float64, device=x.device) if want_stats else None
+    with _dev(x):
+        _lib.check(_lib.lib().drm_op_avgpool2(x.data_ptr(), out.data_ptr(), _lib.ptr(stat), n, c, h, w, _lib.stream_ptr(x.device)))
+    return (out, stat) if want_stats else out
+
+
+@torch.no_grad()
+def encoder_head(x, scale, shift, weight, bias):
+    """The tail of EncoderUNetModel's head, pool="adaptive" (openaimodel.py:922-929; csrc/misc.hip encoder_head_kernel, drm_op_encoder_head):
+    mean_hw(silu(x * scale + shift)) @ weight.T + bias with x [N, C, H, W], scale, shift [N, C] (the GroupNorm tables), weight [O, C], bias [O]
+    -> [N, O]."""
+    x = _lib.require_gpu_tensor(x, "x")
+    if x.ndim != 4:
+        raise RuntimeError(f"encoder_head expects x [N, C, H, W], got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    scale, shift = _lib.require_gpu_tensor(scale, "scale"), _lib.require_gpu_tensor(shift, "shift")
+    weight, bias = _lib.require_gpu_tensor(weight.reshape(weight.shape[0], -1), "weight"), _lib.require_gpu_tensor(bias, "bias")
+    o = weight.shape[0]
+    if tuple(scale.shape) != (n, c) or tuple(shift.shape) != (n, c):
+        raise RuntimeError(f"scale and shift must be [N={n}, C={c}], got {tuple(scale.shape)} and {tuple(shift.shape)}")
+    if tuple(weight.shape) != (o, c) or tuple(bias.shape) != (o,):
+        raise RuntimeError(f"weight must be [O, C={c}] and bias [O], got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    out = torch.empty((n, o), dtype=torch.float32, device=x.device)
+    with _dev(x):
+        _lib.check(_lib.lib().drm_op_encoder_head(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                                   n, c, h, w, o, _lib.stream_ptr(x.device)))
+    return out
+
+
+@torch.no_grad()
 def randn(shape, seed: int, offset: int = 0, device="cuda"):
     """Standard normal from the library's Philox4x32-10 stream."""
     out = torch.empty(shape, dtype=torch.float32, device=device)

@@ -136,6 +136,21 @@ int drm_op_resblock(const float* x0, int C0, int up0, const float* x1, int C1, c
                     int n_params, float* out, int N, int Cout, int H, int W, void* stream);
 /* AttentionBlock._forward (openaimodel.py:325-333, QKVAttentionLegacy :365-381), params: norm.w, norm.b, qkv.w, qkv.b, proj.w, proj.b */
 int drm_op_attention_block(const float* x, const float* const* params, float* out, int N, int C, int H, int W, void* stream);
+/* The stem kernel on its own: input_blocks.0.0 = conv3x3(cat([x, cond], 1)) (openaimodel.py:534, :757; ddpm.py:1527-1529) with the optional
+ * row gather of models/drmnet.py:810-813.  x [B, Cx, H, W], cond [B, Cc, H, W] (NULL when Cc == 0), rows int32 [N] or NULL (then B = N),
+ * w [Cout, Cx + Cc, 3, 3], b [Cout] or NULL -> out NCHW [N, Cout, H, W]; stat (optional) [N, Cout, 2] doubles = (sum, sum of squares) of each
+ * output channel, zeroed by the call.  Op precision fp32 runs the exact fp32 form, every other the fp16 hi / lo split.  Only Cx + Cc in
+ * {4, 6} with Cout == 128 is accepted. */
+int drm_op_stem_conv(const float* x, int Cx, const float* cond, int Cc, const int32_t* rows, const float* w, const float* b, float* out, double* stat,
+                     int N, int Cout, int H, int W, void* stream);
+/* Downsample without conv = AvgPool2d(2, 2) (openaimodel.py:154-160): x NCHW [N, C, H, W] -> out NCHW [N, C, H/2, W/2]; stat (optional)
+ * [N, C, 2] doubles = (sum, sum of squares) of each output channel, zeroed by the call.  C % 4 == 0, H and W even. */
+int drm_op_avgpool2(const float* x, float* out, double* stat, int N, int C, int H, int W, void* stream);
+/* The tail of EncoderUNetModel's head, pool="adaptive" (openaimodel.py:922-929), on GroupNorm tables the caller supplies:
+ * out[n][o] = b[o] + sum_c w[o][c] mean_hw(silu(x[n][c] * scale[n][c] + shift[n][c])).  x NCHW [N, C, H, W], scale, shift [N, C], w [O, C],
+ * b [O] -> out [N, O].  C % 4 == 0. */
+int drm_op_encoder_head(const float* x, const float* scale, const float* shift, const float* w, const float* b, float* out, int N, int C, int H, int W,
+                        int O, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Samplers.
