@@ -46,7 +46,7 @@ SYMBOLS = [
     "drm_unet_load_params_set", "drm_unet_use_set", "drm_set_graph_replay", "drm_set_upconv_split", "drm_graph_launches",
     "drm_map_chain", "drm_masked_log_range", "drm_luminance_scale", "drm_mirmap2envmap", "drm_hdr2ldr", "drm_resize", "drm_profile_variants",
     "drm_render_refmap", "drm_brdf_eval", "drm_validation_losses", "drm_render_light_workspace_bytes",
-    "drm_render_mesh_workspace_bytes", "drm_render_mesh",
+    "drm_render_mesh_workspace_bytes", "drm_render_mesh", "drm_render_mesh_tables",
     "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_mesh_closest_hit",
     "drm_render_normals", "drm_image_from_refmap",
     "drm_brdf_to_merl", "drm_merl_eval", "drm_brdf_error_sums",
@@ -267,6 +267,7 @@ def lib() -> C.CDLL:
     L.drm_render_mesh_workspace_bytes.argtypes = [C.c_int64, i32, i32, i32, i32]
     L.drm_render_mesh_workspace_bytes.restype = C.c_size_t
     L.drm_render_mesh.argtypes = [C.POINTER(Shading), C.POINTER(MeshRender), vp]
+    L.drm_render_mesh_tables.argtypes = [C.POINTER(Shading), C.POINTER(MeshRender), vp]
     L.drm_mesh_bvh_bytes.argtypes = [C.c_int64]
     L.drm_mesh_bvh_bytes.restype = C.c_size_t
     L.drm_mesh_bvh_build.argtypes = [fp, vp, C.c_int64, C.c_int64, vp, C.c_size_t]

@@ -609,6 +609,13 @@ int drm_render_mesh(const drm_shading* shading, const drm_mesh_render* mesh, voi
   });
 }
 
+int drm_render_mesh_tables(const drm_shading* shading, const drm_mesh_render* mesh, void* stream) {
+  return guarded([&]() -> int {
+    DRM_REQUIRE(shading && mesh, "drm_render_mesh_tables: shading or mesh is null");
+    return launch_render_mesh_tables(*shading, *mesh, static_cast<hipStream_t>(stream));
+  });
+}
+
 size_t drm_mesh_bvh_bytes(int64_t F) { return mesh_bvh_bytes((long long)F); }
 
 int drm_mesh_bvh_build(const float* vertex_positions, const int32_t* faces, int64_t V, int64_t F, void* bvh, size_t bytes) {

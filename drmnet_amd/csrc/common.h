@@ -298,6 +298,8 @@ size_t render_mesh_workspace_bytes(long long F, int B, int H, int W, int subpixe
 int launch_mesh_visibility(const float* positions, const int32_t* faces, long long V, long long F, const float* view, int B, int H, int W, int subpixel,
                            float* records, float* hits, hipStream_t s);
 int launch_render_mesh(const drm_shading& sh, const drm_mesh_render& m, hipStream_t s);
+// the same mesh under measured tables (see drm_render_mesh_tables): the same visibility, shading in mesh_table.hip
+int launch_render_mesh_tables(const drm_shading& sh, const drm_mesh_render& m, hipStream_t s);
 // a normal map shaded B ways (see drm_render_normals): normals [Bn][H][W][3] in the view frame, mask uint8 [Bn][H][W] or null
 int launch_render_normals(const drm_shading& sh, const float* normals, const unsigned char* mask, int Bn, int H, int W, float* image, float* alpha,
                           hipStream_t s);

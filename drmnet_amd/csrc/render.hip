@@ -35,7 +35,8 @@
 // it counts, what radiance it reads and what scales its weight.  Every texel fetch is env_taps + bilerp.  Plain holds nothing: the
 // instantiations without light samples and without shadows carry no code and no registers of the others.
 //
-// Also stated once: the traced techniques ask the mesh through one Tracer, the only place that builds a Ray; the shading normal
+// Also stated once: the traced techniques ask the mesh through one Tracer (mesh_shade.h, shared with the mesh under a table,
+// mesh_table.hip, as are the shadowed kernels' launch arguments and the host's mesh checks), the only place that builds a Ray; the shading normal
 // (mix_normals, unit_or_zero), the frame about a normal (duff_frame) and the cosine-weighted direction (cosine_direction) serve the film's
 // hit and the bounce's; mesh_technique builds the technique of a mesh pixel; on the host every render checks its drm_shading through
 // check_shading, every mesh render is launch_render_mesh, and the lit renders share launch_light_tables.
@@ -47,6 +48,7 @@
 
 #include "bvh.h"
 #include "common.h"
+#include "mesh_shade.h"
 #include "normal_map.h"
 #include "render_shared.h"
 
@@ -111,24 +113,7 @@ struct Plain {
   __host__ __device__ __forceinline__ void finish(const Principled&, const ViewRot&, V3, int, int) {}
 };
 
-// What the traced techniques ask the mesh: rays from one point of it, the face the point lies on left out.  The mesh and its tree come with
-// the technique (mesh_technique); from() moves it to a hit sample.  The only place in this file that builds a Ray.
-struct Tracer {
-  MeshRef mesh;
-  BvhView tree;
-  float o[3];       // the ray origin in object space
-  int32_t exclude;  // the face it lies on
-  __host__ __device__ __forceinline__ void from(V3 point, int32_t face) {
-    o[0] = point.x;
-    o[1] = point.y;
-    o[2] = point.z;
-    exclude = face;
-  }
-  __host__ __device__ __forceinline__ Ray ray(V3 w) const { return Ray{{o[0], o[1], o[2]}, {w.x, w.y, w.z}}; }
-  __host__ __device__ __forceinline__ bool occluded(V3 w) const { return bvh_occluded(mesh, tree, ray(w), exclude); }
-  __host__ __device__ __forceinline__ Hit closest(V3 w) const { return bvh_closest(mesh, tree, ray(w), exclude); }
-};
-
+// (Tracer, through which the traced techniques ask the mesh: mesh_shade.h)
 // The shadowed mesh: a direction the BVH finds cut off between the sample's hit point and the environment is dropped before any lookup.
 struct Occluded : Plain {
   Tracer trace;
@@ -400,13 +385,7 @@ __global__ __launch_bounds__(256) void normals_lit_kernel(const float* __restric
 // LIGHT: li holds the light workspace of the B maps (M samples each; see RowMaterial on why the table is not staged in LDS).
 // Without it li is an empty struct.
 // BOUNCE (with SHADOW, without LIGHT): the technique is Bounced instead of Occluded; bo holds bounce_quad.  Without it bo is an empty struct.
-struct NoShadowArgs {};
-struct ShadowArgs {
-  const float* positions;
-  const int32_t* faces;
-  long long V;
-  const void* bvh;
-};
+// (NoShadowArgs, ShadowArgs: mesh_shade.h)
 struct NoLightArgs {};
 struct LightArgs {
   const char* lws;
@@ -426,8 +405,7 @@ __device__ __forceinline__ MeshTechnique<SHADOW, LIGHT, BOUNCE> mesh_technique(c
   MeshTechnique<SHADOW, LIGHT, BOUNCE> t;
   if constexpr (LIGHT) static_cast<LightSampled&>(t) = light_sampled(light_table(li.lws, b, EH, li.M), EH, Q);
   if constexpr (SHADOW) {
-    t.trace.mesh = MeshRef{sh.positions, sh.faces, sh.V, F};
-    t.trace.tree = bvh_view(sh.bvh);
+    trace_mesh(t.trace, sh, F);
   }
   if constexpr (BOUNCE) {
     t.vnormal = vnormal;
@@ -483,7 +461,7 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
       if (n.z > 0.0f) {
         if constexpr (!LIGHT) tech = mesh_technique<SHADOW, LIGHT, BOUNCE>(p, vnormal, F, b, EH, Q, sh, li, bo);
         if constexpr (SHADOW)
-          tech.trace.from(to_world<VIEW>(rot, v3(mesh_sample_x(j * S + sx, W * S), mesh_sample_y(i * S + sy, H * S, (float)H / (float)W), h.w)), f);
+          tech.trace.from(mesh_sample_origin<VIEW>(rot, j * S + sx, i * S + sy, W, H, S, h.w), f);
         normal_lane_sum<VIEW>(p, e, rot, EH, EW, n, Q, lane, 64, acc, tech);
       }
     }
@@ -737,26 +715,18 @@ int launch_render_mesh(const drm_shading& sh, const drm_mesh_render& m, hipStrea
               "render_mesh: bounces is 0, or 1 with shadows, without light samples and with bounce_quad in [1, 16]");
   const int B = sh.B;
   const long long V = m.V, F = m.F;
-  const size_t need = render_mesh_workspace_bytes(F, B, m.H, m.W, m.subpixel);
-  DRM_REQUIRE(need != 0 && V >= 1 && V <= 0x7fffffffLL,
-              "render_mesh: 1 <= F < 2^24 faces, V >= 1 vertices, 1 <= B <= 65535 rows, H and W in [1, 4096], subpixel in [1, 4]");
-  const long long blocks = pixel_blocks((long long)B * m.H * m.W);
-  DRM_REQUIRE(blocks <= 0x7fffffffLL, "render_mesh: B H W too large for one launch");
-  if (!m.workspace || m.workspace_bytes < need || (reinterpret_cast<uintptr_t>(m.workspace) & 15) != 0) {
-    set_error("render_mesh: workspace must be 16-byte aligned and hold drm_render_mesh_workspace_bytes = " + std::to_string(need) + " bytes");
-    return DRM_ERR_WORKSPACE;
-  }
+  MeshLaunch ml;
+  DRM_TRY(plan_mesh_render("render_mesh", B, m, ml));
   DRM_REQUIRE(light_fault.empty(), light_fault);
   if (m.shadows) DRM_TRY(check_device_bvh(m.bvh, m.bvh_bytes, true, F, s, "render_mesh"));
-  float* records = static_cast<float*>(m.workspace);
-  float* hits = records + (size_t)B * F * kMeshRecordWords;
+  float *const records = ml.records, *const hits = ml.hits;
   DRM_TRY(launch_mesh_visibility(m.vertex_positions, m.faces, V, F, sh.view, B, m.H, m.W, m.subpixel, records, hits, s));
   if (lit) launch_light_tables(sh, s);
   // the instantiation: with or without the view, then the technique
   const auto shade = [&](auto with_view) {
     constexpr bool VIEW = decltype(with_view)::value;
     const auto launch = [&](auto kernel, auto shadow, auto li, auto bo) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kRenderWaves), 0, s, sh.z, sh.envmap, sh.view, m.vertex_normals, records, hits, m.image,
+      hipLaunchKernelGGL(kernel, dim3(ml.blocks), dim3(64 * kRenderWaves), 0, s, sh.z, sh.envmap, sh.view, m.vertex_normals, records, hits, m.image,
                          m.normal, m.depth, m.alpha, B, F, m.H, m.W, sh.envmap ? sh.EH : 1, sh.envmap ? sh.EW : 1, sh.quad, m.subpixel, shadow, li, bo);
     };
     const ShadowArgs shadow{m.vertex_positions, m.faces, V, m.bvh};

@@ -1,4 +1,4 @@
-// What the per-normal sums of render.hip (normal_lane_sum: a principled row) and brdf_table.hip (table_lane_sum: a measured table) share:
+// What the per-normal sums of render.hip (normal_lane_sum: a principled row) and brdf_table.h (table_lane_sum: a measured table) share:
 // the three-vector helpers, the frame about a normal and the cosine-weighted direction, the sample sets (the grid point, the visible-normal
 // frame, the GGX sample, its density, the half vector), the principled row with its GGX, Fresnel and diffuse terms and their eval, the
 // environment lookup (env_taps + bilerp), the sensor's normals, the view rotation and the wave butterfly; the two pixel kernels, templates

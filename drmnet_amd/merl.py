@@ -9,12 +9,13 @@
 
 Operator surface of the reference: ``load_merl`` / ``save_merl`` (utils/file_io.py:59-103) and ``bsdf_to_merl``
 (utils/mitsuba3_utils.py:602-638) keep their names, shapes and file format.  ``MeasuredBSDF`` is the measured counterpart of
-``render.PrincipledBSDF``: ``render.eval_bsdf`` / ``render.visualize_bsdf`` take either, ``render.render_table`` renders the sphere and
-``relight.render_normals_measured`` an object image from a normal map under it.  The file format and the packing are host numpy;
+``render.PrincipledBSDF``: ``render.eval_bsdf`` / ``render.visualize_bsdf`` take either, ``render.render_table`` renders the sphere,
+``relight.render_normals_measured`` an object image from a normal map and ``mesh.render_mesh_measured`` an object image of a triangle
+mesh, with or without shadow rays (csrc/mesh_table.hip; ``synthesize --merl``), under it.  The file format and the packing are host numpy;
 export, evaluation and rendering run on the GPU (no CPU path).  Fitting principled parameters to a table and the BRDF-space error metrics are
 drmnet_amd/reflectance.py (csrc/brdf_error.hip); ``--fit`` and ``--compare`` are its command lines.
 
-Out of scope: mesh renders under a table (with or without shadows or bounces), light samples under a table, anisotropic tables, and
+Out of scope: light samples and bounces under a table (on the sphere, a normal map or a mesh), anisotropic tables, and
 table-against-table errors.
 """
 from __future__ import annotations

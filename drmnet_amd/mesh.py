@@ -8,7 +8,8 @@ normal: direct light from the environment map, no interreflection, black backgro
 (``shadows=True``): shadow rays through a bounding-volume hierarchy built on the host (``build_bvh``; csrc/bvh.hip), also offered on their
 own as ``occluded``.  One bounce of interreflection is opt-in on top of it (``bounces=1``): a lobe direction the mesh cuts off reads the
 light its closest hit reflects back; the closest-hit query is offered on its own as ``closest_hit``.  Light sampling is opt-in too (``light_samples=M``: the light samples of ``render.render``, each traced like a lobe
-direction under ``shadows``), for maps with a sun or a lamp a few texels wide.  Loading a mesh, building its BVH and constructing a renderer do not touch the GPU; rendering and ray queries run
+direction under ``shadows``), for maps with a sun or a lamp a few texels wide.  ``render_mesh_measured`` renders the same mesh under measured
+BRDFs (MERL tables, ``merl.MeasuredBSDF``) on csrc/mesh_table.hip, with or without ``shadows``; light samples and bounces under a table are not built.  Loading a mesh, building its BVH and constructing a renderer do not touch the GPU; rendering and ray queries run
 there (no CPU path).
 """
 from __future__ import annotations
@@ -259,30 +260,72 @@ def render_mesh(obj: Mesh, z, brdf_param_names: Sequence[str], envmaps: Optional
     if z.dim() != 2:
         raise ValueError(f"z must be [B, P], got {tuple(z.shape)}")
     B = int(z.shape[0])
-    H, W = (int(image_size), int(image_size)) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
     rows = canonical_rows(z, brdf_param_names).reshape(-1, 6).contiguous()
-    pos, nrm, faces = _mesh_on(obj, dev)
     env, view = _env_and_view(envmaps, view_from, B, dev)
+    shading, _keep = _lib.make_shading(B, z=rows, env=env, view=view, quad=quad, light_samples=light_samples)
+    return _render_call("drm_render_mesh", obj, shading, B, dev, image_size, subpixel, shadows, bvh, bounces=bounces,
+                        bounce_quad=int(bounce_quad) if bounces else 0)
+
+
+def _render_call(entry: str, obj: Mesh, shading, B: int, dev, image_size, subpixel: int, shadows: bool, bvh, **technique):
+    """what the two mesh renders share once the shading is made: the mesh on the device, the workspace, the four outputs, the BVH under
+    ``shadows`` and the call of ``entry`` -> (image, normal, depth, alpha)"""
+    H, W = (int(image_size), int(image_size)) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
+    pos, nrm, faces = _mesh_on(obj, dev)
     lib = _lib.lib()
     V, F = int(pos.shape[0]), int(faces.shape[0])
     nbytes = int(lib.drm_render_mesh_workspace_bytes(F, B, H, W, int(subpixel)))
     if nbytes == 0 or V < 1:
-        raise ValueError(f"render_mesh: F = {F} faces in [1, 2^24), V = {V} >= 1, B = {B} in [1, 65535], image_size {(H, W)} in [1, 4096], "
+        raise ValueError(f"{entry[4:]}: F = {F} faces in [1, 2^24), V = {V} >= 1, B = {B} in [1, 65535], image_size {(H, W)} in [1, 4096], "
                          f"subpixel = {subpixel} in [1, 4]")
     image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
     normal = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.float64, device=dev)
-    shading, _keep = _lib.make_shading(B, z=rows, env=env, view=view, quad=quad, light_samples=light_samples)
     with torch.cuda.device(dev):
         blob = _bvh_on(build_bvh(obj) if bvh is None else bvh, dev) if shadows else None
         m = _lib.sized(_lib.MeshRender, vertex_positions=pos.data_ptr(), vertex_normals=nrm.data_ptr(), faces=faces.data_ptr(), V=V, F=F, H=H, W=W,
                        subpixel=int(subpixel), image=image.data_ptr(), normal=normal.data_ptr(), depth=depth.data_ptr(), alpha=alpha.data_ptr(),
                        workspace=ws.data_ptr(), workspace_bytes=nbytes, shadows=int(blob is not None), bvh=_lib.ptr(blob),
-                       bvh_bytes=0 if blob is None else int(blob.numel()), bounces=bounces, bounce_quad=int(bounce_quad) if bounces else 0)
-        _lib.check(lib.drm_render_mesh(shading, m, _lib.stream_ptr(dev)))
+                       bvh_bytes=0 if blob is None else int(blob.numel()), **technique)
+        _lib.check(getattr(lib, entry)(shading, m, _lib.stream_ptr(dev)))
     return image, normal, depth, alpha
+
+
+@torch.no_grad()
+def render_mesh_measured(obj: Mesh, bsdfs, envmaps: Optional[torch.Tensor] = None, *, image_size, view_from=None, quad: int = QUAD,
+                         subpixel: int = SUBPIXEL, shadows: bool = False, bvh=None, lookup: str = "linear"):
+    """One call of drm_render_mesh_tables: ``render_mesh`` under measured BRDFs (MERL tables) instead of principled rows, with shadow rays
+    under ``shadows=True`` (``bvh`` as in ``render_mesh``).  ``bsdfs`` follows ``relight.render_normals_measured``: one merl.MeasuredBSDF,
+    shared by all rows, or a list of B (equal objects share one device table); B is the number of envmaps [B, EH, EW, 3], or of bsdfs under
+    a white environment (None).  view_from [B, 3] (or None: +z); ``lookup`` is "linear" or "nearest" -> (image [B, 3, H, W], normal
+    [B, 3, H, W] in the view frame, depth [B, 1, H, W], alpha [B, H, W]), what ``render_mesh`` returns.  Every hit is shaded as
+    ``render.render_table`` shades the sphere point with the same normal.  There are no light samples and no bounces under a table.
+    A bad argument is a ValueError before anything touches the GPU; an ``envmaps`` tensor on the CPU, or a machine without a GPU, is a
+    RuntimeError."""
+    from .merl import MeasuredBSDF, device_tables, lookup_mode
+
+    linear = lookup_mode(lookup)
+    if isinstance(envmaps, torch.Tensor):
+        if envmaps.dim() != 4 or envmaps.shape[3] != 3:
+            raise ValueError(f"envmaps must be [B, H, W, 3], got {tuple(envmaps.shape)}")
+        if not envmaps.is_cuda:
+            raise RuntimeError(f"render_mesh_measured runs on the GPU only (drmnet_amd has no CPU path): envmaps is on {envmaps.device}")
+        B = int(envmaps.shape[0])
+    else:
+        B = 1 if isinstance(bsdfs, MeasuredBSDF) else len(list(bsdfs))
+    if not 1 <= B <= 65535:
+        raise ValueError(f"render_mesh_measured: B = {B} rows in [1, 65535]")
+    if isinstance(quad, bool) or not 1 <= int(quad) <= 1024:
+        raise ValueError(f"render_mesh_measured: quad in [1, 1024], got {quad!r}")
+    if view_from is not None and view_rotation(view_from).shape[0] != B:
+        raise ValueError(f"view_from must be [B={B}, 3], got {tuple(torch.as_tensor(view_from).shape)}")
+    dev = _device(envmaps)
+    tables, table_of, alpha = device_tables(bsdfs, B, dev)
+    env, view = _env_and_view(envmaps, view_from, B, dev)
+    shading, _keep = _lib.make_shading(B, tables=(tables, table_of, alpha, linear), env=env, view=view, quad=quad)
+    return _render_call("drm_render_mesh_tables", obj, shading, B, dev, image_size, subpixel, shadows, bvh)
 
 
 class MeshRenderer:

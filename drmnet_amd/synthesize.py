@@ -1,6 +1,6 @@
 """Make the input of ``python -m drmnet_amd.estimate`` from a mesh, a BRDF and an environment map -- the forward model, run forward.
 
-    python -m drmnet_amd.synthesize --mesh M.obj --envmap E.exr --z m R G B r s --view_from x y z --image_size 128 --output_dir D
+    python -m drmnet_amd.synthesize --mesh M.obj --envmap E.exr (--z m R G B r s | --merl material.binary) --view_from x y z --image_size 128 --output_dir D
 
 writes into D the three files ``estimate`` reads,
 
@@ -12,7 +12,10 @@ writes into D the three files ``estimate`` reads,
 
 and ``refmap.exr``: the reflectance map RefMapRenderer renders for the same (z, envmap, view), the ground truth the estimate should approach.
 ``--light_samples`` applies to both renders, so the image and the map it is judged against resolve the same lights.
-``--z`` is the canonical row (metallic, base colour R G B, roughness, specular).  The mesh (.obj, or a .pt dict) is scaled to radius 0.9
+``--z`` is the canonical row (metallic, base colour R G B, roughness, specular).  ``--merl material.binary`` takes its place (exactly one
+of the two): the object is shaded under that measured BRDF (drmnet_amd.mesh.render_mesh_measured, read as ``--merl_lookup`` says;
+``--shadows`` holds, ``--light_samples`` and ``--bounces`` are not built under a table) and ``refmap.exr`` is render.render_table's, so
+``estimate --gt_merl material.binary`` on the written files judges the estimate against the material the image was made with.  The mesh (.obj, or a .pt dict) is scaled to radius 0.9
 so that it fits the film from every view; without ``--envmap`` the environment is white.
 """
 from __future__ import annotations
@@ -31,14 +34,16 @@ NAMES = ("metallic", "base_color.value.R", "base_color.value.G", "base_color.val
 
 def main(argv=None):
     from . import file_io
-    from .mesh import check_bounces, load_mesh, normalize_mesh, render_mesh
-    from .render import render
+    from .mesh import check_bounces, load_mesh, normalize_mesh, render_mesh, render_mesh_measured
+    from .render import render, render_table
 
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     parser.add_argument("--mesh", type=Path, required=True, help="triangle mesh (.obj, or a .pt dict of vertex_positions / vertex_normals / faces)")
     parser.add_argument("--envmap", type=Path, default=None, help="lat-long environment map (.exr); default: white")
-    parser.add_argument("--z", type=float, nargs=6, required=True, metavar=("m", "R", "G", "B", "r", "s"),
-                        help="metallic, base colour R G B, roughness, specular")
+    parser.add_argument("--z", type=float, nargs=6, default=None, metavar=("m", "R", "G", "B", "r", "s"),
+                        help="metallic, base colour R G B, roughness, specular (exactly one of --z and --merl)")
+    parser.add_argument("--merl", type=Path, default=None, help="a measured BRDF (MERL .binary) as the material, in place of --z")
+    parser.add_argument("--merl_lookup", choices=("linear", "nearest"), default="linear", help="how --merl's table is read (default: linear)")
     parser.add_argument("--view_from", type=float, nargs=3, default=[0.0, 0.0, 1.1], metavar=("x", "y", "z"), help="viewer position (off the +-y axis)")
     parser.add_argument("--image_size", type=int, default=128)
     parser.add_argument("--refmap_res", type=int, default=128, help="resolution of refmap.exr")
@@ -51,18 +56,30 @@ def main(argv=None):
                         "(default 0: the lobe quadrature alone)")
     parser.add_argument("--output_dir", type=Path, default=Path("./outputs/"))
     args = parser.parse_args(argv)
+    if (args.z is None) == (args.merl is None):
+        parser.error("exactly one of --z and --merl")
+    if args.merl is not None and (args.light_samples or args.bounces):
+        parser.error("--light_samples and --bounces under --merl are not built: a measured BRDF renders with the quadrature alone, with or without --shadows")
     check_bounces(args.bounces, args.bounce_quad, args.shadows, args.light_samples)
 
     if not torch.cuda.is_available():
         raise RuntimeError("synthesize renders on the GPU (drmnet_amd has no CPU path) and no GPU is visible")
     dev = torch.device("cuda", torch.cuda.current_device())
     obj = normalize_mesh(load_mesh(args.mesh))
-    z = torch.tensor([args.z], dtype=torch.float32, device=dev)
     env = None if args.envmap is None else file_io.load_exr(args.envmap, as_torch=True).to(dev)[None]
     view = torch.tensor([args.view_from], dtype=torch.float32)
-    image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows,
-                                     light_samples=args.light_samples, bounces=args.bounces, bounce_quad=args.bounce_quad)
-    refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view, light_samples=args.light_samples)
+    if args.merl is not None:
+        from .merl import MeasuredBSDF
+
+        bsdf = MeasuredBSDF.from_file(args.merl)
+        image, normal, _, _ = render_mesh_measured(obj, bsdf, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows,
+                                                  lookup=args.merl_lookup)
+        refmap = render_table(bsdf, env, res=args.refmap_res, quad=args.quad, view_from=view, lookup=args.merl_lookup)
+    else:
+        z = torch.tensor([args.z], dtype=torch.float32, device=dev)
+        image, normal, _, _ = render_mesh(obj, z, NAMES, env, image_size=args.image_size, view_from=view, quad=args.quad, shadows=args.shadows,
+                                         light_samples=args.light_samples, bounces=args.bounces, bounce_quad=args.bounce_quad)
+        refmap = render(z, NAMES, env, res=args.refmap_res, quad=args.quad, view_from=view, light_samples=args.light_samples)
     normal = normal[0].permute(1, 2, 0).cpu().numpy()
     mask = np.linalg.norm(normal, axis=-1) > 0.5
     args.output_dir.mkdir(parents=True, exist_ok=True)

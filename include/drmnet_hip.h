@@ -415,8 +415,8 @@ int drm_refmap2refimg(const float* refmap, float* out, uint8_t* mask, int B, int
  *     max(0.001, roughness^2), eta = 2 / (1 - sqrt(0.08 specular)) - 1).
  *     tables, NT, table_of, table_alpha, table_linear: measured BRDFs ("Measured BRDFs" below states the packed layout, the lookup and the
  *     checks made of them).  Row b is under table table_of[b] (NULL: table 0 for all); table_alpha [NT]: the proxy roughness of each table,
- *     in [0.005, 1]; table_linear: the lookup.  Under tables there are no stacks (L == 1), no light samples under a map and no mesh:
- *     otherwise DRM_ERR_INVALID.  1 <= B <= 65535.
+ *     in [0.005, 1]; table_linear: the lookup.  Under tables there are no stacks (L == 1), no light samples under a map and no bounces,
+ *     and a mesh goes through drm_render_mesh_tables, not drm_render_mesh: otherwise DRM_ERR_INVALID.  1 <= B <= 65535.
  *   envmap [B][EH][EW][3]: channels-last lat-long maps (texel (i, j) looks along theta = (i + 1/2) pi / EH, psi = (j + 1/2) 2 pi / EW,
  *     (sin theta sin psi, cos theta, -sin theta cos psi); bilinear, wraps in psi, clamps in theta), or NULL for a white environment (L = 1;
  *     EH, EW and the view are then not read).
@@ -568,7 +568,8 @@ int drm_mesh_closest_hit(const float* vertex_positions, const int32_t* faces, in
 
 /* Object images of a triangle mesh: the input side of the chain (csrc/mesh.hip for visibility, csrc/render.hip for shading).  Replaces
  * MitsubaOrthoRenderer.rendering (utils/mitsuba3_utils.py:433-564: an orthographic camera on a smooth-shaded mesh with image, shading-normal
- * and depth AOVs).  One mesh per call, lit and seen B ways under a drm_shading with principled rows z [B][6] (tables are DRM_ERR_INVALID).
+ * and depth AOVs).  One mesh per call, lit and seen B ways under a drm_shading with principled rows z [B][6] (tables are DRM_ERR_INVALID
+ * here: a mesh under measured tables is drm_render_mesh_tables, below).
  * Every visible point is shaded exactly as drm_render_refmap shades the sphere point with the same normal: direct light from the
  * environment map, and the background is black, not the environment.  Without shadows there is no self-shadowing: it is the model the
  * reflectance map itself assumes.  Zero-initialise drm_mesh_render, set struct_bytes = sizeof(drm_mesh_render), then the members in use.
@@ -656,6 +657,29 @@ typedef struct drm_mesh_render {
 } drm_mesh_render;
 size_t drm_render_mesh_workspace_bytes(int64_t F, int B, int H, int W, int subpixel); /* 0 for arguments drm_render_mesh rejects */
 int drm_render_mesh(const drm_shading* shading, const drm_mesh_render* mesh, void* stream);
+/* The same mesh under measured BRDFs (csrc/mesh_table.hip, mesh_table_shade_kernel): MitsubaOrthoRenderer.rendering with a measured BSDF, the
+ * shapes-under-MERL-materials case.  The two structs, the workspace (drm_render_mesh_workspace_bytes), the limits, the film, the coverage
+ * rule, the shading normal, the four outputs and the setup and visibility launches are drm_render_mesh's; the material of the shading is
+ * its tables ("Measured BRDFs" below), row b under table table_of[b] with proxy roughness table_alpha[table_of[b]].
+ *   Estimator (the contract).  For a hit sample with view-frame unit shading normal n (n.z > 0) the radiance is the per-normal sum of
+ *   drm_render_refmap under tables: both sample sets at the row's table and proxy roughness, each sample l adding
+ *     L(Rot l) f_table(n, v, l) (n.l) / (quad^2 (p_s(l) + p_d(l))),
+ *   so a mesh point is shaded exactly as the sphere point and the normal-map pixel with the same normal.  The pixel is the sum over the
+ *   subpixel^2 samples divided by subpixel^2.
+ *   shadows != 0 (bvh, bvh_bytes as in drm_render_mesh): every sample with a non-zero balance weight -- a GGX sample inside its
+ *   (v.h > 0, n.l > 0, D > 0) branch, a cosine sample where n.l > 0 -- is first traced by the intersection rule above along Rot l from the
+ *   view-space hit point (x_sample, y_sample, z_hit) taken to object space with Rot, the hit face excluded, before the table and the
+ *   environment are read.  An occluded sample contributes nothing, an open one exactly the bits it contributes without shadows: a shadowed
+ *   image is <= the plain one in every pixel and channel under a non-negative map and table.
+ *   fp32 throughout, one wave per pixel, the per-lane order and butterfly of drm_render_mesh, no atomics: bitwise reproducible, and a call of
+ *   B rows equals its rows rendered one by one.
+ *   Not built under a table: light samples, bounces, anisotropic tables.
+ *   DRM_ERR_INVALID, nothing launched and no output touched, drm_last_error naming the argument: a struct_bytes of either struct; z given,
+ *   or no tables (the material); light_samples > 0 under a map; bounces != 0; an argument outside the limits or a bad quadrature; a NULL,
+ *   short or damaged blob under shadows; whatever "Measured BRDFs" rejects of the tables (a table_of value outside [0, NT), an alpha
+ *   outside [0.005, 1] or not finite, ...).  DRM_ERR_WORKSPACE for a missing, misaligned or short mesh workspace.  Everything but the
+ *   blob's header and the table_of / alpha values is decided without reading device memory. */
+int drm_render_mesh_tables(const drm_shading* shading, const drm_mesh_render* mesh, void* stream);
 /* The BSDF value itself, Mitsuba's eval = f(v, l) (n.l) (replaces eval_bsdf / the evaluation behind visualize_bsdf,
  * utils/mitsuba3_utils.py:610-640): z [z_rows][6] with z_rows 1 (one BSDF for every element) or N; n, v (toward the viewer),
  * l (toward the light) [N][3] unit vectors; out [N][3].  0 unless n.v > 0 and n.l > 0. */

@@ -8,7 +8,7 @@
         `rocprofv3 --kernel-trace --stats` the three light kernels and the render show on their own).
     python tools/forward_bench.py render --entries --libs - A.so B.so [--reps 10 --rounds 2] [--mesh_batch 4] [--match table normals]
         one call each of drm_render_refmap (plain, lit, under tables), drm_render_normals (plain, lit, under tables) and drm_render_mesh
-        (plain, shadowed, lit, bounced) at B rows, 128 x 128, maps 128 x 256, quad 32, subpixel 2, M = 1024, a mesh of 20 480 faces; device
+        (plain, shadowed, lit, bounced) and drm_render_mesh_tables (plain, shadowed) at B rows, 128 x 128, maps 128 x 256, quad 32, subpixel 2, M = 1024, a mesh of 20 480 faces; device
         events, the libraries alternating in every round, and whether every library wrote the same bits.  The case labels are those of the
         logs recorded before the entries were merged (DESIGN.md maps them), so old and new logs line up.  Two copies of one library under
         two names give the spread that a difference between two libraries has to exceed.
@@ -168,6 +168,14 @@ def bench_entries(args):
         def meshes(sh, m):
             return mesh_out, lambda: lib.drm_render_mesh(C.byref(sh), C.byref(m), stream)
 
+        def meshes_tables(sh, m):
+            return mesh_out, lambda: lib.drm_render_mesh_tables(C.byref(sh), C.byref(m), stream)
+
+        # (a library from before the entry existed is timed on the others)
+        measured_mesh = {
+            f"drm_render_mesh_tables B={Bm}": meshes_tables(shading(Bm, measured=True), mesh()),
+            f"drm_render_mesh_tables_shadowed B={Bm}": meshes_tables(shading(Bm, measured=True), mesh(**shadowed)),
+        } if hasattr(lib, "drm_render_mesh_tables") else {}
         return {
             "drm_render_refmap_views": refmap(shading(B)),
             f"drm_render_refmap_lit M={M}": refmap(shading(B, lit=True)),
@@ -179,6 +187,7 @@ def bench_entries(args):
             f"drm_render_mesh_shadowed B={Bm}": meshes(shading(Bm), mesh(**shadowed)),
             f"drm_render_mesh_lit B={Bm} M={M}": meshes(shading(Bm, lit=True), mesh()),
             f"drm_render_mesh_bounced B={Bm}": meshes(shading(Bm), mesh(bounces=1, bounce_quad=4, **shadowed)),
+            **measured_mesh,
         }
 
     results, bits = {}, {}
