@@ -33,6 +33,16 @@ def brdf_error_workspace_bytes(C: int) -> int:
     return int(C) * BRDF_ERROR_PARTS * BRDF_ERROR_SUMS * 8
 
 
+IMAGE_ERROR_SUMS = 10  # DRM_IMAGE_ERROR_SUMS
+IMAGE_ERROR_PARTS = 16  # DRM_IMAGE_ERROR_PARTS
+IMAGE_ERROR_MAX_PAIRS = 4096
+
+
+def image_error_workspace_bytes(P: int) -> int:
+    """DRM_IMAGE_ERROR_WORKSPACE_BYTES(P)"""
+    return int(P) * IMAGE_ERROR_PARTS * IMAGE_ERROR_SUMS * 8
+
+
 # every symbol include/drmnet_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
     "drm_abi_version", "drm_last_error",
@@ -49,7 +59,7 @@ SYMBOLS = [
     "drm_render_mesh_workspace_bytes", "drm_render_mesh", "drm_render_mesh_tables",
     "drm_mesh_bvh_bytes", "drm_mesh_bvh_build", "drm_mesh_occluded", "drm_mesh_closest_hit",
     "drm_render_normals", "drm_image_from_refmap",
-    "drm_brdf_to_merl", "drm_merl_eval", "drm_brdf_error_sums",
+    "drm_brdf_to_merl", "drm_merl_eval", "drm_brdf_error_sums", "drm_image_error_sums",
     "drm_obs_forward_process", "drm_diffusion_losses",
     "drm_envmap2mirmap", "drm_rotate_envmap", "drm_mirimg2envmap", "drm_refmap2refimg",
     "drm_op_stem_conv", "drm_op_avgpool2", "drm_op_encoder_head",
@@ -98,6 +108,13 @@ class MeshRender(C.Structure):  # drm_mesh_render
                 ("F", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("subpixel", C.c_int32), ("image", C.c_void_p), ("normal", C.c_void_p),
                 ("depth", C.c_void_p), ("alpha", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("shadows", C.c_int32),
                 ("bvh", C.c_void_p), ("bvh_bytes", C.c_size_t), ("bounces", C.c_int32), ("bounce_quad", C.c_int32)]
+
+
+class ImageError(C.Structure):  # drm_image_error
+    _fields_ = [("struct_bytes", C.c_uint32), ("a", C.c_void_p), ("a_count", C.c_int32), ("a_batch_stride", C.c_int64), ("a_pixel_stride", C.c_int64),
+                ("a_channel_stride", C.c_int64), ("b", C.c_void_p), ("b_count", C.c_int32), ("b_batch_stride", C.c_int64), ("b_pixel_stride", C.c_int64),
+                ("b_channel_stride", C.c_int64), ("mask", C.c_void_p), ("mask_count", C.c_int32), ("HW", C.c_int64), ("pairs", C.c_void_p), ("P", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("sums", C.c_void_p)]
 
 
 class DrmnetCfg(C.Structure):
@@ -278,6 +295,7 @@ def lib() -> C.CDLL:
     L.drm_brdf_to_merl.argtypes = [fp, i32, fp, vp]
     L.drm_merl_eval.argtypes = [fp, i32, vp, fp, fp, fp, fp, C.c_int64, i32, vp]
     L.drm_brdf_error_sums.argtypes = [fp, i32, fp, fp, vp, C.c_size_t, vp, vp]
+    L.drm_image_error_sums.argtypes = [C.POINTER(ImageError), vp]
     L.drm_validation_losses.argtypes =[fp, fp, fp, vp, fp, fp, fp, vp, fp, C.c_double, i32, C.c_double, C.c_double, i32, C.c_int64, i32, vp, C.c_size_t,
                                         fp, vp]
     L.drm_obs_forward_process.argtypes = [fp, fp, vp, fp, fp, i32, C.c_float, i32, fp, fp, fp, C.c_uint64, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]

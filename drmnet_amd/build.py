@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(CSRC, "libdrmnet_hip.so")
-SOURCES = ["conv.hip", "conv_split.hip", "conv_plan.hip", "gn.hip", "attn.hip", "attn_flash.hip", "attn_plan.hip", "misc.hip", "stemhead.hip", "refmap.hip", "transform.hip", "sphere_warp.hip", "render.hip", "brdf_table.hip", "mesh_table.hip", "brdf_error.hip", "mesh.hip", "bvh.hip", "losses.hip", "obs_forward.hip", "engine.hip", "samplers.hip", "abi.hip", "profiler.hip"]
+SOURCES = ["conv.hip", "conv_split.hip", "conv_plan.hip", "gn.hip", "attn.hip", "attn_flash.hip", "attn_plan.hip", "misc.hip", "stemhead.hip", "refmap.hip", "transform.hip", "sphere_warp.hip", "render.hip", "brdf_table.hip", "mesh_table.hip", "brdf_error.hip", "image_error.hip", "mesh.hip", "bvh.hip", "losses.hip", "obs_forward.hip", "engine.hip", "samplers.hip", "abi.hip", "profiler.hip"]
 # conv_split2.hip is compiled once per (TAPS, TERMS) pair of its kernel template (-DDRM_S2_UNIT=10 * TAPS + TERMS), fourteen objects built in parallel
 # instead of one 4.5-minute translation unit: the DRM_S2_UNITS list of csrc/conv_forms.h (tests/test_conv_plan_cpu.py compares the two)
 S2_UNITS = [92, 93, 13, 90, 10, 91, 11, 94, 14, 42, 43, 40, 41, 44]  # (slowest first; 4x: the parity form of a 3x3 over a nearest-x2 input)

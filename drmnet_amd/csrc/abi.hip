@@ -675,6 +675,15 @@ int drm_brdf_error_sums(const float* z, int C, const float* table, const float* 
   });
 }
 
+// ------------------------------------------------------------------------------------------------ image-space errors (image_error.hip)
+
+int drm_image_error_sums(const drm_image_error* args, void* stream) {
+  return guarded([&]() -> int {
+    DRM_REQUIRE(args, "drm_image_error_sums: args is null");
+    return launch_image_error_sums(*args, static_cast<hipStream_t>(stream));
+  });
+}
+
 // ------------------------------------------------------------------------------------------------ validation losses (losses.hip)
 
 int drm_validation_losses(const float* model_out, const float* Lr_k, const float* Lr_km1, const int32_t* K, const float* z_out, const float* z_k,

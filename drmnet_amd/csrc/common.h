@@ -322,6 +322,8 @@ int launch_merl_eval(const float* tables, int NT, const int32_t* table_of, const
                      int linear, hipStream_t s);
 // BRDF-space error sums of C principled rows against a packed table or a principled row (brdf_error.hip): see drm_brdf_error_sums
 int launch_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* ws, size_t ws_bytes, double* sums, hipStream_t s);
+// image-space error sums of P image pairs on a mask (image_error.hip): see drm_image_error_sums
+int launch_image_error_sums(const drm_image_error& args, hipStream_t s);
 
 // misc kernels (misc.hip)
 // absmax_bits (optional): [N][pack_input_absmax_parts(H, W)] words, every one written: max |element| of one block of a packed image as fp32 bits

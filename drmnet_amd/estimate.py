@@ -17,6 +17,11 @@ camera frame the estimated map is in; sample_Lr0.exr; and sample_gt_errors.json.
 with) or `--gt_merl M.binary` (the table `relight --merl` rendered under; the two exclude each other) it also judges the estimated BRDF in
 BRDF space (drmnet_amd/reflectance.py): sample_gt_errors.json gains "brdf", and under a measured truth "brdf_fit", the best principled fit of
 the table, the floor the estimate is to be read against.
+DRMNet is stochastic: `estimate_samples` draws N estimates of one image in one batch (the reflectance-map gather once, one DDIM run and
+one DRMNet loop at batch N), and with `--num_samples N` (1 ... 64, default 1: the path and the files above, unchanged) `--select
+rerender|medoid|first` (default rerender) names the draw that becomes the estimate every other file is written from, `--seed S` fixes the
+draws, and samples.json (per-draw zK, K and re-render errors, the pairwise matrix, the medoid), samples_Lr0.npy, sample_mean_env.png and
+sample_std.exr are added (drmnet_amd/samples.py, on the batched image-error kernel csrc/image_error.hip).
 """
 from __future__ import annotations
 
@@ -74,25 +79,44 @@ def estimate_batch(DRMNet_model, ObsNet_model, input_imgs: torch.Tensor, input_n
     hooks = hooks or {}
     refmap_res = DRMNet_model.ds.size
     refmaps, refmasks = [], []
-    marks = []  # hooks["timing"]: per-stage device time (ms) of this call, measured with events on the current stream
-
-    def mark(name):
-        if "timing" in hooks:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            marks.append((name, ev))
-
-    mark("start")
+    timer = _StageTimer(hooks)
+    timer.mark("start")
     for img, nrm, mask in zip(input_imgs, input_normals, masks):
         if erode_kernel_size > 0:
             mask = erode_mask(mask, erode_kernel_size)
         rm, mk = refmap_mask_make(img[mask], nrm[mask], res=refmap_res, angle_threshold=np.pi / 128 / 2)  # (scripts/estimate.py:57)
         refmaps.append(rm.permute(2, 0, 1))
         refmasks.append(mk)
+    timer.mark("refmap_gather")
+    return _chain_rows(DRMNet_model, ObsNet_model, refmaps, refmasks, hooks.get("cond_noise"), early_exit, seed, hooks, timer)
+
+
+class _StageTimer:
+    """hooks["timing"]: per-stage device time (ms) of one call, measured with events on the current stream and added to what is there"""
+
+    def __init__(self, hooks: dict):
+        self.hooks, self.marks = hooks, []
+
+    def mark(self, name: str) -> None:
+        if "timing" in self.hooks:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.marks.append((name, ev))
+
+    def finish(self) -> None:
+        if self.marks:
+            self.marks[-1][1].synchronize()
+            for (_, e0), (name, e1) in zip(self.marks[:-1], self.marks[1:]):
+                self.hooks["timing"][name] = self.hooks["timing"].get(name, 0.0) + e0.elapsed_time(e1)
+
+
+def _chain_rows(DRMNet_model, ObsNet_model, refmaps, refmasks, cond_noise, early_exit: bool, seed: Optional[int], hooks: dict, timer: _StageTimer):
+    """What ``estimate_batch`` and ``estimate_samples`` share once every row has its raw reflectance map [3, res, res] and mask: ONE ObsNet
+    DDIM run and ONE DRMNet loop over the rows -> (Lr0 [B, 3, res, res], zK [B, z_dim], K [B]).  hooks["stages"], where given, receives
+    the batched intermediate products (cond, inpaint, LrK)."""
     B = len(refmaps)
-    mark("refmap_gather")
     batch = {"tag": [f"obj{i}" for i in range(B)], "raw_refmap": torch.stack(refmaps), "raw_refmask": torch.stack(refmasks)}
-    c, _, _ = ObsNet_model.get_cond_for_predict(batch, noise=hooks.get("cond_noise"))
+    c, _, _ = ObsNet_model.get_cond_for_predict(batch, noise=cond_noise)
     use_ddim = ObsNet_model.ddim_steps is not None
     extra = {} if seed is None else {"seed": seed}
     obs_extra = {k: hooks[k] for k in ("x_T", "noise") if k in hooks}
@@ -100,7 +124,7 @@ def estimate_batch(DRMNet_model, ObsNet_model, input_imgs: torch.Tensor, input_n
         samples, _ = ObsNet_model.sample_log(cond=c, batch_size=B, ddim=use_ddim, ddim_steps=ObsNet_model.ddim_steps, eta=ObsNet_model.ddim_eta,
                                              **extra, **obs_extra)
     inpaint = ObsNet_model.ds.rescale(ObsNet_model.decode_first_stage(samples))
-    mark("obsnet_sampler")
+    timer.mark("obsnet_sampler")
     LrK, _, illnet_c, refnet_c, _ = DRMNet_model.get_input_for_predict({"tag": batch["tag"], "LrK": inpaint})
     loop_extra = {k: hooks[k] for k in ("noise0", "step_noise") if k in hooks}
     with DRMNet_model.ema_scope():
@@ -108,12 +132,44 @@ def estimate_batch(DRMNet_model, ObsNet_model, input_imgs: torch.Tensor, input_n
     Lr0 = DRMNet_model.ds.rescale(DRMNet_model.decode_first_stage(samples)).clip(0)
     if DRMNet_model.refmap_input_scaler is not None:
         Lr0 = Lr0 / DRMNet_model.normalizing_scale[:, None, None, None]
-    mark("drmnet_loop")
-    if marks:
-        marks[-1][1].synchronize()
-        for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
-            hooks["timing"][name] = hooks["timing"].get(name, 0.0) + e0.elapsed_time(e1)
+    timer.mark("drmnet_loop")
+    timer.finish()
+    if "stages" in hooks:
+        hooks["stages"].update(cond=c, inpaint=inpaint, LrK=LrK)
     return Lr0, zK_est, K
+
+
+MAX_SAMPLES = 64  # one image's draws are ranked against each other by one launch of N^2 <= 4096 pairs (samples.pairwise_distances)
+SELECT_KINDS = ("rerender", "medoid", "first")  # what samples.select chooses by
+
+
+@torch.no_grad()
+def estimate_samples(DRMNet_model, ObsNet_model, input_img: torch.Tensor, input_normal: torch.Tensor, mask: torch.Tensor, num_samples: int,
+                     erode_kernel_size: int = 5, *, early_exit: bool = True, seed: Optional[int] = None, hooks: Optional[dict] = None):
+    """N draws of ONE object image in one call: DRMNet is stochastic, and what it returns for an image is one of many plausible
+    (illumination, reflectance) pairs.  The erosion and the reflectance-map gather run once; the same raw map and mask stand on N batch
+    rows, and the rest is ``estimate_batch``'s statement order -- one ObsNet DDIM run and one DRMNet loop at batch N -- so the rows differ
+    through the noise alone.  input_img / input_normal [H, W, 3], mask [H, W] bool, 1 <= num_samples <= 64
+    -> (Lr0 [N, 3, res, res], zK [N, z_dim], K [N]).
+    ``seed``: the samplers get it, and the padding noise of ``get_cond_for_predict`` is ops.randn under seed + 1 (the rule validation_step
+    has for its second pass), so a seed fixes every draw; None leaves the draws to the samplers' and torch's generators.  ``hooks`` are
+    ``estimate_batch``'s, batched over the N rows (hooks["cond_noise"] stands in for the seeded padding noise)."""
+    hooks = hooks or {}
+    if isinstance(num_samples, bool) or not 1 <= int(num_samples) <= MAX_SAMPLES:
+        raise ValueError(f"estimate_samples: num_samples in [1, {MAX_SAMPLES}], got {num_samples!r}")
+    N = int(num_samples)
+    timer = _StageTimer(hooks)
+    timer.mark("start")
+    if erode_kernel_size > 0:
+        mask = erode_mask(mask, erode_kernel_size)
+    rm, mk = refmap_mask_make(input_img[mask], input_normal[mask], res=DRMNet_model.ds.size, angle_threshold=np.pi / 128 / 2)  # (scripts/estimate.py:57)
+    timer.mark("refmap_gather")
+    cond_noise = hooks.get("cond_noise")
+    if cond_noise is None and seed is not None and ObsNet_model.padding_mode == "noise":
+        from . import ops
+
+        cond_noise = ops.randn((N, rm.shape[2], ObsNet_model.image_size, ObsNet_model.image_size), int(seed) + 1, device=rm.device)
+    return _chain_rows(DRMNet_model, ObsNet_model, [rm.permute(2, 0, 1)] * N, [mk] * N, cond_noise, early_exit, seed, hooks, timer)
 
 
 def save_brdf_png(path, zK, brdf_param_names) -> None:
@@ -148,14 +204,28 @@ def parser() -> argparse.ArgumentParser:
                         help="the true principled row (metallic, base colour R G B, roughness, specular): also report the estimated BRDF's error")
     parser.add_argument("--gt_merl", type=Path, default=None,
                         help="the true measured BRDF (a MERL .binary): also report the estimated BRDF's error and the best principled fit of the table")
+    parser.add_argument("--num_samples", type=int, default=1,
+                        help=f"draw N estimates of the image in one batch, in [1, {MAX_SAMPLES}]; N > 1 keeps the draw --select names and adds "
+                             "samples.json, samples_Lr0.npy, sample_mean_env.png and sample_std.exr (default: 1)")
+    parser.add_argument("--select", choices=SELECT_KINDS, default=None,
+                        help="which of the N draws becomes the estimate: the lowest re-render error against the input image, the draw closest to "
+                             "all the others, or the first (default: rerender); needs --num_samples > 1")
+    parser.add_argument("--seed", type=int, default=None, help="fix the N draws; needs --num_samples > 1")
     return parser
 
 
 def parse_args(argv=None) -> argparse.Namespace:
-    """the command line, with the two rules argparse cannot state: --gt_envmap and --gt_view_from come as a pair, and --gt_z and --gt_merl
-    exclude each other"""
+    """the command line, with the rules argparse cannot state: --gt_envmap and --gt_view_from come as a pair; --gt_z and --gt_merl exclude
+    each other; --num_samples is in [1, 64]; --select and --seed are errors unless --num_samples > 1 (one draw has nothing to choose from, and
+    without the flag the draws stay where the reference takes them), and with N > 1 --select defaults to rerender"""
     p = parser()
     args = p.parse_args(argv)
+    if not 1 <= args.num_samples <= MAX_SAMPLES:
+        p.error(f"--num_samples in [1, {MAX_SAMPLES}], got {args.num_samples}")
+    if args.num_samples == 1 and (args.select is not None or args.seed is not None):
+        p.error("--select and --seed need --num_samples > 1: a single draw is the reference's, taken as it takes it")
+    if args.num_samples > 1 and args.select is None:
+        args.select = "rerender"
     if (args.gt_envmap is None) != (args.gt_view_from is None):
         p.error("--gt_envmap and --gt_view_from come as a pair: the true map is in the world frame, the estimate in the camera's")
     if args.gt_z is not None and args.gt_merl is not None:
@@ -266,9 +336,21 @@ def main(argv=None, *, models=None, hooks: Optional[dict] = None):
     hooks = dict(hooks or {})
     if args.rerender:
         hooks.setdefault("stages", {})
-    Lr0_sample, zK_est = estimate(drmnet_model, obsnet_model, input_img, input_normal, mask, hooks=hooks)
+    if args.num_samples > 1:
+        from . import samples
+
+        draws = estimate_samples(drmnet_model, obsnet_model, input_img, input_normal, mask, args.num_samples, seed=args.seed, hooks=hooks)
+        report = samples.rank(drmnet_model, *draws, input_img, input_normal, mask, args.select)
+        Lr0_sample, zK_est = draws[0][report["selected"]], draws[1][report["selected"]]
+        if args.rerender:
+            hooks["stages"]["inpaint"] = hooks["stages"]["inpaint"][report["selected"]]
+    else:
+        Lr0_sample, zK_est = estimate(drmnet_model, obsnet_model, input_img, input_normal, mask, hooks=hooks)
     envmap_est = drmnet_model.r0toenvmap(Lr0_sample[None], (drmnet_model.image_size, drmnet_model.image_size * 2))[0]  # [H, W, 3]
     args.output_dir.mkdir(exist_ok=True)
+    if args.num_samples > 1:
+        samples.write_samples(args.output_dir, drmnet_model, draws[0], draws[1], dict(report, num_samples=args.num_samples, seed=args.seed))
+        print(f"kept draw {report['selected']} of {args.num_samples} (--select {args.select}; the medoid is draw {report['medoid']})")
     file_io.save_png(args.output_dir / "sample_env.png", hdr2ldr(envmap_est.cpu().numpy()))
     save_brdf_png(args.output_dir / "sample_brdf.png", zK_est, drmnet_model.brdf_param_names)
     np.save(args.output_dir / "sample_brdf.npy", zK_est.cpu().numpy())

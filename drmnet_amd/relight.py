@@ -210,6 +210,110 @@ def image_errors(a, b, mask) -> Dict[str, float]:
             "rmse_log10": float(np.sqrt(np.mean(log * log))) if log.size else 0.0, "n_log": int(both.sum())}
 
 
+# the sums of drm_image_error_sums, in the order of include/drmnet_hip.h (DRM_IMAGE_ERROR_*)
+IMAGE_SUM_NAMES = ("n", "aa", "bb", "ab", "l2", "n_log", "d", "dd", "l2_scaled", "dd_centred")
+
+
+def _image_stack(who: str, name: str, x, H: int, W: int):
+    """``x`` as drm_image_error_sums reads a stack: [3, H, W] / [B, 3, H, W] (channel-first) or [H, W, 3] / [B, H, W, 3] (channel-last; a
+    shape that is both, H = W = 3, is read channel-last as ``image_errors`` reads it) -> (tensor [B, ., ., .] fp32, count, (batch, pixel,
+    channel) strides in elements).  The tensor is ``x`` itself wherever its rows of pixels lie at one stride; it is copied only if not."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4):
+        raise ValueError(f"{who}: {name} must be a tensor [3, H, W], [H, W, 3] or a stack of either, got {type(x).__name__} {tuple(getattr(x, 'shape', ()))}")
+    t = x if x.dim() == 4 else x[None]
+    if tuple(t.shape[1:]) == (H, W, 3):
+        c, h, w = 3, 1, 2
+    elif tuple(t.shape[1:]) == (3, H, W):
+        c, h, w = 1, 2, 3
+    else:
+        raise ValueError(f"{who}: {name} must be [.., 3, H={H}, W={W}] or [.., H={H}, W={W}, 3] like the mask, got {tuple(x.shape)}")
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    if not (H == 1 or W == 1 or t.stride(h) == W * t.stride(w)):
+        t = t.contiguous()
+    pixel = t.stride(w) if W > 1 else (t.stride(h) if H > 1 else 1)
+    return t, int(t.shape[0]), (int(t.stride(0)), int(pixel), int(t.stride(c)))
+
+
+def _check_pairs(who: str, pairs, counts) -> np.ndarray:
+    """``pairs`` as int32 [P, 3] on the host, every triple inside ``counts`` = (Ba, Bb, Bm); None: row i against row i, a stack of one shared"""
+    if pairs is None:
+        P = max(counts)
+        if any(n not in (1, P) for n in counts):
+            raise ValueError(f"{who}: without pairs the stacks hold 1 or P = {P} rows each, got a {counts[0]}, b {counts[1]}, mask {counts[2]}")
+        table = np.stack([np.arange(P) if n > 1 else np.zeros(P, dtype=np.int64) for n in counts], axis=1)
+    else:
+        table = np.asarray(pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs)
+        if table.ndim != 2 or table.shape[1] != 3 or table.dtype.kind not in "iu":
+            raise ValueError(f"{who}: pairs must be integers [P, 3] = (ia, ib, im), got {table.dtype} {table.shape}")
+    P = int(table.shape[0])
+    if not 1 <= P <= _lib.IMAGE_ERROR_MAX_PAIRS:
+        raise ValueError(f"{who}: P = {P} pairs in [1, {_lib.IMAGE_ERROR_MAX_PAIRS}]")
+    for col, (name, n) in enumerate(zip(("ia", "ib", "im"), counts)):
+        if table[:, col].min() < 0 or table[:, col].max() >= n:
+            raise ValueError(f"{who}: pairs[:, {col}] ({name}) must be in [0, {n}), got {int(table[:, col].min())} .. {int(table[:, col].max())}")
+    return np.ascontiguousarray(table, dtype=np.int32)
+
+
+@torch.no_grad()
+def image_error_sums(a, b, mask, *, pairs=None) -> torch.Tensor:
+    """One call of drm_image_error_sums (csrc/image_error.hip): P pairs of images scored on a mask in one launch sequence, nothing brought to
+    the host.  a, b: [B, 3, H, W] (as ``render_normals`` returns) or [B, H, W, 3] (as ``load_exr`` gives), each its own layout, or single
+    images; a strided batch goes in without a copy.  mask [H, W] or [Bm, H, W] (non-zero = counted).  pairs: integers [P, 3] = (ia, ib, im),
+    1 <= P <= 4096, checked against the stacks on the host; None: row i against row i, a stack of one shared by all
+    -> torch.float64 [P, 10] on the device, the sums of IMAGE_SUM_NAMES (include/drmnet_hip.h states them).  A pair gives the same bits
+    alone, anywhere in any list of pairs, and in two calls.  A bad argument is a ValueError before anything touches the GPU; a tensor on
+    the CPU is a RuntimeError."""
+    who = "image_error_sums"
+    m = torch.as_tensor(mask)
+    if m.dim() not in (2, 3) or m.numel() == 0:
+        raise ValueError(f"{who}: mask must be [H, W] or [Bm, H, W], got {tuple(m.shape)}")
+    H, W = int(m.shape[-2]), int(m.shape[-1])
+    Bm = 1 if m.dim() == 2 else int(m.shape[0])
+    ta, Ba, sa = _image_stack(who, "a", a, H, W)
+    tb, Bb, sb = _image_stack(who, "b", b, H, W)
+    table = _check_pairs(who, pairs, (Ba, Bb, Bm))
+    _gpu_only(who, a=a, b=b)
+    dev = _device(a, b)
+    m8 = (m.to(dev) != 0).to(torch.uint8).reshape(Bm, H * W).contiguous()
+    P = int(table.shape[0])
+    triples = torch.from_numpy(table).to(dev)
+    nbytes = _lib.image_error_workspace_bytes(P)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    sums = torch.empty((P, _lib.IMAGE_ERROR_SUMS), dtype=torch.float64, device=dev)
+    args = _lib.sized(_lib.ImageError, a=ta.data_ptr(), a_count=Ba, a_batch_stride=sa[0], a_pixel_stride=sa[1], a_channel_stride=sa[2],
+                      b=tb.data_ptr(), b_count=Bb, b_batch_stride=sb[0], b_pixel_stride=sb[1], b_channel_stride=sb[2],
+                      mask=m8.data_ptr(), mask_count=Bm, HW=H * W, pairs=triples.data_ptr(), P=P, workspace=ws.data_ptr(), workspace_bytes=nbytes,
+                      sums=sums.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().drm_image_error_sums(args, _lib.stream_ptr(dev)))
+    return sums
+
+
+def errors_from_image_sums(s) -> Dict[str, float]:
+    """the figures of ``image_errors`` from one row of the ten sums, with its zero-denominator rules, and ``rmse_log10_scaled``: the log
+    error once the best common factor is removed (the root mean square of d about its mean)"""
+    s = np.asarray(s, dtype=np.float64)
+    if s.shape != (len(IMAGE_SUM_NAMES),):
+        raise ValueError(f"errors_from_image_sums: one row of {len(IMAGE_SUM_NAMES)} sums, got {s.shape}")
+    n, aa, bb, ab, l2, n_log, _, dd, l2_scaled, dd_centred = (float(v) for v in s)
+    nb = float(np.sqrt(bb))
+
+    def rel(dsq: float) -> float:
+        d = float(np.sqrt(dsq))
+        return d / nb if nb > 0 else (0.0 if d == 0 else float("inf"))
+
+    return {"n": int(n), "rel_l2": rel(l2), "scale": ab / aa if aa > 0 else 0.0, "rel_l2_scaled": rel(l2_scaled),
+            "rmse_log10": float(np.sqrt(dd / n_log)) if n_log > 0 else 0.0, "n_log": int(n_log),
+            "rmse_log10_scaled": float(np.sqrt(dd_centred / n_log)) if n_log > 0 else 0.0}
+
+
+def image_errors_batch(a, b, mask, *, pairs=None):
+    """``image_errors`` for P pairs at once on the GPU (``image_error_sums`` takes the arguments; one device-to-host copy of [P, 10] doubles)
+    -> a list of P dicts with the keys of ``image_errors`` and ``rmse_log10_scaled``."""
+    return [errors_from_image_sums(row) for row in image_error_sums(a, b, mask, pairs=pairs).cpu().numpy()]
+
+
 def object_mask(input_normal: torch.Tensor, input_mask: Optional[torch.Tensor]) -> torch.Tensor:
     """the mask rule of ``estimate``'s command line (scripts/estimate.py:127-135): |normal| > 0.5, and the PNG mask where one is given"""
     normal_mask = torch.linalg.norm(input_normal, dim=-1) > 0.5

@@ -745,6 +745,63 @@ int drm_merl_eval(const float* tables, int NT, const int32_t* table_of, const fl
 int drm_brdf_error_sums(const float* z, int C, const float* table, const float* z_target, double* workspace, size_t workspace_bytes, double* sums,
                         void* stream);
 
+/* drm_image_error_sums (csrc/image_error.hip; serves drmnet_amd/relight.py: image_error_sums, image_errors_batch, and drmnet_amd/samples.py,
+ *   which ranks the draws of estimate --num_samples): P pairs of images scored on a mask in one call, the image-space twin of
+ *   drm_brdf_error_sums.  Zero-initialise drm_image_error, set struct_bytes = sizeof(drm_image_error), then every member.  All pointers
+ *   are device pointers.
+ *   a, b: two stacks of fp32 images of HW pixels and three channels; element (i, pixel q, channel c) of a stack is
+ *     data[i batch_stride + q pixel_stride + c channel_stride] (strides in elements: channel-first [B][3][HW] is (3 HW, 1, HW), channel-last
+ *     [B][HW][3] is (3 HW, 3, 1); a batch stride larger than an image, or 0, goes in as it is).
+ *   mask: uint8 [mask_count][HW], non-zero = counted.  pairs: int32 [P][3] = (ia, ib, im), 1 <= P <= 4096: image ia of a against image ib of
+ *     b on mask im.  The triples are device data and are not brought to the host: a triple outside [0, a_count) x [0, b_count) x [0, mask_count)
+ *     reads nothing and gives ten NaNs (callers check their triples before the upload, as drmnet_amd.relight does).
+ *   sums: double [P][DRM_IMAGE_ERROR_SUMS], over the masked pixels and their three channels, element arithmetic in fp64:
+ *     [DRM_IMAGE_ERROR_N]      the masked pixels (pixels, not entries)
+ *     [DRM_IMAGE_ERROR_AA], [DRM_IMAGE_ERROR_BB], [DRM_IMAGE_ERROR_AB]   sums of a^2, b^2, a b
+ *     [DRM_IMAGE_ERROR_L2]     sum of (a - b)^2
+ *     [DRM_IMAGE_ERROR_N_LOG]  the entries with a > 0 and b > 0
+ *     [DRM_IMAGE_ERROR_D], [DRM_IMAGE_ERROR_DD]   sums of d = log10 a - log10 b and of d^2, over those entries
+ *     [DRM_IMAGE_ERROR_L2_SCALED]  sum of (s a - b)^2, s = sum AB / sum AA (0 unless sum AA > 0)
+ *     [DRM_IMAGE_ERROR_DD_CENTRED] sum of (d - sum D / n_log)^2 (the mean is 0 where n_log is 0)
+ *   The last two are a second pass over the pixels, which forms s and the mean on the device from the first pass's parts added in the order
+ *   the results are; the one-pass identities BB - AB^2 / AA and DD - D^2 / n_log cancel and are not used.  Three launches, no host
+ *   synchronisation.  Sums are added in a fixed order without atomics that depends on the pixel's place alone: a pair gives the same bits
+ *   alone, at any place in any list of pairs, and in two calls.  Non-finite values propagate as they do in fp64 arithmetic.
+ *   workspace: DRM_IMAGE_ERROR_WORKSPACE_BYTES(P) of device memory, 8-byte aligned, contents irrelevant.
+ *   DRM_ERR_INVALID, nothing launched, drm_last_error naming what is wrong: struct_bytes; a NULL a, b, mask, pairs, workspace or sums; P
+ *   outside [1, 4096]; HW < 1; a count < 1; a workspace smaller than the macro; workspace or sums not 8-byte aligned. */
+#define DRM_IMAGE_ERROR_SUMS 10
+#define DRM_IMAGE_ERROR_N 0
+#define DRM_IMAGE_ERROR_AA 1
+#define DRM_IMAGE_ERROR_BB 2
+#define DRM_IMAGE_ERROR_AB 3
+#define DRM_IMAGE_ERROR_L2 4
+#define DRM_IMAGE_ERROR_N_LOG 5
+#define DRM_IMAGE_ERROR_D 6
+#define DRM_IMAGE_ERROR_DD 7
+#define DRM_IMAGE_ERROR_L2_SCALED 8
+#define DRM_IMAGE_ERROR_DD_CENTRED 9
+#define DRM_IMAGE_ERROR_PARTS 16
+#define DRM_IMAGE_ERROR_WORKSPACE_BYTES(P) ((size_t)(P) * DRM_IMAGE_ERROR_PARTS * DRM_IMAGE_ERROR_SUMS * sizeof(double))
+typedef struct drm_image_error {
+  uint32_t struct_bytes;
+  const float* a;
+  int32_t a_count;
+  int64_t a_batch_stride, a_pixel_stride, a_channel_stride;
+  const float* b;
+  int32_t b_count;
+  int64_t b_batch_stride, b_pixel_stride, b_channel_stride;
+  const uint8_t* mask;
+  int32_t mask_count;
+  int64_t HW;
+  const int32_t* pairs;
+  int32_t P;
+  void* workspace;
+  size_t workspace_bytes;
+  double* sums;
+} drm_image_error;
+int drm_image_error_sums(const drm_image_error* args, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The validation losses (csrc/losses.hip).
  * ------------------------------------------------------------------------------------------- */

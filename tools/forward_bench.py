@@ -19,6 +19,10 @@
         the same for one pass of ObsNetDiffusion's validation at full width (configs/obsnet/eval_obsnet.yaml's network with the validation
         keys of the reference's train_obsnet.yaml, synthetic weights, 128 x 128, 128 x 256 maps, random sparse masks): get_input (render,
         masked transform, conditioning half of drm_obs_forward_process), q_sample half + network, drm_diffusion_losses.
+    python tools/forward_bench.py image_errors [--reps 10 --rounds 2]
+        64 draws of one 128 x 128 object image ranked by re-render error (samples.rerender_errors end to end, the image-error call alone, its
+        launches alone) against the same 64 comparisons through the host path relight.image_errors, and the 4096 pairs of
+        samples.pairwise_distances at N = 64; device events around each call (the host work of a call ends inside its window).
 """
 import argparse
 import ctypes as C
@@ -319,9 +323,75 @@ def bench_obs_step(args):
     print(f"ObsNet validation step B={B} {args.precision}: wall {wall:.1f} ms per pass of one weight set; losses {out.tolist()}", flush=True)
 
 
+def bench_image_errors(args):
+    """image_errors: N = 64 draws of one 128 x 128 object image ranked (samples.rerender_errors: warp, render, one image-error call of 64
+    pairs), the image-error call alone, its three launches alone, the same 64 comparisons through the host path relight.image_errors, and
+    samples.pairwise_distances at N = 64 (4096 pairs of 128 x 128 mirror maps) with its launches alone"""
+    import numpy as np
+
+    from drmnet_amd import _lib, ops, relight, samples
+    from drmnet_amd.synthesize import NAMES
+
+    class Model:  # what samples.rerender_errors asks of a DRMNet: the mirror-map warp (no basis division), the map size, the parameter names
+        image_size, brdf_param_names = 128, NAMES
+
+        @staticmethod
+        def r0toenvmap(r0, shape):
+            return ops.mirmap2envmap(r0, shape, channels_last=True)
+
+    dev = torch.device("cuda:0")
+    N, H, W = 64, 128, 128
+    g = torch.Generator().manual_seed(4)
+    Lr0 = (torch.rand((N, 3, 128, 128), generator=g) + 0.05).to(dev)
+    zK = torch.rand((N, 6), generator=g).to(dev)
+    y, x = torch.meshgrid(torch.linspace(1, -1, H), torch.linspace(-1, 1, W), indexing="ij")
+    r2 = x * x + y * y
+    normal = torch.stack([x, y, torch.sqrt((1 - r2).clamp_min(0))], dim=-1).to(dev)
+    mask = (r2 < 0.98).to(dev)
+    envs = Model.r0toenvmap(Lr0, (128, 256))
+    images, _ = relight.render_normals(normal, zK, NAMES, envs, mask=mask)
+    target = images[0].permute(1, 2, 0).contiguous() * 1.1 + 0.01
+
+    def launches(a, b, m, pairs):
+        """the entry alone on prepared arguments: what a caller that keeps its buffers pays"""
+        ta, Ba, sa = relight._image_stack("bench", "a", a, *m.shape[-2:])
+        tb, Bb, sb = relight._image_stack("bench", "b", b, *m.shape[-2:])
+        m8 = (m != 0).to(torch.uint8).reshape(-1, m.shape[-2] * m.shape[-1]).contiguous()
+        P = len(pairs)
+        triples = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(dev)
+        nbytes = _lib.image_error_workspace_bytes(P)
+        ws, sums = torch.empty(nbytes // 8, dtype=torch.float64, device=dev), torch.empty((P, 10), dtype=torch.float64, device=dev)
+        s = _lib.sized(_lib.ImageError, a=ta.data_ptr(), a_count=Ba, a_batch_stride=sa[0], a_pixel_stride=sa[1], a_channel_stride=sa[2], b=tb.data_ptr(),
+                       b_count=Bb, b_batch_stride=sb[0], b_pixel_stride=sb[1], b_channel_stride=sb[2], mask=m8.data_ptr(), mask_count=int(m8.shape[0]),
+                       HW=int(m8.shape[1]), pairs=triples.data_ptr(), P=P, workspace=ws.data_ptr(), workspace_bytes=nbytes, sums=sums.data_ptr())
+        keep = (ta, tb, m8, triples, ws, sums)
+        return lambda: (_lib.check(_lib.lib().drm_image_error_sums(s, _lib.stream_ptr(dev))), keep)[0]
+
+    def host_loop():
+        return [relight.image_errors(images[i].permute(1, 2, 0), target, mask) for i in range(N)]
+
+    i, j = np.divmod(np.arange(N * N), N)
+    cases = [("samples.rerender_errors N=64 (warp + render + errors, figures on the host)", lambda: samples.rerender_errors(Model, Lr0, zK, target, normal, mask)),
+             ("relight.image_errors_batch 64 pairs (call + [64, 10] copy + figures)", lambda: relight.image_errors_batch(images, target, mask)),
+             ("drm_image_error_sums 64 pairs, launches alone", launches(images, target, mask, [(k, 0, 0) for k in range(N)])),
+             ("relight.image_errors x 64 (the host path: 2 x 64 copies + numpy)", host_loop),
+             ("samples.pairwise_distances N=64 (4096 pairs, figures on the host)", lambda: samples.pairwise_distances(Lr0)),
+             ("drm_image_error_sums 4096 pairs, launches alone", launches(Lr0, Lr0, torch.ones((128, 128), device=dev), np.stack([i, j, 0 * i], axis=1)))]
+    results = {}
+    for _ in range(args.rounds):
+        for name, fn in cases:
+            results.setdefault(name, []).extend(timed(fn, args.reps))
+    batch, host = relight.image_errors_batch(images, target, mask), host_loop()
+    worst = max(abs(b[k] - h[k]) / max(abs(h[k]), 1e-300) for b, h in zip(batch, host) for k in h if h[k] != 0)
+    print(f"image errors, {N} renders of {H}x{W} against one input, {int(mask.sum())} masked pixels: batch against host path, largest relative difference {worst:.2e}")
+    for name, ms in results.items():
+        ms = sorted(ms)
+        print(f"{name}: median {ms[len(ms) // 2]:.3f} ms  min {ms[0]:.3f}  max {ms[-1]:.3f}  (n={len(ms)})", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["render", "step", "obs_step"])
+    ap.add_argument("what", choices=["render", "step", "obs_step", "image_errors"])
     ap.add_argument("--libs", nargs="*", default=["-"])
     ap.add_argument("--stack", type=int, default=4)
     ap.add_argument("--batch", type=int, default=20)
@@ -333,4 +403,4 @@ if __name__ == "__main__":
     ap.add_argument("--mesh_batch", type=int, default=0, help="render --entries: rows of the mesh entries (default: --batch)")
     ap.add_argument("--match", nargs="*", default=[], help="render --entries: only the entries whose name contains one of these")
     a = ap.parse_args()
-    {"render": bench_render, "step": bench_step, "obs_step": bench_obs_step}[a.what](a)
+    {"render": bench_render, "step": bench_step, "obs_step": bench_obs_step, "image_errors": bench_image_errors}[a.what](a)
