@@ -56,16 +56,17 @@ __device__ __forceinline__ float apply_map(int op, float arg, float v, float lo,
 }
 
 // grid (blocks over one image's elements, B): every thread maps four consecutive elements through the whole chain
+// `aligned`: both pointers are 16-byte aligned (launch_map_chain), so a quad at an element index that is a multiple of four may move as a float4
 __global__ __launch_bounds__(256) void map_chain_kernel(const float* __restrict__ x, float* __restrict__ out, long long per_image, MapChain ch,
                                                         const float* __restrict__ lo, const float* __restrict__ hi,
-                                                        const float* __restrict__ scale) {
+                                                        const float* __restrict__ scale, int aligned) {
   const int b = blockIdx.y;
   const float l = lo ? lo[b] : 0.f, h = hi ? hi[b] : 1.f, sc = scale ? scale[b] : 1.f;
   const long long base = (long long)b * per_image;
   const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i0 >= per_image) return;
   float v[4];
-  const bool full = (i0 + 3 < per_image) && (((base + i0) & 3) == 0);
+  const bool full = aligned && (i0 + 3 < per_image) && (((base + i0) & 3) == 0);
   if (full) {
     const float4 t = *reinterpret_cast<const float4*>(x + base + i0);
     v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
@@ -100,7 +101,10 @@ int launch_map_chain(const float* x, float* out, long long per_image, int B, con
     ch.arg[j] = args ? args[j] : 0.f;
   }
   const long long quads = (per_image + 3) / 4;
-  hipLaunchKernelGGL(map_chain_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, s, x, out, per_image, ch, lo, hi, scale);
+  // a contiguous view at a storage offset that is no multiple of four elements is 4-byte but not 16-byte aligned: scalar accesses then
+  const int aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  hipLaunchKernelGGL(map_chain_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, s, x, out, per_image, ch, lo, hi, scale,
+                     aligned);
   DRM_HIP_CHECK(hipGetLastError());
   return DRM_OK;
 }
@@ -120,9 +124,14 @@ __device__ __forceinline__ T block_reduce(T v, F f, T* red /*[8]*/, T ident) {
   return r;
 }
 
+// max / min that keep a NaN operand, as torch's amax / amin do (fmaxf / fminf drop it); the bits of every other pair are fmaxf's / fminf's
+__device__ __forceinline__ float nan_max(float a, float c) { return a != a ? a : c != c ? c : fmaxf(a, c); }
+__device__ __forceinline__ float nan_min(float a, float c) { return a != a ? a : c != c ? c : fminf(a, c); }
+
 // dynamic_normalize branch of "normalizedLogarithmic" (basedataset.py:63-69), one workgroup per image:
 //   linearmax = max(x * mask);  hi = log10(linearmax);  lo = log10(min(x * mask + (1 - mask) * linearmax))
 // x [B][C][HW] (already lower-bounded by the maps in front of it), mask [B][HW] fp32 0/1 (broadcast over channels).
+// Poison survives as in the reference: a NaN inside the mask, or a non-finite value outside it (Inf * 0), makes both statistics NaN.
 __global__ __launch_bounds__(512) void masked_log_range_kernel(const float* __restrict__ x, const float* __restrict__ mask, int C, int HW,
                                                                float* __restrict__ lo, float* __restrict__ hi) {
   __shared__ float red[8];
@@ -131,14 +140,14 @@ __global__ __launch_bounds__(512) void masked_log_range_kernel(const float* __re
   const float* mb = mask + (size_t)b * HW;
   const int n = C * HW;
   float mx = -INFINITY;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, xb[i] * mb[i % HW]);
-  mx = block_reduce(mx, [](float a, float c) { return fmaxf(a, c); }, red, -INFINITY);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) mx = nan_max(mx, xb[i] * mb[i % HW]);
+  mx = block_reduce(mx, [](float a, float c) { return nan_max(a, c); }, red, -INFINITY);
   float mn = INFINITY;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const float m = mb[i % HW];
-    mn = fminf(mn, xb[i] * m + (1.0f - m) * mx);
+    mn = nan_min(mn, xb[i] * m + (1.0f - m) * mx);
   }
-  mn = block_reduce(mn, [](float a, float c) { return fminf(a, c); }, red, INFINITY);
+  mn = block_reduce(mn, [](float a, float c) { return nan_min(a, c); }, red, INFINITY);
   if (threadIdx.x == 0) {
     hi[b] = log10f(mx);
     lo[b] = log10f(mn);
@@ -163,6 +172,8 @@ __global__ __launch_bounds__(512) void luminance_scale_kernel(const float* __res
     if (L > 0.f) {
       sum += (double)logf(fmaxf(L, 1e-5f));
       cnt += 1.0;
+    } else if (L != L) {
+      sum += (double)L;  // the reference multiplies log(NaN) by the lit mask: NaN * 0 stays NaN and so does the scale
     }
   }
   auto add = [](double a, double c) { return a + c; };
@@ -232,7 +243,8 @@ int launch_mirmap2envmap(const float* mir, const float* basis, float* out, int B
 
 // ------------------------------------------------------------------------------------------------ tone map
 // hdr2ldr (utils/tonemap.py:4-9): coeff = alpha / exp(mean over lit pixels of log(L + 1e-7)); out = clip(x coeff, 0, 1)^(1/gamma).
-// x [HW][3] (channels last, one image), mask optional uint8 [HW].  Single workgroup: reduction, then the map.
+// x [HW][3] (channels last, one image), mask optional uint8 [HW].  Single workgroup: reduction, then the map.  Poison survives as in the
+// reference: a NaN luminance anywhere makes every pixel NaN, and a pixel whose product with the coefficient is NaN stays NaN.
 __global__ __launch_bounds__(1024) void hdr2ldr_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask, int HW, float alpha,
                                                        float inv_gamma, float* __restrict__ out) {
   __shared__ double red[16];
@@ -243,13 +255,18 @@ __global__ __launch_bounds__(1024) void hdr2ldr_kernel(const float* __restrict__
     if (lit) {
       sum += (double)logf(fmaxf(L, 0.f) + 1e-7f);
       cnt += 1.0;
+    } else if (L != L || L == INFINITY) {
+      sum += (double)NAN;  // the reference multiplies log(L) by the lit mask: NaN * 0 and Inf * 0 are NaN, and then so is every pixel
     }
   }
   auto add = [](double a, double c) { return a + c; };
   sum = block_reduce(sum, add, red, 0.0);
   cnt = block_reduce(cnt, add, red, 0.0);
   const float coeff = alpha / expf((float)(sum / cnt));
-  for (int i = threadIdx.x; i < 3 * HW; i += blockDim.x) out[i] = powf(fminf(fmaxf(x[i] * coeff, 0.f), 1.f), inv_gamma);
+  for (int i = threadIdx.x; i < 3 * HW; i += blockDim.x) {
+    const float t = x[i] * coeff;
+    out[i] = powf(t <= 0.f ? 0.f : t > 1.f ? 1.f : t, inv_gamma);  // NaN stays NaN like numpy's clip (fmaxf would turn it into 0)
+  }
 }
 
 int launch_hdr2ldr(const float* x, const unsigned char* mask, int HW, float alpha, float gamma, float* out, hipStream_t s) {

@@ -378,6 +378,9 @@ def map_chain(x, steps, lo=None, hi=None, scale=None, out=None):
     for n, t in (("lo", lo), ("hi", hi), ("scale", scale)):
         if t is not None and t.numel() != b:
             raise RuntimeError(f"{n} must have one entry per image ({b}), got {t.numel()}")
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous()):
+        raise RuntimeError(f"out must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on {x.device}; got {out.dtype} "
+                           f"{tuple(out.shape)} on {out.device}, contiguous: {out.is_contiguous()}")
     res = torch.empty_like(x) if out is None else out
     src = x
     steps = list(steps)
